@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the HIP step engine on MATE-4v8-9, batch 4096 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,11 +15,22 @@ buffers; an environment whose episode ends inside a rollout idles until the rese
 are NOT counted in `value`); `--rollout 0` launches step_kernel once per step.
 
 Timing: W untimed warm-up steps (plus one untimed launch of every launch shape of the timed region, so that no buffer is
-allocated and no kernel is first loaded inside it), then the timed region of EXACTLY K steps, bracketed by a barrier +
-torch.cuda.synchronize() on both sides, is run `--rep-warmup` (3) untimed + `--reps` (5; 21 when the region is one short
-launch, e.g. the driver's `--steps 20`: 0.17 ms) timed times and the MEDIAN of the timed ones is reported (`ms_per_step` x
-`steps` = the median repetition).  The episode-statistics gathers run INSIDE the region, each behind the launch whose episodes
-it carries (a region of fewer launches than `--stats-interval` gathers once, behind its last launch).
+allocated and no kernel is first loaded inside it, and ~0.25 s of clock warm-up), then `--rep-warmup` (3) untimed passes
+through the measuring loop (each at most one warm-up chunk long), then the batch is restarted -- seed(0) + reset() + W steps
+again, so that the timed steps start from the same state in every run, whatever the time-based warm-up ran -- and the timed
+region of EXACTLY K steps, bracketed by a barrier + torch.cuda.synchronize() on both sides, runs once: `ms_per_step` x `steps` =
+the region.  `--reps M` times it M times back to back and reports the MEDIAN repetition (`--full`: 5, or 21 when the region is
+one short launch, e.g. `--steps 20`: 0.17 ms; its untimed passes are K steps long).  The episode-statistics gathers run INSIDE
+the region, each behind the launch whose episodes it carries (a region of fewer launches than `--stats-interval` gathers once,
+behind its last launch).
+
+`--dump-outputs DIR` writes, after the timed region, what its last step returned to the caller -- camera_obs [N, Nc, Dc],
+target_obs [N, Nt, Dt] and scalars [N, 8], float32 -- as DIR/<name>.npy (observation rows of environments that idled in that
+step, scalars[:, 2] == 2, hold whatever the buffer held and are written as zeros).  Beyond 64 MB in all, a fixed sample of the
+environments (numpy default_rng(0), the same rows in every array) is written instead.  Same arguments, same files.
+
+A plain run measures the headline and nothing else.  `--full` adds what takes runs of its own: the HBM probe of the roofline's
+measured peak, the side measurements of tools/bench_extras.py and the CPU baseline (see OUTPUT), and the repetitions above.
 
 `--gpus N` (N > 1) started without a torchrun environment launches the N ranks itself (a `torch.distributed.run` child process,
 started before this process touches the GPU) and exits with its status; under torchrun WORLD_SIZE must equal N.  The batch is
@@ -27,18 +38,18 @@ sharded (4096 environments per rank, env index = rank * 4096 + i; no data-path c
 statistics on a side stream.
 
 OUTPUT.  Rank 0 prints the driver's JSON line LAST, at most 3000 bytes (`headline_line`): the contract's keys, `config`,
-`roofline`, `cpu_baseline` and `details_file`.  Everything else -- the full-precision record, every repetition, start-up times,
-the side measurements of tools/bench_extras.py (`learner_flows`, `other_configs`, `reset_amortised`, `n1_api`) -- goes to the
-details file (`--details`, default bench_details.json next to this file), and a few numbers of the side measurements are printed
-as one `{"side": ...}` line (<= 3500 bytes) BEFORE the headline.
+`roofline`, `cpu_baseline` (`--full`) and `details_file`.  Everything else -- the full-precision record, every repetition, start-up
+times, the side measurements of tools/bench_extras.py (`--full`: `learner_flows`, `other_configs`, `reset_amortised`, `n1_api`) --
+goes to the details file (`--details`, default bench_details.json next to this file), and a few numbers of the side measurements
+are printed as one `{"side": ...}` line (<= 3500 bytes) BEFORE the headline.
   roofline      HBM roofline of the dominant kernel (rollout_kernel, or step_kernel with --rollout 0): `achieved` = algorithmic
                 bytes per launch (7504 B/env-step x the env-steps of one launch) / average launch duration measured
                 with HIP events on the launch stream over the timed region; `frac` = achieved / `peak` (vendor 8 TB/s).
                 `traffic` = HBM bytes of one launch of this shape from the committed rocprofv3 PMC passes, `frac_traffic` = traffic
                 / this run's kernel time / peak: the HBM utilisation (a fused launch keeps state, geometry and actions in LDS, so
                 `frac` prices bytes that never move).  `peak_measured` = the largest of the copy / fill / read rates of this box
-                under the library's own streaming kernels (mate_engine_hbm_probe), each also listed.
-  cpu_baseline  the CPU oracle (oracle/, a parity-checked port of the reference's step path) stepping + packing f32 observations
+                under the library's own streaming kernels (mate_engine_hbm_probe, `--full`), each also listed.
+  cpu_baseline  (`--full`) the CPU oracle (oracle/, a parity-checked port of the reference's step path) stepping + packing f32 observations
                 for the same workload on the host cores.
 
 `--force-collectives` runs every collective of the N-rank path on ONE rank: the `nccl` (= RCCL) process group with
@@ -161,11 +172,18 @@ def parse_args(argv=None):
     ap.add_argument('--steps', type=int, default=2048)
     ap.add_argument('--warmup', type=int, default=128)
     ap.add_argument('--reps', type=int, default=0,
-                    help='repetitions of the timed region; the median is reported (default 0 = 5, or 21 when the region is a single short launch -- '
-                         'under a millisecond: one preempted host thread moves a median of five)')
+                    help='repetitions of the timed region; the median is reported (default 0 = 1; with --full 5, or 21 when the region is a single '
+                         'short launch -- under a millisecond: one preempted host thread moves a median of five)')
     ap.add_argument('--rep-warmup', type=int, default=3,
                     help='untimed repetitions of the whole measuring loop (region + its bookkeeping) before the timed ones: the first '
-                         'passes through that loop are slower than its steady state (clocks, lazily loaded code), whatever ran before')
+                         'passes through that loop are slower than its steady state (clocks, lazily loaded code), whatever ran before; '
+                         'each at most one warm-up chunk long (--full: the whole region)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: the HBM probe of roofline.peak_measured, the side measurements (reset_amortised, '
+                         'other_configs, learner_flows, n1_api), the CPU baseline, and five (21) repetitions of the timed region by default')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed region, write what its last step returned (camera_obs, target_obs, scalars; float32) as DIR/<name>.npy, '
+                         'at most 64 MB in all (a fixed sample of the environments beyond that)')
     ap.add_argument('--batch', type=int, default=BATCH_PER_GPU, help='environments per GPU')
     ap.add_argument('--workload', default=WORKLOAD)
     ap.add_argument('--policy', choices=['random', 'greedy', 'external'], default='random',
@@ -189,8 +207,8 @@ def parse_args(argv=None):
     ap.add_argument('--versus-reset-interval', type=int, default=64,
                     help='learner_flows / versus_greedy: one restart of the finished environments per this many steps (Greedy episodes end after ~1.2 k steps)')
     ap.add_argument('--graph-steps', type=int, default=64, help='external policy: step + auto-reset pairs captured per HIP graph (0 = direct launches)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the per_step_launch / external_actions side measurements')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full without the per_step_launch / external_actions side measurements (learner_flows)')
     ap.add_argument('--cpu-seconds', type=float, default=10.0)
     ap.add_argument('--dry-run', action='store_true', help='launcher / reduction plumbing on CPU with gloo: measures nothing')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
@@ -199,12 +217,12 @@ def parse_args(argv=None):
     ap.add_argument('--deterministic', action='store_true', help='fixed-length clock warm-up instead of the time-based one (reproducible final state)')
     ap.add_argument('--dump', default='', help='every rank saves its final state and last outputs to <path>.rank<r>.pt')
     ap.add_argument('--max-episode-steps', type=int, default=0, help='override the scenario\'s time limit (tests: episodes that end inside a short run)')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the BASELINE config 3 / 4-shard / 5-shard side measurements')
+    ap.add_argument('--no-other-configs', action='store_true', help='--full without the BASELINE config 3 / 4-shard / 5-shard side measurements')
     ap.add_argument('--other-seconds', type=float, default=1.0, help='timed seconds per entry of other_configs')
     ap.add_argument('--force-collectives', action='store_true',
                     help='one rank: initialise the process group anyway (nccl = RCCL with device_id, or --backend gloo) and run every collective of the '
                          'N-rank path -- barrier, the side-stream all_gather of the episode statistics, the job-level reduction')
-    ap.add_argument('--no-side-measurements', action='store_true', help='skip reset_amortised / n1_api')
+    ap.add_argument('--no-side-measurements', action='store_true', help='--full without reset_amortised / n1_api')
     ap.add_argument('--details', default='', help='file the full record is written to (default: bench_details.json next to bench.py); the printed line carries its path')
     return ap.parse_args(argv)
 
@@ -311,6 +329,38 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
 
 
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs files together
+
+
+def dump_outputs(torch, directory, arrays, rank=0, idle_rows=False):
+    """`--dump-outputs`: the [N, ...] arrays of the timed region's last step as float32 / float64 DIR/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy).  `idle_rows`: rows of environments that idled in that step (scalars[:, 2] == 2: a rollout launch does not
+    write their observation rows, which hold whatever the buffer held) are written as zeros.  Beyond DUMP_LIMIT bytes in all, the same
+    fixed sample of the environments (numpy default_rng(0)) is taken from every array."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        out[name] = t.to(torch.float64) if t.dtype == torch.float64 else t.to(torch.float32)
+    if idle_rows and 'scalars' in out:
+        idle = out['scalars'][:, 2] == 2
+        for name, t in out.items():
+            if name != 'scalars':
+                out[name] = t.masked_fill(idle.view((-1,) + (1,) * (t.dim() - 1)), 0)
+    n = out['scalars'].shape[0]
+    per_env = sum(t[:1].numel() * t.element_size() for t in out.values())
+    if per_env * n > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT // per_env, replace=False))
+        index = torch.from_numpy(keep).to(out['scalars'].device)
+        out = {name: t.index_select(0, index) for name, t in out.items()}
+    suffix = '' if rank == 0 else f'.rank{rank}'
+    for name, t in out.items():
+        np.save(os.path.join(directory, name + suffix + '.npy'), t.cpu().numpy())
+
+
 OUT = sys.stdout       # where emit() prints; main() points it at the process's REAL stdout and sends everything else to stderr
 
 
@@ -403,6 +453,7 @@ def main():
     rollout_resets = args.rollout_reset_interval if args.rollout_reset_interval > 0 else (2 if args.policy == 'greedy' else max(1, 128 // max(R, 1)))
     rollout = lambda n, auto_reset=True: rollout_fn(n, auto_reset=rollout_resets)     # noqa: E731
     gather = StatsGather(torch, dist, distributed, eng, host_staged=host_staged) if args.stats_interval > 0 else None
+    last = {}        # what the latest rollout launch returned (its [n][N][...] views): --dump-outputs takes the last row
 
     def run(steps, timed=False):
         """exactly `steps` env.step()s of the whole batch"""
@@ -419,7 +470,7 @@ def main():
             # (through round 5 `value` was taken with that gather's marker ahead of the region: +8 % on the driver's 20-step region)
             short = timed and gather is not None and len(lengths) < args.stats_interval
             for i, n in enumerate(lengths):
-                rollout(n, auto_reset=True)
+                last['rollout'] = rollout(n, auto_reset=True)
                 if timed and gather is not None and ((i + 1) % args.stats_interval == 0 or (short and i == len(lengths) - 1)):
                     gather.submit()
         else:
@@ -450,8 +501,8 @@ def main():
     extra_steps = 0
     eng.kernel_time(enable=1 if R > 0 else STEP_SAMPLE)     # ... with the dispatch-event launch path of the timed region (events created, runtime warmed)
     t_warm = time.perf_counter()
+    chunk = min(args.steps, 8 * R) if R > 0 else 64      # back to back like the timed region (sustained, not boost, clocks)
     while (extra_steps < 4 * args.steps) if args.deterministic else (time.perf_counter() - t_warm < 0.25):
-        chunk = min(args.steps, 8 * R) if R > 0 else 64      # back to back like the timed region (sustained, not boost, clocks)
         run(chunk)
         extra_steps += chunk
         torch.cuda.synchronize()
@@ -468,21 +519,36 @@ def main():
             torch.cuda.synchronize()
 
     if args.reps <= 0:
-        args.reps = 21 if (R > 0 and args.steps <= R and args.steps * args.batch <= (1 << 18)) else 5
+        args.reps = 1 if not args.full else 21 if (R > 0 and args.steps <= R and args.steps * args.batch <= (1 << 18)) else 5
     from mate_amd.distributed import reduce_job
     startup['startup_s'] = time.perf_counter() - t_main      # everything of this rank's main() before the first pass through the measuring loop
     short_region = (R > 0 and -(-args.steps // R) < args.stats_interval) or (R == 0 and external is None and args.steps < args.stats_interval * 128)
     rep_ms, rep_executed, kernel_times = [], [], []
     for rep in range(max(0, args.rep_warmup) + max(1, args.reps)):
+        if rep == max(0, args.rep_warmup):
+            # the timed steps start from the same state in every run with these arguments (--dump-outputs compares runs output for output):
+            # the batch W steps after a seeded reset (mate_engine_seed rewinds every Philox counter, reset() every batched-reset interval),
+            # whatever number of steps the time-based warm-up ran before
+            if external is not None:
+                external.stepper.close()          # (the step counter back to the host: seed() refuses a device-resident one)
+            eng.seed(0)
+            eng.reset()
+            if external is not None:              # (fresh action buffers too: the stand-in policy flips their sign at every step)
+                external = ExternalActions(torch, eng, args.graph_steps, args.step_reset_interval)
+                external.run(min(args.steps, max(args.graph_steps, 1) + args.steps % max(args.graph_steps, 1)))
+            run(args.warmup)
+            torch.cuda.synchronize()
+        # an untimed pass is one warm-up chunk of the region (--full: the whole region); the timed ones are exactly K steps
+        region = args.steps if (args.full or rep >= max(0, args.rep_warmup)) else min(args.steps, chunk)
         eng.kernel_time(enable=1 if R > 0 else STEP_SAMPLE)   # HIP-event pair around every launch of the dominant kernel (every 17th one-step launch)
         barrier()
         idle0 = eng.idle_steps()
         allocated0 = torch.cuda.memory_allocated()
         t0 = time.perf_counter()
-        run(args.steps, timed=True)
+        run(region, timed=True)
         barrier()
         elapsed = time.perf_counter() - t0
-        executed = args.batch * args.steps - (eng.idle_steps() - idle0)   # env-steps actually simulated by this rank
+        executed = args.batch * region - (eng.idle_steps() - idle0)   # env-steps actually simulated by this rank
         assert torch.cuda.memory_allocated() <= allocated0, 'allocation inside the timed region'
         kernel_times.append(eng.kernel_time(enable=False))
         stats = eng.scalars[:, [1, 3, 6]].mean(dim=0)    # reward, coverage, delivered: logging only
@@ -509,6 +575,12 @@ def main():
         dist.all_gather(per_rank, mine)
     startup_line = {k: [round(float(t[i]), 3) for t in per_rank] for i, k in enumerate(keys)}
 
+    if args.dump_outputs:
+        if R > 0:
+            cam, tgt, sc = (t[-1] for t in last['rollout'])
+        else:
+            cam, tgt, sc = eng.camera_obs, eng.target_obs, eng.scalars
+        dump_outputs(torch, args.dump_outputs, {'camera_obs': cam, 'target_obs': tgt, 'scalars': sc}, rank, idle_rows=R > 0)
     if args.dump:      # every rank: the final state and the last outputs of its shard (compared across shardings by the tests)
         torch.cuda.synchronize()
         torch.save({'rank': rank, 'world': world, 'first_env_index': rank * args.batch, 'state': eng.export_state().cpu(),
@@ -517,7 +589,7 @@ def main():
                    f'{args.dump}.rank{rank}.pt')
     if rank == 0:
         from mate_amd._native import hbm_rates
-        rates = hbm_rates(local_rank) if not args.dump else {}
+        rates = hbm_rates(local_rank) if (args.full and not args.dump) else {}
         total_envs = args.batch * world
         value = executed / elapsed            # == total_envs * steps / elapsed unless environments idled for a batched reset
         b_alg = algorithmic_bytes(eng.num_cameras, eng.num_targets, eng.num_obstacles)
@@ -557,7 +629,8 @@ def main():
                 'fused_note': 'fused launch: state, geometry and actions of the 8d per-step bytes stay in LDS; frac_traffic is the HBM utilisation' if R > 0 else None,
             },
             'timing': {'reps': len(rep_ms), 'rep_ms': [round(v, 4) for v in rep_ms], 'rep_warmup': max(0, args.rep_warmup), 'warmup_extra_steps': extra_steps,
-                       'definition': 'median repetition of the K-step timed region; statistics gathers inside the region, each behind the launch whose episodes it carries'},
+                       'definition': ('median repetition of the K-step timed region' if len(rep_ms) > 1 else 'one pass through the K-step timed region')
+                                     + ', which starts W steps after seed(0) + reset(); statistics gathers inside the region, each behind the launch whose episodes it carries'},
             'episode_stats': {'mean_target_reward': float(stats[0]), 'mean_coverage_rate': float(stats[1]),
                               'mean_delivered': float(stats[2]), 'gathered_in_loop': gathered_stats,
                               'stats_gather': 'none' if gather is None else 'once, behind the last launch of the region' if short_region
@@ -566,7 +639,7 @@ def main():
             'observation_block_candidates_gbs': [[round(x) for x in r] for r in getattr(eng, 'block_rates', [])],
         }
         default_case = world == 1 and args.policy == 'random' and args.workload == WORKLOAD and args.batch == BATCH_PER_GPU
-        side_wanted = not args.dump and world == 1 and args.policy == 'random'
+        side_wanted = args.full and not args.dump and world == 1 and args.policy == 'random'
         if side_wanted and not (args.no_side_measurements and args.no_other_configs and args.no_extras):
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
             import bench_extras as X
@@ -585,7 +658,7 @@ def main():
                                          for b in batches]
             if default_case and not args.no_side_measurements:
                 full['n1_api'] = X.measure_n1_api(torch)
-        if not args.no_cpu_baseline and world == 1 and args.policy == 'random' and args.workload == WORKLOAD:
+        if args.full and not args.no_cpu_baseline and world == 1 and args.policy == 'random' and args.workload == WORKLOAD:
             full['cpu_baseline'] = cpu_baseline(args.cpu_seconds)
         emit(full, args.details)
     if distributed:

@@ -16,6 +16,7 @@ Fixture families:
   kat_perceive.npz                   F3 Camera.perceive on crafted geometry (entities.py:491-511)
   reset_<cfg>_s<seed>.npz            F1 reset() with EVERY random draw on a tape (environment.py:679-834)
   chain_<cfg>_s<seed>.npz            the example trainers' whole wrapper chain for a camera learner (examples/ippo/camera/config.py:19-51)
+  host_reference.npz                 scenario files, read_config() and observation layout (`make_golden.py host`)
 
 Random draws are captured by replacing each RandomState with a recording proxy
 (the reference source is not modified): every in-sector `binomial(1, tau)` draw
@@ -982,8 +983,67 @@ def chain_fixture(name, config, seed, learner_steps, frame_skip=5, levels=5, coe
           f'{os.path.getsize(path) / 1024:.0f} KiB')
 
 
+def _plain(value):
+    """JSON-ready copy of a configuration value (numpy scalars and arrays become Python numbers and lists)."""
+    if isinstance(value, dict):
+        return {str(k): _plain(v) for k, v in value.items()}
+    if isinstance(value, (list, tuple)):
+        return [_plain(v) for v in value]
+    if isinstance(value, np.ndarray):
+        return _plain(value.tolist())
+    if isinstance(value, np.generic):
+        return value.item()
+    return value
+
+
+LAYOUT_SHAPES = ((4, 2, 9), (4, 8, 9), (8, 8, 9), (4, 8, 0), (0, 8, 32), (1, 1, 0))
+READ_CONFIG_FILES = ('MATE-4v2-9.yaml', 'MATE-4v8-9.yaml', 'MATE-8v8-9.yaml', 'MATE-4v8-0.yaml', 'MATE-Navigation.yaml', 'MATE-1v1-0.yaml')
+
+
+def host_fixture(name='host_reference'):
+    """What the host-side tests compare against (tests/test_host_logic.py): the reference's scenario files as parsed
+    mappings, what its read_config() returns for six of them, and its observation layout (mate/constants.py) for six
+    entity counts."""
+    import glob
+    import yaml
+    from mate import constants as R
+    from mate.environment import read_config as ref_read
+    assets = {}
+    for f in sorted(glob.glob(os.path.join(REFERENCE, 'mate', 'assets', '*.yaml'))):
+        with open(f) as fh:
+            assets[os.path.basename(f)] = _plain(yaml.safe_load(fh))
+    configs = {}
+    for cfg_name in READ_CONFIG_FILES:
+        ref = ref_read(cfg_name)
+        entry = {key: _plain(ref[key]) for key in ('max_episode_steps', 'reward_type', 'num_cargoes_per_target', 'high_capacity_target_split',
+                                                    'targets_start_with_cargoes', 'bounty_factor', 'shuffle_entities')}
+        for ent in ('camera', 'target', 'obstacle'):
+            boxes = ref[ent].get('location_random_range', [])
+            entry[ent] = {'location_random_range': [[float(b.low[0]), float(b.high[0]), float(b.low[1]), float(b.high[1])] for b in boxes],
+                          'items': {k: _plain(v) for k, v in ref[ent].items() if k not in ('location', 'location_random_range', 'radius_random_range')}}
+        configs[cfg_name] = entry
+    arrays, slices = {}, {}
+    for nums in LAYOUT_SHAPES:
+        tag = '%d-%d-%d' % nums
+        for team in ('camera', 'target'):
+            space = getattr(R, f'{team}_observation_space_of')(*nums)
+            arrays[f'{tag}/{team}_low'], arrays[f'{tag}/{team}_high'] = np.asarray(space.low), np.asarray(space.high)
+            arrays[f'{tag}/{team}_indices'] = np.asarray(getattr(R, f'{team}_observation_indices_of')(*nums))
+            arrays[f'{tag}/{team}_coordinate_mask'] = np.asarray(getattr(R, f'{team}_coordinate_mask_of')(*nums))
+            slices[f'{tag}/{team}'] = {k: _plain([s.start, s.stop, s.step]) for k, s in getattr(R, f'{team}_observation_slices_of')(*nums).items()}
+    arrays['warehouses'] = np.asarray(R.WAREHOUSES)
+    arrays['warehouse_radius'] = np.asarray(R.WAREHOUSE_RADIUS)
+    arrays['preserved_space_high'] = np.asarray(R.PRESERVED_SPACE.high)
+    np.savez_compressed(os.path.join(HERE, name + '.npz'), assets_json=np.array(json.dumps(assets, sort_keys=True)),
+                        read_config_json=np.array(json.dumps(configs, sort_keys=True)), slices_json=np.array(json.dumps(slices, sort_keys=True)),
+                        **arrays)
+
+
 def main():
     check_binomial_model()
+    if sys.argv[1:] == ['host']:
+        host_fixture()
+        return
     if sys.argv[1:] == ['chain']:
         chain_fixture('chain_4v8-9_s15', 'MATE-4v8-9.yaml', 15, learner_steps=13)
         chain_fixture('chain_target_2v4-0_s16', 'MATE-2v4-0.yaml', 16, learner_steps=24, frame_skip=10, team='target', reduction='none',

@@ -177,3 +177,43 @@ def test_reduce_job_runs_its_collectives_on_one_rank_when_forced():
             dist.all_reduce = real
     finally:
         dist.destroy_process_group()
+
+
+def test_bench_dump_outputs_are_float_arrays_of_the_last_step_within_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one float32 .npy per returned array; the observation rows of environments that idled in the
+    step (scalars[:, 2] == 2) as zeros; beyond the size limit the same seeded sample of environments in every array, every time."""
+    import numpy as np
+    import torch
+    import bench
+    n = 64
+    cam = torch.arange(n * 2 * 3, dtype=torch.float32).view(n, 2, 3) + 1.0
+    tgt = torch.full((n, 4, 5), 7.0, dtype=torch.float32)
+    sc = torch.zeros(n, 8, dtype=torch.float32)
+    sc[:, 0] = torch.arange(n, dtype=torch.float32)            # the environment index, to follow the sample
+    sc[5, 2] = 2.0
+    arrays = {'camera_obs': cam, 'target_obs': tgt, 'scalars': sc}
+    bench.dump_outputs(torch, str(tmp_path / 'all'), arrays, idle_rows=True)
+    got = {name: np.load(tmp_path / 'all' / f'{name}.npy') for name in arrays}
+    assert all(a.dtype == np.float32 for a in got.values()) and got['camera_obs'].shape == (n, 2, 3)
+    assert not got['camera_obs'][5].any() and not got['target_obs'][5].any()
+    keep = np.arange(n) != 5
+    assert np.array_equal(got['camera_obs'][keep], cam.numpy()[keep]) and np.array_equal(got['scalars'], sc.numpy())
+    assert torch.equal(cam[5], torch.arange(30, 36, dtype=torch.float32).view(2, 3) + 1.0)      # (the caller's tensors untouched)
+    per_env = (2 * 3 + 4 * 5 + 8) * 4
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 10 * per_env)
+    for name in ('s1', 's2'):
+        bench.dump_outputs(torch, str(tmp_path / name), arrays, idle_rows=True)
+    part = {name: np.load(tmp_path / 's1' / f'{name}.npy') for name in arrays}
+    assert sum(a.nbytes for a in part.values()) <= 10 * per_env and part['scalars'].shape == (10, 8)
+    rows = part['scalars'][:, 0].astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(part['target_obs'], got['target_obs'][rows])
+    assert np.array_equal(part['camera_obs'], got['camera_obs'][rows])
+    assert all(np.array_equal(part[name], np.load(tmp_path / 's2' / f'{name}.npy')) for name in arrays)
+
+
+def test_bench_plain_run_leaves_the_side_measurements_to_full():
+    """A plain run times the K steps once; --full adds the repetitions, the HBM probe, the side measurements and the CPU baseline."""
+    import bench
+    plain, full = bench.parse_args(['--steps', '20']), bench.parse_args(['--steps', '20', '--full'])
+    assert not plain.full and full.full and plain.reps == full.reps == 0 and plain.dump_outputs == ''
+    assert bench.parse_args(['--dump-outputs', 'out']).dump_outputs == 'out'

@@ -1,41 +1,30 @@
 """CPU-only tests of the host side: scenario data, configuration reader, observation layout,
-C-ABI library symbols, sharding helper.  Comparisons against the upstream reference run only where
-/root/reference exists (the build container); they are skipped elsewhere."""
+C-ABI library symbols, sharding helper.  Comparisons against the upstream reference read what it
+returned from tests/golden/host_reference.npz (recorded by `make_golden.py host`)."""
 import ctypes
-import glob
+import json
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = '/root/reference'
-HAVE_REF = os.path.isdir(os.path.join(REFERENCE, 'mate'))
+HOST_FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'host_reference.npz')
 
 
 @pytest.fixture(scope='module')
-def ref_mate():
-    if not HAVE_REF:
-        pytest.skip('upstream reference not available here')
-    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden', 'gymshim'))
-    sys.path.insert(0, REFERENCE)
-    import gym  # noqa: F401  (the build-owned shim)
-    import mate
-    return mate
+def ref_host():
+    with np.load(HOST_FIXTURE) as fx:
+        return {k: fx[k] for k in fx.files}
 
 
-def test_scenarios_match_reference_assets():
-    if not HAVE_REF:
-        pytest.skip('upstream reference not available here')
-    import yaml
+def test_scenarios_match_reference_assets(ref_host):
     from mate_amd import scenarios
-    files = sorted(glob.glob(os.path.join(REFERENCE, 'mate', 'assets', '*.yaml')))
-    assert len(files) == len(scenarios.SCENARIOS) == 18
-    for f in files:
-        with open(f) as fh:
-            assert yaml.safe_load(fh) == scenarios.scenario(os.path.basename(f)), f
+    assets = json.loads(str(ref_host['assets_json']))
+    assert len(assets) == len(scenarios.SCENARIOS) == 18
+    for name, data in assets.items():
+        assert data == scenarios.scenario(name), name
 
 
 def test_read_config_defaults_and_errors():
@@ -59,40 +48,40 @@ def test_read_config_defaults_and_errors():
         read_config('MATE-4v8-9.yaml', reward_type='shaped')
 
 
-def test_read_config_matches_reference(ref_mate):
+def test_read_config_matches_reference(ref_host):
     from mate_amd.config import read_config
-    from mate.environment import read_config as ref_read
-    for name in ('MATE-4v2-9.yaml', 'MATE-4v8-9.yaml', 'MATE-8v8-9.yaml', 'MATE-4v8-0.yaml', 'MATE-Navigation.yaml', 'MATE-1v1-0.yaml'):
-        mine, ref = read_config(name), ref_read(name)
+    configs = json.loads(str(ref_host['read_config_json']))
+    assert len(configs) == 6
+    for name, ref in configs.items():
+        mine = read_config(name)
         for key in ('max_episode_steps', 'reward_type', 'num_cargoes_per_target', 'high_capacity_target_split',
                     'targets_start_with_cargoes', 'bounty_factor', 'shuffle_entities'):
             assert mine[key] == ref[key], (name, key)
         for ent in ('camera', 'target', 'obstacle'):
-            boxes = ref[ent].get('location_random_range', [])
+            boxes = ref[ent]['location_random_range']
             got = mine[ent].get('location_random_range', [])
             assert len(boxes) == len(got)
             for b, g in zip(boxes, got):
-                assert [b.low[0], b.high[0], b.low[1], b.high[1]] == g
-            for k, v in ref[ent].items():
-                if k not in ('location', 'location_random_range', 'radius_random_range'):
-                    assert mine[ent][k] == v, (name, ent, k)
+                assert b == g
+            for k, v in ref[ent]['items'].items():
+                assert mine[ent][k] == v, (name, ent, k)
 
 
-def test_observation_layout_matches_reference(ref_mate):
-    from mate import constants as R
+def test_observation_layout_matches_reference(ref_host):
     from mate_amd import constants as C
+    slices = json.loads(str(ref_host['slices_json']))
     for nums in ((4, 2, 9), (4, 8, 9), (8, 8, 9), (4, 8, 0), (0, 8, 32), (1, 1, 0)):
-        for mine, ref in ((C.camera_observation_space_of(*nums), R.camera_observation_space_of(*nums)),
-                          (C.target_observation_space_of(*nums), R.target_observation_space_of(*nums))):
-            assert np.array_equal(mine.low, ref.low) and np.array_equal(mine.high, ref.high)
-        assert np.array_equal(C.camera_observation_indices_of(*nums), R.camera_observation_indices_of(*nums))
-        assert np.array_equal(C.target_observation_indices_of(*nums), R.target_observation_indices_of(*nums))
-        assert C.camera_observation_slices_of(*nums) == R.camera_observation_slices_of(*nums)
-        assert C.target_observation_slices_of(*nums) == R.target_observation_slices_of(*nums)
-        assert np.array_equal(C.camera_coordinate_mask_of(*nums), R.camera_coordinate_mask_of(*nums))
-        assert np.array_equal(C.target_coordinate_mask_of(*nums), R.target_coordinate_mask_of(*nums))
-    assert np.array_equal(C.WAREHOUSES, R.WAREHOUSES) and C.WAREHOUSE_RADIUS == R.WAREHOUSE_RADIUS
-    assert np.array_equal(C.PRESERVED_SPACE.high, R.PRESERVED_SPACE.high)
+        tag = '%d-%d-%d' % nums
+        for team, space in (('camera', C.camera_observation_space_of(*nums)), ('target', C.target_observation_space_of(*nums))):
+            assert np.array_equal(space.low, ref_host[f'{tag}/{team}_low']) and np.array_equal(space.high, ref_host[f'{tag}/{team}_high'])
+        assert np.array_equal(C.camera_observation_indices_of(*nums), ref_host[f'{tag}/camera_indices'])
+        assert np.array_equal(C.target_observation_indices_of(*nums), ref_host[f'{tag}/target_indices'])
+        for team, mine in (('camera', C.camera_observation_slices_of(*nums)), ('target', C.target_observation_slices_of(*nums))):
+            assert {k: [s.start, s.stop, s.step] for k, s in mine.items()} == slices[f'{tag}/{team}']
+        assert np.array_equal(C.camera_coordinate_mask_of(*nums), ref_host[f'{tag}/camera_coordinate_mask'])
+        assert np.array_equal(C.target_coordinate_mask_of(*nums), ref_host[f'{tag}/target_coordinate_mask'])
+    assert np.array_equal(C.WAREHOUSES, ref_host['warehouses']) and C.WAREHOUSE_RADIUS == ref_host['warehouse_radius']
+    assert np.array_equal(C.PRESERVED_SPACE.high, ref_host['preserved_space_high'])
 
 
 def test_c_abi_library_exports_every_declared_symbol():
