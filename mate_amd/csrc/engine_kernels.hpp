@@ -6,21 +6,11 @@
 // and then works on with lanes mapped to (entity, entity) pairs; wave ballots produce the
 // visibility masks; the observation rows are gathered from an LDS scratch through a
 // per-scenario descriptor table and stored as contiguous 16-byte-per-lane rows.
+//
+// The phase-clock stamps and ISA marks in the kernels below are the profiling hooks of instrument.hpp: empty in the shipped library.
 #pragma once
 #include "device_math.hpp"
-
-// Measurement hooks (phases compiled out or executed twice, a fake occlusion record, plain row stores): experiment builds only --
-// experiments.hpp says what each does.  The shipped library sees the defaults below: every phase once, the real record,
-// non-temporal row stores.
-#if defined(MATE_ABLATE) || defined(MATE_DOUBLE) || defined(MATE_LUT_FAKE) || defined(MATE_STORE_PLAIN)
-#include "experiments.hpp"
-#else
-#define MATE_PHASE(bit, ...) do { __VA_ARGS__; } while (0)
-#define MATE_PHASE_AGAIN(bit, ...) do { } while (0)
-#define MATE_ZOOM_ITERATIONS 20
-#define MATE_LUT_TABLE_OF(lc) (lc)
-#define MATE_ROW_STORE(v, dst) __builtin_nontemporal_store((v), (dst))
-#endif
+#include "instrument.hpp"
 
 namespace mate {
 
@@ -142,16 +132,6 @@ __host__ __device__ constexpr int sub_wave_of(int Nc, int Nt, int No) {
          : (Nc == 4 && Nt == 8 && No == 0) ? 2
          : 1;
 }
-// (experiment, -DMATE_SUB_EIGHT: eight per wave where the agents fit eight lanes and the agents' (sender, recipient) pairs one round)
-__host__ __device__ constexpr int sub_wave_eight(int Nc, int Nt, int No) {
-#ifdef MATE_SUB_EIGHT
-    return (Nc <= 2 && Nt <= 4 && Nc * Nt <= 8) ? 8 : sub_wave_of(Nc, Nt, No);
-#elif defined(MATE_SUB_TWO)      // (experiment: two per wave where four are the rule)
-    return sub_wave_of(Nc, Nt, No) == 4 ? 2 : sub_wave_of(Nc, Nt, No);
-#else
-    return sub_wave_of(Nc, Nt, No);
-#endif
-}
 
 // Kernel shape policies: AnyShape reads every constant from the device-resident Params on demand;
 // FixedShape<Nc, Nt, No> is compiled for one scenario shape (the host picks it when the counts match).
@@ -190,7 +170,7 @@ struct FixedShape {
     static constexpr int kHeldGC = (kRowsC + kRowsT <= 12) ? kRowsC : 2, kHeldGT = (kRowsC + kRowsT <= 12) ? kRowsT : 6;
     static constexpr int kChunksC = NC * (13 + 9 + 5 * NT + 4 * NO + 7 * NC) / 4, kChunksT = NT * (13 + 14 + 7 * NC + 4 * NO + 5 * NT) / 4;
     // Environments per wave of the fused rollouts (sub_wave_of below): the scenarios whose agents and visibility pairs fill a quarter of a wave
-    static constexpr int kSubWave = sub_wave_eight(NC, NT, NO);
+    static constexpr int kSubWave = sub_wave_of(NC, NT, NO);
     static constexpr int kGreedyBlocks = 4;
     static constexpr bool kGreedyHeld = true;
     // (MATE-8v8-9 sits at 63 of the 64 registers of full occupancy: with the state's stores ahead of the packer it needs 65)
@@ -273,36 +253,6 @@ struct Ptrs {
 };
 constexpr int32_t kDoneTag = 4;
 
-#ifdef MATE_PHASE_CLOCKS
-#define PHASE_STAMP(i) do { if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#define SUB_STAMP(c, i) do { if ((c).lane == 0 && (c).g.phase_clocks) (c).g.phase_clocks[(c).env * kClockStride + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#elif defined(MATE_ISA_MARKS)      // tools/isa_phases.py: phase boundaries of step_kernel as comments in the -S output (no instruction is emitted)
-#define PHASE_STAMP(i) asm volatile("; ==== MATE_STEP_PHASE " #i)
-#define SUB_STAMP(c, i) asm volatile("; ==== MATE_STEP_SUB " #i)
-#else
-#define PHASE_STAMP(i) do { } while (0)
-#define SUB_STAMP(c, i) do { } while (0)
-#endif
-#ifdef MATE_SUB_CLOCKS
-constexpr int kClockStride = 32;      // stamps per environment in Ptrs::phase_clocks
-#else
-constexpr int kClockStride = 16;
-#endif
-// Sub-phase accumulators of the fused rollout (python -m mate_amd.build --variant sub -DMATE_PHASE_CLOCKS -DMATE_SUB_CLOCKS;
-// tools/archive/rollout_subphases.py): cycles summed over a launch's steps into Ctx::sub[0..7] (sub[15]: the previous stamp), events counted
-// in the stamp buffer itself.
-#if defined(MATE_PHASE_CLOCKS) && defined(MATE_SUB_CLOCKS)
-#define SUB_ACC(c, i) do { if ((c).sub) { const long long t_sub = (long long)__builtin_amdgcn_s_memtime(); (c).sub[i] += t_sub - (c).sub[15]; (c).sub[15] = t_sub; } } while (0)
-// (slots 24..31 of the environment's 32: callable under divergent control flow)
-#define SUB_COUNT(c, i, cond) do { const unsigned long long b_sub = __ballot(cond); \
-    if ((c).sub && b_sub != 0ull && (c).lane == __ffsll((long long)b_sub) - 1 && (c).g.phase_clocks) \
-        atomicAdd(reinterpret_cast<unsigned long long *>((c).g.phase_clocks) + (c).env * kClockStride + 24 + (i), 1ull); } while (0)
-#else
-#define SUB_ACC(c, i) do { } while (0)
-#define SUB_COUNT(c, i, cond) do { } while (0)
-#endif
-#define SUB_START(c) do { if ((c).sub) (c).sub[15] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-
 // Phase-keyed issue priority.  The SIMD arbiter serves its oldest wave first, so the four co-resident
 // environment-waves of a SIMD finish one after the other and the last one runs its tail alone, with nobody
 // to hide its LDS/HBM round trips (measured: wave lifetimes 27k..41k cycles by wave slot).  Lowering a
@@ -366,7 +316,7 @@ struct Ctx {
     const Ptrs &g;
     const int flow;               // a compile-time constant of the kernel instantiation (folds once Ctx is scalarised)
     int lane;                     // lane inside the environment's group, [0, L)
-    int shift = 0;                // the group's first hardware lane (0 when L == 64)
+    const int shift;              // the group's first hardware lane (0 when L == 64)
     int64_t env;
     int64_t out;                  // row of this environment in the output buffers (env, or step*N + env in rollouts)
     double *st, *dy, *tmp;
@@ -382,14 +332,19 @@ struct Ctx {
     const double *act_cam = nullptr, *act_tgt = nullptr;   // FLOW_GREEDY: this step's joint actions in LDS ([Nc][2], [Nt][2])
     float *pub = nullptr, *img = nullptr;                  // row-image mode: public-state table, observation rows (Params::off_pub / off_img)
 
-    long long *sub = nullptr;     // (profiling variant: SUB_ACC / SUB_COUNT)
     bool pivots = true;           // sector_resolve: use the pivot angles of an overflow record (kernels at their register limit -- the generic
                                   // fused rollouts, the fused Greedy rollouts -- take the two-trip quarter path instead: same bracket, same limit)
     bool statics_done = false;    // fused rollouts, steps after the first: what never changes inside an episode (static
                                   // mask words and flags, obstacle / capacity slots of the scratch) is in LDS already
 
+    // a whole wave (L == 64: the group's first lane is 0)
     __device__ __forceinline__ Ctx(const Params &p_, const Ptrs &g_, unsigned char *wave_base, int lane_, int64_t env_, int flow_ = FLOW_ANY)
-        : p(p_), g(g_), flow(flow_), lane(lane_), env(env_), out(env_) {
+        : Ctx(p_, g_, wave_base, lane_, env_, flow_, 0) {
+        static_assert(L == 64, "a sub-wave group's context is made with the group's first hardware lane");
+    }
+    // a group of L lanes, `shift_` its first hardware lane
+    __device__ __forceinline__ Ctx(const Params &p_, const Ptrs &g_, unsigned char *wave_base, int lane_, int64_t env_, int flow_, int shift_)
+        : p(p_), g(g_), flow(flow_), lane(lane_), shift(shift_), env(env_), out(env_) {
         st = reinterpret_cast<double *>(wave_base + p.off_st);
         dy = reinterpret_cast<double *>(wave_base + p.off_dy);
         di = reinterpret_cast<int32_t *>(dy + p.DF);
@@ -772,12 +727,8 @@ __device__ __forceinline__ void simulate_targets(Ctx<ObsT, L> &c, const StepDraw
             // `step.norm = step_size` (entities.py:649-650) goes through the polar form in the reference
             // (s*(cos, sin) of atan2(a)); rescaling the vector is the same quantity to within the
             // last-place noise a device atan2/sincos would add anyway, at a tenth of the instructions.
-#ifdef MATE_POLAR_CLAMP
-            set_norm_polar(vx, vy, step_size); n = step_size;
-#else
             const double k = div_nz(step_size, n);
             vx = ax * k; vy = ay * k; n = step_size;
-#endif
         }
         desx = ox + vx; desy = oy + vy;
         if (!carried) { c.snorm(t) = n; if (!ballot_screen && !group_screen) { c.near(t) = 0; c.near(p.Nt + t) = 0; } }
@@ -954,7 +905,7 @@ __host__ __device__ constexpr int pivot_stride(int count) { return (count - 1 + 
 constexpr int kQuarterKnots = 4 * (kDegSlots - 1) + 1;
 // The records' cells: kCellsPerDegree per degree (round 4: two -- a cell holds the knots from the last one at or below its start on,
 // so one in 115 cells of a MATE-4v8-9 table overflows its record instead of one in 24, and the slowest waves of a launch are the
-// ones that overflow at almost every step, tools/archive/rollout_subphases.py).  Cell starts c / kCellsPerDegree - 180 are exact in f64.
+// ones that overflow at almost every step, profiles/r04_rollout_subphases.txt).  Cell starts c / kCellsPerDegree - 180 are exact in f64.
 constexpr int kCellsPerDegree = 2;
 constexpr int kLutCells = 360 * kCellsPerDegree;
 __host__ __device__ __forceinline__ double cell_start(int c) { return (double)c * (1.0 / kCellsPerDegree) - 180.0; }
@@ -1220,7 +1171,7 @@ __device__ __forceinline__ SectorEval sector_eval_held(Ctx<ObsT> &c, const Range
 template <typename ObsT, int L>
 __device__ __forceinline__ void sector_fetch(const Ctx<ObsT, L> &c, const SectorEval &e, double2 (&w)[kDegWords]) {
     if (e.need) {
-        const double2 *rec = c.g.lut_deg + (MATE_LUT_TABLE_OF(e.lc) * kLutCells + degree_of(e.x)) * kDegWords;
+        const double2 *rec = c.g.lut_deg + (e.lc * kLutCells + degree_of(e.x)) * kDegWords;
 #pragma unroll
         for (int i = 0; i < kDegWords; ++i) w[i] = rec[i];
     }
@@ -1231,7 +1182,6 @@ __device__ __forceinline__ bool sector_resolve(const Ctx<ObsT, L> &c, const Sect
     if (!e.need) return e.seen;
     bool overflow;
     double limit = segment_interp(w, e.x, overflow);
-    SUB_COUNT(c, 1, overflow);                           // ... with a lookup in a degree that overflows its record
     if (overflow) {
         int start = (int)w[0].y, count = (int)w[1].x;
         const double2 *knots = c.g.lut_knots + e.lc * c.p.kmax;
@@ -1479,10 +1429,7 @@ __device__ __forceinline__ void update_view(Ctx<ObsT, L> &c, uint32_t tick, uint
             sector_fetch(c, pending, w);
         }
         SUB_STAMP(c, 13);
-        SUB_ACC(c, 0);                                   // sector geometry + fetch issued
-        SUB_COUNT(c, 0, pending.need);                   // steps with an occlusion lookup
         range_tests();
-        SUB_ACC(c, 1);                                   // range tests
         if (both_in_flight) {
             const bool seen = sector_resolve(c, early, w_early);
             if (lane < p.n_sector) set_flag(c, lane, seen);
@@ -1490,7 +1437,6 @@ __device__ __forceinline__ void update_view(Ctx<ObsT, L> &c, uint32_t tick, uint
         }
         if (last >= 0) {
             const bool seen = sector_resolve(c, pending, w);
-            SUB_ACC(c, 2);                               // wait for the record + interpolation (+ overflow trips)
             if (!c.image() && last * L + lane < p.n_sector) set_flag(c, last * L + lane, seen);
             seen_out |= (uint32_t)seen;
             const unsigned long long b = c.ballot(seen);
@@ -1794,9 +1740,9 @@ __device__ __forceinline__ void fill_scratch(Ctx<ObsT, L> &c) {
 
 // The observation rows leave through this store: non-temporal (a write-once stream; -9 % kernel time against plain stores, profiles/HISTORY.md 3.1)
 template <typename V>
-__device__ __forceinline__ void stream_store(V v, V *dst) { MATE_ROW_STORE(v, dst); }
+__device__ __forceinline__ void stream_store(V v, V *dst) { __builtin_nontemporal_store(v, dst); }
 template <typename V>
-__device__ __forceinline__ void stream_store(V v, __attribute__((address_space(1))) V *dst) { MATE_ROW_STORE(v, dst); }
+__device__ __forceinline__ void stream_store(V v, __attribute__((address_space(1))) V *dst) { __builtin_nontemporal_store(v, dst); }
 template <typename ObsT> struct Vec;
 template <> struct Vec<float> { using type = float4; static constexpr int W = 4; };
 template <> struct Vec<double> { using type = double2; static constexpr int W = 2; };
@@ -2364,16 +2310,10 @@ __device__ __forceinline__ void simulate_targets_held(Ctx<ObsT> &c, const StepDr
         const double ox = h.x, oy = h.y;
         double vx = ax, vy = ay;
         double n = norm2(ax, ay);
-#ifdef MATE_POLAR_CLAMP
-        if (n > step_size) { set_norm_polar(vx, vy, step_size); n = step_size; }
-#else
         if (n > step_size) { const double k = div_nz(step_size, n); vx = ax * k; vy = ay * k; n = step_size; }      // entities.py:649-650
-#endif
         const double desx = ox + vx, desy = oy + vy;
         uint64_t todo = near_field(p, carried, t);
         bool n_known = true;
-        SUB_ACC(c, 5);                                   // targets: the step vector
-        SUB_COUNT(c, 2, todo != 0ull);                   // steps with a collision candidate
         while (todo) {
             const int k = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
@@ -2385,11 +2325,9 @@ __device__ __forceinline__ void simulate_targets_held(Ctx<ObsT> &c, const StepDr
             if (n != 0.0 && fma(dy, dy, dx * dx) > reach * reach * (1.0 + 1e-12)) continue;
             obstruct_tangential(ox, oy, vx, vy, n, n_known, cx, cy, cr);
         }
-        SUB_ACC(c, 6);                                   // targets: the candidates' circles
         const double nx = clip_uniform(ox + vx, -kTerrain, kTerrain);   // entities.py:664-666
         const double ny = clip_uniform(oy + vy, -kTerrain, kTerrain);
         const bool colliding = (fabs(nx - desx) > 1e-6) || (fabs(ny - desy) > 1e-6);  // entities.py:668
-        SUB_COUNT(c, 3, colliding);                      // steps in which a target was deflected
         h.x = nx; h.y = ny;
         const int slot = c.tgt_slot(t);
         c.ex[slot] = nx; c.ey[slot] = ny; c.exf[slot] = (float)nx; c.eyf[slot] = (float)ny;
@@ -2528,10 +2466,8 @@ void step_kernel(const Params *__restrict__ pp, const Ptrs g) {
     const Shape shape(pp);
     const Params &p = shape.get();   // scenario constants live in device memory: scalar loads on demand instead of ~80 pinned SGPRs
     extern __shared__ __align__(16) unsigned char smem[];
-#ifdef MATE_PHASE_CLOCKS
-    const long long t_begin = (long long)__builtin_amdgcn_s_memtime();
-    const long long r_begin = (long long)__builtin_amdgcn_s_memrealtime();   // constant 100 MHz: calibrates the s_memtime ticks
-#endif
+    MATE_PROF(const long long t_begin = (long long)__builtin_amdgcn_s_memtime();
+              const long long r_begin = (long long)__builtin_amdgcn_s_memrealtime();)   // constant 100 MHz: calibrates the s_memtime ticks
     // tick and list parity: launch arguments, or the device-resident counter (graph-replayable launches, see Params)
     // (no select: the host keeps dev_tick = dev_group = 0 in the device parameters while it counts itself, and passes
     // parity = 0 and tick = the offset inside the reset interval while the device counts)
@@ -2552,17 +2488,8 @@ void step_kernel(const Params *__restrict__ pp, const Ptrs g) {
     const Ptrs &gk = kernarg_ptrs(g);
     // the four waves of a workgroup never synchronise: each owns one environment and its LDS slice
     Ctx<ObsT> c(p, gk, smem + wave * p.lds_wave_bytes, lane, env, FLOW);
-#ifdef MATE_PHASE_CLOCKS
-    if (lane == 0 && g.phase_clocks) {
-        g.phase_clocks[env * kClockStride + 0] = t_begin;
-    }
-#endif
+    MATE_PROF(if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + 0] = t_begin;)
     PHASE_STAMP(1);
-#ifdef MATE_PHASE_CLOCKS
-#define SKIP(bit) (g.debug_skip & (bit))
-#else
-#define SKIP(bit) false
-#endif
     const StepDraws draws = load_records_with_draws(c, tick, !SKIP(1));
     const int mode = c.mode();
     if (c.freeze_done() && mode != MODE_OBSERVE) {
@@ -2632,9 +2559,7 @@ void step_kernel(const Params *__restrict__ pp, const Ptrs g) {
     PHASE_STAMP(7);
     if (!Shape::kEarlyStateStore && mode != MODE_OBSERVE) store_dynamic(c);
     PHASE_STAMP(8);
-#ifdef MATE_PHASE_CLOCKS
-    if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_begin;
-#endif
+    MATE_PROF(if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_begin;)
 }
 
 // =============================================================================================
@@ -2809,11 +2734,6 @@ void step_split_kernel(const Params *__restrict__ pp, const Ptrs g) {
     phase_prio(g.stagger, 0);
     const Ptrs &gk = kernarg_ptrs(g);
     Ctx<ObsT> c(p, gk, smem + pair * p.lds_wave_bytes, lane, env, FLOW);
-#ifdef MATE_PHASE_CLOCKS      // per-wave stamps: slots 0-7 wave A, 8-15 wave B (tools/archive/split_phases.py)
-#define SPLIT_STAMP(i) do { if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + role * 8 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SPLIT_STAMP(i) do { } while (0)
-#endif
     SPLIT_STAMP(0);
     // ---- records into registers (both waves: all of both records), the step's draws under their latency
     const double *s = c.g.stat + env * p.SW;
@@ -2978,15 +2898,9 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
     const int64_t env = (int64_t)blockIdx.x * (4 * E) + slot;
     if (env >= g.N) return;               // (E > 1: the groups past the end of the batch leave; the others go on under their EXEC mask)
     const Ptrs &gk = kernarg_ptrs(g);     // launch arguments read where they are used (see step_kernel)
-#ifdef MATE_PHASE_CLOCKS      // the launch's prologue, in s_memtime ticks since the wave began: slots 8..11 (tools/archive/rollout_prologue.py), 12 the epilogue
-    const long long t_wave = (long long)__builtin_amdgcn_s_memtime();
-#define PROLOGUE_STAMP(i) do { if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + (i)] = (long long)__builtin_amdgcn_s_memtime() - t_wave; } while (0)
-#else
-#define PROLOGUE_STAMP(i) do { } while (0)
-#endif
+    MATE_PROF(const long long t_wave = (long long)__builtin_amdgcn_s_memtime();)
     {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env);
-        c.shift = shift;
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_ANY, shift);
         load_records(c);
         wave_sync();
         build_entities(c);
@@ -3008,7 +2922,7 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
     constexpr int kGC = E == 1 ? Shape::kHeldGC : (kSubC + kSubT <= 12 ? kSubC : 2), kGT = E == 1 ? Shape::kHeldGT : (kSubC + kSubT <= 12 ? kSubT : 6);
     PackDescriptorsT<kGC, kGT> held;
     if constexpr (!IMAGE) {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW);
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW, shift);
         load_pack_descriptors(c, held);      // (indices clamped: harmless when another pack path runs)
     }
     RangeRoles roles;                        // the lane's range-test pairs and limits, static inside an episode
@@ -3035,20 +2949,15 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
     uint32_t hw_id;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
     const int wave_slot = (int)(hw_id & 15u);
-#ifdef MATE_PHASE_CLOCKS
-    long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // cycles per phase summed over the steps of this launch
-#ifdef MATE_SUB_CLOCKS
-    long long sub[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (SUB_ACC: 0..7 cycles of sub-phases, 15 the previous stamp)
-#endif
-    long long t_prev = (long long)__builtin_amdgcn_s_memtime();
-    const long long t_first = t_prev, r_first = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
+    MATE_PROF(long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // cycles per phase summed over the steps of this launch
+              long long t_prev = (long long)__builtin_amdgcn_s_memtime();
+              const long long t_first = t_prev, r_first = (long long)__builtin_amdgcn_s_memrealtime();)
     bool stepped = false;            // a full step has written the static mask words, flags and scratch slots
     int last_gw = -1;                // fill_scratch: the goal word behind the target's goal / cargo slots
     DrawCarry carry{0u, 0u, 0xffffffffu};
     DrawRole draws_of_lane;
     {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW);
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW, shift);
         draws_of_lane = draw_role(c);
     }
     // The register-resident step (HeldState): the row-image shapes under the random-policy flow
@@ -3085,8 +2994,7 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
         // (... and the held roles: predicates derived from them would otherwise be hoisted out of the loop as SGPR masks, which
         // the kernel has no scalar registers left for -- each came back as two v_readlane per step)
         if constexpr (HOLD_ROLES) pin_roles(roles, p.range_rounds, IMAGE, p.sector_rounds == 1);
-        Ctx<ObsT, L> c(p, gk, smem + slot_r * p.lds_wave_bytes, lane_r, env_r, FLOW);
-        c.shift = shift;
+        Ctx<ObsT, L> c(p, gk, smem + slot_r * p.lds_wave_bytes, lane_r, env_r, FLOW, shift);
         c.out = (int64_t)r * g.N + env_r;
         c.statics_done = stepped;
         c.pivots = Shape::kGreedyHeld;      // (the compiled shapes; the generic kernel has no registers to spare)
@@ -3105,105 +3013,74 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
             if (turn & 2) { if (turn & 1) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); }
             else { if (turn & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
         }
-#ifdef MATE_PHASE_CLOCKS
-#define ROLL_STAMP(i) do { const long long t_now = (long long)__builtin_amdgcn_s_memtime(); acc[i] += t_now - t_prev; t_prev = t_now; } while (0)
-#elif defined(MATE_ISA_MARKS)      // tools/isa_phases.py: phase boundaries as comments in the -S output (no instruction is emitted)
-#define ROLL_STAMP(i) asm volatile("; ==== MATE_PHASE_END " #i)
-#else
-#define ROLL_STAMP(i) do { } while (0)
-#endif
         ROLL_STAMP(7);         // loop overhead: from the end of the previous step to here
         StepDraws draws{0.0, 0.0};
         pin_draw_role(draws_of_lane);
-        MATE_PHASE(1, draws = step_draws(c, tick, &carry, &draws_of_lane));
+        draws = step_draws(c, tick, &carry, &draws_of_lane);
         if constexpr (FLOW == FLOW_ACT_F32) draws = prefetch_action(c);      // (the per-step flows' step(actions) on this kernel: the agents' lanes carry the caller's joint action)
-        MATE_PHASE_AGAIN(1, DrawCarry again = carry; again.block = 0xffffffffu; const StepDraws d2 = step_draws(c, tick, &again); draws.a0 += 0.0 * d2.a0);
         ROLL_STAMP(0);
         if constexpr (HELDSTATE) {
-            MATE_PHASE(2, simulate_cameras_held(c, draws, h));
+            simulate_cameras_held(c, draws, h);
             ROLL_STAMP(1);
-#ifdef MATE_SUB_CLOCKS
-            c.sub = sub;
-#endif
-            SUB_START(c);
-            MATE_PHASE(4, simulate_targets_held(c, draws, near, h));
-            SUB_ACC(c, 7);                               // targets: clip, entity table
+            simulate_targets_held(c, draws, near, h);
             ROLL_STAMP(2);
             uint32_t seen = 0u;
             unsigned long long sector_ballot = 0ull;
-            SUB_START(c);
-            MATE_PHASE(8, update_view<true, true>(c, tick, S_TRANSMIT, true, roles, seen, &near, &sector_ballot));
-            SUB_ACC(c, 3);                               // mask words, static bits
-            MATE_PHASE_AGAIN(8, uint32_t again; update_view<true, true>(c, tick, S_TRANSMIT, true, roles, again, &near, &sector_ballot); seen |= again);
+            update_view<true, true>(c, tick, S_TRANSMIT, true, roles, seen, &near, &sector_ballot);
             bool tracked; int inside;
             view_tail_held(c, sector_ballot, h, tracked, inside);
-            SUB_ACC(c, 4);                               // tracked bits, warehouses
             ROLL_STAMP(3);
-            MATE_PHASE(16, finished = assign_and_score_held(c, tick, g.scalars, h, tracked, inside));
+            finished = assign_and_score_held(c, tick, g.scalars, h, tracked, inside);
             ROLL_STAMP(4);
-            MATE_PHASE(32, image_targets_held(c, h, last_gw); image_blocks(c, roles, seen));
+            image_targets_held(c, h, last_gw); image_blocks(c, roles, seen);
             ROLL_STAMP(5);
             // (measured and dropped: the rows of step r leaving in the MIDDLE of step r + 1, behind its occlusion wait, so that their
             // acknowledgements have a whole step before the next wait instead of 40 % of one -- no faster)
-            MATE_PHASE(64, image_store(c, cam_low, tgt_low); store_masks(c));
+            image_store(c, cam_low, tgt_low); store_masks(c);
             wave_sync();
             stepped = true;
             ROLL_STAMP(6);
             continue;
         }
-        MATE_PHASE(2, simulate_cameras(c, draws, true));
-        MATE_PHASE_AGAIN(2, wave_sync(); simulate_cameras(c, StepDraws{0.0, 0.0}, true));      // (a zero action: the same instructions, the same state)
+        simulate_cameras(c, draws, true);
         ROLL_STAMP(1);
-        MATE_PHASE(4, simulate_targets(c, draws, HOLD_ROLES ? &near : nullptr));
+        simulate_targets(c, draws, HOLD_ROLES ? &near : nullptr);
         ROLL_STAMP(2);
         uint32_t seen = 0u;
-        MATE_PHASE(8, update_view<HOLD_ROLES, true>(c, tick, S_TRANSMIT, true, roles, seen, HOLD_ROLES ? &near : nullptr));
-        MATE_PHASE_AGAIN(8, uint32_t again; update_view<HOLD_ROLES, true>(c, tick, S_TRANSMIT, true, roles, again, HOLD_ROLES ? &near : nullptr); seen |= again);
+        update_view<HOLD_ROLES, true>(c, tick, S_TRANSMIT, true, roles, seen, HOLD_ROLES ? &near : nullptr);
         ROLL_STAMP(3);
-        MATE_PHASE(16, assign_and_score(c, tick, g.scalars));
+        assign_and_score(c, tick, g.scalars);
         ROLL_STAMP(4);
         if constexpr (IMAGE) {
-            MATE_PHASE(32, image_targets(c, last_gw); image_blocks(c, roles, seen));
+            image_targets(c, last_gw); image_blocks(c, roles, seen);
             ROLL_STAMP(5);
-            MATE_PHASE(64, image_store(c, cam_low, tgt_low); store_masks(c));
-            MATE_PHASE_AGAIN(32, int gw2 = last_gw; image_targets(c, gw2); image_blocks(c, roles, seen));
-            MATE_PHASE_AGAIN(64, wave_sync(); image_store(c, cam_low, tgt_low));
+            image_store(c, cam_low, tgt_low); store_masks(c);
         } else {
-        MATE_PHASE(32, fill_scratch(c, last_gw));
-        ROLL_STAMP(5);
-        MATE_PHASE(64, pack_observations<true, Shape::kGreedyHeld>(c, held));
+            fill_scratch(c, last_gw);
+            ROLL_STAMP(5);
+            pack_observations<true, Shape::kGreedyHeld>(c, held);
         }
         wave_sync();
         stepped = true;
         ROLL_STAMP(6);
     }
-#ifdef MATE_PHASE_CLOCKS
-    if (lane == 0 && g.phase_clocks)
-        for (int i = 0; i < 8; ++i) g.phase_clocks[env * kClockStride + i] = acc[i];
-    if (lane == 0 && g.phase_clocks) {      // clock calibration: s_memtime ticks against the constant 100 MHz counter
-        uint32_t hwid, xccid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xccid));
-        g.phase_clocks[env * kClockStride + 13] = ((long long)xccid << 32) | (long long)hwid;
-        g.phase_clocks[env * kClockStride + 14] = (long long)__builtin_amdgcn_s_memtime() - t_first;
-        g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_first;
-    }
-#endif
-#ifdef MATE_PHASE_CLOCKS
-    const long long t_epilogue = (long long)__builtin_amdgcn_s_memtime();
-#ifdef MATE_SUB_CLOCKS
-    if (lane == 0 && g.phase_clocks)
-        for (int i = 0; i < 8; ++i) g.phase_clocks[env * kClockStride + 16 + i] = sub[i];
-#endif
-#endif
+    MATE_PROF(if (lane == 0 && g.phase_clocks)
+                  for (int i = 0; i < 8; ++i) g.phase_clocks[env * kClockStride + i] = acc[i];
+              if (lane == 0 && g.phase_clocks) {      // clock calibration: s_memtime ticks against the constant 100 MHz counter
+                  uint32_t hwid, xccid;
+                  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+                  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xccid));
+                  g.phase_clocks[env * kClockStride + 13] = ((long long)xccid << 32) | (long long)hwid;
+                  g.phase_clocks[env * kClockStride + 14] = (long long)__builtin_amdgcn_s_memtime() - t_first;
+                  g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_first;
+              }
+              const long long t_epilogue = (long long)__builtin_amdgcn_s_memtime();)
     {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env);
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_ANY, shift);
         if constexpr (HELDSTATE) held_store(c, h);
         store_dynamic(c);
     }
-#ifdef MATE_PHASE_CLOCKS
-    if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + 12] = (long long)__builtin_amdgcn_s_memtime() - t_epilogue;
-#endif
+    MATE_PROF(if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + 12] = (long long)__builtin_amdgcn_s_memtime() - t_epilogue;)
 }
 
 }  // namespace mate

@@ -122,9 +122,10 @@ __device__ __forceinline__ double sin_deg_0_90(double deg) {
 // with Kc = area_product / distance^2.  The map is a contraction (|f'| <= 0.65), so last-place differences do not grow: the
 // quotient is taken as Kc * (1/(1+sin))^2 with a Newton-refined reciprocal.  (An Estrin-form polynomial -- half the dependent
 // depth -- was no faster: the solving wave shares its SIMD with three others and is issue-bound, not latency-bound.)
+constexpr int kZoomIterations = 20;
 __device__ __forceinline__ double zoom_fixed_point(double Kc) {
     double b = 180.0;
-    for (int it = 0; it < MATE_ZOOM_ITERATIONS; ++it) {
+    for (int it = 0; it < kZoomIterations; ++it) {
         const double half = b * 0.5;
         const double y = 1.0 + sin_deg_0_90(half < 90.0 ? half : 90.0);
         double r = __builtin_amdgcn_rcp(y);
@@ -157,15 +158,16 @@ __device__ __forceinline__ double zoom_lookup(const PolicyPtrs &q, double K) {
 // `di` the static and dynamic records, `mk` the packed view masks of the previous step.  One wave, one environment.  Joint
 // actions go to q.cam_act / q.tgt_act when `active` and `publish`, and to lds_cam_act / lds_tgt_act when those are given (the
 // fused rollout steps from them and publishes the last executed step's once per launch).
-// `L` lanes per environment (Ctx): camera c is lane c of the environment's group, target t lane L / 2 + t (32 + t in a whole wave);
-// `shift` the group's first hardware lane.  The draws are keyed by the lane a role has in a WHOLE wave (camera c: c, target t: 32 + t,
+// `L` lanes per environment (Ctx): camera c is lane c of the environment's group, target t lane L / 2 + t (32 + t in a whole wave).
+// The draws are keyed by the lane a role has in a WHOLE wave (camera c: c, target t: 32 + t,
 // pair k: k), so every L draws the same numbers.
 template <typename ObsT, int L = 64>
 __device__ __forceinline__ void greedy_policy_body(const Params &p, const PolicyPtrs &q, PolCtx<ObsT> &a, const double *st, const double *dy,
                                                    const int32_t *di, const uint32_t *mk,
                                                    int wave, int lane, int64_t env, bool active, double *lds_cam_act, double *lds_tgt_act,
-                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true, int shift = 0) {
+                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true) {
     constexpr int TB = L / 2;                       // the target agents' first lane
+    const int shift = (int)(threadIdx.x & 63) & ~(L - 1);      // the group's first hardware lane (0 when L == 64)
     auto group_ballot = [&](bool x) -> unsigned long long {
         if constexpr (L == 64) return __ballot(x);
         else return (__ballot(x) >> shift) & ((1ull << L) - 1ull);
@@ -176,13 +178,6 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     // runs its agent.reset at its own first call of an episode (`fresh_c` / `fresh_t`), so what the acting team does never depends
     // on it: every draw is keyed by (environment, tick, stream, lane).  The camera agents are three quarters of this function's
     // chain (11.5 k of a 32 k-cycle learner-versus-greedy step at 4096 x MATE-4v8-9 before; the camera learner's step skips them).
-#ifdef MATE_PHASE_CLOCKS
-#define POL_STAMP(i) do { if (acc) { const long long t_now = (long long)__builtin_amdgcn_s_memtime(); acc[i] += t_now - *t_prev; *t_prev = t_now; } } while (0)
-#elif defined(MATE_ISA_MARKS)
-#define POL_STAMP(i) asm volatile("; ==== MATE_GREEDY_PHASE " #i)
-#else
-#define POL_STAMP(i) do { } while (0)
-#endif
     const int Nc = p.Nc, Nt = p.Nt;
     auto cam_x = [&](int c) { return st[c]; };
     auto cam_y = [&](int c) { return st[Nc + c]; };
@@ -576,15 +571,9 @@ constexpr int sub_held_chunks(bool camera) { return ((camera ? Shape::kChunksC :
 // environment each -- the small scenarios, whose agents and visibility pairs fill a quarter of a wave: every vector instruction then
 // advances E environments.  A workgroup holds 4 E environments (wave w, group s: environment (4 block + w) E + s); the groups of a wave
 // share nothing but the instruction stream.  E > 1 runs the phase functions written for any L (no held roles, no carried collision
-// screen); same results as E = 1, bit for bit (tests/test_gpu_subwave.py).
-#ifndef MATE_SUB_HOLD
-#define MATE_SUB_HOLD 1        // (experiments: 0 = the sub-wave groups fetch their row descriptors at every step)
-#endif
-#ifndef MATE_SUB_BLOCKS
-#define MATE_SUB_BLOCKS 4      // (experiments: workgroups per CU the sub-wave kernels' register budget is set for)
-#endif
+// screen); same results as E = 1, bit for bit (tests/test_gpu_subwave.py).  Their register budget is set for four workgroups per CU.
 template <typename ObsT, typename Shape, int E = 1>
-__global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCKS) void rollout_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const PolicyPtrs q_arg) {
+__global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : 4) void rollout_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const PolicyPtrs q_arg) {
     constexpr int L = 64 / E;
     static_assert(E == 1 || E == 2 || E == 4 || E == 8, "environments per wave");
     const PolicyPtrs &q = kernarg_policy_ptrs(q_arg);
@@ -611,8 +600,7 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
     PolCtx<ObsT> a(p, q, pol_base);
     double *act_cam = a.f + (q.PW + policy_staging_words(p.Nc, p.Nt)), *act_tgt = act_cam + 2 * p.Nc;
     {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY);
-        c.shift = shift;
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY, shift);
         // pipelined restarts (Ptrs::pipelined): an environment tagged for this launch's list parity goes live; one that is not
         // live at entry -- tagged for the other parity, or finished and in the hands of the reset running under this launch --
         // is left alone: no step and, at the end, no store (the reset may be rewriting its records right now).  Whether it is
@@ -662,21 +650,16 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
     constexpr bool IMAGE = E == 1 && Shape::kImage;   // row-image mode (engine_kernels.hpp: image_statics)
     // the row chunks a lane holds descriptors of: all of them where they are few (E = 1: Shape::kHeldGC / GT; a group of L lanes: L per round)
     constexpr int kGC = E == 1 ? Shape::kHeldGC : sub_held_chunks<Shape, L>(true), kGT = E == 1 ? Shape::kHeldGT : sub_held_chunks<Shape, L>(false);
-    constexpr bool HOLD = Shape::kGreedyHeld && (E == 1 || (MATE_SUB_HOLD && kGC + kGT <= 12));
+    constexpr bool HOLD = Shape::kGreedyHeld && (E == 1 || kGC + kGT <= 12);
     PackDescriptorsT<HOLD ? kGC : kPackGC, HOLD ? kGT : kPackGT> held;
     RangeRoles roles;
     {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY);
-        c.shift = shift;
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY, shift);
         if constexpr (IMAGE) { range_roles(c, roles); pin_roles(roles); image_statics(c); }
         else if constexpr (HOLD) { if (packs_rows_f32(c)) load_pack_descriptors(c, held); }
     }
     // the lane's range-test roles held in registers, and with them the collision screen carried from step to step (NearCarry)
-#ifdef MATE_NO_GREEDY_ROLES      // (experiment: what the held lane roles and the carried collision screen are worth)
-    constexpr bool ROLES = false;
-#else
     constexpr bool ROLES = E == 1 && Shape::kGreedyRoles;
-#endif
     NearCarry near{};
     if constexpr (ROLES) {
         Ctx<ObsT> c(p, gk, smem + wave * p.lds_wave_bytes, lane, env, FLOW_GREEDY);
@@ -689,19 +672,9 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
     const int wave_slot = (int)(hw_id & 15u);
     bool stepped = false;                                          // statics written (see Ctx::statics_done)
     DrawCarry carry{0u, 0u, 0xffffffffu};
-#ifdef MATE_PHASE_CLOCKS
-    long long acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 0-6 as in rollout_kernel, 7 loop, 8 agents observe, 11 communicate, 12 choose, 9 the zoom solve, 10 the actions
-    long long t_prev = (long long)__builtin_amdgcn_s_memtime();
-    const long long t_first = t_prev, r_first = (long long)__builtin_amdgcn_s_memrealtime();
-#define GREEDY_STAMP(i) do { const long long t_now = (long long)__builtin_amdgcn_s_memtime(); acc[i] += t_now - t_prev; t_prev = t_now; } while (0)
-#define GREEDY_ACC acc, &t_prev
-#elif defined(MATE_ISA_MARKS)      // tools/isa_phases.py: phase boundaries as comments in the -S output (no instruction is emitted)
-#define GREEDY_STAMP(i) asm volatile("; ==== MATE_GREEDY_PHASE " #i)
-#define GREEDY_ACC nullptr, nullptr
-#else
-#define GREEDY_STAMP(i) do { } while (0)
-#define GREEDY_ACC nullptr, nullptr
-#endif
+    MATE_PROF(long long acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // 0-6 as in rollout_kernel, 7 loop, 8 agents observe, 11 communicate, 12 choose, 9 the zoom solve, 10 the actions
+              long long t_prev = (long long)__builtin_amdgcn_s_memtime();
+              const long long t_first = t_prev, r_first = (long long)__builtin_amdgcn_s_memrealtime();)
 #pragma clang loop unroll(disable)
     for (int r = 0; r < g.rollout_steps; ++r) {
         int lane_r = lane, wave_r = wave, slot_r = slot;          // opaque per iteration, see rollout_kernel
@@ -715,8 +688,7 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
         const int64_t env_w = (int64_t)blockIdx.x * (4 * E) + slot_r;
         const int64_t env_r = env_w < g.N ? env_w : g.N - 1;
         if constexpr (ROLES) pin_roles(roles, p.range_rounds, IMAGE, p.sector_rounds == 1);
-        Ctx<ObsT, L> c(p, gk, smem + slot_r * p.lds_wave_bytes, lane_r, env_r, FLOW_GREEDY);
-        c.shift = shift;
+        Ctx<ObsT, L> c(p, gk, smem + slot_r * p.lds_wave_bytes, lane_r, env_r, FLOW_GREEDY, shift);
         c.out = (int64_t)r * g.N + env_r;
         c.act_cam = act_cam; c.act_tgt = act_tgt;
         c.statics_done = stepped;
@@ -736,7 +708,7 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
             continue;
         }
         // (the joint actions stay in LDS; the last executed step's are published once, at the end of the launch)
-        MATE_PHASE(128, greedy_policy_body<ObsT, L>(p, q, a, c.st, c.dy, c.di, c.mask, wave_r, lane_r, env_r, true, act_cam, act_tgt, GREEDY_ACC, false, shift));
+        greedy_policy_body<ObsT, L>(p, q, a, c.st, c.dy, c.di, c.mask, wave_r, lane_r, env_r, true, act_cam, act_tgt, PROF_ACC(acc, t_prev), false);
         wave_sync();
         GREEDY_STAMP(10);
         if (q.caller_team >= 0) {
@@ -745,43 +717,39 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : MATE_SUB_BLOCK
         }
         const uint32_t tick = p.dev_tick + g.tick + (uint32_t)r;
         StepDraws draws{0.0, 0.0};
-        MATE_PHASE(1, draws = step_draws(c, tick, &carry));       // see-through uniforms only (mode() is MODE_STEP)
+        draws = step_draws(c, tick, &carry);       // see-through uniforms only (mode() is MODE_STEP)
         GREEDY_STAMP(0);
-        MATE_PHASE(2, simulate_cameras(c, draws, true));
+        simulate_cameras(c, draws, true);
         GREEDY_STAMP(1);
-        MATE_PHASE(4, simulate_targets(c, draws, ROLES ? &near : nullptr));
+        simulate_targets(c, draws, ROLES ? &near : nullptr);
         GREEDY_STAMP(2);
         uint32_t seen = 0u;
-        MATE_PHASE(8,
-            if constexpr (ROLES) update_view<true, true>(c, tick, S_TRANSMIT, true, roles, seen, &near);
-            else { RangeRoles none; update_view<false, true>(c, tick, S_TRANSMIT, true, none); });
+        if constexpr (ROLES) update_view<true, true>(c, tick, S_TRANSMIT, true, roles, seen, &near);
+        else { RangeRoles none; update_view<false, true>(c, tick, S_TRANSMIT, true, none); }
         GREEDY_STAMP(3);
-        MATE_PHASE(16, assign_and_score(c, tick, g.scalars));
+        assign_and_score(c, tick, g.scalars);
         GREEDY_STAMP(4);
         if constexpr (IMAGE) {
-            MATE_PHASE(32, image_targets(c, last_gw); image_blocks(c, roles, seen));
+            image_targets(c, last_gw); image_blocks(c, roles, seen);
             GREEDY_STAMP(5);
-            MATE_PHASE(64, image_store(c); store_masks(c));
+            image_store(c); store_masks(c);
         } else {
-        MATE_PHASE(32, fill_scratch(c));
-        GREEDY_STAMP(5);
-        MATE_PHASE(64,
+            fill_scratch(c);
+            GREEDY_STAMP(5);
             if constexpr (HOLD) pack_observations<true, Shape::kGreedyHeld>(c, held);
-            else { PackDescriptors now; pack_observations<false, Shape::kGreedyHeld>(c, now); });
+            else { PackDescriptors now; pack_observations<false, Shape::kGreedyHeld>(c, now); }
         }
         wave_sync();
         stepped = true;
         GREEDY_STAMP(6);
     }
-#ifdef MATE_PHASE_CLOCKS
-    if (in_batch && lane == 0 && g.phase_clocks) {
+    MATE_PROF(if (in_batch && lane == 0 && g.phase_clocks) {
         for (int i = 0; i < 13; ++i) g.phase_clocks[env * kClockStride + i] = acc[i];
         g.phase_clocks[env * kClockStride + 14] = (long long)__builtin_amdgcn_s_memtime() - t_first;
         g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_first;
-    }
-#endif
+    })
     if (in_batch && !untouched) {
-        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY);
+        Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY, shift);
         store_dynamic(c);
         double *dst = q.pol + env * q.PW;
         for (int k = lane; k < q.PW; k += L) dst[k] = a.f[k];
@@ -850,15 +818,10 @@ void step_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const Polic
     if (w_n > 128) pw2 = pol_src[lane + 128 < w_n ? lane + 128 : 0];
     uint32_t mw0 = q.masks[env * p.MW + (lane < p.MW ? lane : 0)];
     asm volatile("" : "+v"(pw0), "+v"(pw1), "+v"(pw2), "+v"(mw0));
-#ifdef MATE_PHASE_CLOCKS      // per-wave stamps (tools/versus_phases.py): 0 begin, 1 records, 2 entity table, 3 agents, 4 kinematics, 5 view, 6 goals, 7 rows, 8 end;
-    const long long r_begin = (long long)__builtin_amdgcn_s_memrealtime();      // 9-13: the agents' sub-phases (observe, zoom, actions, communicate, choose)
-    long long pol_acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pol_prev = 0;
-#define SG_STAMP(i) do { if (lane == 0 && g.phase_clocks) g.phase_clocks[env * kClockStride + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#define SG_ACC pol_acc, &pol_prev
-#else
-#define SG_STAMP(i) do { } while (0)
-#define SG_ACC nullptr, nullptr
-#endif
+    // (per-wave stamps, tools/versus_phases.py: 0 begin, 1 records, 2 entity table, 3 agents, 4 kinematics, 5 view, 6 goals, 7 rows, 8 end;
+    // 9-13 the agents' sub-phases: observe, zoom, actions, communicate, choose)
+    MATE_PROF(const long long r_begin = (long long)__builtin_amdgcn_s_memrealtime();
+              long long pol_acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pol_prev = 0;)
     SG_STAMP(0);
     const StepDraws draws = load_records_with_draws(c, tick, true);
     double *pol_lds = a.f + w_lo;
@@ -885,10 +848,8 @@ void step_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const Polic
     build_entities(c);
     wave_sync();
     SG_STAMP(2);
-#ifdef MATE_PHASE_CLOCKS
-    pol_prev = (long long)__builtin_amdgcn_s_memtime();
-#endif
-    greedy_policy_body<ObsT>(p, q, a, c.st, c.dy, c.di, mk, wave, lane, env, true, act_cam, act_tgt, SG_ACC, false);
+    MATE_PROF(pol_prev = (long long)__builtin_amdgcn_s_memtime();)
+    greedy_policy_body<ObsT>(p, q, a, c.st, c.dy, c.di, mk, wave, lane, env, true, act_cam, act_tgt, PROF_ACC(pol_acc, pol_prev), false);
     wave_sync();
     if (q.caller_team >= 0) {
         load_caller_actions(c, q.caller_team, act_cam, act_tgt);
@@ -925,12 +886,10 @@ void step_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const Polic
     if (early_desc) pack_observations<true>(c, pack_desc); else pack_observations<false>(c, pack_desc);
     SG_STAMP(7);
     SG_STAMP(8);
-#ifdef MATE_PHASE_CLOCKS
-    if (lane == 0 && g.phase_clocks) {
+    MATE_PROF(if (lane == 0 && g.phase_clocks) {
         for (int i = 8; i < 13; ++i) g.phase_clocks[env * kClockStride + 1 + i] = pol_acc[i];
         g.phase_clocks[env * kClockStride + 15] = (long long)__builtin_amdgcn_s_memrealtime() - r_begin;
-    }
-#endif
+    })
 }
 
 }  // namespace mate
