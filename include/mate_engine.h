@@ -85,6 +85,8 @@
 extern "C" {
 #endif
 
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows) is purely additive -- new symbols,
+ * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
 enum {
@@ -351,6 +353,40 @@ int mate_engine_set_action_grids(mate_engine *engine, const double *camera_grid,
  * (layout documented in DESIGN.md; used by state(), the attribute views and the parity tests). */
 int mate_engine_export_state(mate_engine *engine, double *dst_dev, void *stream);
 int mate_engine_import_state(mate_engine *engine, const double *src_dev, void *stream);
+
+/* Global state rows: MultiAgentTracking.state() (environment.py:894-906) of every environment, written on the device -- what the
+ * reference's centralised-critic trainers (MAPPO, MADDPG, QMIX-style mixers, I2C, TarMAC) read after every reset() and step()
+ * (examples/utils/wrappers.py:170-225).  One row of S = mate_layout.state_dim reals per environment, in the reference's order:
+ *   preserved_data (13; element 3, the agent index of an observation row, is 0) | per camera state(private=True) (9) |
+ *   per target state(private=True) (14) | per obstacle state() (3) | freights (Nt) | bounties (Nt) | remaining_cargoes (16)
+ * `out_dtype`: MATE_OBS_F32 or MATE_OBS_F64, whatever the engine's obs_dtype is.  A raw row's camera / target blocks are bit-identical
+ * to elements [13:22] / [13:27] of that agent's plain observation row of the same type.  `scale` / `bias` (host arrays [S], both or
+ * neither): an affine map per element, out = value * scale + bias (no fused multiply-add), e.g. mate.normalize_observation(state,
+ * env.state_space) (mate/agents/utils.py:97-127: minus `low` where bounded below, then 2 x / (high - low) - 1 where bounded on both
+ * sides; what examples/utils/wrappers.py:188, 225 apply) -- the tables are copied.  The output is one densely packed [N][S] array in
+ * caller-owned device memory, 16-byte aligned (rows themselves are in general not: S = 81, 111, 193, 253 ...).
+ *
+ * mate_engine_enable_state_rows attaches `dst_dev` (NULL detaches; MATE_ESTATE before the first reset / import_state).  While
+ * attached, every call that leaves new records behind -- reset / reset_tape (masked ones included), step, step_random, step_greedy,
+ * step_versus_greedy, observe, import_state, rollout_random / rollout_greedy / rollout_versus_greedy -- enqueues ONE more launch, the
+ * last of the call on the call's stream, that rewrites all N rows.  "Last" is behind the auto-reset launch where the call has one:
+ * with auto_reset = 1 a restarted environment's state row and observation rows both show the new episode while the scalar record keeps
+ * describing the finished step; under a batched restart (auto_reset = k > 1) an idling environment's row keeps its terminal state
+ * until the restart launch.  A fused rollout leaves the state after its LAST frame only (what FrameSkip over a centralised-training
+ * wrapper hands the learner).  The launch is capturable -- no host synchronisation, no allocation, the same arguments at every call
+ * -- so an interval captured under mate_engine_device_tick contains it and a replay refreshes the rows.  Enabling itself writes
+ * nothing (follow it with mate_engine_state_rows or any of the calls above) and waits for the handle's launches in flight.
+ * Pipelined restarts (auto_reset = MATE_RESET_PIPELINED / -m of mate_engine_rollout_greedy) rewrite records on the engine's side
+ * stream under the caller's next launches, where a reader of the records would race with them: with rows attached that mode
+ * returns MATE_ESTATE (it is a Greedy-vs-Greedy measurement flow without a learner).
+ *
+ * mate_engine_state_rows: one such launch on `stream` into any buffer, nothing attached (the on-demand form, as
+ * mate_engine_export_state is for the checkpoint).  With a map that differs from the previous on-demand call's it first waits for
+ * the handle's launches in flight and uploads the table; the same map again costs neither.
+ * MATE_EINVAL: NULL engine, an out_dtype other than the two, one of scale / bias without the other, a misaligned buffer (NULL in the
+ * on-demand form); MATE_ESTATE: before the first reset / import_state. */
+int mate_engine_enable_state_rows(mate_engine *engine, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias);
+int mate_engine_state_rows(mate_engine *engine, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias, void *stream);
 
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,

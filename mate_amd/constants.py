@@ -75,6 +75,26 @@ def target_observation_space_of(num_cameras, num_targets, num_obstacles):
     return _row_space(_TGT_PRIV, [(_CAM_PUB, num_cameras), (_OBS, num_obstacles), (_TGT_PUB, num_targets)])
 
 
+@functools.lru_cache(maxsize=None)
+def state_space_of(num_cameras, num_targets, num_obstacles):
+    """Box of MultiAgentTracking.state() (environment.py:450-466 of the reference): preserved data, every entity's private state,
+    then freights | bounties | remaining cargoes, bounded below by 0 only."""
+    tail = 2 * num_targets + NUM_WAREHOUSES ** 2
+    low = np.concatenate([PRESERVED_SPACE.low] + [CAMERA_STATE_SPACE_PRIVATE.low] * num_cameras + [TARGET_STATE_SPACE_PRIVATE.low] * num_targets
+                         + [OBSTACLE_STATE_SPACE.low] * num_obstacles + [np.zeros(tail)])
+    high = np.concatenate([PRESERVED_SPACE.high] + [CAMERA_STATE_SPACE_PRIVATE.high] * num_cameras + [TARGET_STATE_SPACE_PRIVATE.high] * num_targets
+                          + [OBSTACLE_STATE_SPACE.high] * num_obstacles + [np.full(tail, np.inf)])
+    return _box(low, high)
+
+
+def normalized_state_space_of(num_cameras, num_targets, num_obstacles):
+    """The state box after mate.normalize_observation, as RLlibMultiAgentCentralizedTraining derives it (examples/utils/wrappers.py:114-121)."""
+    space = state_space_of(num_cameras, num_targets, num_obstacles)
+    scale, bias = spaces.rescale_affine(space)
+    with np.errstate(invalid='ignore'):
+        return _box(scale * space.low + bias, scale * space.high + bias)
+
+
 def observation_space_of(team, num_cameras, num_targets, num_obstacles):
     fn = (camera_observation_space_of, target_observation_space_of)[team.value]
     return fn(num_cameras, num_targets, num_obstacles)

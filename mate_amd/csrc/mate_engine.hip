@@ -20,6 +20,7 @@
 #include "reset_kernels.hpp"
 #include "policy_kernels.hpp"
 #include "aux_kernels.hpp"
+#include "state_rows.hpp"
 
 using namespace mate;
 
@@ -191,6 +192,13 @@ struct mate_engine {
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
+    // global state rows (mate_engine_enable_state_rows): the caller's [N][S] buffer every record-changing call refreshes, its type,
+    // its (scale, bias) table on the device (null: raw rows); and the table of the last on-demand call (mate_engine_state_rows)
+    void *state_dst = nullptr;
+    bool state_f64 = false;
+    void *d_state_ab = nullptr, *d_state_ab_demand = nullptr;
+    const void *state_ab = nullptr;
+    std::vector<double> state_demand_table;      // scale[S] | bias[S] | type, as uploaded to d_state_ab_demand
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -714,7 +722,97 @@ static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_
     return MATE_OK;
 }
 
-extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
+
+// ---- global state rows (csrc/state_rows.hpp)
+// One state_rows_kernel launch: the rows of all environments into `dst`.  Capturable: no allocation, no synchronisation, the same
+// arguments at every call.  Environments per workgroup: 16, or fewer where the tile (records + rows) would take more than 40 KB of LDS.
+static int launch_state_rows(mate_engine *e, void *dst, bool f64, const void *ab, hipStream_t stream) {
+    const Params &p = e->p;
+    const int S = state_dim_of(p.Nc, p.Nt, p.No), sz = f64 ? 8 : 4;
+    int E = 16;
+    while (E > 4 && state_rows_lds_bytes(p.SW, p.DW, S, E, sz) > 40 * 1024) E /= 2;
+    const size_t lds = (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz);
+    const unsigned blocks = (unsigned)((e->N + E - 1) / E);
+    if (f64) hipLaunchKernelGGL(state_rows_kernel<double>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
+                                reinterpret_cast<double *>(dst), reinterpret_cast<const double *>(ab), (const int32_t)E);
+    else hipLaunchKernelGGL(state_rows_kernel<float>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
+                            reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(ab), (const int32_t)E);
+    HIP_TRY(hipGetLastError());
+    return MATE_OK;
+}
+
+// Behind every entry point that leaves new records: the attached rows, as the call's LAST launch on its stream -- behind the
+// auto-reset launch where the call has one, so that a restarted environment's row and observation rows show the same episode.
+static int refresh_state_rows(mate_engine *e, int rc, void *stream) {
+    if (rc != MATE_OK || !e || !e->state_dst) return rc;
+    return launch_state_rows(e, e->state_dst, e->state_f64, e->state_ab, (hipStream_t)stream);
+}
+
+// (scale, bias) host arrays -> the kernel's interleaved table in the row type
+static int upload_state_table(mate_engine *e, void **table, const double *scale, const double *bias, bool f64) {
+    const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
+    if (!*table) {
+        unsigned char *buf = nullptr;
+        const int rc = dev_alloc(e, &buf, (size_t)2 * S * 8);
+        if (rc != MATE_OK) return rc;
+        *table = buf;
+    }
+    if (f64) {
+        std::vector<double> ab((size_t)2 * S);
+        for (int j = 0; j < S; ++j) { ab[2 * j] = scale[j]; ab[2 * j + 1] = bias[j]; }
+        HIP_TRY(hipMemcpy(*table, ab.data(), ab.size() * 8, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> ab((size_t)2 * S);
+        for (int j = 0; j < S; ++j) { ab[2 * j] = (float)scale[j]; ab[2 * j + 1] = (float)bias[j]; }
+        HIP_TRY(hipMemcpy(*table, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
+    }
+    return MATE_OK;
+}
+
+static int check_state_rows_args(const mate_engine *e, const void *dst, int32_t out_dtype, const double *scale, const double *bias) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (out_dtype != MATE_OBS_F32 && out_dtype != MATE_OBS_F64) return fail(MATE_EINVAL, "state rows: out_dtype must be MATE_OBS_F32 or MATE_OBS_F64");
+    if ((scale != nullptr) != (bias != nullptr)) return fail(MATE_EINVAL, "state rows: scale without bias (or bias without scale)");
+    if (reinterpret_cast<uintptr_t>(dst) & 15u) return fail(MATE_EINVAL, "state rows: the output buffer must be 16-byte aligned");
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_enable_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias) {
+    { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
+    if (!dst_dev) { e->state_dst = nullptr; e->state_ab = nullptr; return MATE_OK; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_state_rows called before reset() (or import_state)");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the table while it is rewritten)
+    const bool f64 = out_dtype == MATE_OBS_F64;
+    if (scale) { const int rc = upload_state_table(e, &e->d_state_ab, scale, bias, f64); if (rc != MATE_OK) return rc; }
+    e->state_dst = dst_dev; e->state_f64 = f64; e->state_ab = scale ? e->d_state_ab : nullptr;
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias, void *stream) {
+    { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
+    if (!dst_dev) return fail(MATE_EINVAL, "state_rows: null output buffer");
+    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "state_rows called before reset() (or import_state)");
+    HIP_TRY(hipSetDevice(e->device));
+    const bool f64 = out_dtype == MATE_OBS_F64;
+    if (scale) {      // the table of the previous call is kept: the same map again costs no upload and no wait
+        const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
+        std::vector<double> table((size_t)2 * S + 1);
+        std::copy(scale, scale + S, table.begin()); std::copy(bias, bias + S, table.begin() + S); table[(size_t)2 * S] = f64 ? 1.0 : 0.0;
+        if (table.size() != e->state_demand_table.size() || std::memcmp(table.data(), e->state_demand_table.data(), table.size() * 8) != 0) {
+            HIP_TRY(wait_for_launches(e));      // (an earlier on-demand launch may still read the old table)
+            e->state_demand_table.clear();
+            const int rc = upload_state_table(e, &e->d_state_ab_demand, scale, bias, f64);
+            if (rc != MATE_OK) return rc;
+            e->state_demand_table = table;
+        }
+    }
+    note_stream(e, (hipStream_t)stream);
+    return launch_state_rows(e, dst_dev, f64, scale ? e->d_state_ab_demand : nullptr, (hipStream_t)stream);
+}
+
+static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(hipSetDevice(e->device));
@@ -733,9 +831,13 @@ extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, co
     return rc;
 }
 
+extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
+    return refresh_state_rows(e, reset_impl(e, env_mask_dev, io, stream), stream);
+}
+
 // reset() with every random draw taken from a tape recorded from the reference (parity runs).
-extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
-                                      int32_t tape_len, int32_t *draws_used_dev, void *stream) {
+static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
+                           int32_t tape_len, int32_t *draws_used_dev, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     if (!tape_dev || tape_len < 1) return fail(MATE_EINVAL, "reset_tape needs a tape");
@@ -748,6 +850,11 @@ extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_de
     int rc = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream);
     if (rc == MATE_OK && !env_mask_dev) e->was_reset = true;
     return rc;
+}
+
+extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
+                                      int32_t tape_len, int32_t *draws_used_dev, void *stream) {
+    return refresh_state_rows(e, reset_tape_impl(e, env_mask_dev, io, tape_dev, tape_len, draws_used_dev, stream), stream);
 }
 
 extern "C" int mate_engine_rebuild_luts(mate_engine *e, void *stream) {
@@ -848,7 +955,7 @@ extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *str
     }
     HIP_TRY(hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
     e->dev_tick = enable != 0;
-    if (!enable) return flush_pending(e, 0, stream);
+    if (!enable) return refresh_state_rows(e, flush_pending(e, 0, stream), stream);      // (an open interval's finished environments restart here)
     return MATE_OK;
 }
 
@@ -943,10 +1050,10 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
 }
 
 extern "C" int mate_engine_step(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
-    return launch_step(e, io, MODE_STEP, auto_reset, (hipStream_t)stream);
+    return refresh_state_rows(e, launch_step(e, io, MODE_STEP, auto_reset, (hipStream_t)stream), stream);
 }
 extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
-    return launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream);
+    return refresh_state_rows(e, launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream), stream);
 }
 // Environments per wave of a fused launch (engine_kernels.hpp, Ctx<ObsT, L>): the shape's E = 4 where the sub-wave kernels exist and
 //   mode 1: always;
@@ -962,7 +1069,7 @@ static int sub_wave_of_launch(const mate_engine *e, bool greedy) {
     return e->sub.sub_wave;
 }
 
-extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
+static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = leave_pipelined(e, (hipStream_t)stream_); if (rc_ != MATE_OK) return rc_; }
     if (!e->was_reset) return fail(MATE_ESTATE, "rollout called before reset() (or import_state)");
@@ -1012,6 +1119,10 @@ extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io
         if (rc != MATE_OK) return rc;
     }
     return MATE_OK;
+}
+
+extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
+    return refresh_state_rows(e, rollout_random_impl(e, io, steps, auto_reset, stream), stream);      // (the state after the launch's last frame)
 }
 
 // LDS per workgroup of the two one-launch forms of a step with the on-device agents
@@ -1141,12 +1252,12 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
 }
 
 extern "C" int mate_engine_step_greedy(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
-    return step_with_policies(e, -1, io, tape, auto_reset, (hipStream_t)stream);
+    return refresh_state_rows(e, step_with_policies(e, -1, io, tape, auto_reset, (hipStream_t)stream), stream);
 }
 
 extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    return step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream);
+    return refresh_state_rows(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), stream);
 }
 
 // `per_step`: ONE fused (agents act, environment steps) launch with the semantics of the per-step flows -- outputs in the
@@ -1174,6 +1285,8 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (auto_reset < -(1 << 16)) return fail(MATE_EINVAL, "auto_reset = %d: pipelined restarts every -auto_reset launches take 1 .. 65536", auto_reset);
     const int pipe_every = pipelined ? -auto_reset : 1;
     if (pipelined && (per_step || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
+    // (the restarts run on the engine's side stream UNDER the next launches: a state-row launch on the caller's stream would read records they rewrite)
+    if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset > 1 ? (auto_reset | (per_step ? kStepFlow : kRolloutFlow)) : auto_reset, stream); if (rc != MATE_OK) return rc; }
@@ -1301,12 +1414,12 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
 }
 
 extern "C" int mate_engine_rollout_greedy(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
-    return rollout_with_policies(e, -1, io, steps, auto_reset, stream);
+    return refresh_state_rows(e, rollout_with_policies(e, -1, io, steps, auto_reset, stream), stream);
 }
 
 extern "C" int mate_engine_rollout_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    return rollout_with_policies(e, team, io, steps, auto_reset, stream);
+    return refresh_state_rows(e, rollout_with_policies(e, team, io, steps, auto_reset, stream), stream);
 }
 
 // Copy the joint actions the last mate_engine_step_greedy produced into caller buffers ([N][Nc][2], [N][Nt][2] f64).
@@ -1322,7 +1435,7 @@ extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions
 }
 
 extern "C" int mate_engine_observe(mate_engine *e, const mate_step_io *io, void *stream) {
-    return launch_step(e, io, MODE_OBSERVE, 0, (hipStream_t)stream);
+    return refresh_state_rows(e, launch_step(e, io, MODE_OBSERVE, 0, (hipStream_t)stream), stream);
 }
 
 extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *stream) {
@@ -1349,7 +1462,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     HIP_TRY(hipMemcpy(&tick, reinterpret_cast<const int32_t *>(e->g.dyn + e->p.DF) + e->p.Nt * TI_STRIDE + EI_TICK, sizeof(tick), hipMemcpyDeviceToHost));
     e->tick = (uint32_t)tick;
     e->was_reset = true;
-    return MATE_OK;
+    return refresh_state_rows(e, MATE_OK, stream);
 }
 
 extern "C" int mate_engine_lut_read(mate_engine *e, int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {

@@ -104,6 +104,8 @@ class Engine:
             # running sums over finished episodes (mate_amd.distributed.EpisodeStats.FIELDS): count, return, length, coverage, delivered
             self.episode_stats = torch.zeros(5, dtype=torch.float64, device=self.device)
         check(self.lib.mate_engine_set_episode_stats(self._h, ctypes.c_void_p(self.episode_stats.data_ptr())))
+        self.state_dim = layout.state_dim
+        self.state = None                 # [N, state_dim] while state rows are attached (enable_state_rows)
 
     def close(self):
         if getattr(self, '_h', None):
@@ -164,17 +166,7 @@ class Engine:
         kernel's packer.  The affine map of the rescale comes from the observation-space bounds
         (mate_amd.constants), exactly as `rescale_observation` derives it."""
         from mate_amd import constants as consts
-
-        def affine(space):
-            low, high = np.asarray(space.low, dtype=np.float64), np.asarray(space.high, dtype=np.float64)
-            scale, bias = np.ones_like(low), np.zeros_like(low)
-            below = np.isfinite(low)
-            both = below & np.isfinite(high) & (high > low)
-            bias[below] = -low[below]                      # rescaled[bounded_below] -= low
-            span = np.where(both, high - low, 1.0)
-            scale[both] = 2.0 / span[both]                 # rescaled[mask] = 2 * rescaled / (high - low) - 1
-            bias[both] = -2.0 * low[both] / span[both] - 1.0
-            return np.ascontiguousarray(scale), np.ascontiguousarray(bias)
+        from mate_amd.spaces import rescale_affine as affine
 
         nums = (self.num_cameras, self.num_targets, self.num_obstacles)
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
@@ -522,6 +514,49 @@ class Engine:
         check(self.lib.mate_engine_export_state(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ global state rows (centralised critics)
+    def _state_affine(self, normalize):
+        """Host (scale, bias) of mate.normalize_observation over the state space, as ctypes pointers (+ the arrays, to keep alive)."""
+        if not normalize:
+            return None, None, ()
+        from mate_amd import constants as consts
+        from mate_amd.spaces import rescale_affine
+        scale, bias = rescale_affine(consts.state_space_of(self.num_cameras, self.num_targets, self.num_obstacles))
+        assert scale.shape == (self.state_dim,)
+        return scale.ctypes.data_as(ctypes.c_void_p), bias.ctypes.data_as(ctypes.c_void_p), (scale, bias)
+
+    def enable_state_rows(self, normalize=False, dtype=None):
+        """Keep `Engine.state` ([N, state_dim], `dtype` = float32 / float64, default obs_dtype) current: the global state of every
+        environment (MultiAgentTracking.state(), environment.py:894-906 of the reference), rewritten on the device as the last launch
+        of every reset / step / observe / import_state / fused rollout (there: the state after the launch's last frame), raw or --
+        `normalize` -- as mate.normalize_observation(state, state_space).  Call after the first reset().  Captured by the graphs a
+        Stepper builds afterwards (a replay refreshes the tensor).  Returns the tensor, already filled."""
+        dtype = dtype or self.obs_dtype
+        assert dtype in (torch.float32, torch.float64)
+        scale, bias, keep = self._state_affine(normalize)
+        with torch.cuda.device(self.device):
+            state = torch.zeros((self.num_envs, self.state_dim), dtype=dtype, device=self.device)
+        check(self.lib.mate_engine_enable_state_rows(self._h, ctypes.c_void_p(state.data_ptr()), int(dtype == torch.float64), scale, bias))
+        self.state, self.state_normalized = state, bool(normalize)
+        return self.state_rows(out=state, normalize=normalize)
+
+    def disable_state_rows(self):
+        """Detach the state rows: the calls go back to their launch sequence without them; `Engine.state` becomes None."""
+        check(self.lib.mate_engine_enable_state_rows(self._h, None, 0, None, None))
+        self.state = None
+
+    def state_rows(self, out=None, normalize=False, dtype=None):
+        """The global state rows of the current records, written by one launch on the current stream into `out` ([N, state_dim],
+        float32 / float64, contiguous; default: a new tensor of `dtype`, default obs_dtype).  Nothing is attached."""
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty((self.num_envs, self.state_dim), dtype=dtype or self.obs_dtype, device=self.device)
+        assert out.dtype in (torch.float32, torch.float64) and out.is_contiguous() and out.device == self.device \
+            and out.shape == (self.num_envs, self.state_dim)
+        scale, bias, keep = self._state_affine(normalize)
+        check(self.lib.mate_engine_state_rows(self._h, ctypes.c_void_p(out.data_ptr()), int(out.dtype == torch.float64), scale, bias, self._stream()))
+        return out
+
     # One copy per step for the N = 1 NumPy API (mate_amd.environment): the output tensors and an export_state buffer become views of
     # ONE device allocation, and fetch_host() brings a step's results over in a single transfer (five blocking copies of a few KB each
     # were a third of that API's 250 us per step).
@@ -781,6 +816,12 @@ class Stepper:
         eng = self.eng
         return eng.camera_obs, eng.target_obs, eng.scalars
 
+    @property
+    def state(self):
+        """The engine's state rows ([N, state_dim]) when it has them attached (Engine.enable_state_rows BEFORE the stepper is built, so
+        that the captured intervals contain the launch): the same tensor, refreshed by every step and every replay; else None."""
+        return self.eng.state
+
     def close(self):
         if self.graph is not None:
             torch.cuda.synchronize(self.eng.device)
@@ -835,6 +876,11 @@ class EngineGroups:
 
     def reset(self):
         return self.each(lambda g, eng: eng.reset())
+
+    def enable_state_rows(self, normalize=False, dtype=None):
+        """Engine.enable_state_rows on every group, each on its own stream; returns the groups' state tensors (group g holds the rows
+        of the global environments [g N / G, (g + 1) N / G))."""
+        return self.each(lambda g, eng: eng.enable_state_rows(normalize=normalize, dtype=dtype))
 
     def synchronize(self):
         for s in self.streams:

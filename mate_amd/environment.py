@@ -266,12 +266,7 @@ class _ScenarioMixin:
         self.camera_state_space_public, self.camera_state_space_private = consts.CAMERA_STATE_SPACE_PUBLIC, consts.CAMERA_STATE_SPACE_PRIVATE
         self.target_state_space_public, self.target_state_space_private = consts.TARGET_STATE_SPACE_PUBLIC, consts.TARGET_STATE_SPACE_PRIVATE
         self.obstacle_state_space = consts.OBSTACLE_STATE_SPACE
-        tail = 2 * Nt + consts.NUM_WAREHOUSES ** 2
-        low = np.concatenate([consts.PRESERVED_SPACE.low] + [consts.CAMERA_STATE_SPACE_PRIVATE.low] * Nc + [consts.TARGET_STATE_SPACE_PRIVATE.low] * Nt
-                             + [consts.OBSTACLE_STATE_SPACE.low] * No + [np.zeros(tail)])
-        high = np.concatenate([consts.PRESERVED_SPACE.high] + [consts.CAMERA_STATE_SPACE_PRIVATE.high] * Nc + [consts.TARGET_STATE_SPACE_PRIVATE.high] * Nt
-                              + [consts.OBSTACLE_STATE_SPACE.high] * No + [np.full(tail, np.inf)])
-        self.state_space = box(low, high)
+        self.state_space = consts.state_space_of(Nc, Nt, No)
         self.freight_scale = float(np.ceil(consts.TERRAIN_WIDTH / self.target_step_size))
         self.bounty_scale = float(np.ceil(self.freight_scale * self.bounty_factor))
         self.reward_scale = self.freight_scale + self.bounty_scale
@@ -638,7 +633,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
-                 discrete_camera_levels=None, discrete_target_levels=None, **kwargs):
+                 discrete_camera_levels=None, discrete_target_levels=None, state_rows=False, **kwargs):
+        assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
         self.engine = Engine(self.config, self.num_envs, device=device, seed=seed, first_env_index=first_env_index, obs_dtype=obs_dtype)
@@ -661,12 +657,28 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if discrete_camera_levels or discrete_target_levels:
             self.engine.set_action_grids(discrete_camera_levels, discrete_target_levels)
 
+        # the global state for centralised critics (RLlibMultiAgentCentralizedTraining, examples/utils/wrappers.py:114-121, 170-225):
+        # True = raw rows, 'normalized' = mate.normalize_observation(state, state_space) fused into the row writer
+        self.state_rows = state_rows
+        if state_rows == 'normalized':
+            self.state_space = consts.normalized_state_space_of(self.num_cameras, self.num_targets, self.num_obstacles)
+
     def seed(self, seed):
         self.engine.seed(int(seed))
         return [int(seed)]
 
+    def state(self):
+        """The global state of every environment, [num_envs, state_dim] on the GPU (state() of the reference, environment.py:894-906,
+        per environment; normalised when built with state_rows='normalized').  With `state_rows` the engine keeps the tensor current
+        behind every reset / step / rollout and this returns it (the same tensor every time); without, one on-demand launch."""
+        if self.state_rows and self.engine.state is not None:
+            return self.engine.state
+        return self.engine.state_rows(normalize=self.state_rows == 'normalized')
+
     def reset(self, env_mask=None):
         out = self.engine.reset(env_mask)
+        if self.state_rows and self.engine.state is None:      # (rows attach to records that exist: from the first reset on)
+            self.engine.enable_state_rows(normalize=self.state_rows == 'normalized')
         for shaper in self.__dict__.get('_target_shapers', {}).values():
             shaper.observe_reset()
         return out

@@ -86,6 +86,20 @@ except Exception:  # gym missing (as in the build image)
             return iter(self.spaces)
 
 
+def rescale_affine(space):
+    """(scale, bias) with `scale * x + bias` == mate.normalize_observation(x, space) (mate/agents/utils.py:97-127 of the reference):
+    subtract `low` where the box is bounded below, then `2 x / (high - low) - 1` where it is bounded on both sides and `high > low`."""
+    low, high = np.asarray(space.low, dtype=np.float64), np.asarray(space.high, dtype=np.float64)
+    scale, bias = np.ones_like(low), np.zeros_like(low)
+    below = np.isfinite(low)
+    both = below & np.isfinite(high) & (high > low)
+    bias[below] = -low[below]                      # rescaled[bounded_below] -= low
+    span = np.where(both, high - low, 1.0)
+    scale[both] = 2.0 / span[both]                 # rescaled[mask] = 2 * rescaled / (high - low) - 1
+    bias[both] = -2.0 * low[both] / span[both] - 1.0
+    return np.ascontiguousarray(scale), np.ascontiguousarray(bias)
+
+
 def _square_grid(levels):
     """`levels` x `levels` grid on [-1, 1]^2, x fastest (np.meshgrid of two linspaces, discrete_action_spaces.py:107-113)."""
     if not (isinstance(levels, (int, np.integer)) and levels >= 3 and levels % 2 == 1):
