@@ -1,7 +1,6 @@
 // mate_engine.hip -- host side of the C ABI declared in include/mate_engine.h.
 // Plain HIP runtime: no torch types cross this boundary (device pointers + sizes only).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -9,6 +8,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -74,33 +74,16 @@ static int fail(int code, const char *fmt, ...) {
 // one.  (The fused Greedy rollout keeps the descriptor packer: with the agents' memory next to a 6 KB row image only three
 // workgroups fit a CU -- 3072 of the 4096 environments of a MATE-4v8-9 batch resident -- and a second pass costs more than
 // the packer's instructions.)
-static void pick_kernels(int Nc, int Nt, int No, bool f64, bool generic, bool no_image, StepFn *step, StepFn *rollout, PolicyFn *policy, PolicyFn *rollout_greedy,
-                         int *specialised, int *image, StepFn *split, PolicyFn *step_greedy, KernelSet *sub) {
-    *specialised = 0; *image = 0;
-    sub->rollout_sub[0] = sub->rollout_sub[1] = sub->rollout_sub[2] = nullptr; sub->rollout_greedy_sub = nullptr; sub->sub_wave = 1;
-    *step_greedy = f64 ? nullptr : (PolicyFn)step_greedy_kernel<float, AnyShape>;
-    for (int i = 0; i < 3; ++i) split[i] = nullptr;      // the two-wave step (step_split_kernel): f32 observations, the folded flows
-    if (!generic) {
-        KernelSet k{};
-        if (pick_kernels_group0(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group1(Nc, Nt, No, f64, no_image, &k) ||
-            pick_kernels_group2(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group3(Nc, Nt, No, f64, no_image, &k) ||
-            pick_kernels_group4(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group5(Nc, Nt, No, f64, no_image, &k)) {
-            for (int i = 0; i < 3; ++i) { step[i] = k.step[i]; split[i] = k.split[i]; }
-            rollout[0] = k.rollout[0]; rollout[1] = k.rollout[1];
-            *policy = k.policy; *rollout_greedy = k.rollout_greedy; *step_greedy = k.step_greedy;
-            *specialised = 1; *image = k.image;
-            sub->rollout_sub[0] = k.rollout_sub[0]; sub->rollout_sub[1] = k.rollout_sub[1]; sub->rollout_sub[2] = k.rollout_sub[2]; sub->rollout_greedy_sub = k.rollout_greedy_sub; sub->sub_wave = k.sub_wave;
-            return;
-        }
+static KernelSet pick_kernels(int Nc, int Nt, int No, bool f64, bool generic, bool no_image) {
+    KernelSet k;
+    if (!generic && (pick_kernels_group0(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group1(Nc, Nt, No, f64, no_image, &k) ||
+                     pick_kernels_group2(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group3(Nc, Nt, No, f64, no_image, &k) ||
+                     pick_kernels_group4(Nc, Nt, No, f64, no_image, &k) || pick_kernels_group5(Nc, Nt, No, f64, no_image, &k))) {
+        k.specialised = 1;
+        return k;
     }
-    step[FLOW_ANY] = f64 ? (StepFn)step_kernel<double, AnyShape> : (StepFn)step_kernel<float, AnyShape>;
-    step[FLOW_RANDOM] = f64 ? step[FLOW_ANY] : (StepFn)step_kernel<float, AnyShape, FLOW_RANDOM>;
-    step[FLOW_ACT_F32] = f64 ? step[FLOW_ANY] : (StepFn)step_kernel<float, AnyShape, FLOW_ACT_F32>;
-    if (!f64) { split[FLOW_RANDOM] = (StepFn)step_split_kernel<float, AnyShape, FLOW_RANDOM>; split[FLOW_ACT_F32] = (StepFn)step_split_kernel<float, AnyShape, FLOW_ACT_F32>; }
-    rollout[0] = f64 ? (StepFn)rollout_kernel<double, AnyShape> : (StepFn)rollout_kernel<float, AnyShape>;
-    rollout[1] = f64 ? rollout[0] : (StepFn)rollout_kernel<float, AnyShape, FLOW_RANDOM>;
-    *policy = f64 ? (PolicyFn)greedy_policy_kernel<double, AnyShape> : (PolicyFn)greedy_policy_kernel<float, AnyShape>;
-    *rollout_greedy = f64 ? (PolicyFn)rollout_greedy_kernel<double, AnyShape> : (PolicyFn)rollout_greedy_kernel<float, AnyShape>;
+    // the generic set: AnyShape has no row-image form and no sub-wave kernels; its step_greedy_kernel exists
+    return f64 ? f64_kernels<AnyShape>() : f32_kernels<AnyShape, void, true>(no_image);
 }
 
 // Environment switches (all read ONCE, in mate_engine_create; documented in include/mate_engine.h).
@@ -116,8 +99,10 @@ struct Switches {
     int step_split = -1;           // MATE_STEP_SPLIT=0 / 1: the one-wave / two-wave form of the per-step kernel in the folded flows (-1: by batch size)
     bool zoom_iterate = false;     // MATE_ZOOM_ITERATE=1: the greedy camera agents iterate the zoom solve (greedy.py:139-145) instead of reading its table
     bool step_sub_wave = true;     // MATE_STEP_SUBWAVE=0: the per-step Greedy flows of the small scenarios stay on step_greedy_kernel where the fused ones run sub-wave groups
-    int sub_wave_mode = 2;         // MATE_SUBWAVE=0 / 1: one environment per wave in the fused rollouts of the small scenarios too / the shape's number in EVERY fused launch (default 2: where it measured faster; mate_engine_set_sub_wave switches at run time)
+    int sub_wave_mode = 2;         // MATE_SUBWAVE=0 / 1: one environment per wave in the fused rollouts of the small scenarios too / the shape's number in EVERY fused launch (default 2: where it measured faster, sub_wave_of_launch).  The one switch that changes after create: mate_engine_set_sub_wave
     bool step_greedy_rollout = false;   // MATE_STEP_GREEDY_ROLLOUT=1: the one-launch form of step_greedy / step_versus_greedy on rollout_greedy_kernel with one step (round 3) instead of step_greedy_kernel
+    bool pipelined_low_priority = true; // MATE_PIPELINED_PRIORITY=0: the side stream of the pipelined restarts at the default priority instead of the device's lowest
+    bool pipelined_serial = false;      // MATE_PIPELINED_SERIAL=1: the pipelined-restart protocol with the resets on the CALLER's stream (the tests' reference)
 };
 static Switches read_switches() {
     Switches w;
@@ -135,6 +120,8 @@ static Switches read_switches() {
     if (const char *v = getenv("MATE_STEP_SUBWAVE")) w.step_sub_wave = atoi(v) != 0;
     if (const char *v = getenv("MATE_SUBWAVE")) w.sub_wave_mode = atoi(v) == 0 ? 0 : 1;
     if (const char *v = getenv("MATE_STEP_SPLIT")) w.step_split = atoi(v) != 0;
+    if (const char *v = getenv("MATE_PIPELINED_PRIORITY")) w.pipelined_low_priority = atoi(v) != 0;
+    w.pipelined_serial = flag("MATE_PIPELINED_SERIAL");
     return w;
 }
 
@@ -162,25 +149,15 @@ struct mate_engine {
     // event behind the last rollout launch, one event per list parity behind the reset that consumed that list
     bool pipelined = false;          // records may carry "restarted" tags (Ptrs::pipelined): leave_pipelined() before anything else runs
     int pipe_every = 1, pipe_count = 0;   // ... one restart launch behind every pipe_every-th rollout launch (auto_reset = -pipe_every); launches into the interval
-    bool pipelined_serial = false;   // MATE_PIPELINED_SERIAL=1: the same protocol with the resets on the CALLER's stream (the tests' reference)
     hipStream_t side = nullptr;
     hipEvent_t ev_launch = nullptr, ev_reset[2] = {nullptr, nullptr};
     bool reset_in_flight[2] = {false, false};
     size_t step_lds = 0, reset_lds = 0;
-    int image = 0;                         // the fused rollouts (random-policy flow, greedy) run their row-image compilation ...
-    size_t image_wave_bytes = 0;           // ... whose per-environment LDS slice is this
-    PolicyFn policy_fn = nullptr, rollout_greedy_fn = nullptr;
-    // E environments per wave (engine_kernels.hpp, Ctx): the fused rollouts of the small scenarios; sub_wave = the E in use (1: one wave per environment)
-    KernelSet sub{};
-    int sub_mode = 2;              // 0: one environment per wave; 1: the shape's E wherever it is compiled; 2 (default): where it measured faster (sub_wave_of_launch)
+    KernelSet k{};                 // kernels chosen at create (pick_kernels): shape-specialised when compiled for these counts
+    size_t image_wave_bytes = 0;   // per-environment LDS slice of the row-image rollout (k.image), else of the plain one
     int64_t cus = 256;             // compute units of the device
-    PolicyFn step_greedy_fn = nullptr;     // step_greedy_kernel: the per-step flows with the on-device agents as ONE launch (f32 observations), or null
-    StepFn split_fn[3] = {nullptr, nullptr, nullptr};      // step_split_kernel per flow (two waves per environment), or null
-    int split_on = 0;                                      // ... and whether launch_step uses it (MATE_STEP_SPLIT, or the batch is one resident generation)
-    StepFn step_fn[3] = {nullptr, nullptr, nullptr}, rollout_fn[2] = {nullptr, nullptr};   // kernels chosen at create: shape-specialised when compiled for these counts; step_fn[flow]
+    int split_on = 0;              // launch_step uses k.split (MATE_STEP_SPLIT, or the batch is one resident generation)
     int last_flow = 0;
-    bool flow_generic = false;                        // MATE_FLOW_GENERIC=1: every launch runs the FLOW_ANY kernel (tests)
-    int specialised = 0;
     std::vector<void *> allocs;
     // on-device rule-based policies (mate_engine_step_greedy)
     bool policy_ready = false;
@@ -221,6 +198,51 @@ static hipError_t wait_for_launches(mate_engine *e) {
     // everything launched so far has drained: the bookkeeping starts afresh (the next launch, on whatever stream, is the only one in flight)
     if (err == hipSuccess) { e->multi_stream = false; e->launched = false; }
     return err;
+}
+
+// The opening of an entry point that launches on `stream`: the pipelined-restart mode is left and, for the calls that need an
+// episode in progress (`who`: their name in the message), a reset must have run.  Of a host-side accessor: the launches drain.
+static int enter(mate_engine *e, hipStream_t stream, const char *who = nullptr) {
+    { const int rc = leave_pipelined(e, stream); if (rc != MATE_OK) return rc; }
+    if (who && !e->was_reset) return fail(MATE_ESTATE, "%s called before reset() (or import_state)", who);
+    HIP_TRY(hipSetDevice(e->device));
+    return MATE_OK;
+}
+static int enter_host(mate_engine *e) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));
+    return MATE_OK;
+}
+
+// body(float{}) or body(double{}): the statements that differ by the observation (or row) type only
+template <class Body>
+static auto with_obs_type(bool f64, Body &&body) { return f64 ? body(double{}) : body(float{}); }
+
+// Opt a kernel in to `bytes` of dynamic LDS (null: a kernel this engine does not have).
+static hipError_t set_dynamic_lds(const void *fn, size_t bytes) {
+    return fn ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+}
+template <class... P>
+static hipError_t set_dynamic_lds(void (*fn)(P...), size_t bytes) { return set_dynamic_lds(reinterpret_cast<const void *>(fn), bytes); }
+
+// Kernel timing: every e->timing-th eligible launch takes a pair of events from the pool, attached to the dispatch itself
+// (the extended launch): the elapsed time is the kernel's own begin->end, without the marker-packet latency separate
+// hipEventRecord calls would add.  An untimed launch is a plain one: stream capture records it.
+struct Timed { hipEvent_t a = nullptr, b = nullptr; };
+static int take_timing_events(mate_engine *e, bool eligible, Timed *out) {
+    if (!eligible || e->timing <= 0 || (e->timing_tick++ % e->timing) != 0) return MATE_OK;
+    if (e->events_used == e->events.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
+        e->events.emplace_back(a, b);
+    }
+    out->a = e->events[e->events_used].first; out->b = e->events[e->events_used].second; ++e->events_used;
+    return MATE_OK;
+}
+template <class... P>
+static void launch(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Timed t, std::common_type_t<P>... args) {
+    if (t.a) hipExtLaunchKernelGGL(fn, grid, block, lds, stream, t.a, t.b, 0, args...);
+    else hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
 }
 
 extern "C" const char *mate_engine_last_error(void) { return g_error.c_str(); }
@@ -288,8 +310,7 @@ static void build_descriptors(const Params &p, std::vector<uint32_t> &desc, int 
     const int sz = p.obs_f64 ? 8 : 4;
     auto D = [&](int src, int flag) { return (uint32_t)(p.off_scratch + src * sz) | ((uint32_t)(p.off_flags + flag * sz) << 16); };   // flag slots: Params::fs_*
     const int ALWAYS = p.fs_always;
-    const int SC_ZERO = 0, SC_ONE = 1, SC_CONST = 2, SC_IDX = 14;
-    (void)SC_ZERO;
+    const int SC_ONE = 1, SC_CONST = 2, SC_IDX = 14;      // (slot 0 holds zero)
     desc.assign((size_t)p.tgt_table_off + round_up(p.tgt_elems, 4), D(0, ALWAYS));
     auto preserved = [&](uint32_t *row, int index) {   // environment.py:499-501, 941
         row[0] = D(SC_CONST + 0, ALWAYS); row[1] = D(SC_CONST + 1, ALWAYS); row[2] = D(SC_CONST + 2, ALWAYS);
@@ -396,10 +417,8 @@ extern "C" int mate_engine_create(const mate_config *cfg, int64_t num_envs, int3
     p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32); p.first_env = (uint32_t)first_env_index;
     e->step_lds = 4 * (size_t)p.lds_wave_bytes;
     e->sw = read_switches();
-    pick_kernels(Nc, Nt, No, p.obs_f64 != 0, e->sw.generic, e->sw.no_image, e->step_fn, e->rollout_fn, &e->policy_fn, &e->rollout_greedy_fn, &e->specialised, &e->image, e->split_fn, &e->step_greedy_fn, &e->sub);
-    e->sub_mode = e->sw.sub_wave_mode;
-    { Params pi = p; fill_shape(pi, Nc, Nt, No, false, true); e->image_wave_bytes = e->image ? (size_t)pi.lds_wave_bytes : (size_t)p.lds_wave_bytes; }
-    e->flow_generic = e->sw.flow_generic;
+    e->k = pick_kernels(Nc, Nt, No, p.obs_f64 != 0, e->sw.generic, e->sw.no_image);
+    { Params pi = p; fill_shape(pi, Nc, Nt, No, false, true); e->image_wave_bytes = e->k.image ? (size_t)pi.lds_wave_bytes : (size_t)p.lds_wave_bytes; }
     if (p.lds_wave_bytes > 0xffff) { delete e; return fail(MATE_EINVAL, "scenario too large for 16-bit LDS descriptors"); }
     ResetLds &rl = e->rl;
     layout_reset_lds(p, rl, std::max(512, next_pow2(Nc > 0 ? 360 + No * 185 + 1 : 1)));
@@ -457,19 +476,16 @@ extern "C" int mate_engine_create(const mate_config *cfg, int64_t num_envs, int3
         if ((rc = dev_alloc(e, &d_desc, (size_t)p.desc_table_bytes / 4))) break;
         if (hipMemcpy(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(MATE_EHIP, "descriptor upload failed"); break; }
         g.desc = d_desc;
-        if (p.obs_f64) {
-            std::vector<double> s; build_scratch_init(p, *cfg, s);
-            double *d = nullptr;
-            if ((rc = dev_alloc(e, &d, s.size()))) break;
-            if (hipMemcpy(d, s.data(), s.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(MATE_EHIP, "scratch upload failed"); break; }
+        rc = with_obs_type(p.obs_f64 != 0, [&](auto tag) -> int {
+            using T = decltype(tag);
+            std::vector<T> s; build_scratch_init(p, *cfg, s);
+            T *d = nullptr;
+            if (const int rc_ = dev_alloc(e, &d, s.size())) return rc_;
+            if (hipMemcpy(d, s.data(), s.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail(MATE_EHIP, "scratch upload failed");
             g.scratch_init = d;
-        } else {
-            std::vector<float> s; build_scratch_init(p, *cfg, s);
-            float *d = nullptr;
-            if ((rc = dev_alloc(e, &d, s.size()))) break;
-            if (hipMemcpy(d, s.data(), s.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(MATE_EHIP, "scratch upload failed"); break; }
-            g.scratch_init = d;
-        }
+            return MATE_OK;
+        });
+        if (rc) break;
         std::vector<double> ranges((size_t)(Nc + No + Nt) * 4, 0.0);
         if (Nc) std::memcpy(ranges.data(), cfg->camera_location_ranges, sizeof(double) * 4 * Nc);
         if (No) std::memcpy(ranges.data() + 4 * Nc, cfg->obstacle_location_ranges, sizeof(double) * 4 * No);
@@ -484,22 +500,13 @@ extern "C" int mate_engine_create(const mate_config *cfg, int64_t num_envs, int3
     if (rc == MATE_OK && hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MATE_EHIP, "params upload failed");
     if (rc == MATE_OK) {
         // opt in to large dynamic LDS
+        const KernelSet &k = e->k;
         hipError_t err = hipSuccess;
-        for (int f = 0; f < 3 && err == hipSuccess; ++f)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->step_fn[f]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->step_lds);
-        for (int f = 0; f < 2 && err == hipSuccess; ++f)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rollout_fn[f]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(f == 1 && e->image ? 4 * e->image_wave_bytes : e->step_lds));
-        for (int f = 0; f < 3 && err == hipSuccess && e->sub.rollout_sub[f]; ++f)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->sub.rollout_sub[f]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(e->sub.sub_wave * e->step_lds));
-        if (err != hipSuccess) {
-        } else if (p.obs_f64) {
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&reset_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->reset_lds);
-
-        } else {
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(&reset_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->reset_lds);
-
-        }
+        auto opt_in = [&](auto fn, size_t bytes) { if (err == hipSuccess) err = set_dynamic_lds(fn, bytes); };
+        for (int f = 0; f < 3; ++f) opt_in(k.step[f], e->step_lds);
+        for (int f = 0; f < 2; ++f) opt_in(k.rollout[f], f == 1 && k.image ? 4 * e->image_wave_bytes : e->step_lds);
+        for (int f = 0; f < 3; ++f) opt_in(k.rollout_sub[f], k.sub_wave * e->step_lds);
+        with_obs_type(p.obs_f64 != 0, [&](auto tag) { opt_in(&reset_kernel<decltype(tag)>, e->reset_lds); });
         if (err != hipSuccess) rc = fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
     }
     if (rc != MATE_OK) { mate_engine_destroy(e); return rc; }
@@ -520,6 +527,17 @@ extern "C" int mate_engine_destroy(mate_engine *e) {
     for (void *ptr : e->allocs) (void)hipFree(ptr);
     delete e;
     return MATE_OK;
+}
+
+// (a[i], b[i]) host arrays -> an interleaved (scale, bias) table in the kernels' row type, at `dst` on the device
+static int upload_interleaved(void *dst, const double *a, const double *b, size_t n, bool f64) {
+    return with_obs_type(f64, [&](auto tag) -> int {
+        using T = decltype(tag);
+        std::vector<T> ab(2 * n);
+        for (size_t i = 0; i < n; ++i) { ab[2 * i] = (T)a[i]; ab[2 * i + 1] = (T)b[i]; }
+        HIP_TRY(hipMemcpy(dst, ab.data(), ab.size() * sizeof(T), hipMemcpyHostToDevice));
+        return MATE_OK;
+    });
 }
 
 static int apply_obs_tables(mate_engine *e) {
@@ -571,15 +589,7 @@ static int apply_obs_tables(mate_engine *e) {
         if ((rc = dev_alloc(e, &buf, 2 * n * (size_t)sz))) return rc;
         e->d_xab = buf;
     }
-    if (p.obs_f64) {
-        std::vector<double> ab(2 * n);
-        for (size_t i = 0; i < n; ++i) { ab[2 * i] = a[i]; ab[2 * i + 1] = b[i]; }
-        HIP_TRY(hipMemcpy(e->d_xab, ab.data(), ab.size() * 8, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> ab(2 * n);
-        for (size_t i = 0; i < n; ++i) { ab[2 * i] = (float)a[i]; ab[2 * i + 1] = (float)b[i]; }
-        HIP_TRY(hipMemcpy(e->d_xab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_interleaved(e->d_xab, a.data(), b.data(), n, p.obs_f64 != 0))) return rc;
     e->g.xab = e->d_xab;
     e->g.xdesc = e->d_xdesc;
     return MATE_OK;
@@ -591,8 +601,7 @@ extern "C" int mate_engine_set_obs_transform(mate_engine *e, int32_t relative, c
                                              const double *tgt_scale, const double *tgt_bias) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if ((cam_scale && !cam_bias) || (tgt_scale && !tgt_bias)) return fail(MATE_EINVAL, "scale without bias");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     const Params &p = e->p;
     e->xf_relative = relative != 0;
     e->xf_cam = cam_scale != nullptr; e->xf_tgt = tgt_scale != nullptr;
@@ -606,8 +615,7 @@ extern "C" int mate_engine_set_obs_transform(mate_engine *e, int32_t relative, c
 extern "C" int mate_engine_set_obs_mode(mate_engine *e, int32_t camera_mode, int32_t target_mode) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (camera_mode < 0 || camera_mode > 2 || target_mode < 0 || target_mode > 2) return fail(MATE_EINVAL, "observation mode must be 0 (plain), 1 (enhanced) or 2 (shared field of view)");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     e->cam_mode = camera_mode; e->tgt_mode = target_mode;
     return apply_obs_tables(e);
 }
@@ -615,8 +623,7 @@ extern "C" int mate_engine_set_obs_mode(mate_engine *e, int32_t camera_mode, int
 extern "C" int mate_engine_set_action_grids(mate_engine *e, const double *camera_grid, int32_t n_cam, const double *target_grid, int32_t n_tgt) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (n_cam < 0 || n_tgt < 0 || (n_cam > 0 && !camera_grid) || (n_tgt > 0 && !target_grid)) return fail(MATE_EINVAL, "invalid action grid");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     auto upload = [&](const double *src, int n, const double2 **dst, int32_t *count) -> int {
         *dst = nullptr; *count = 0;
         if (n == 0) return MATE_OK;
@@ -641,7 +648,7 @@ extern "C" int mate_engine_get_layout(const mate_engine *e, mate_layout *out) {
     out->bit_camera_target = 0; out->bit_camera_camera = p.bit_cc; out->bit_target_row = p.bit_range;
     out->bit_camera_obstacle = p.bit_camobs;
     out->export_width = p.export_width; out->lut_capacity = p.kmax; out->scalars_per_env = 8;
-    out->specialised = e->specialised;
+    out->specialised = e->k.specialised;
     return MATE_OK;
 }
 
@@ -649,8 +656,7 @@ extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (e->dev_tick) return fail(MATE_ESTATE, "seed() while the step counter is device-resident (mate_engine_device_tick)");
     e->p.seed_lo = (uint32_t)seed; e->p.seed_hi = (uint32_t)(seed >> 32);
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
     // the reference re-creates its generators (environment.py:1219-1225): the same seed gives the same episodes again,
     // whatever ran before.  Here: the key, and every counter that enters a Philox counter word (episode, tick) rewound.
@@ -671,6 +677,15 @@ static void apply_io(Ptrs &g, const mate_step_io *io) {
     g.cam_obs = io->camera_obs_dev; g.tgt_obs = io->target_obs_dev; g.scalars = io->scalars_dev; g.masks = io->masks_dev;
 }
 
+// The record pointers of a restart launch: the buffers of `io` receive the restarted environments' first observations and masks
+// (null: state only), never `scalars` -- the finished step's reward / done stay -- and nothing is read from a tape.
+static Ptrs restart_ptrs(const mate_engine *e, const mate_step_io *io = nullptr) {
+    Ptrs r = e->g;
+    apply_io(r, io);
+    r.scalars = nullptr; r.tape_ct = nullptr; r.tape_goal = nullptr;
+    return r;
+}
+
 static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_t stream, bool split_done = false) {
     g.mode = MODE_OBSERVE; g.reset_kind = kind; g.parity = e->parity; g.freeze_done = 0;
     note_stream(e, stream);
@@ -680,8 +695,9 @@ static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_
         if (e->rl.sort_in_hbm && (ph & PH_LUT)) items = std::min<int64_t>(items, kSortGridCap);     // grid-stride loop; one scratch slice per workgroup
         if (grid > 0) items = grid;
         const ResetLds rl = layout ? *layout : e->rl;
-        if (p.obs_f64) hipLaunchKernelGGL(reset_kernel<double>, dim3((unsigned)items), dim3(threads), lds, stream, (const Params *)e->d_params, (const Ptrs)g, (const ResetLds)rl, (const int32_t)ph);
-        else hipLaunchKernelGGL(reset_kernel<float>, dim3((unsigned)items), dim3(threads), lds, stream, (const Params *)e->d_params, (const Ptrs)g, (const ResetLds)rl, (const int32_t)ph);
+        with_obs_type(p.obs_f64 != 0, [&](auto tag) {
+            hipLaunchKernelGGL(reset_kernel<decltype(tag)>, dim3((unsigned)items), dim3(threads), lds, stream, (const Params *)e->d_params, (const Ptrs)g, (const ResetLds)rl, (const int32_t)ph);
+        });
     };
     // The immediate auto-reset (RESET_DONE) is launched after EVERY step and is idle almost always: it stays one
     // launch.  Whole-batch, masked and batched (flagged) resets are split -- and so are the list-driven resets of the
@@ -733,10 +749,11 @@ static int launch_state_rows(mate_engine *e, void *dst, bool f64, const void *ab
     while (E > 4 && state_rows_lds_bytes(p.SW, p.DW, S, E, sz) > 40 * 1024) E /= 2;
     const size_t lds = (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz);
     const unsigned blocks = (unsigned)((e->N + E - 1) / E);
-    if (f64) hipLaunchKernelGGL(state_rows_kernel<double>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
-                                reinterpret_cast<double *>(dst), reinterpret_cast<const double *>(ab), (const int32_t)E);
-    else hipLaunchKernelGGL(state_rows_kernel<float>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
-                            reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(ab), (const int32_t)E);
+    with_obs_type(f64, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(state_rows_kernel<T>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
+                           reinterpret_cast<T *>(dst), reinterpret_cast<const T *>(ab), (const int32_t)E);
+    });
     HIP_TRY(hipGetLastError());
     return MATE_OK;
 }
@@ -757,16 +774,7 @@ static int upload_state_table(mate_engine *e, void **table, const double *scale,
         if (rc != MATE_OK) return rc;
         *table = buf;
     }
-    if (f64) {
-        std::vector<double> ab((size_t)2 * S);
-        for (int j = 0; j < S; ++j) { ab[2 * j] = scale[j]; ab[2 * j + 1] = bias[j]; }
-        HIP_TRY(hipMemcpy(*table, ab.data(), ab.size() * 8, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> ab((size_t)2 * S);
-        for (int j = 0; j < S; ++j) { ab[2 * j] = (float)scale[j]; ab[2 * j + 1] = (float)bias[j]; }
-        HIP_TRY(hipMemcpy(*table, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
-    }
-    return MATE_OK;
+    return upload_interleaved(*table, scale, bias, (size_t)S, f64);
 }
 
 static int check_state_rows_args(const mate_engine *e, const void *dst, int32_t out_dtype, const double *scale, const double *bias) {
@@ -792,9 +800,7 @@ extern "C" int mate_engine_enable_state_rows(mate_engine *e, void *dst_dev, int3
 extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias, void *stream) {
     { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
     if (!dst_dev) return fail(MATE_EINVAL, "state_rows: null output buffer");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    if (!e->was_reset) return fail(MATE_ESTATE, "state_rows called before reset() (or import_state)");
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, (hipStream_t)stream, "state_rows"); if (rc_ != MATE_OK) return rc_; }
     const bool f64 = out_dtype == MATE_OBS_F64;
     if (scale) {      // the table of the previous call is kept: the same map again costs no upload and no wait
         const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
@@ -814,8 +820,7 @@ extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out
 
 static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     Ptrs g = e->g;
     apply_io(g, io);
     g.tape_ct = nullptr; g.tape_goal = nullptr;
@@ -839,9 +844,8 @@ extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, co
 static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
                            int32_t tape_len, int32_t *draws_used_dev, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     if (!tape_dev || tape_len < 1) return fail(MATE_EINVAL, "reset_tape needs a tape");
-    HIP_TRY(hipSetDevice(e->device));
     Ptrs g = e->g;
     apply_io(g, io);
     g.tape_goal = nullptr;                  // io->tape_camera_target_dev: see-through uniforms of the first view
@@ -859,11 +863,8 @@ extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_de
 
 extern "C" int mate_engine_rebuild_luts(mate_engine *e, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    HIP_TRY(hipSetDevice(e->device));
-    Ptrs g = e->g;
-    apply_io(g, nullptr);
-    return launch_reset(e, g, RESET_ALL, PH_LUT, (hipStream_t)stream);
+    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    return launch_reset(e, restart_ptrs(e), RESET_ALL, PH_LUT, (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_set_episode_stats(mate_engine *e, double *stats_dev) {
@@ -887,18 +888,14 @@ extern "C" int mate_engine_snapshot_episode_stats(mate_engine *e, double *dst_de
     return MATE_OK;
 }
 
-static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_t stream, bool split_done);
-
 // A batched-reset interval (auto_reset = k > 1) is in progress and the caller changes the mode: restart what has finished
 // so far now, by flag, and forget the lists.
-// `key`: auto_reset of the call that is about to run, tagged with its flow (kStepFlow / kRolloutFlow) when it batches.
+// `auto_reset`, `flow_tag`: of the call that is about to run -- an interval belongs to one k and one flow (kStepFlow / kRolloutFlow).
 constexpr int kStepFlow = 0x10000, kRolloutFlow = 0x20000;
-static int flush_pending(mate_engine *e, int key, hipStream_t stream) {
-    if (e->steps_since_reset == 0 || key == e->pending_interval) return MATE_OK;
+static int flush_pending(mate_engine *e, int auto_reset, int flow_tag, hipStream_t stream) {
+    if (e->steps_since_reset == 0 || (auto_reset > 1 ? (auto_reset | flow_tag) : auto_reset) == e->pending_interval) return MATE_OK;
     if (e->dev_tick) return fail(MATE_ESTATE, "auto_reset changed inside a reset interval while the step counter is device-resident");
-    Ptrs r = e->g;
-    r.cam_act = r.tgt_act = nullptr; r.tape_ct = r.tape_goal = nullptr; r.cam_obs = r.tgt_obs = nullptr; r.scalars = nullptr; r.masks = nullptr;
-    int rc = launch_reset(e, r, RESET_FLAGGED, PH_PLACE | PH_LUT | PH_VIEW, stream);
+    int rc = launch_reset(e, restart_ptrs(e), RESET_FLAGGED, PH_PLACE | PH_LUT | PH_VIEW, stream);
     if (rc != MATE_OK) return rc;
     HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
     e->steps_since_reset = 0; e->pending_interval = 0;
@@ -915,8 +912,7 @@ static int leave_pipelined(mate_engine *e, hipStream_t stream) {
     for (int q = 0; q < 2; ++q)
         if (e->reset_in_flight[q]) { HIP_TRY(hipStreamWaitEvent(stream, e->ev_reset[q], 0)); e->reset_in_flight[q] = false; }
     if (e->pipe_count > 0) {         // an interval left open (restarts behind every pipe_every-th launch): what it has listed restarts now
-        Ptrs r = e->g;
-        apply_io(r, nullptr);
+        Ptrs r = restart_ptrs(e);
         r.pipelined = 1;
         int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, true);
         if (rc != MATE_OK) return rc;
@@ -933,13 +929,12 @@ static int leave_pipelined(mate_engine *e, hipStream_t stream) {
 
 extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream_); if (rc_ != MATE_OK) return rc_; }
     hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     if ((enable != 0) == e->dev_tick && (!enable || enable == e->dev_interval)) return MATE_OK;
     if (enable && e->dev_tick) return fail(MATE_ESTATE, "device_tick: already enabled with interval %d", e->dev_interval);
-    if (enable) { int rc = flush_pending(e, 0, stream); if (rc != MATE_OK) return rc; }
+    if (enable) { int rc = flush_pending(e, 0, 0, stream); if (rc != MATE_OK) return rc; }
     HIP_TRY(hipStreamSynchronize(stream));
     if (enable) {
         e->p.dev_tick = e->tick; e->p.dev_group = (uint32_t)e->parity; e->p.dev_tick_on = 1;
@@ -955,25 +950,62 @@ extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *str
     }
     HIP_TRY(hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
     e->dev_tick = enable != 0;
-    if (!enable) return refresh_state_rows(e, flush_pending(e, 0, stream), stream);      // (an open interval's finished environments restart here)
+    if (!enable) return refresh_state_rows(e, flush_pending(e, 0, 0, stream), stream);      // (an open interval's finished environments restart here)
     return MATE_OK;
 }
 
 static int sub_wave_of_launch(const mate_engine *e, bool greedy);
 
+// Device-resident step counter: the auto-reset launch advances it, so every stepping call uses the interval it was enabled with, and
+// the launches of one reset interval all run the same number of frames (1: the per-step flows; K: FrameSkip launches).
+// `one_frame_call`: step() and its kin, whose message names the mismatch from their side.
+static int check_device_tick(mate_engine *e, int auto_reset, int frames, bool one_frame_call) {
+    if (!e->dev_tick) return MATE_OK;
+    if (auto_reset != e->dev_interval)
+        return fail(MATE_ESTATE, "with a device-resident step counter (mate_engine_device_tick) step() needs auto_reset = %d: the auto-reset launch advances it", e->dev_interval);
+    if (e->steps_since_reset == 0) e->dev_frames = frames;
+    else if (e->dev_frames != frames)
+        return one_frame_call ? fail(MATE_ESTATE, "device-resident step counter: a one-frame step inside a reset interval of %d-frame launches", e->dev_frames)
+                              : fail(MATE_ESTATE, "device-resident step counter: %d frames per launch inside a reset interval that began with %d", frames, e->dev_frames);
+    return MATE_OK;
+}
+
+// Behind a stepping launch: restart what has finished.  auto_reset = 1: now (list `parity`, which the launch appended to);
+// k > 1: the finished environments idle, and the k-th launch of the interval restarts them together.  0 (or less): nothing.
+// What differs between the flows is spelled by the caller:
+struct Restart {
+    const mate_step_io *io;      // the restart writes first observations and masks here (restart_ptrs); null: state only
+    bool keep_actions;           // ... with the call's action pointers and encoding still in the record pointers
+    int kind_batched;            // the interval's restart: RESET_DONE (by the lists: the per-step flows) or RESET_FLAGGED (the fused rollouts); immediate: RESET_DONE
+    int phases;
+    bool split_immediate, split_batched;   // launch_reset's split_done: a list-driven restart as placement / tables / view launches
+    uint32_t frames;             // steps per launch: the restart advances a device-resident counter by frames * auto_reset (0: the flow has none)
+    int flow_tag;                // kStepFlow / kRolloutFlow
+};
+static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, hipStream_t stream) {
+    if (auto_reset < 1) return MATE_OK;
+    const bool batched = auto_reset > 1;
+    if (batched) {
+        e->pending_interval = auto_reset | how.flow_tag;
+        if (++e->steps_since_reset < auto_reset) return MATE_OK;
+    }
+    e->steps_since_reset = 0; e->pending_interval = 0;
+    Ptrs r = restart_ptrs(e, how.io);
+    if (!how.keep_actions) { r.cam_act = r.tgt_act = nullptr; r.act_f64 = 0; r.act_discrete = 0; }
+    r.tick_advance = how.frames * (uint32_t)auto_reset;
+    const int kind = batched ? how.kind_batched : RESET_DONE;
+    const int rc = launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate);
+    if (rc != MATE_OK) return rc;
+    if (kind == RESET_DONE && !e->dev_tick) e->parity ^= 1;      // (the list is consumed: the next launches append to the other one)
+    return MATE_OK;
+}
+
 static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
-    if (!e->was_reset) return fail(MATE_ESTATE, "step()/observe() called before reset() (or import_state)");
-    if (e->dev_tick && mode != MODE_OBSERVE && auto_reset != e->dev_interval)
-        return fail(MATE_ESTATE, "with a device-resident step counter (mate_engine_device_tick) step() needs auto_reset = %d: the auto-reset launch advances it", e->dev_interval);
-    if (e->dev_tick && mode != MODE_OBSERVE) {      // (one frame per launch: see rollout_with_policies)
-        if (e->steps_since_reset == 0) e->dev_frames = 1;
-        else if (e->dev_frames != 1) return fail(MATE_ESTATE, "device-resident step counter: a one-frame step inside a reset interval of %d-frame launches", e->dev_frames);
-    }
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
+    if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
-    if (mode != MODE_OBSERVE) { int rc = flush_pending(e, auto_reset > 1 ? (auto_reset | kStepFlow) : auto_reset, stream); if (rc != MATE_OK) return rc; }
+    if (mode != MODE_OBSERVE) { int rc = flush_pending(e, auto_reset, kStepFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
     apply_io(g, io);
     if (e->greedy_team_bits) g.act_f64 |= e->greedy_team_bits;          // the on-device agents' team(s): f64 joint actions
@@ -985,21 +1017,11 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     // auto_reset = 1: finished environments restart inside this call; k > 1: they idle (listed for it) and restart together every k-th call
     g.freeze_done = auto_reset > 1;
     if (mode == MODE_OBSERVE || auto_reset == 0) g.done_count = nullptr;
-    const unsigned blocks = (unsigned)((e->N + 3) / 4);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e->timing > 0 && !e->dev_tick && mode != MODE_OBSERVE && (e->timing_tick++ % e->timing) == 0) {
-        if (e->events_used == e->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-            e->events.emplace_back(a, b);
-        }
-        ev0 = e->events[e->events_used].first; ev1 = e->events[e->events_used].second; ++e->events_used;
-    }
-    // start/stop events attached to the dispatch itself (hipExtLaunchKernelGGL): the elapsed time is the
-    // kernel's own begin->end, without the marker-packet latency separate hipEventRecord calls would add
+    Timed t;
+    { const int rc_ = take_timing_events(e, !e->dev_tick && mode != MODE_OBSERVE, &t); if (rc_ != MATE_OK) return rc_; }
     // the kernel compiled for this launch's switches (enum Flow), when they are the common ones
     int flow = FLOW_ANY;
-    if (!e->flow_generic && !g.tape_ct && !g.tape_goal && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab &&
+    if (!e->sw.flow_generic && !g.tape_ct && !g.tape_goal && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab &&
         g.scratch_init && (g.cam_obs || e->p.Nc == 0) && g.tgt_obs && g.scalars) {
         if (mode == MODE_STEP_RANDOM) flow = FLOW_RANDOM;
         else if (mode == MODE_STEP) flow = FLOW_ACT_F32;      // caller-supplied real-valued actions, f32 or f64 per team
@@ -1008,45 +1030,20 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     // The small scenarios' steps on the sub-wave rollout kernel with ONE step (four environments per wave; Ptrs::per_step), where their fused flows run
     // it: from 32 environments per CU on (sub_wave_of_launch).  Not for auto_reset = 0 in the device-counted mode... every mode but observe().
     const int E = (mode != MODE_OBSERVE && e->sw.step_sub_wave && !e->p.obs_f64) ? sub_wave_of_launch(e, false) : 1;
-    if (E > 1) {
+    if (E > 1) {      // (FLOW_ANY / FLOW_RANDOM / FLOW_ACT_F32: the same switches folded as in step_kernel)
         g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0;
-        const StepFn fn = e->sub.rollout_sub[flow];      // (FLOW_ANY / FLOW_RANDOM / FLOW_ACT_F32: the same switches folded as in step_kernel)
-        const unsigned sub_blocks = (unsigned)((e->N + 4 * E - 1) / (4 * E));
-        if (ev0) hipExtLaunchKernelGGL(fn, dim3(sub_blocks), dim3(256), E * e->step_lds, stream, ev0, ev1, 0, (const Params *)e->d_params, (const Ptrs)g);
-        else hipLaunchKernelGGL(fn, dim3(sub_blocks), dim3(256), E * e->step_lds, stream, (const Params *)e->d_params, (const Ptrs)g);   // (capturable)
+        launch(e->k.rollout_sub[flow], dim3((unsigned)((e->N + 4 * E - 1) / (4 * E))), dim3(256), E * e->step_lds, stream, t, e->d_params, g);
+    } else if (e->split_on && e->k.split[flow]) {      // two waves per environment: one 128-thread workgroup each
+        launch(e->k.split[flow], dim3((unsigned)e->N), dim3(128), e->step_lds / 4, stream, t, e->d_params, g);
+    } else {
+        launch(e->k.step[flow], dim3((unsigned)((e->N + 3) / 4)), dim3(256), e->step_lds, stream, t, e->d_params, g);
     }
-    else if (e->split_on && e->split_fn[flow]) {      // two waves per environment: one 128-thread workgroup each
-        const StepFn fn = e->split_fn[flow];
-        const dim3 grid((unsigned)e->N), block(128);
-        if (ev0) hipExtLaunchKernelGGL(fn, grid, block, e->step_lds / 4, stream, ev0, ev1, 0, (const Params *)e->d_params, (const Ptrs)g);
-        else hipLaunchKernelGGL(fn, grid, block, e->step_lds / 4, stream, (const Params *)e->d_params, (const Ptrs)g);
-    }
-    else if (ev0) hipExtLaunchKernelGGL(e->step_fn[flow], dim3(blocks), dim3(256), e->step_lds, stream, ev0, ev1, 0, (const Params *)e->d_params, (const Ptrs)g);
-    else hipLaunchKernelGGL(e->step_fn[flow], dim3(blocks), dim3(256), e->step_lds, stream, (const Params *)e->d_params, (const Ptrs)g);   // (capturable)
     HIP_TRY(hipGetLastError());
-    if (mode != MODE_OBSERVE && !e->dev_tick) e->tick += 1;
-    if (mode != MODE_OBSERVE && auto_reset == 1) {
-        Ptrs r = e->g;
-        apply_io(r, io);
-        r.scalars = nullptr; r.tape_ct = nullptr; r.tape_goal = nullptr;   // keep the finished step's reward/done
-        r.tick_advance = 1u;
-        int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream);
-        if (rc != MATE_OK) return rc;
-        if (!e->dev_tick) e->parity ^= 1;
-    } else if (mode != MODE_OBSERVE && auto_reset > 1) {
-        e->pending_interval = auto_reset | kStepFlow;
-        if (++e->steps_since_reset >= auto_reset) {       // the interval's one reset launch: everything its steps listed
-            e->steps_since_reset = 0; e->pending_interval = 0;
-            Ptrs r = e->g;
-            apply_io(r, io);
-            r.scalars = nullptr; r.tape_ct = nullptr; r.tape_goal = nullptr;
-            r.tick_advance = (uint32_t)auto_reset;
-            int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, e->greedy_team_bits != 0);
-            if (rc != MATE_OK) return rc;
-            if (!e->dev_tick) e->parity ^= 1;
-        }
-    }
-    return MATE_OK;
+    if (mode == MODE_OBSERVE) return MATE_OK;
+    if (!e->dev_tick) e->tick += 1;
+    // (the restart writes the caller's observation buffers and masks; the immediate one, idle almost always, stays ONE launch, and so
+    // does the interval's unless the on-device agents play: their ~1.2 k-step episodes finish somewhere in the batch all the time)
+    return restart_finished(e, auto_reset, Restart{io, true, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, false, e->greedy_team_bits != 0, 1u, kStepFlow}, stream);
 }
 
 extern "C" int mate_engine_step(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
@@ -1062,23 +1059,22 @@ extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, i
 //           under the random policy, every shape but MATE-4v4-*, whose one-per-wave rollout (the register-resident row image) is as fast.
 //           Greedy flows x1.2 .. 3.3, random-policy flows x1.1 .. 2.9 there.
 static int sub_wave_of_launch(const mate_engine *e, bool greedy) {
-    if (e->sub_mode == 0 || e->sub.sub_wave <= 1 || !(greedy ? (const void *)e->sub.rollout_greedy_sub : (const void *)e->sub.rollout_sub[0])) return 1;
-    if (e->sub_mode == 1) return e->sub.sub_wave;
+    const int mode = e->sw.sub_wave_mode;
+    if (mode == 0 || e->k.sub_wave <= 1 || !(greedy ? (const void *)e->k.rollout_greedy_sub : (const void *)e->k.rollout_sub[0])) return 1;
+    if (mode == 1) return e->k.sub_wave;
     if (e->N < 32 * e->cus) return 1;
     if (!greedy && e->p.Nc * e->p.Nt >= 16) return 1;      // MATE-4v4-*: the row-image kernel is as fast or faster (x0.72 .. 1.14)
-    return e->sub.sub_wave;
+    return e->k.sub_wave;
 }
 
 static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream_); if (rc_ != MATE_OK) return rc_; }
-    if (!e->was_reset) return fail(MATE_ESTATE, "rollout called before reset() (or import_state)");
+    hipStream_t stream = (hipStream_t)stream_;
+    { const int rc_ = enter(e, stream, "rollout"); if (rc_ != MATE_OK) return rc_; }
     if (e->dev_tick) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(e->device));
     note_stream(e, stream);
-    { int rc = flush_pending(e, auto_reset > 1 ? (auto_reset | kRolloutFlow) : auto_reset, stream); if (rc != MATE_OK) return rc; }
+    { int rc = flush_pending(e, auto_reset, kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
     apply_io(g, io);
     g.mode = MODE_STEP_RANDOM; g.parity = e->parity; g.reset_kind = -1; g.tick = e->tick; g.rollout_steps = steps;
@@ -1087,38 +1083,19 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     if (auto_reset != 1) g.done_count = nullptr;     // no list: nothing restarts (0), or a batched reset finds the finished ones by their flag (k > 1)
     const int E = sub_wave_of_launch(e, false);      // environments per wave (1, or the small scenarios' 4)
     const unsigned blocks = (unsigned)((e->N + 4 * E - 1) / (4 * E));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e->timing > 0 && (e->timing_tick++ % e->timing) == 0) {
-        if (e->events_used == e->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-            e->events.emplace_back(a, b);
-        }
-        ev0 = e->events[e->events_used].first; ev1 = e->events[e->events_used].second; ++e->events_used;
-    }
-    const int flow = (!e->flow_generic && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab && g.scratch_init &&
+    Timed t;
+    { const int rc_ = take_timing_events(e, true, &t); if (rc_ != MATE_OK) return rc_; }
+    const int flow = (!e->sw.flow_generic && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab && g.scratch_init &&
                       (g.cam_obs || e->p.Nc == 0) && g.tgt_obs && g.scalars) ? FLOW_RANDOM : FLOW_ANY;
     e->last_flow = flow;
-    if (E > 1) hipExtLaunchKernelGGL(e->sub.rollout_sub[flow], dim3(blocks), dim3(256), E * e->step_lds, stream, ev0, ev1, 0, (const Params *)e->d_params, (const Ptrs)g);
-    else
-    hipExtLaunchKernelGGL(e->rollout_fn[flow], dim3(blocks), dim3(256), (flow == FLOW_RANDOM && e->image) ? 4 * e->image_wave_bytes : e->step_lds, stream, ev0, ev1, 0,
-                          (const Params *)e->d_params, (const Ptrs)g);
+    const StepFn fn = E > 1 ? e->k.rollout_sub[flow] : e->k.rollout[flow];
+    const size_t lds = E > 1 ? E * e->step_lds : (flow == FLOW_RANDOM && e->k.image) ? 4 * e->image_wave_bytes : e->step_lds;
+    // (this flow has always gone through the extended launch, timed or not -- null events: not through launch())
+    hipExtLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
-    if (auto_reset == 1) {
-        Ptrs r = e->g;
-        apply_io(r, nullptr);     // state only: the next rollout observes the fresh episode on its first step
-        int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT, stream);
-        if (rc != MATE_OK) return rc;
-        e->parity ^= 1;
-    } else if (auto_reset > 1 && (e->pending_interval = auto_reset | kRolloutFlow, ++e->steps_since_reset >= auto_reset)) {      // batched: every k-th launch restarts all finished environments
-        e->steps_since_reset = 0; e->pending_interval = 0;
-        Ptrs r = e->g;
-        apply_io(r, nullptr);
-        int rc = launch_reset(e, r, RESET_FLAGGED, PH_PLACE | PH_LUT, stream);
-        if (rc != MATE_OK) return rc;
-    }
-    return MATE_OK;
+    // (state only, placement and tables: the next rollout observes the fresh episode on its first step)
+    return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, PH_PLACE | PH_LUT, false, false, 0u, kRolloutFlow}, stream);
 }
 
 extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
@@ -1132,7 +1109,7 @@ static size_t fused_rollout_lds(const mate_engine *e, int E = 1) { return (size_
 static size_t step_greedy_lds(const mate_engine *e, bool cameras = true) {
     return 4 * (size_t)e->p.lds_wave_bytes + 4 * (size_t)step_greedy_slice_bytes(e->q.PW, e->q.TW, e->p.Nc, e->p.Nt, e->p.MW, cameras);
 }
-static bool use_step_greedy(const mate_engine *e) { return e->step_greedy_fn && !e->sw.step_greedy_rollout && step_greedy_lds(e) <= 160 * 1024; }
+static bool use_step_greedy(const mate_engine *e) { return e->k.step_greedy && !e->sw.step_greedy_rollout && step_greedy_lds(e) <= 160 * 1024; }
 
 static int policy_enable(mate_engine *e) {
     if (e->policy_ready) return MATE_OK;
@@ -1173,16 +1150,14 @@ static int policy_enable(mate_engine *e) {
         HIP_TRY(hipMemcpy(d_tab, tab.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         q.zoom_tab = d_tab; q.zoom_inv_h = kInvH; q.zoom_n = e->sw.zoom_iterate ? 0 : n;      // 0 entries: zoom_lookup iterates
     }
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->policy_fn), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * q.lds_bytes + 1024);
-    if (err == hipSuccess) {
-        const size_t fused = 4 * (size_t)p.lds_wave_bytes + 4 * (size_t)policy_slice_bytes(q.PW, p.Nc, p.Nt) + 1024;
-        if (fused <= 160 * 1024)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rollout_greedy_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused);
-        if (err == hipSuccess && e->sub.rollout_greedy_sub && fused_rollout_lds(e, e->sub.sub_wave) <= 160 * 1024)
-            err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->sub.rollout_greedy_sub), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_rollout_lds(e, e->sub.sub_wave));
-    }
-    if (err == hipSuccess && e->step_greedy_fn && step_greedy_lds(e) <= 160 * 1024)
-        err = hipFuncSetAttribute(reinterpret_cast<const void *>(e->step_greedy_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_greedy_lds(e));
+    // dynamic LDS of the agents' kernel and of the one-launch forms that fit a workgroup (fused_rollout_lds, step_greedy_lds)
+    const KernelSet &k = e->k;
+    hipError_t err = hipSuccess;
+    auto opt_in = [&](PolicyFn fn, size_t bytes) { if (err == hipSuccess && bytes <= 160 * 1024) err = set_dynamic_lds(fn, bytes); };
+    err = set_dynamic_lds(k.policy, 4 * (size_t)q.lds_bytes + 1024);
+    opt_in(k.rollout_greedy, fused_rollout_lds(e));
+    opt_in(k.rollout_greedy_sub, fused_rollout_lds(e, k.sub_wave));
+    opt_in(k.step_greedy, step_greedy_lds(e));
     if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
     e->policy_ready = true;
     return MATE_OK;
@@ -1219,10 +1194,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (team_caller >= 0 && (!io || !(team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev)))
         return fail(MATE_EINVAL, "step_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
     // the checks launch_step would make only after the policy launch below has advanced the agents' memory: a rejected call must leave it alone
-    if (e->dev_tick && auto_reset != e->dev_interval)
-        return fail(MATE_ESTATE, "with a device-resident step counter (mate_engine_device_tick) step() needs auto_reset = %d: the auto-reset launch advances it", e->dev_interval);
-    if (e->dev_tick && e->steps_since_reset != 0 && e->dev_frames != 1)
-        return fail(MATE_ESTATE, "device-resident step counter: a one-frame step inside a reset interval of %d-frame launches", e->dev_frames);
+    { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, stream);
     PolicyPtrs q = e->q;
@@ -1237,8 +1209,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     const unsigned blocks = (unsigned)((e->N + 3) / 4);
     Ptrs gp = e->g;
     gp.freeze_done = auto_reset > 1;
-    hipLaunchKernelGGL(e->policy_fn, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream,   // + the shared zoom-solve exchange
-                       (const Params *)e->d_params, (const Ptrs)gp, (const PolicyPtrs)q);
+    launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
     HIP_TRY(hipGetLastError());
     mate_step_io io2;
     if (io) io2 = *io; else std::memset(&io2, 0, sizeof(io2));
@@ -1271,12 +1242,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     // (device-resident counter: the per-step flows, and the K-frame launches of a learner against the greedy opponents -- FrameSkip in a
     // HIP graph; the auto-reset launch behind every auto_reset-th launch advances the counter by auto_reset * K)
     if (e->dev_tick && !per_step && team_caller < 0) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
-    if (e->dev_tick && auto_reset != e->dev_interval)
-        return fail(MATE_ESTATE, "with a device-resident step counter (mate_engine_device_tick) step() needs auto_reset = %d: the auto-reset launch advances it", e->dev_interval);
-    if (e->dev_tick) {
-        if (e->steps_since_reset == 0) e->dev_frames = steps;
-        else if (e->dev_frames != steps) return fail(MATE_ESTATE, "device-resident step counter: %d frames per launch inside a reset interval that began with %d", steps, e->dev_frames);
-    }
+    { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }
     if (!e->policy_ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
     hipStream_t stream = (hipStream_t)stream_;
@@ -1289,20 +1255,17 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
-    { int rc = flush_pending(e, auto_reset > 1 ? (auto_reset | (per_step ? kStepFlow : kRolloutFlow)) : auto_reset, stream); if (rc != MATE_OK) return rc; }
+    { int rc = flush_pending(e, auto_reset, per_step ? kStepFlow : kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
     if (pipelined && !e->side) {
         {   // the LOWEST priority the device offers (MATE_PIPELINED_PRIORITY=0: default priority): the resets' latency-bound workgroups
             // should take the slots the rollout launch leaves free -- its tail --, not displace its workgroups
             int least = 0, greatest = 0;
             HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            const char *pv = getenv("MATE_PIPELINED_PRIORITY");
-            if (pv && atoi(pv) == 0) HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+            if (!e->sw.pipelined_low_priority) HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
             else HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, least));
         }
         HIP_TRY(hipEventCreateWithFlags(&e->ev_launch, hipEventDisableTiming));
         for (int q = 0; q < 2; ++q) HIP_TRY(hipEventCreateWithFlags(&e->ev_reset[q], hipEventDisableTiming));
-        const char *v = getenv("MATE_PIPELINED_SERIAL");
-        e->pipelined_serial = v && atoi(v) != 0;
     }
     if (pipelined && !e->pipelined) {                // entering the mode: both lists empty, nothing in flight
         HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
@@ -1325,9 +1288,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     // E environments per wave: the fused launches of the small scenarios -- and their PER-STEP Greedy flows too (step_greedy / step_versus_greedy:
     // the one-step form of the sub-wave rollout kernel instead of step_greedy_kernel: MATE-2v4-0 x 16 384 against the greedy cameras 38.2 -> 20.5 us
     // per step, x1.2 .. 1.9 from 8192 environments on; same bytes; MATE_STEP_SUBWAVE=0 keeps step_greedy_kernel)
-    const int E = ((!per_step || e->sw.step_sub_wave) && fused_rollout_lds(e, e->sub.sub_wave) <= 160 * 1024) ? sub_wave_of_launch(e, true) : 1;
+    const int E = ((!per_step || e->sw.step_sub_wave) && fused_rollout_lds(e, e->k.sub_wave) <= 160 * 1024) ? sub_wave_of_launch(e, true) : 1;
     const bool light = per_step && use_step_greedy(e) && E == 1;
-    const PolicyFn fn = light ? e->step_greedy_fn : E > 1 ? e->sub.rollout_greedy_sub : e->rollout_greedy_fn;
+    const PolicyFn fn = light ? e->k.step_greedy : E > 1 ? e->k.rollout_greedy_sub : e->k.rollout_greedy;
     // (the caller plays the cameras: step_greedy_kernel holds the target agents' section only -- a smaller slice, one more workgroup per CU)
     const size_t lds = light ? step_greedy_lds(e, team_caller != 0) : fused_rollout_lds(e, E);
     if (lds > 160 * 1024) return fail(MATE_EINVAL, "rollout_greedy: %zu bytes of LDS per workgroup do not fit", lds);
@@ -1346,70 +1309,35 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     std::memset(&q.tape, 0, sizeof(q.tape));
     q.caller_team = team_caller;
     const unsigned blocks = (unsigned)((e->N + 4 * E - 1) / (4 * E));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e->timing > 0 && !e->dev_tick && (e->timing_tick++ % e->timing) == 0) {
-        if (e->events_used == e->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-            e->events.emplace_back(a, b);
-        }
-        ev0 = e->events[e->events_used].first; ev1 = e->events[e->events_used].second; ++e->events_used;
-    }
+    Timed t;
+    { const int rc_ = take_timing_events(e, !e->dev_tick, &t); if (rc_ != MATE_OK) return rc_; }
     e->last_flow = light ? FLOW_STEP_GREEDY : FLOW_GREEDY;
-    if (ev0) hipExtLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, stream, ev0, ev1, 0, (const Params *)e->d_params, (const Ptrs)g, (const PolicyPtrs)q);
-    else hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)g, (const PolicyPtrs)q);   // (capturable)
+    launch(fn, dim3(blocks), dim3(256), lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     if (!e->dev_tick) e->tick += (uint32_t)steps;
-    if (per_step) {
-        const bool now = auto_reset == 1 || (auto_reset > 1 && (e->pending_interval = auto_reset | kStepFlow, ++e->steps_since_reset >= auto_reset));
-        if (now) {
-            e->steps_since_reset = 0; e->pending_interval = 0;
-            Ptrs r = e->g;
-            apply_io(r, io);
-            r.cam_act = r.tgt_act = nullptr; r.act_f64 = 0; r.act_discrete = 0;
-            r.scalars = nullptr; r.tape_ct = nullptr; r.tape_goal = nullptr;   // keep the finished step's reward / done
-            r.tick_advance = (uint32_t)auto_reset;
-            // (the immediate restart, idle almost always, stays ONE launch; the interval's restart is split: placement / tables / view)
-            int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, auto_reset > 1);
-            if (rc != MATE_OK) return rc;
-            if (!e->dev_tick) e->parity ^= 1;
-        }
-        return MATE_OK;
-    }
-    if (pipelined && ++e->pipe_count < e->pipe_every) {
-        // inside a restart interval: the following launches append to the same list; what has finished idles (listed) until the interval's restart
-    } else if (pipelined) {
-        e->pipe_count = 0;
-        // the reset of what THIS launch (this interval of launches) finishes (list `parity`): on the side stream, behind this launch, under the next ones
-        hipStream_t rs = e->pipelined_serial ? stream : e->side;
-        if (!e->pipelined_serial) { HIP_TRY(hipEventRecord(e->ev_launch, stream)); HIP_TRY(hipStreamWaitEvent(rs, e->ev_launch, 0)); }
-        Ptrs r = e->g;
-        apply_io(r, nullptr);
-        r.pipelined = 1;
-        const bool multi_before = e->multi_stream;
-        int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, rs, true);
-        if (rc != MATE_OK) return rc;
-        HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), rs));      // (the list is consumed: the launch after next appends to it afresh)
-        if (!e->pipelined_serial) { HIP_TRY(hipEventRecord(e->ev_reset[e->parity], rs)); e->reset_in_flight[e->parity] = true; }
-        // (launch_reset noted the side stream: the accessors order it through leave_pipelined's event waits, so it neither becomes
-        // the stream they wait for nor counts as a second stream of the CALLER's -- which would turn every accessor into a device-wide wait)
-        e->last_stream = stream; e->multi_stream = multi_before;
-        e->parity ^= 1;
-    } else if (auto_reset == 1) {
-        Ptrs r = e->g;
-        apply_io(r, nullptr);     // state and the engine's own masks: the agents of the next rollout act on the fresh view
-        r.tick_advance = (uint32_t)steps;
-        int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, true);
-        if (rc != MATE_OK) return rc;
-        if (!e->dev_tick) e->parity ^= 1;
-    } else if (auto_reset > 1 && (e->pending_interval = auto_reset | kRolloutFlow, ++e->steps_since_reset >= auto_reset)) {
-        e->steps_since_reset = 0; e->pending_interval = 0;
-        Ptrs r = e->g;
-        apply_io(r, nullptr);
-        r.tick_advance = (uint32_t)auto_reset * (uint32_t)steps;
-        int rc = launch_reset(e, r, RESET_FLAGGED, PH_PLACE | PH_LUT | PH_VIEW, stream);
-        if (rc != MATE_OK) return rc;
-    }
+    const int full = PH_PLACE | PH_LUT | PH_VIEW;
+    // per-step: list-driven restarts that write the restarted environments' first observations into the caller's buffers (not its
+    // actions' encoding); the immediate one, idle almost always, stays ONE launch, the interval's is split: placement / tables / view
+    if (per_step) return restart_finished(e, auto_reset, Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, stream);
+    // fused: state and the engine's own masks -- the agents of the next rollout act on the fresh view; the interval's restart by flag
+    if (!pipelined) return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow}, stream);
+    if (++e->pipe_count < e->pipe_every) return MATE_OK;      // inside a restart interval: the following launches append to the same list; what has finished idles (listed) until the interval's restart
+    e->pipe_count = 0;
+    // the reset of what THIS launch (this interval of launches) finishes (list `parity`): on the side stream, behind this launch, under the next ones
+    const bool serial = e->sw.pipelined_serial;
+    hipStream_t rs = serial ? stream : e->side;
+    if (!serial) { HIP_TRY(hipEventRecord(e->ev_launch, stream)); HIP_TRY(hipStreamWaitEvent(rs, e->ev_launch, 0)); }
+    Ptrs r = restart_ptrs(e);
+    r.pipelined = 1;
+    const bool multi_before = e->multi_stream;
+    int rc = launch_reset(e, r, RESET_DONE, full, rs, true);
+    if (rc != MATE_OK) return rc;
+    HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), rs));      // (the list is consumed: the launch after next appends to it afresh)
+    if (!serial) { HIP_TRY(hipEventRecord(e->ev_reset[e->parity], rs)); e->reset_in_flight[e->parity] = true; }
+    // (launch_reset noted the side stream: the accessors order it through leave_pipelined's event waits, so it neither becomes
+    // the stream they wait for nor counts as a second stream of the CALLER's -- which would turn every accessor into a device-wide wait)
+    e->last_stream = stream; e->multi_stream = multi_before;
+    e->parity ^= 1;
     return MATE_OK;
 }
 
@@ -1440,8 +1368,7 @@ extern "C" int mate_engine_observe(mate_engine *e, const mate_step_io *io, void 
 
 extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *stream) {
     if (!e || !dst_dev) return fail(MATE_EINVAL, "null argument");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(export_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, dst_dev);
     HIP_TRY(hipGetLastError());
@@ -1451,8 +1378,7 @@ extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *s
 extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, void *stream) {
     if (!e || !src_dev) return fail(MATE_EINVAL, "null argument");
     if (e->dev_tick) return fail(MATE_ESTATE, "import_state while the step counter is device-resident (mate_engine_device_tick)");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(import_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, src_dev);
     HIP_TRY(hipGetLastError());
@@ -1465,37 +1391,44 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     return refresh_state_rows(e, MATE_OK, stream);
 }
 
-extern "C" int mate_engine_lut_read(mate_engine *e, int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {
-    if (!e || !phis || !rhos || !count) return fail(MATE_EINVAL, "null argument");
-    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "lut_read: index out of range");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+// One camera's knot table (inner or outer boundary) to the host / from the host.  `who`: the entry point's name in the messages.
+static int lut_read_from(mate_engine *e, const double2 *knots_dev, const int32_t *counts_dev, int kmax, const char *who,
+                         int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {
+    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "%s: index out of range", who);
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     const int64_t lc = env * e->p.Nc + camera;
     int32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, e->g.lut_count + lc, sizeof(n), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n, counts_dev + lc, sizeof(n), hipMemcpyDeviceToHost));
     *count = n;
-    if (n > capacity) return fail(MATE_EINVAL, "lut_read: capacity %d < %d knots", capacity, n);
+    if (n > capacity) return fail(MATE_EINVAL, "%s: capacity %d < %d knots", who, capacity, n);
     std::vector<double2> knots((size_t)n);
-    HIP_TRY(hipMemcpy(knots.data(), e->g.lut_knots + lc * e->p.kmax, sizeof(double2) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(knots.data(), knots_dev + lc * kmax, sizeof(double2) * (size_t)n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) { phis[i] = knots[i].x; rhos[i] = knots[i].y; }
     return MATE_OK;
+}
+// (the front half of a write: the checks, the launches drained, the knots packed and on the device with their count)
+static int lut_write_to(mate_engine *e, double2 *knots_dev, int32_t *counts_dev, int kmax, const char *who,
+                        int64_t env, int32_t camera, const double *phis, const double *rhos, int32_t n) {
+    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "%s: index out of range", who);
+    if (n < 2 || n > kmax) return fail(MATE_EINVAL, "%s: %d knots do not fit (capacity %d)", who, n, kmax);
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    std::vector<double2> knots((size_t)n);
+    for (int i = 0; i < n; ++i) { knots[i].x = phis[i]; knots[i].y = rhos[i]; }
+    const int64_t lc = env * e->p.Nc + camera;
+    HIP_TRY(hipMemcpy(knots_dev + lc * kmax, knots.data(), sizeof(double2) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(counts_dev + lc, &n, sizeof(n), hipMemcpyHostToDevice));
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_lut_read(mate_engine *e, int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {
+    if (!e || !phis || !rhos || !count) return fail(MATE_EINVAL, "null argument");
+    return lut_read_from(e, e->g.lut_knots, e->g.lut_count, e->p.kmax, "lut_read", env, camera, phis, rhos, capacity, count);
 }
 
 extern "C" int mate_engine_lut_read_outer(mate_engine *e, int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {
     if (!e || !phis || !rhos || !count) return fail(MATE_EINVAL, "null argument");
     if (!e->g.lut_knots_outer) return fail(MATE_ESTATE, "outer boundary not enabled (mate_engine_enable_outer_boundary)");
-    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "lut_read_outer: index out of range");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
-    const int64_t lc = env * e->p.Nc + camera;
-    int32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, e->g.lut_count_outer + lc, sizeof(n), hipMemcpyDeviceToHost));
-    *count = n;
-    if (n > capacity) return fail(MATE_EINVAL, "lut_read_outer: capacity %d < %d knots", capacity, n);
-    std::vector<double2> knots((size_t)n);
-    HIP_TRY(hipMemcpy(knots.data(), e->g.lut_knots_outer + lc * e->g.kmax_outer, sizeof(double2) * (size_t)n, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) { phis[i] = knots[i].x; rhos[i] = knots[i].y; }
-    return MATE_OK;
+    return lut_read_from(e, e->g.lut_knots_outer, e->g.lut_count_outer, e->g.kmax_outer, "lut_read_outer", env, camera, phis, rhos, capacity, count);
 }
 
 // Camera.boundary_outer / sight_range_outer_func (entities.py:419-448, 479): built by every later reset /
@@ -1505,8 +1438,7 @@ extern "C" int mate_engine_enable_outer_boundary(mate_engine *e, int32_t *capaci
     const Params &p = e->p;
     if (p.Nc == 0) return fail(MATE_EINVAL, "no cameras in this scenario");
     if (e->g.lut_knots_outer) { if (capacity) *capacity = e->g.kmax_outer; return MATE_OK; }
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     // 360 + per obstacle (arc <= 181 rays + two 21-point flanks) rays are sorted in LDS
     const int rays = 360 + p.No * (181 + 42) + 1;
     ResetLds rl = e->rl;
@@ -1523,8 +1455,7 @@ extern "C" int mate_engine_enable_outer_boundary(mate_engine *e, int32_t *capaci
     int rc = dev_alloc(e, &knots, (size_t)e->N * p.Nc * kmax_outer);
     if (rc == MATE_OK) rc = dev_alloc(e, &counts, (size_t)e->N * p.Nc);
     if (rc != MATE_OK) return rc;
-    hipError_t err = p.obs_f64 ? hipFuncSetAttribute(reinterpret_cast<const void *>(&reset_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, roff)
-                               : hipFuncSetAttribute(reinterpret_cast<const void *>(&reset_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, roff);
+    const hipError_t err = with_obs_type(p.obs_f64 != 0, [&](auto tag) { return set_dynamic_lds(&reset_kernel<decltype(tag)>, (size_t)roff); });
     if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
     e->rl = rl; e->reset_lds = (size_t)roff;
     setup_two_tier(e);
@@ -1536,16 +1467,7 @@ extern "C" int mate_engine_enable_outer_boundary(mate_engine *e, int32_t *capaci
 extern "C" int mate_engine_lut_write_outer(mate_engine *e, int64_t env, int32_t camera, const double *phis, const double *rhos, int32_t n) {
     if (!e || !phis || !rhos) return fail(MATE_EINVAL, "null argument");
     if (!e->g.lut_knots_outer) return fail(MATE_ESTATE, "outer boundary not enabled (mate_engine_enable_outer_boundary)");
-    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "lut_write_outer: index out of range");
-    if (n < 2 || n > e->g.kmax_outer) return fail(MATE_EINVAL, "lut_write_outer: %d knots do not fit (capacity %d)", n, e->g.kmax_outer);
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
-    std::vector<double2> knots((size_t)n);
-    for (int i = 0; i < n; ++i) { knots[i].x = phis[i]; knots[i].y = rhos[i]; }
-    const int64_t lc = env * e->p.Nc + camera;
-    HIP_TRY(hipMemcpy(e->g.lut_knots_outer + lc * e->g.kmax_outer, knots.data(), sizeof(double2) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->g.lut_count_outer + lc, &n, sizeof(n), hipMemcpyHostToDevice));
-    return MATE_OK;
+    return lut_write_to(e, e->g.lut_knots_outer, e->g.lut_count_outer, e->g.kmax_outer, "lut_write_outer", env, camera, phis, rhos, n);
 }
 
 extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_dev, double *matrix_dev, double *scores_dev, void *stream) {
@@ -1554,9 +1476,7 @@ extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_d
     if (e->p.Nc == 0) return fail(MATE_EINVAL, "no cameras in this scenario");
     if (e->p.Nt > kAuxMaxTargets) return fail(MATE_EINVAL, "soft_coverage: at most %d targets", kAuxMaxTargets);
     if (!e->g.lut_knots_outer) return fail(MATE_ESTATE, "outer boundary not enabled (mate_engine_enable_outer_boundary)");
-    { const int rc_ = leave_pipelined(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    if (!e->was_reset) return fail(MATE_ESTATE, "soft_coverage called before reset() (or import_state)");
-    HIP_TRY(hipSetDevice(e->device));
+    { const int rc_ = enter(e, (hipStream_t)stream, "soft_coverage"); if (rc_ != MATE_OK) return rc_; }
     const int64_t items = e->N * e->p.Nc;
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(soft_coverage_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
@@ -1567,13 +1487,9 @@ extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_d
 
 extern "C" int mate_engine_lut_write(mate_engine *e, int64_t env, int32_t camera, const double *phis, const double *rhos, int32_t n) {
     if (!e || !phis || !rhos) return fail(MATE_EINVAL, "null argument");
-    if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "lut_write: index out of range");
-    if (n < 2 || n > e->p.kmax) return fail(MATE_EINVAL, "lut_write: %d knots do not fit (capacity %d)", n, e->p.kmax);
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
-    std::vector<double2> knots((size_t)n);
+    { const int rc_ = lut_write_to(e, e->g.lut_knots, e->g.lut_count, e->p.kmax, "lut_write", env, camera, phis, rhos, n); if (rc_ != MATE_OK) return rc_; }
+    // the inner table's indices: built on the host, as the device builder in reset_kernels.hpp builds them
     std::vector<uint16_t> bucket((size_t)e->p.nbucket, 0);
-    for (int i = 0; i < n; ++i) { knots[i].x = phis[i]; knots[i].y = rhos[i]; }
     // per-degree index: bucket[d] = last knot with angle <= d - 180 (exact integer knots exist in real tables)
     int j = 0;
     for (int d = 0; d <= 361; ++d) {
@@ -1623,9 +1539,7 @@ extern "C" int mate_engine_lut_write(mate_engine *e, int64_t env, int32_t camera
         }
     }
     HIP_TRY(hipMemcpy(e->g.lut_deg + lc * kLutCells * kDegWords, deg.data(), sizeof(double2) * deg.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->g.lut_knots + lc * e->p.kmax, knots.data(), sizeof(double2) * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->g.lut_bucket + lc * e->p.nbucket, bucket.data(), sizeof(uint16_t) * bucket.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->g.lut_count + lc, &n, sizeof(n), hipMemcpyHostToDevice));
     return MATE_OK;
 }
 
@@ -1645,8 +1559,7 @@ extern "C" int mate_engine_debug_skip(mate_engine *e, int32_t mask) {
 // Total number of (environment, step) slots spent idle waiting for a batched reset (auto_reset > 1) since creation.
 extern "C" int mate_engine_idle_steps(mate_engine *e, int64_t *total) {
     if (!e || !total) return fail(MATE_EINVAL, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(wait_for_launches(e));
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     std::vector<int32_t> host((size_t)e->N);
     HIP_TRY(hipMemcpy(host.data(), e->g.idle_steps, sizeof(int32_t) * host.size(), hipMemcpyDeviceToHost));
     int64_t sum = 0;
@@ -1844,7 +1757,7 @@ extern "C" int mate_engine_hbm_probe(int32_t device, const void *src, void *dst,
 extern "C" int mate_engine_set_sub_wave(mate_engine *e, int32_t enable, int32_t *in_use) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (enable > 2) return fail(MATE_EINVAL, "set_sub_wave: 0 (one per wave), 1 (the shape's number), 2 (where it measured faster) or negative (query)");
-    if (enable >= 0) e->sub_mode = enable;      // (negative: a query)
+    if (enable >= 0) e->sw.sub_wave_mode = enable;      // (negative: a query)
     if (in_use) { in_use[0] = sub_wave_of_launch(e, true); }
     return MATE_OK;
 }

@@ -23,57 +23,11 @@
 namespace mate {
 
 bool MATE_GROUP_FN(int Nc, int Nt, int No, bool f64, bool no_image, KernelSet *out) {
-#define MATE_F32_KERNELS(C, T, O)                                                                                       \
-        out->step[FLOW_ANY] = (StepFn)step_kernel<float, FixedShape<C, T, O, false>>;                                   \
-        out->step[FLOW_RANDOM] = (StepFn)step_kernel<float, FixedShape<C, T, O, false>, FLOW_RANDOM>;                   \
-        out->step[FLOW_ACT_F32] = (StepFn)step_kernel<float, FixedShape<C, T, O, false>, FLOW_ACT_F32>;                 \
-        out->split[FLOW_ANY] = nullptr;                                                                                 \
-        out->split[FLOW_RANDOM] = (StepFn)step_split_kernel<float, FixedShape<C, T, O, false>, FLOW_RANDOM>;            \
-        out->split[FLOW_ACT_F32] = (StepFn)step_split_kernel<float, FixedShape<C, T, O, false>, FLOW_ACT_F32>;          \
-        out->rollout[0] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false>>;                                    \
-        out->rollout[1] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false>, FLOW_RANDOM>;                       \
-        out->policy = (PolicyFn)greedy_policy_kernel<float, FixedShape<C, T, O, false>>;                                \
-        out->rollout_greedy = (PolicyFn)rollout_greedy_kernel<float, FixedShape<C, T, O, false>>;                       \
-        out->step_greedy = nullptr;                                                                                     \
-        if constexpr (step_greedy_compiled(C, T, O)) out->step_greedy = (PolicyFn)step_greedy_kernel<float, FixedShape<C, T, O, false>>;       \
-        out->image = 0;                                                                                                 \
-        out->rollout_sub[0] = out->rollout_sub[1] = out->rollout_sub[2] = nullptr; out->rollout_greedy_sub = nullptr; out->sub_wave = 1;      \
-        if constexpr (FixedShape<C, T, O, false>::kSubWave > 1) {                                                       \
-            constexpr int E_ = FixedShape<C, T, O, false>::kSubWave;                                                    \
-            out->rollout_sub[0] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false>, FLOW_ANY, E_>;              \
-            out->rollout_sub[1] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false>, FLOW_RANDOM, E_>;           \
-            out->rollout_sub[2] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false>, FLOW_ACT_F32, E_>;          \
-            out->rollout_greedy_sub = (PolicyFn)rollout_greedy_kernel<float, FixedShape<C, T, O, false>, E_>;           \
-            out->sub_wave = E_;                                                                                         \
-        }                                                                                                               \
-        if constexpr (image_fits(C, T, O)) {                                                                            \
-            if (!no_image) { out->rollout[1] = (StepFn)rollout_kernel<float, FixedShape<C, T, O, false, true>, FLOW_RANDOM>; out->image = 1; }     \
-        }
-#define X(C, T, O)                                                                                                      \
-    if (Nc == C && Nt == T && No == O) {                                                                                \
-        if (f64) {                                                                                                      \
-            out->step[FLOW_ANY] = out->step[FLOW_RANDOM] = out->step[FLOW_ACT_F32] = (StepFn)step_kernel<double, FixedShape<C, T, O, true>>;       \
-            out->split[0] = out->split[1] = out->split[2] = nullptr;                                                    \
-            out->rollout[0] = out->rollout[1] = (StepFn)rollout_kernel<double, FixedShape<C, T, O, true>>;              \
-            out->policy = (PolicyFn)greedy_policy_kernel<double, FixedShape<C, T, O, true>>;                            \
-            out->rollout_greedy = (PolicyFn)rollout_greedy_kernel<double, FixedShape<C, T, O, true>>;                   \
-            out->step_greedy = nullptr;      /* (f64 observations: the two-launch form) */                              \
-            out->image = 0;                                                                                             \
-            out->rollout_sub[0] = out->rollout_sub[1] = out->rollout_sub[2] = nullptr; out->rollout_greedy_sub = nullptr; out->sub_wave = 1;  \
-        } else { MATE_F32_KERNELS(C, T, O) }                                                                            \
-        return true;                                                                                                    \
-    }
-#define Y(C, T, O)                                                                                                      \
-    if (Nc == C && Nt == T && No == O) {                                                                                \
-        if (f64) return false;                                                                                          \
-        MATE_F32_KERNELS(C, T, O)                                                                                       \
-        return true;                                                                                                    \
-    }
+#define X(C, T, O) if (Nc == C && Nt == T && No == O) { *out = f64 ? f64_kernels<FixedShape<C, T, O, true>>() : fixed_f32_kernels<C, T, O>(no_image); return true; }
+#define Y(C, T, O) if (Nc == C && Nt == T && No == O) { if (f64) return false; *out = fixed_f32_kernels<C, T, O>(no_image); return true; }
     MATE_GROUP_SHAPES(X, Y)
 #undef X
 #undef Y
-#undef MATE_F32_KERNELS
-    (void)no_image; (void)f64;
     return false;
 }
 
