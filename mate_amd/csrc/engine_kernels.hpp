@@ -165,6 +165,9 @@ struct FixedShape {
     static_assert(!IMAGE || (!F64 && image_fits(NC, NT, NO)), "row-image mode: f32 observations of a shape that fits");
     static constexpr bool kHoldRoles = shape_range_rounds(NC, NT, NO) <= (IMAGE ? 5 : 3);      // 5 words per round: three rounds fit beside the held descriptors, five where the row image needs none
     static constexpr bool kGreedyRoles = shape_range_rounds(NC, NT, NO) <= 4;    // rollout_greedy_kernel: MATE-8v8-9's four rounds too
+    // the carried collision screen (near_field) cuts a target's NK = NC + NO bits out of one 64-bit field with `(1ull << NK) - 1` and moves
+    // the camera bits up by `<< NO`: a compiled shape that carries its screen needs fewer than 64 circles (the generic kernels never carry it)
+    static_assert(!(kHoldRoles || kGreedyRoles) || NC + NO < 64, "near_field: a carried screen holds at most 63 circles per target");
     // observation descriptors the fused rollouts hold per lane: all chunks of the shape's rows (up to twelve uint4)
     static constexpr int kRowsC = (NC * (13 + 9 + 5 * NT + 4 * NO + 7 * NC) / 4 + 63) / 64, kRowsT = (NT * (13 + 14 + 7 * NC + 4 * NO + 5 * NT) / 4 + 63) / 64;
     static constexpr int kHeldGC = (kRowsC + kRowsT <= 12) ? kRowsC : 2, kHeldGT = (kRowsC + kRowsT <= 12) ? kRowsT : 6;
@@ -804,7 +807,8 @@ __device__ __forceinline__ void simulate_targets(Ctx<ObsT, L> &c, const StepDraw
             const float nn = (float)c.snorm(tt);
             const float reach = nn + c.erf[j] + 1e-3f;
             const bool far = d2 > reach * reach;
-            if (nn != 0.0f && !far) atomicOr(&c.near(k < 32 ? tt : p.Nt + tt), 1 << (k & 31));
+            // (two words name circles 0 .. 63; the cameras beyond them -- NK goes up to 80 -- are walked unscreened below)
+            if (nn != 0.0f && !far && k < 64) atomicOr(&c.near(k < 32 ? tt : p.Nt + tt), (int32_t)(1u << (k & 31)));
         }
     }
     wave_sync();
@@ -813,6 +817,7 @@ __device__ __forceinline__ void simulate_targets(Ctx<ObsT, L> &c, const StepDraw
     if (is_target) {
         uint64_t todo = (carried || ballot_screen || group_screen) ? todo_carried : ((uint64_t)(uint32_t)c.near(t) | ((uint64_t)(uint32_t)c.near(p.Nt + t) << 32));
         bool n_known = true;
+        const float n0 = (float)n;          // the screen's `nn`: a step of no length touches nothing
         while (todo) {
             const int k = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
@@ -825,6 +830,19 @@ __device__ __forceinline__ void simulate_targets(Ctx<ObsT, L> &c, const StepDraw
             if (n != 0.0 && fma(dy, dy, dx * dx) > reach * reach * (1.0 + 1e-12)) continue;
             obstruct_tangential(ox, oy, vx, vy, n, n_known, cx, cy, cr);
         }
+        // Circles 64 .. NK - 1 (cameras: 1 camera + 64 obstacles is enough) have no bit in `todo`: every one of them goes through
+        // the walk's own exact reach test, behind the screened ones, in index order.  Only the LDS form meets them -- the other
+        // three take NK <= 64 -- and a compiled shape, whose NK is a constant below 64, keeps no trace of this loop.
+        if (!carried && !ballot_screen && !group_screen && n0 != 0.0f)
+            for (int k = 64; k < p.NK; ++k) {
+                double cx, cy, cr;
+                c.circle(k, cx, cy, cr);
+                if (!n_known) { n = norm2(vx, vy); n_known = true; }
+                const double dx = cx - ox, dy = cy - oy;
+                const double reach = n + cr;
+                if (n != 0.0 && fma(dy, dy, dx * dx) > reach * reach * (1.0 + 1e-12)) continue;
+                obstruct_tangential(ox, oy, vx, vy, n, n_known, cx, cy, cr);
+            }
         const double nx = clip_uniform(ox + vx, -kTerrain, kTerrain);   // entities.py:664-666
         const double ny = clip_uniform(oy + vy, -kTerrain, kTerrain);
         const bool colliding = (fabs(nx - desx) > 1e-6) || (fabs(ny - desy) > 1e-6);  // entities.py:668

@@ -311,6 +311,8 @@ def make_trace(name, config, seed, policy, steps, overrides=None, tweak=None, f6
         'max_target_team_episode_reward': np.float64(env.max_target_team_episode_reward),
         'target_step_size': np.float64(env.target_step_size),
     }
+    if overrides and set(overrides) - {'max_episode_steps'}:      # a scenario of its own: the consumers rebuild it from the file + these
+        out['overrides'] = np.str_(json.dumps(overrides, sort_keys=True))
     for k, v in snapshot_static(env).items():
         out['static/' + k] = v
     for k, v in snapshot_dynamic(env).items():
@@ -1039,6 +1041,16 @@ def host_fixture(name='host_reference'):
                         **arrays)
 
 
+def past_64_circles():
+    """Overrides of MATE-2v2-9 for a 2v3-64 scenario: cameras fixed at (-200, -200) and (200, 200), 64 small obstacles on the
+    8 x 8 grid around them, three targets in a box around camera 1."""
+    sites = [(float(x), float(y)) for y in range(-700, 701, 200) for x in range(-700, 701, 200)]
+    return {'shuffle_entities': False,
+            'camera': {'location': [[-200.0, -200.0], [200.0, 200.0]]},
+            'target': {'location_random_range': [[200.0 - 58.0, 200.0 + 58.0, 200.0 - 58.0, 200.0 + 58.0]] * 3},
+            'obstacle': {'location_random_range': [[x - 25.0, x + 25.0, y - 25.0, y + 25.0] for x, y in sites], 'radius_random_range': [6.0, 16.0]}}
+
+
 def main():
     check_binomial_model()
     if sys.argv[1:] == ['host']:
@@ -1137,6 +1149,9 @@ def main():
         ('trace_2v4-0_greedy_s5',    'MATE-2v4-0.yaml',        5, 'greedy',  160, None, None),
         ('trace_2v2-9_random_s6',    'MATE-2v2-9.yaml',        6, 'random',   96, None, None),
         ('trace_1v1-9_greedy_s7',    'MATE-1v1-9.yaml',        7, 'greedy',  128, None, None),
+        # more than 64 circles (2 cameras behind 64 obstacles: circles 64 and 65 of a target's walk), the three targets starting beside
+        # camera 1: pins the ORACLE where the shipped shapes do not reach (tests/shape_edges.py has the geometry)
+        ('trace_2v3-64_random_s8',   'MATE-2v2-9.yaml',        8, 'random',   60, past_64_circles(), None),
     ]
     only = sys.argv[1:]
     for name, config, seed, policy, steps, overrides, tweak in plan:

@@ -13,7 +13,10 @@ STATE_KEYS = ['cam_x', 'cam_y', 'obs_x', 'obs_y', 'obs_radius', 'tgt_capacity', 
 
 
 def config_of_fixture(fx):
-    return read_config(str(fx['config_file']), max_episode_steps=int(fx['max_episode_steps']))
+    """The scenario a trace fixture was recorded with: its file, the overrides of a scenario of its own (2v3-64), its time limit."""
+    import json
+    overrides = json.loads(str(fx['overrides'])) if 'overrides' in fx else {}
+    return read_config(str(fx['config_file']), **dict(overrides, max_episode_steps=int(fx['max_episode_steps'])))
 
 
 def fixture_state(fx, prefix='reset/', index=None):
