@@ -85,7 +85,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -387,6 +387,57 @@ int mate_engine_import_state(mate_engine *engine, const double *src_dev, void *s
  * on-demand form); MATE_ESTATE: before the first reset / import_state. */
 int mate_engine_enable_state_rows(mate_engine *engine, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias);
 int mate_engine_state_rows(mate_engine *engine, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias, void *stream);
+
+/* Shaped per-agent rewards: the reference's AuxiliaryCameraRewards (mate/wrappers/auxiliary_camera_rewards.py:110-176) and
+ * AuxiliaryTargetRewards (mate/wrappers/auxiliary_target_rewards.py:128-203) -- the last wrapper of every example trainer's chain
+ * (examples/<algorithm>/camera/config.py, .../target/config.py) -- with one coefficient per term, written on the device by one launch attached to the engine.
+ * Per agent: the sum, in the order below, of coefficient * term over the terms whose coefficient is not exactly 0 (no fused
+ * multiply-add), then the team's reduction, the reduced value written to every agent's slot.
+ *   camera terms [7]:  raw_reward (scalar column 0), coverage_rate, real_coverage_rate, mean_transport_rate (columns 3, 4, 5: the f32
+ *                      step record widened to f64), soft_coverage_score (the per-camera score of mate_engine_soft_coverage),
+ *                      num_tracked (bits of camera_target_view_mask), baseline (1)
+ *   target terms [10]: raw_reward (column 1), coverage_rate, real_coverage_rate, mean_transport_rate, normalized_goal_distance
+ *                      (distance to the rim of the goal warehouse, without a goal of the nearest non-empty one, with all of them empty
+ *                      half the terrain; over the terrain width), sparse_delivery (the goal differs from the one the previous launch
+ *                      saw, that one was >= 0, same episode: environment.py:1320-1322), soft_coverage_score (the score matrix summed over
+ *                      the cameras that see the target, else tanh of its maximum), is_tracked, is_colliding, baseline (1)
+ * `*_rows_dev`: [N][Nc] / [N][Nt] of `out_dtype` (MATE_OBS_F32 / MATE_OBS_F64, whatever the engine's obs_dtype is), caller-owned; a NULL
+ * team is absent.  `*_terms_dev` (optional, with that team's rows): [N][Nc][7] / [N][Nt][10] f64, every term of the last launch (the
+ * reference's info['auxiliary_reward_<key>']).  `*_coefficients_dev`: DEVICE arrays [7] / [10] f64 the launch reads every time -- a
+ * training-progress schedule rewrites them in place, between the replays of a captured graph too.  `soft_coverage` != 0: the
+ * soft_coverage_score terms exist -- every reward launch is preceded by the soft-coverage launch into engine-owned buffers (needs
+ * cameras and mate_engine_enable_outer_boundary); without it that term reads NaN, which a non-zero coefficient carries into the row.
+ * `accumulate` != 0: rows += shaped instead of rows = shaped (FrameSkip's sum over per-step launches; the caller zeroes the rows when
+ * it consumes them).
+ *
+ * While attached (NULL `config` detaches):
+ *   step / step_random / step_greedy / step_versus_greedy and the fused rollout_* (there: state and scalar / mask rows of the launch's
+ *   LAST frame, sparse_delivery against the previous reward launch) enqueue the reward launch BEHIND the stepping launch and AHEAD of the
+ *   restart of finished episodes: the rows describe the step `scalars_dev` describes, the terminal one included, under every
+ *   auto_reset.  These calls then need io->scalars_dev and io->masks_dev (MATE_EINVAL otherwise).  An environment whose scalar record
+ *   says done = 2 (idling under a batched restart) contributes nothing: zero rows, nothing added when accumulating.
+ *   Behind every restart launch the engine issues (immediate, batched, a flushed interval) and behind reset / reset_tape / import_state
+ *   one more launch refreshes only the goals / episode the next sparse_delivery is measured against.  observe: no launch.
+ *   With state rows attached too: stepping launch, reward launch, restart, refresh, state rows last.
+ *   Pipelined restarts (MATE_RESET_PIPELINED / -m) return MATE_ESTATE, as with state rows.
+ * No allocation, no synchronisation, the same arguments at every call: an interval captured under mate_engine_device_tick contains the
+ * launches.  Enabling itself waits for the handle's launches in flight and runs one refresh launch.
+ * MATE_ESTATE: before the first reset / import_state; soft_coverage without the outer boundary.  MATE_EINVAL: no team, a camera team
+ * (or soft_coverage) in a scenario without cameras, rows without coefficients, terms without rows, a misaligned buffer, an unknown
+ * out_dtype or reduction (MATE_REDUCE_MIN is the camera wrapper's alone). */
+enum { MATE_REDUCE_NONE = 0, MATE_REDUCE_MEAN = 1, MATE_REDUCE_SUM = 2, MATE_REDUCE_MAX = 3, MATE_REDUCE_MIN = 4 };
+#define MATE_CAMERA_REWARD_TERMS 7
+#define MATE_TARGET_REWARD_TERMS 10
+typedef struct mate_reward_rows {
+    void *camera_rows_dev, *target_rows_dev;
+    double *camera_terms_dev, *target_terms_dev;
+    int32_t out_dtype;
+    int32_t camera_reduction, target_reduction;
+    int32_t accumulate;
+    int32_t soft_coverage;
+    const double *camera_coefficients_dev, *target_coefficients_dev;
+} mate_reward_rows;
+int mate_engine_enable_reward_rows(mate_engine *engine, const mate_reward_rows *config);
 
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,

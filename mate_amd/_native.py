@@ -7,7 +7,7 @@ module raises, and every engine call that returns a non-zero status raises
 import ctypes
 import os
 
-__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
+__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'MateRewardRows', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
 
 LIB_PATH = os.environ.get('MATE_ENGINE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libmate_engine.so')
 
@@ -15,7 +15,7 @@ EXPORTED_SYMBOLS = (
     'mate_engine_last_error', 'mate_engine_abi_version', 'mate_engine_create', 'mate_engine_destroy',
     'mate_engine_get_layout', 'mate_engine_set_obs_transform', 'mate_engine_set_obs_mode', 'mate_engine_set_action_grids', 'mate_engine_seed', 'mate_engine_reset', 'mate_engine_reset_tape', 'mate_engine_step', 'mate_engine_device_tick', 'mate_engine_set_episode_stats', 'mate_engine_snapshot_episode_stats', 'mate_engine_step_random',
     'mate_engine_rollout_random', 'mate_engine_policy_enable', 'mate_engine_step_greedy', 'mate_engine_step_versus_greedy', 'mate_engine_rollout_greedy', 'mate_engine_rollout_versus_greedy', 'mate_engine_policy_actions',
-    'mate_engine_observe', 'mate_engine_export_state', 'mate_engine_import_state', 'mate_engine_enable_state_rows', 'mate_engine_state_rows', 'mate_engine_lut_read',
+    'mate_engine_observe', 'mate_engine_export_state', 'mate_engine_import_state', 'mate_engine_enable_state_rows', 'mate_engine_state_rows', 'mate_engine_enable_reward_rows', 'mate_engine_lut_read',
     'mate_engine_block_alloc', 'mate_engine_block_free', 'mate_engine_block_probe', 'mate_engine_set_store_form',
     'mate_engine_memory_hold', 'mate_engine_memory_release', 'mate_engine_hbm_probe', 'mate_engine_set_sub_wave',
     'mate_engine_lut_write', 'mate_engine_enable_outer_boundary', 'mate_engine_lut_read_outer', 'mate_engine_lut_write_outer', 'mate_engine_soft_coverage', 'mate_engine_rebuild_luts', 'mate_engine_idle_steps', 'mate_engine_kernel_time', 'mate_engine_last_flow',
@@ -71,6 +71,17 @@ class MateStepIO(ctypes.Structure):
     ]
 
 
+class MateRewardRows(ctypes.Structure):
+    """mate_reward_rows: the attachment of the shaped-reward launch (mate_engine_enable_reward_rows)."""
+    _fields_ = [
+        ('camera_rows_dev', ctypes.c_void_p), ('target_rows_dev', ctypes.c_void_p),
+        ('camera_terms_dev', ctypes.c_void_p), ('target_terms_dev', ctypes.c_void_p),
+        ('out_dtype', ctypes.c_int32), ('camera_reduction', ctypes.c_int32), ('target_reduction', ctypes.c_int32),
+        ('accumulate', ctypes.c_int32), ('soft_coverage', ctypes.c_int32),
+        ('camera_coefficients_dev', ctypes.c_void_p), ('target_coefficients_dev', ctypes.c_void_p),
+    ]
+
+
 lib = None
 
 
@@ -116,6 +127,7 @@ def load():
     handle.mate_engine_import_state.argtypes = [P, P, P]
     handle.mate_engine_enable_state_rows.argtypes = [P, P, I32, P, P]
     handle.mate_engine_state_rows.argtypes = [P, P, I32, P, P, P]
+    handle.mate_engine_enable_reward_rows.argtypes = [P, ctypes.POINTER(MateRewardRows)]
     handle.mate_engine_lut_read.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_lut_read_outer.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_enable_outer_boundary.argtypes = [P, ctypes.POINTER(I32)]

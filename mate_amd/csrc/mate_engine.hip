@@ -21,6 +21,7 @@
 #include "policy_kernels.hpp"
 #include "aux_kernels.hpp"
 #include "state_rows.hpp"
+#include "reward_rows.hpp"
 
 using namespace mate;
 
@@ -176,6 +177,12 @@ struct mate_engine {
     void *d_state_ab = nullptr, *d_state_ab_demand = nullptr;
     const void *state_ab = nullptr;
     std::vector<double> state_demand_table;      // scale[S] | bias[S] | type, as uploaded to d_state_ab_demand
+    // shaped reward rows (mate_engine_enable_reward_rows): the attached launch's arguments (scalars, masks and mode are the launch's own),
+    // the row type, whether the soft-coverage launch goes in front, and the engine-owned buffers (kept across re-attachments)
+    bool reward_on = false, reward_f64 = false, reward_soft = false, reward_accumulate = false;
+    RewardArgs reward{};
+    int32_t *d_reward_snapshot = nullptr;
+    double *d_reward_matrix = nullptr, *d_reward_scores = nullptr;
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -818,6 +825,92 @@ extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out
     return launch_state_rows(e, dst_dev, f64, scale ? e->d_state_ab_demand : nullptr, (hipStream_t)stream);
 }
 
+// ---- shaped reward rows (csrc/reward_rows.hpp)
+// One reward_rows_kernel launch (the soft-coverage launch in front where that term exists).  Capturable: no allocation, no
+// synchronisation, the same arguments at every call.
+static int launch_reward_rows(mate_engine *e, int mode, const float *scalars, const uint32_t *masks, hipStream_t stream) {
+    RewardArgs a = e->reward;
+    a.mode = mode; a.scalars = scalars; a.masks = masks;
+    if (mode != REWARD_SNAPSHOT && e->reward_soft) {
+        const int64_t items = e->N * e->p.Nc;
+        hipLaunchKernelGGL(soft_coverage_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream,
+                           (const Params *)e->d_params, (const Ptrs)e->g, masks, e->d_reward_matrix, e->d_reward_scores);
+    }
+    const unsigned blocks = (unsigned)((e->N + kRewardEnvsPerBlock - 1) / kRewardEnvsPerBlock);
+    const size_t lds = (size_t)reward_rows_lds_bytes(e->p.DW);
+    with_obs_type(e->reward_f64, [&](auto tag) {
+        hipLaunchKernelGGL(reward_rows_kernel<decltype(tag)>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g, (const RewardArgs)a);
+    });
+    HIP_TRY(hipGetLastError());
+    return MATE_OK;
+}
+// Ahead of a stepping launch: the reward launch behind it reads the step's scalar record and masks.
+static int check_reward_io(const mate_engine *e, const mate_step_io *io) {
+    if (e->reward_on && (!io || !io->scalars_dev || !io->masks_dev))
+        return fail(MATE_EINVAL, "reward rows are attached (mate_engine_enable_reward_rows): the call needs io->scalars_dev and io->masks_dev");
+    return MATE_OK;
+}
+// Behind a stepping launch, ahead of the restart of what it finished: the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers).
+static int reward_rows_of_step(mate_engine *e, const mate_step_io *io, int frames, hipStream_t stream) {
+    if (!e->reward_on) return MATE_OK;
+    const size_t last = (size_t)(frames - 1) * (size_t)e->N;
+    return launch_reward_rows(e, e->reward_accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
+}
+// Behind a restart launch, a reset or an import: the goals and episodes the next step's sparse_delivery is measured against.
+static int refresh_reward_snapshot(mate_engine *e, int rc, hipStream_t stream) {
+    if (rc != MATE_OK || !e || !e->reward_on) return rc;
+    return launch_reward_rows(e, REWARD_SNAPSHOT, nullptr, nullptr, stream);
+}
+
+extern "C" int mate_engine_enable_reward_rows(mate_engine *e, const mate_reward_rows *cfg) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!cfg) { e->reward_on = false; return MATE_OK; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_reward_rows called before reset() (or import_state)");
+    const Params &p = e->p;
+    const bool f64 = cfg->out_dtype == MATE_OBS_F64;
+    if (cfg->out_dtype != MATE_OBS_F32 && !f64) return fail(MATE_EINVAL, "reward rows: out_dtype must be MATE_OBS_F32 or MATE_OBS_F64");
+    if (!cfg->camera_rows_dev && !cfg->target_rows_dev) return fail(MATE_EINVAL, "reward rows: no team (both row buffers are null)");
+    if (cfg->camera_rows_dev && p.Nc == 0) return fail(MATE_EINVAL, "reward rows: the scenario has no cameras to shape rewards for");
+    if ((cfg->camera_rows_dev && !cfg->camera_coefficients_dev) || (cfg->target_rows_dev && !cfg->target_coefficients_dev))
+        return fail(MATE_EINVAL, "reward rows: a team without its coefficient table");
+    if ((cfg->camera_terms_dev && !cfg->camera_rows_dev) || (cfg->target_terms_dev && !cfg->target_rows_dev))
+        return fail(MATE_EINVAL, "reward rows: term rows without that team's reward rows");
+    const uintptr_t row_align = f64 ? 7u : 3u;
+    auto misaligned = [](const void *ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; };
+    if (misaligned(cfg->camera_rows_dev, row_align) || misaligned(cfg->target_rows_dev, row_align) || misaligned(cfg->camera_terms_dev, 7u) ||
+        misaligned(cfg->target_terms_dev, 7u) || misaligned(cfg->camera_coefficients_dev, 7u) || misaligned(cfg->target_coefficients_dev, 7u))
+        return fail(MATE_EINVAL, "reward rows: a buffer is not aligned to its element size");
+    if (cfg->camera_reduction < MATE_REDUCE_NONE || cfg->camera_reduction > MATE_REDUCE_MIN)
+        return fail(MATE_EINVAL, "reward rows: camera_reduction must be one of MATE_REDUCE_NONE .. MATE_REDUCE_MIN");
+    if (cfg->target_reduction < MATE_REDUCE_NONE || cfg->target_reduction > MATE_REDUCE_MAX)
+        return fail(MATE_EINVAL, "reward rows: target_reduction must be one of MATE_REDUCE_NONE .. MATE_REDUCE_MAX");
+    if (cfg->soft_coverage && p.Nc == 0) return fail(MATE_EINVAL, "reward rows: soft_coverage_score needs cameras");
+    if (cfg->soft_coverage && !e->g.lut_knots_outer) return fail(MATE_ESTATE, "reward rows: soft_coverage_score needs the outer boundary (mate_engine_enable_outer_boundary)");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the arguments while they change)
+    int rc = MATE_OK;
+    if (!e->d_reward_snapshot && (rc = dev_alloc(e, &e->d_reward_snapshot, (size_t)e->N * (p.Nt + 1)))) return rc;
+    if (cfg->soft_coverage && !e->d_reward_matrix) {
+        if ((rc = dev_alloc(e, &e->d_reward_matrix, (size_t)e->N * p.Nc * p.Nt))) return rc;
+        if ((rc = dev_alloc(e, &e->d_reward_scores, (size_t)e->N * p.Nc))) return rc;
+    }
+    mate_layout layout;
+    if ((rc = mate_engine_get_layout(e, &layout))) return rc;
+    RewardArgs a{};
+    a.snapshot = e->d_reward_snapshot;
+    a.cam_rows = cfg->camera_rows_dev; a.tgt_rows = cfg->target_rows_dev;
+    a.cam_terms = cfg->camera_terms_dev; a.tgt_terms = cfg->target_terms_dev;
+    a.cam_coef = cfg->camera_coefficients_dev; a.tgt_coef = cfg->target_coefficients_dev;
+    a.soft_matrix = cfg->soft_coverage ? e->d_reward_matrix : nullptr; a.soft_scores = cfg->soft_coverage ? e->d_reward_scores : nullptr;
+    a.cam_reduction = cfg->camera_reduction; a.tgt_reduction = cfg->target_reduction;
+    a.bit_ct = layout.bit_camera_target;
+    e->reward = a; e->reward_f64 = f64; e->reward_soft = cfg->soft_coverage != 0; e->reward_accumulate = cfg->accumulate != 0;
+    e->reward_on = true;
+    // the goals and episodes of the records as they are: the first step's sparse_delivery is measured against them
+    note_stream(e, e->last_stream);
+    return refresh_reward_snapshot(e, MATE_OK, e->last_stream);
+}
+
 static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
@@ -837,7 +930,7 @@ static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_st
 }
 
 extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
-    return refresh_state_rows(e, reset_impl(e, env_mask_dev, io, stream), stream);
+    return refresh_state_rows(e, refresh_reward_snapshot(e, reset_impl(e, env_mask_dev, io, stream), (hipStream_t)stream), stream);
 }
 
 // reset() with every random draw taken from a tape recorded from the reference (parity runs).
@@ -858,7 +951,7 @@ static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const ma
 
 extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
                                       int32_t tape_len, int32_t *draws_used_dev, void *stream) {
-    return refresh_state_rows(e, reset_tape_impl(e, env_mask_dev, io, tape_dev, tape_len, draws_used_dev, stream), stream);
+    return refresh_state_rows(e, refresh_reward_snapshot(e, reset_tape_impl(e, env_mask_dev, io, tape_dev, tape_len, draws_used_dev, stream), (hipStream_t)stream), stream);
 }
 
 extern "C" int mate_engine_rebuild_luts(mate_engine *e, void *stream) {
@@ -899,7 +992,7 @@ static int flush_pending(mate_engine *e, int auto_reset, int flow_tag, hipStream
     if (rc != MATE_OK) return rc;
     HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
     e->steps_since_reset = 0; e->pending_interval = 0;
-    return MATE_OK;
+    return refresh_reward_snapshot(e, MATE_OK, stream);
 }
 
 // Device-resident step counter: see Params::dev_tick.  enable = k >= 1: the host's tick goes to the device and stays there,
@@ -997,13 +1090,14 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
     const int rc = launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate);
     if (rc != MATE_OK) return rc;
     if (kind == RESET_DONE && !e->dev_tick) e->parity ^= 1;      // (the list is consumed: the next launches append to the other one)
-    return MATE_OK;
+    return refresh_reward_snapshot(e, MATE_OK, stream);      // (new episodes: their goals are what the next step's sparse_delivery compares with)
 }
 
 static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
     if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
+    if (mode != MODE_OBSERVE) { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     if (mode != MODE_OBSERVE) { int rc = flush_pending(e, auto_reset, kStepFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
@@ -1041,6 +1135,7 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     HIP_TRY(hipGetLastError());
     if (mode == MODE_OBSERVE) return MATE_OK;
     if (!e->dev_tick) e->tick += 1;
+    { const int rc_ = reward_rows_of_step(e, io, 1, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
     // (the restart writes the caller's observation buffers and masks; the immediate one, idle almost always, stays ONE launch, and so
     // does the interval's unless the on-device agents play: their ~1.2 k-step episodes finish somewhere in the batch all the time)
     return restart_finished(e, auto_reset, Restart{io, true, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, false, e->greedy_team_bits != 0, 1u, kStepFlow}, stream);
@@ -1073,6 +1168,7 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     { const int rc_ = enter(e, stream, "rollout"); if (rc_ != MATE_OK) return rc_; }
     if (e->dev_tick) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
+    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset, kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
@@ -1094,6 +1190,7 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     hipExtLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
+    { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
     // (state only, placement and tables: the next rollout observes the fresh episode on its first step)
     return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, PH_PLACE | PH_LUT, false, false, 0u, kRolloutFlow}, stream);
 }
@@ -1179,6 +1276,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     // (pipelined restarts still in flight rewrite records, masks and `done` tags on the side stream: the agents' kernel of the
     // two-launch form reads all three, so the mode is left HERE, not only in launch_step behind it)
     { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone)
     // One launch (agents + step fused, rollout_greedy_kernel with one step) unless something needs the two-launch form: recorded
     // agent draws, tapes of the step itself, fused observation post-processing, a missing output, a workgroup that does not fit
     if (e->policy_ready && e->was_reset && !e->sw.policy_split && !tape && io && !io->tape_camera_target_dev && !io->tape_goal_dev &&
@@ -1253,6 +1351,8 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (pipelined && (per_step || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
     // (the restarts run on the engine's side stream UNDER the next launches: a state-row launch on the caller's stream would read records they rewrite)
     if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
+    if (pipelined && e->reward_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while reward rows are attached (mate_engine_enable_reward_rows): detach them first");
+    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset, per_step ? kStepFlow : kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
@@ -1315,6 +1415,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     launch(fn, dim3(blocks), dim3(256), lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     if (!e->dev_tick) e->tick += (uint32_t)steps;
+    { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
     const int full = PH_PLACE | PH_LUT | PH_VIEW;
     // per-step: list-driven restarts that write the restarted environments' first observations into the caller's buffers (not its
     // actions' encoding); the immediate one, idle almost always, stays ONE launch, the interval's is split: placement / tables / view
@@ -1388,7 +1489,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     HIP_TRY(hipMemcpy(&tick, reinterpret_cast<const int32_t *>(e->g.dyn + e->p.DF) + e->p.Nt * TI_STRIDE + EI_TICK, sizeof(tick), hipMemcpyDeviceToHost));
     e->tick = (uint32_t)tick;
     e->was_reset = true;
-    return refresh_state_rows(e, MATE_OK, stream);
+    return refresh_state_rows(e, refresh_reward_snapshot(e, MATE_OK, (hipStream_t)stream), stream);
 }
 
 // One camera's knot table (inner or outer boundary) to the host / from the host.  `who`: the entry point's name in the messages.

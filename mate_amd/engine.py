@@ -10,9 +10,9 @@ import numpy as np
 import torch
 
 from mate_amd import _native
-from mate_amd._native import MateConfig, MateLayout, MatePolicyTape, MateStepIO, check
+from mate_amd._native import MateConfig, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 
-__all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'SCALAR_NAMES']
+__all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'SCALAR_NAMES', 'REWARD_REDUCTIONS']
 
 SCALAR_NAMES = ('camera_team_reward', 'target_team_reward', 'done', 'coverage_rate', 'real_coverage_rate',
                 'mean_transport_rate', 'num_delivered_cargoes', 'normalized_target_team_reward')
@@ -35,6 +35,37 @@ def export_layout(Nc, Nt, No):
         layout[name] = (off, shape)
         off += int(np.prod(shape)) if shape else 1
     return layout, off
+
+
+REWARD_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2, 'max': 3, 'min': 4}      # MATE_REDUCE_* (include/mate_engine.h)
+
+
+def reward_term_keys(team):
+    """The terms of a team's shaped reward in the order of its coefficient table (mate_engine_enable_reward_rows): the key tuples of
+    the torch shapers, BatchedMultiAgentTracking.AUXILIARY_REWARD_KEYS and AuxiliaryTargetRewards.ACCEPTABLE_KEYS."""
+    assert team in ('camera', 'target')
+    if team == 'camera':
+        from mate_amd.environment import BatchedMultiAgentTracking
+        return BatchedMultiAgentTracking.AUXILIARY_REWARD_KEYS
+    from mate_amd.auxiliary_rewards import AuxiliaryTargetRewards
+    return AuxiliaryTargetRewards.ACCEPTABLE_KEYS
+
+
+def reward_coefficient_table(team, coefficients, reduction='none'):
+    """(coefficients in the order of the team's key tuple, absent keys 0.0; MATE_REDUCE_* code) of one team's (coefficients, reduction),
+    with the key and reduction assertions of the torch shapers (the reference wrappers' messages)."""
+    keys = reward_term_keys(team)
+    if team == 'camera':
+        assert reduction in ('mean', 'sum', 'max', 'min', 'none'), f'Invalid reduction method {reduction}.'
+    else:                                                # auxiliary_target_rewards.py:84-88 (no 'min' there)
+        assert reduction in ('mean', 'sum', 'max', 'none'), (
+            f'Invalid reduction method {reduction}. The reduction method should be one of ("mean", "sum", "max") (for shared reward), '
+            f'or "none" for no reduction (for individual reward).')
+    assert set(keys).issuperset(coefficients.keys()), (
+        f'The coefficient mapping only accepts keys in {keys}. Got list(coefficients.keys()) = {list(coefficients.keys())}.')
+    for key, coefficient in coefficients.items():
+        assert isinstance(coefficient, (int, float)), f'only constant coefficients are supported on the batched path (got {key!r}: {coefficient!r})'
+    return [float(coefficients.get(key, 0.0)) for key in keys], REWARD_REDUCTIONS[reduction]
 
 
 class Engine:
@@ -106,6 +137,10 @@ class Engine:
         check(self.lib.mate_engine_set_episode_stats(self._h, ctypes.c_void_p(self.episode_stats.data_ptr())))
         self.state_dim = layout.state_dim
         self.state = None                 # [N, state_dim] while state rows are attached (enable_state_rows)
+        # while reward rows are attached (enable_reward_rows): [N, Nc] / [N, Nt] shaped rewards, [N, Nc, 7] / [N, Nt, 10] f64 terms,
+        # and the two coefficient tables on the device ({'camera': [7], 'target': [10]} f64)
+        self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
+        self.reward_coefficients = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -557,6 +592,65 @@ class Engine:
         check(self.lib.mate_engine_state_rows(self._h, ctypes.c_void_p(out.data_ptr()), int(out.dtype == torch.float64), scale, bias, self._stream()))
         return out
 
+    # ------------------------------------------------------------------ shaped reward rows (AuxiliaryCameraRewards / AuxiliaryTargetRewards)
+    def enable_reward_rows(self, camera=None, target=None, dtype=torch.float64, accumulate=False, terms=False):
+        """Keep the shaped per-agent rewards of the reference's AuxiliaryCameraRewards / AuxiliaryTargetRewards wrappers current on
+        the device: `camera` / `target` = (coefficients dict, reduction) per team (None: that team is absent), as the torch shapers
+        take them.  From now on every step / step_random / step_greedy / step_versus_greedy / fused rollout enqueues one more launch
+        behind the stepping launch and AHEAD of the restart of finished episodes, which writes `camera_reward_rows` [N, Nc] and
+        `target_reward_rows` [N, Nt] (`dtype`: float64 / float32) -- the rows describe the step `scalars` describes, the terminal one
+        included, under every auto_reset -- and, with `terms`, every term into `camera_reward_terms` [N, Nc, 7] /
+        `target_reward_terms` [N, Nt, 10] (f64; the order of AUXILIARY_REWARD_KEYS / ACCEPTABLE_KEYS: the reference's
+        info['auxiliary_reward_<key>']).  `accumulate`: rows += shaped (FrameSkip's sum over per-step launches; zero the rows with
+        `.zero_()` when consumed).  `reward_coefficients` = {'camera': [7], 'target': [10]} f64 device tensors the launch reads every
+        time: writing into them in place applies a training-progress schedule, between the replays of a captured graph too.
+
+        Call after the first reset(); a Stepper built afterwards captures the launches.  The stepping calls then need their masks
+        output (step_random(want_masks=True), rollouts with want_masks=True).  Constant coefficients only: the reference's callable
+        coefficients of (agent_id, episode_id, episode_step, ...) differ per environment and are out of scope.  A fused K-frame
+        rollout leaves the rows of its LAST frame (sparse_delivery against the previous reward launch): per-frame shaped rewards
+        inside one launch are out of scope -- FrameSkip with shaped rewards is K per-step launches in a graph with accumulate=True.
+        Returns (camera_reward_rows, target_reward_rows)."""
+        assert camera is not None or target is not None, 'enable_reward_rows needs at least one team'
+        assert dtype in (torch.float32, torch.float64)
+        tables = {team: reward_coefficient_table(team, *spec) for team, spec in (('camera', camera), ('target', target)) if spec is not None}
+        soft = any('soft_coverage_score' in spec[0] for spec in (camera, target) if spec is not None)
+        if soft:
+            assert self.num_cameras > 0, 'soft_coverage_score needs cameras (the reference takes a max over them)'
+            if not getattr(self, 'outer_capacity', 0):
+                self.enable_outer_boundary()         # built at every reset from now on; once now for the running episodes
+                self.rebuild_luts()
+        N, agents, widths = self.num_envs, {'camera': self.num_cameras, 'target': self.num_targets}, {'camera': 7, 'target': 10}
+        cfg = MateRewardRows()
+        cfg.out_dtype, cfg.accumulate, cfg.soft_coverage = int(dtype == torch.float64), int(bool(accumulate)), int(soft)
+        rows, term_rows, coefficients = {}, {}, {}
+        with torch.cuda.device(self.device):
+            for team, (table, reduction) in tables.items():
+                # (a team without agents keeps a non-null pointer: the engine refuses it by name instead of taking it for absent)
+                # (an empty view reports a null data_ptr(): the pointer is the buffer's own)
+                buffer = torch.zeros(max(N * agents[team], 1), dtype=dtype, device=self.device)
+                rows[team] = buffer[:N * agents[team]].view(N, agents[team])
+                coefficients[team] = torch.tensor(table, dtype=torch.float64, device=self.device)
+                setattr(cfg, team + '_rows_dev', buffer.data_ptr())
+                setattr(cfg, team + '_coefficients_dev', coefficients[team].data_ptr())
+                setattr(cfg, team + '_reduction', reduction)
+                if terms:
+                    term_rows[team] = torch.zeros((N, agents[team], widths[team]), dtype=torch.float64, device=self.device)
+                    setattr(cfg, team + '_terms_dev', term_rows[team].data_ptr() or None)
+        torch.cuda.current_stream(self.device).synchronize()      # (the tables are on the device before the engine's first launch reads them)
+        check(self.lib.mate_engine_enable_reward_rows(self._h, ctypes.byref(cfg)))
+        self.camera_reward_rows, self.target_reward_rows = rows.get('camera'), rows.get('target')
+        self.camera_reward_terms, self.target_reward_terms = term_rows.get('camera'), term_rows.get('target')
+        self.reward_coefficients = coefficients
+        self.__dict__.pop('_random_io', None)
+        return self.camera_reward_rows, self.target_reward_rows
+
+    def disable_reward_rows(self):
+        """Detach the reward rows: the calls go back to their launch sequence without them; the tensors become None."""
+        check(self.lib.mate_engine_enable_reward_rows(self._h, None))
+        self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
+        self.reward_coefficients = None
+
     # One copy per step for the N = 1 NumPy API (mate_amd.environment): the output tensors and an export_state buffer become views of
     # ONE device allocation, and fetch_host() brings a step's results over in a single transfer (five blocking copies of a few KB each
     # were a third of that API's 250 us per step).
@@ -762,11 +856,12 @@ class Stepper:
             'action tensors must be contiguous f32/f64 (or int32 grid indices) on the engine device'
         self.outputs = None
         if self.frame_skip > 1:
-            buf = eng.reserve_rollout(self.frame_skip)
+            shaped = eng.reward_coefficients is not None      # (the reward launch reads the last frame's masks)
+            buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
             self.io.camera_obs_dev = buf['camera_obs'].data_ptr() if eng.num_cameras else None
             self.io.target_obs_dev = buf['target_obs'].data_ptr()
             self.io.scalars_dev = buf['scalars'].data_ptr()
-            self.io.masks_dev = None
+            self.io.masks_dev = buf['masks'].data_ptr() if shaped else None
             self.outputs = (buf['camera_obs'][:self.frame_skip], buf['target_obs'][:self.frame_skip], buf['scalars'][:self.frame_skip])
             self.keep = (self.keep, buf)
         self.ref = ctypes.byref(self.io)
@@ -821,6 +916,14 @@ class Stepper:
         """The engine's state rows ([N, state_dim]) when it has them attached (Engine.enable_state_rows BEFORE the stepper is built, so
         that the captured intervals contain the launch): the same tensor, refreshed by every step and every replay; else None."""
         return self.eng.state
+
+    # The engine's shaped reward rows when it has them attached (Engine.enable_reward_rows BEFORE the stepper is built, so that the
+    # captured intervals contain the launches): the same tensors, rewritten (or, accumulating, added to) by every step and every replay.
+    camera_reward_rows = property(lambda self: self.eng.camera_reward_rows)
+    target_reward_rows = property(lambda self: self.eng.target_reward_rows)
+    camera_reward_terms = property(lambda self: self.eng.camera_reward_terms)
+    target_reward_terms = property(lambda self: self.eng.target_reward_terms)
+    reward_coefficients = property(lambda self: self.eng.reward_coefficients)
 
     def close(self):
         if self.graph is not None:

@@ -629,11 +629,16 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         (cam_obs, tgt_obs), (r_cam, r_tgt), done, info = env.step((cam_act, tgt_act))
 
     `first_env_index` makes the RNG streams of a shard equal to those of the same environments in a
-    larger single-GPU batch (sharding invariance)."""
+    larger single-GPU batch (sharding invariance).
+
+    `camera_reward_shaping` / `target_reward_shaping` = (coefficients, reduction): the reference's AuxiliaryCameraRewards /
+    AuxiliaryTargetRewards wrappers as one device launch behind every stepping call; `shaped_rewards()`
+    returns the two tensors ([num_envs, agents], `reward_dtype`).  What step() and the rest return does not change."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
-                 discrete_camera_levels=None, discrete_target_levels=None, state_rows=False, **kwargs):
+                 discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
+                 camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
@@ -662,6 +667,14 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         self.state_rows = state_rows
         if state_rows == 'normalized':
             self.state_space = consts.normalized_state_space_of(self.num_cameras, self.num_targets, self.num_obstacles)
+        # AuxiliaryCameraRewards / AuxiliaryTargetRewards (the last wrapper of the example trainers' chains) as a launch attached to the
+        # engine: (coefficients, reduction) per team, checked now, attached behind the first reset() (Engine.enable_reward_rows)
+        from mate_amd.engine import reward_coefficient_table
+        self._reward_shaping = {team: (dict(spec[0]), spec[1]) for team, spec in (('camera', camera_reward_shaping), ('target', target_reward_shaping))
+                                if spec is not None}
+        for team, spec in self._reward_shaping.items():
+            reward_coefficient_table(team, *spec)
+        self._reward_dtype = reward_dtype
 
     def seed(self, seed):
         self.engine.seed(int(seed))
@@ -675,10 +688,18 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             return self.engine.state
         return self.engine.state_rows(normalize=self.state_rows == 'normalized')
 
+    def shaped_rewards(self):
+        """(camera rows [num_envs, num_cameras], target rows [num_envs, num_targets]) of the step that last ran -- the shaped rewards of
+        `camera_reward_shaping` / `target_reward_shaping` (None for a team without one), written on the device behind every stepping
+        call and ahead of the auto-reset: the terminal step's rewards too.  The same tensors every time, from the first reset() on."""
+        return self.engine.camera_reward_rows, self.engine.target_reward_rows
+
     def reset(self, env_mask=None):
         out = self.engine.reset(env_mask)
         if self.state_rows and self.engine.state is None:      # (rows attach to records that exist: from the first reset on)
             self.engine.enable_state_rows(normalize=self.state_rows == 'normalized')
+        if self._reward_shaping and self.engine.reward_coefficients is None:
+            self.engine.enable_reward_rows(camera=self._reward_shaping.get('camera'), target=self._reward_shaping.get('target'), dtype=self._reward_dtype)
         for shaper in self.__dict__.get('_target_shapers', {}).values():
             shaper.observe_reset()
         return out
@@ -696,7 +717,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def step_random(self):
         """One step under the on-device uniform random policy (no action tensors)."""
-        self.engine.step_random(auto_reset=self.auto_reset)
+        self.engine.step_random(auto_reset=self.auto_reset, want_masks=bool(self._reward_shaping))
         return self._result()
 
     def _rollout_result(self, out):
@@ -709,14 +730,14 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     def rollout_random(self, steps):
         """`steps` env.step(random action) iterations in ONE launch (the fastest flow, profiles/HISTORY.md 3.1b): every tensor of
         step()'s result with a leading [steps] axis.  Finished episodes restart after the launch."""
-        return self._rollout_result(self.engine.rollout_random(steps, auto_reset=int(self.auto_reset)))
+        return self._rollout_result(self.engine.rollout_random(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def rollout_greedy(self, steps):
         """`steps` iterations of mate.group_step with the reference's Greedy camera / target agents + env.step in ONE
         launch (agents on the device, profiles/HISTORY.md 3.1c)."""
         if not getattr(self, '_policies_on', False):
             raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
-        return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset)))
+        return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def enable_greedy_policies(self):
         self.engine.enable_policies()
@@ -737,7 +758,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         result; `rewards.sum(0)` is the wrapper's reward, `done.any(0)` its done."""
         if not getattr(self, '_policies_on', False):
             raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
-        return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset)))
+        return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def masks(self):
         return self.engine.unpack_masks()
