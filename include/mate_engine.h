@@ -517,8 +517,10 @@ int mate_engine_block_probe(int32_t device, void *block, int64_t bytes, int32_t 
  * own number in every fused launch; 2 (the default; MATE_SUBWAVE=0 / MATE_SUBWAVE=1 in the environment make 0 / 1 the default) = where it measured faster:
  * batches of at least 32 environments per compute unit, and under the random policy every such shape but MATE-4v4-* (whose
  * one-per-wave rollout, carried by the register-resident row image, is as fast); negative = leave it as it is.  `*in_use` (may be NULL) receives
- * the number the Greedy rollouts of this engine now run with (1 for a shape without such kernels).  Takes effect from the next launch
- * on; no state changes. */
+ * the number ONE flow now runs with: the fused Greedy rollouts (mate_engine_rollout_greedy / _rollout_versus_greedy), exactly as their launch is
+ * planned, the fit of the sub-wave workgroup in the LDS included (1 for a shape without such kernels).  The other flows decide on top of it: the
+ * random-policy flows and mate_engine_step / _step_random keep one per wave for MATE-4v4-* in mode 2 and for MATE-4v8-0 always, the per-step
+ * flows follow MATE_STEP_SUBWAVE, f64 observations always run one per wave.  Takes effect from the next launch on; no state changes. */
 int mate_engine_set_sub_wave(mate_engine *engine, int32_t enable, int32_t *in_use);
 /* The HBM rates of THIS GPU as this library's own streaming kernels see them (the yardsticks beside the vendor peak in bench.py's
  * roofline object): `mode` 0 = read `src` and write `dst` (read + write bytes counted), 1 = write `dst` only (non-temporal stores, as the row

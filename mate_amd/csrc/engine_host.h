@@ -1,0 +1,185 @@
+// engine_host.h -- the host's state of one engine (struct mate_engine, the environment switches) and the launch plans: the pure decisions over
+// that state of which kernel a stepping entry point runs, on how many workgroups, with how much LDS.  Host only: included by mate_engine.hip, never
+// by the shape-group translation units; nothing here calls HIP.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/mate_engine.h"
+#include "reset_kernels.hpp"
+#include "reward_rows.hpp"
+#include "shape_groups.hpp"
+
+using namespace mate;
+
+constexpr size_t kLdsCeiling = 160 * 1024;     // LDS one workgroup can have: what a launch's static + dynamic bytes must fit
+
+// Environment switches (all read ONCE, in mate_engine_create; documented in include/mate_engine.h).
+struct Switches {
+    bool generic = false;          // MATE_GENERIC=1: generic (AnyShape) kernels even for a shape with a compiled specialisation
+    bool flow_generic = false;     // MATE_FLOW_GENERIC=1: every launch runs the FLOW_ANY kernel
+    int stagger = -1;              // MATE_STAGGER=<5 digits>: per-phase wave priorities of step_kernel (-1: by batch size)
+    int lut_small_cap = 0;         // MATE_LUT_SMALL_CAP=<rays>: sort-array size of the small-LDS table launch (0: half the full size)
+    bool reset_monolithic = false; // MATE_RESET_MONOLITHIC=1: resets as one launch instead of placement / tables / view
+    int rollout_rotate = 1;        // MATE_ROLLOUT_ROTATE=0: no wave-priority rotation in the fused rollouts
+    bool no_image = false;         // MATE_NO_IMAGE=1: the fused rollouts pack observations through the descriptor table even where the row-image compilation exists
+    bool policy_split = false;     // MATE_POLICY_SPLIT=1: step_greedy / step_versus_greedy as two launches (agents' kernel, step kernel) even when the fused one-launch form applies
+    int step_split = -1;           // MATE_STEP_SPLIT=0 / 1: the one-wave / two-wave form of the per-step kernel in the folded flows (-1: by batch size)
+    bool zoom_iterate = false;     // MATE_ZOOM_ITERATE=1: the greedy camera agents iterate the zoom solve (greedy.py:139-145) instead of reading its table
+    bool step_sub_wave = true;     // MATE_STEP_SUBWAVE=0: the per-step Greedy flows of the small scenarios stay on step_greedy_kernel where the fused ones run sub-wave groups
+    int sub_wave_mode = 2;         // MATE_SUBWAVE=0 / 1: one environment per wave in the fused rollouts of the small scenarios too / the shape's number in EVERY fused launch (default 2: where it measured faster, sub_wave_of_launch).  The one switch that changes after create: mate_engine_set_sub_wave
+    bool step_greedy_rollout = false;   // MATE_STEP_GREEDY_ROLLOUT=1: the one-launch form of step_greedy / step_versus_greedy on rollout_greedy_kernel with one step (round 3) instead of step_greedy_kernel
+    bool pipelined_low_priority = true; // MATE_PIPELINED_PRIORITY=0: the side stream of the pipelined restarts at the default priority instead of the device's lowest
+    bool pipelined_serial = false;      // MATE_PIPELINED_SERIAL=1: the pipelined-restart protocol with the resets on the CALLER's stream (the tests' reference)
+};
+struct mate_engine {
+    Switches sw{};
+    hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
+    bool launched = false, multi_stream = false;   // ... unless launches went to more than one stream since the last wait (then: the device)
+    Params p{};
+    Params *d_params = nullptr;   // device copy read by the kernels
+    Ptrs g{};
+    ResetLds rl{};
+    ResetLds rl_small{};       // two-tier table launches (launch_reset): the layout with half-size sort arrays; sort_cap 0 = off
+    mate_config cfg{};
+    int device = 0;
+    int64_t N = 0;
+    int parity = 0;
+    uint32_t tick = 0;         // Philox tick of the next step launch
+    int64_t steps_since_reset = 0;   // batched auto-reset bookkeeping
+    bool was_reset = false;
+    bool dev_tick = false;     // mate_engine_device_tick: the step counter lives on the device (graph-replayable launches)
+    int dev_frames = 1;        // ... frames per launch of the reset interval in progress (1: the per-step flows; K: FrameSkip launches, rollout_versus_greedy)
+    int dev_interval = 1;      // ... and the auto-reset interval every step() must then use
+    int pending_interval = 0;  // auto_reset value of the batched-reset interval in progress (steps_since_reset > 0)
+    // pipelined restarts (mate_engine_rollout_greedy with auto_reset = MATE_RESET_PIPELINED): the side stream the resets run on, the
+    // event behind the last rollout launch, one event per list parity behind the reset that consumed that list
+    bool pipelined = false;          // records may carry "restarted" tags (Ptrs::pipelined): leave_pipelined() before anything else runs
+    int pipe_every = 1, pipe_count = 0;   // ... one restart launch behind every pipe_every-th rollout launch (auto_reset = -pipe_every); launches into the interval
+    hipStream_t side = nullptr;
+    hipEvent_t ev_launch = nullptr, ev_reset[2] = {nullptr, nullptr};
+    bool reset_in_flight[2] = {false, false};
+    size_t step_lds = 0, reset_lds = 0;
+    KernelSet k{};                 // kernels chosen at create (pick_kernels): shape-specialised when compiled for these counts
+    size_t image_wave_bytes = 0;   // per-environment LDS slice of the row-image rollout (k.image), else of the plain one
+    int64_t cus = 256;             // compute units of the device
+    int split_on = 0;              // launch_step uses k.split (MATE_STEP_SPLIT, or the batch is one resident generation)
+    int last_flow = 0;
+    std::vector<void *> allocs;
+    // on-device rule-based policies (mate_engine_step_greedy)
+    bool policy_ready = false;
+    PolicyPtrs q{};
+    int greedy_team_bits = 0;  // during mate_engine_step_greedy / _step_versus_greedy: teams whose joint action the policy kernel wrote
+    // observation post-processing fused into the packer (set_obs_mode / set_obs_transform)
+    int cam_mode = 0, tgt_mode = 0;
+    bool xf_relative = false, xf_cam = false, xf_tgt = false;
+    std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
+    uint2 *d_xdesc = nullptr;
+    void *d_xab = nullptr;
+    // global state rows (mate_engine_enable_state_rows): the caller's [N][S] buffer every record-changing call refreshes, its type,
+    // its (scale, bias) table on the device (null: raw rows); and the table of the last on-demand call (mate_engine_state_rows)
+    void *state_dst = nullptr;
+    bool state_f64 = false;
+    void *d_state_ab = nullptr, *d_state_ab_demand = nullptr;
+    const void *state_ab = nullptr;
+    std::vector<double> state_demand_table;      // scale[S] | bias[S] | type, as uploaded to d_state_ab_demand
+    // shaped reward rows (mate_engine_enable_reward_rows): the attached launch's arguments (scalars, masks and mode are the launch's own),
+    // the row type, whether the soft-coverage launch goes in front, and the engine-owned buffers (kept across re-attachments)
+    bool reward_on = false, reward_f64 = false, reward_soft = false, reward_accumulate = false;
+    RewardArgs reward{};
+    int32_t *d_reward_snapshot = nullptr;
+    double *d_reward_matrix = nullptr, *d_reward_scores = nullptr;
+    // kernel timing (HIP events on the launch stream)
+    int timing = 0;            // 0 = off, k = time every k-th step launch
+    int64_t timing_tick = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    size_t events_used = 0;
+};
+
+// ---- launch plans
+// What a stepping entry point launches is decided HERE, as a value, by three pure functions of the engine (and of the call's record pointers where
+// the flow depends on them): no HIP call, no allocation, nothing written, no environment variable read.  Everything else reads the plan: the launch
+// sites launch it, policy_enable opts in what plan_with_policies can return, step_with_policies asks whether it fits, set_sub_wave reports its E.
+struct LaunchPlan {
+    StepFn step = nullptr; PolicyFn policy = nullptr;      // the kernel: of launch_step and rollout_random_impl, or of rollout_with_policies
+    int E = 1;                                             // environments per wave (engine_kernels.hpp, Ctx<ObsT, L>)
+    unsigned blocks = 0, threads = 256;
+    size_t lds = 0;                                        // dynamic LDS per workgroup
+    int last_flow = FLOW_ANY;                              // what mate_engine_last_flow reports behind the launch
+    bool fits() const { return lds <= kLdsCeiling; }
+};
+static unsigned blocks_of(const mate_engine *e, int envs_per_block) { return (unsigned)((e->N + envs_per_block - 1) / envs_per_block); }
+
+// Environments per wave the sub-wave kernels of a flow run with: the shape's E = 4 (2: MATE-4v8-0's Greedy flows) where they exist and
+//   mode 1: always;
+//   mode 2: where they measured faster (profiles/r06_subwave_probe.txt) -- batches of at least 32 environments per CU (8192 on an MI355X:
+//           below that a launch has one wave per SIMD or less and is latency-bound whatever the lane use: x0.6 .. 1.1 at 4096), and,
+//           under the random policy, every shape but MATE-4v4-*, whose one-per-wave rollout (the register-resident row image) is as fast.
+//           Greedy flows x1.2 .. 3.3, random-policy flows x1.1 .. 2.9 there.
+static int sub_wave_of_launch(const mate_engine *e, bool greedy) {
+    const int mode = e->sw.sub_wave_mode;
+    if (mode == 0 || e->k.sub_wave <= 1 || !(greedy ? (const void *)e->k.rollout_greedy_sub : (const void *)e->k.rollout_sub[0])) return 1;
+    if (mode == 1) return e->k.sub_wave;
+    if (e->N < 32 * e->cus) return 1;
+    if (!greedy && e->p.Nc * e->p.Nt >= 16) return 1;      // MATE-4v4-*: the row-image kernel is as fast or faster (x0.72 .. 1.14)
+    return e->k.sub_wave;
+}
+// The compilation for the call's switches (enum Flow), when they are the common ones
+static int folded_flow(const mate_engine *e, int mode, const Ptrs &g) {
+    const bool common = !e->sw.flow_generic && !g.tape_ct && !g.tape_goal && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab &&
+                        g.scratch_init && (g.cam_obs || e->p.Nc == 0) && g.tgt_obs && g.scalars;
+    if (common && mode == MODE_STEP_RANDOM) return FLOW_RANDOM;
+    if (common && mode == MODE_STEP) return FLOW_ACT_F32;      // caller-supplied real-valued actions, f32 or f64 per team
+    return FLOW_ANY;
+}
+
+// step() / step_random() / observe(); `g`: the call's record pointers (apply_io), mode set
+static LaunchPlan plan_step(const mate_engine *e, int mode, const Ptrs &g) {
+    LaunchPlan pl;
+    const int flow = pl.last_flow = folded_flow(e, mode, g);
+    // The small scenarios' steps on the sub-wave rollout kernel with ONE step (Ptrs::per_step; the same switches folded as in step_kernel), where
+    // their fused flows run it: from 32 environments per CU on.  Every mode but observe(); MATE_STEP_SUBWAVE=0 keeps the per-step kernels.
+    pl.E = (mode != MODE_OBSERVE && e->sw.step_sub_wave && !e->p.obs_f64) ? sub_wave_of_launch(e, false) : 1;
+    if (pl.E > 1) { pl.step = e->k.rollout_sub[flow]; pl.blocks = blocks_of(e, 4 * pl.E); pl.lds = pl.E * e->step_lds; }
+    else if (e->split_on && e->k.split[flow]) { pl.step = e->k.split[flow]; pl.blocks = blocks_of(e, 1); pl.threads = 128; pl.lds = e->step_lds / 4; }      // two waves per environment: one 128-thread workgroup each
+    else { pl.step = e->k.step[flow]; pl.blocks = blocks_of(e, 4); pl.lds = e->step_lds; }
+    return pl;
+}
+// rollout_random(); `g`: the call's record pointers, tapes cleared
+static LaunchPlan plan_rollout_random(const mate_engine *e, const Ptrs &g) {
+    LaunchPlan pl;
+    const int flow = pl.last_flow = folded_flow(e, MODE_STEP_RANDOM, g);
+    pl.E = sub_wave_of_launch(e, false);
+    pl.blocks = blocks_of(e, 4 * pl.E);
+    if (pl.E > 1) { pl.step = e->k.rollout_sub[flow]; pl.lds = pl.E * e->step_lds; }
+    else { pl.step = e->k.rollout[flow]; pl.lds = (flow == FLOW_RANDOM && e->k.image) ? 4 * e->image_wave_bytes : e->step_lds; }
+    return pl;
+}
+// The three kernels a launch with the on-device agents can be, each with its workgroup's LDS: the environments' slices and the agents' (+ 1024 bytes: the
+// exchange area of the zoom solve the agents once shared -- nothing reads it since the solve became a table lookup; the one-per-wave rollout keeps its size, the sub-wave
+// launches, whose occupancy the LDS bounds, do without).  The caller plays the cameras: step_greedy_kernel holds the target agents' section only (one more workgroup per CU).
+enum PolicyForm { FORM_ROLLOUT, FORM_ROLLOUT_SUB, FORM_STEP_GREEDY, kPolicyForms };
+static LaunchPlan policy_form(const mate_engine *e, int form, int team_caller) {
+    const Params &p = e->p;
+    LaunchPlan pl;
+    pl.policy = form == FORM_STEP_GREEDY ? e->k.step_greedy : form == FORM_ROLLOUT_SUB ? e->k.rollout_greedy_sub : e->k.rollout_greedy;
+    pl.last_flow = form == FORM_STEP_GREEDY ? FLOW_STEP_GREEDY : FLOW_GREEDY;
+    pl.E = form == FORM_ROLLOUT_SUB ? e->k.sub_wave : 1;
+    pl.blocks = blocks_of(e, 4 * pl.E);
+    const int slice = form == FORM_STEP_GREEDY ? step_greedy_slice_bytes(e->q.PW, e->q.TW, p.Nc, p.Nt, p.MW, team_caller != 0) : policy_slice_bytes(e->q.PW, p.Nc, p.Nt);
+    pl.lds = (size_t)pl.E * (4 * (size_t)p.lds_wave_bytes + 4 * (size_t)slice) + (form != FORM_STEP_GREEDY && pl.E == 1 ? 1024 : 0);
+    return pl;
+}
+// rollout_greedy() / rollout_versus_greedy() and (`per_step`) the one-launch step_greedy() / step_versus_greedy().  The fused rollouts run rollout_greedy_kernel, E
+// environments per wave where the sub-wave workgroup fits; the per-step flows follow them there (its one-step form: MATE-2v4-0 x 16 384 against the greedy cameras
+// 38.2 -> 20.5 us per step, x1.2 .. 1.9 from 8192 environments on; same bytes; MATE_STEP_SUBWAVE=0: not) and run step_greedy_kernel (step_kernel's sequence with
+// the agents in front) elsewhere, where it exists and fits -- MATE_STEP_GREEDY_ROLLOUT=1: rollout_greedy_kernel with one step.
+static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int team_caller) {
+    const bool sub = (!per_step || e->sw.step_sub_wave) && sub_wave_of_launch(e, true) > 1 && policy_form(e, FORM_ROLLOUT_SUB, team_caller).fits();
+    const bool light = per_step && !sub && e->k.step_greedy && !e->sw.step_greedy_rollout && policy_form(e, FORM_STEP_GREEDY, -1).fits();
+    return policy_form(e, sub ? FORM_ROLLOUT_SUB : light ? FORM_STEP_GREEDY : FORM_ROLLOUT, team_caller);
+}

@@ -22,6 +22,7 @@
 #include "aux_kernels.hpp"
 #include "state_rows.hpp"
 #include "reward_rows.hpp"
+#include "engine_host.h"
 
 using namespace mate;
 
@@ -42,8 +43,6 @@ static int fail(int code, const char *fmt, ...) {
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) { (void)hipGetLastError(); return fail(MATE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); }    \
     } while (0)
-
-#include "shape_groups.hpp"
 
 // Without -DMATE_SPLIT_BUILD (a plain `hipcc mate_engine.hip`, as the experiment scripts under tools/ do) the shape groups are
 // compiled right here, one after the other; mate_amd/build.py compiles them as translation units of their own, in parallel.
@@ -87,24 +86,6 @@ static KernelSet pick_kernels(int Nc, int Nt, int No, bool f64, bool generic, bo
     return f64 ? f64_kernels<AnyShape>() : f32_kernels<AnyShape, void, true>(no_image);
 }
 
-// Environment switches (all read ONCE, in mate_engine_create; documented in include/mate_engine.h).
-struct Switches {
-    bool generic = false;          // MATE_GENERIC=1: generic (AnyShape) kernels even for a shape with a compiled specialisation
-    bool flow_generic = false;     // MATE_FLOW_GENERIC=1: every launch runs the FLOW_ANY kernel
-    int stagger = -1;              // MATE_STAGGER=<5 digits>: per-phase wave priorities of step_kernel (-1: by batch size)
-    int lut_small_cap = 0;         // MATE_LUT_SMALL_CAP=<rays>: sort-array size of the small-LDS table launch (0: half the full size)
-    bool reset_monolithic = false; // MATE_RESET_MONOLITHIC=1: resets as one launch instead of placement / tables / view
-    int rollout_rotate = 1;        // MATE_ROLLOUT_ROTATE=0: no wave-priority rotation in the fused rollouts
-    bool no_image = false;         // MATE_NO_IMAGE=1: the fused rollouts pack observations through the descriptor table even where the row-image compilation exists
-    bool policy_split = false;     // MATE_POLICY_SPLIT=1: step_greedy / step_versus_greedy as two launches (agents' kernel, step kernel) even when the fused one-launch form applies
-    int step_split = -1;           // MATE_STEP_SPLIT=0 / 1: the one-wave / two-wave form of the per-step kernel in the folded flows (-1: by batch size)
-    bool zoom_iterate = false;     // MATE_ZOOM_ITERATE=1: the greedy camera agents iterate the zoom solve (greedy.py:139-145) instead of reading its table
-    bool step_sub_wave = true;     // MATE_STEP_SUBWAVE=0: the per-step Greedy flows of the small scenarios stay on step_greedy_kernel where the fused ones run sub-wave groups
-    int sub_wave_mode = 2;         // MATE_SUBWAVE=0 / 1: one environment per wave in the fused rollouts of the small scenarios too / the shape's number in EVERY fused launch (default 2: where it measured faster, sub_wave_of_launch).  The one switch that changes after create: mate_engine_set_sub_wave
-    bool step_greedy_rollout = false;   // MATE_STEP_GREEDY_ROLLOUT=1: the one-launch form of step_greedy / step_versus_greedy on rollout_greedy_kernel with one step (round 3) instead of step_greedy_kernel
-    bool pipelined_low_priority = true; // MATE_PIPELINED_PRIORITY=0: the side stream of the pipelined restarts at the default priority instead of the device's lowest
-    bool pipelined_serial = false;      // MATE_PIPELINED_SERIAL=1: the pipelined-restart protocol with the resets on the CALLER's stream (the tests' reference)
-};
 static Switches read_switches() {
     Switches w;
     auto flag = [](const char *name) { const char *v = getenv(name); return v && atoi(v) != 0; };
@@ -125,70 +106,6 @@ static Switches read_switches() {
     w.pipelined_serial = flag("MATE_PIPELINED_SERIAL");
     return w;
 }
-
-struct mate_engine {
-    Switches sw{};
-    hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
-    bool launched = false, multi_stream = false;   // ... unless launches went to more than one stream since the last wait (then: the device)
-    Params p{};
-    Params *d_params = nullptr;   // device copy read by the kernels
-    Ptrs g{};
-    ResetLds rl{};
-    ResetLds rl_small{};       // two-tier table launches (launch_reset): the layout with half-size sort arrays; sort_cap 0 = off
-    mate_config cfg{};
-    int device = 0;
-    int64_t N = 0;
-    int parity = 0;
-    uint32_t tick = 0;         // Philox tick of the next step launch
-    int64_t steps_since_reset = 0;   // batched auto-reset bookkeeping
-    bool was_reset = false;
-    bool dev_tick = false;     // mate_engine_device_tick: the step counter lives on the device (graph-replayable launches)
-    int dev_frames = 1;        // ... frames per launch of the reset interval in progress (1: the per-step flows; K: FrameSkip launches, rollout_versus_greedy)
-    int dev_interval = 1;      // ... and the auto-reset interval every step() must then use
-    int pending_interval = 0;  // auto_reset value of the batched-reset interval in progress (steps_since_reset > 0)
-    // pipelined restarts (mate_engine_rollout_greedy with auto_reset = MATE_RESET_PIPELINED): the side stream the resets run on, the
-    // event behind the last rollout launch, one event per list parity behind the reset that consumed that list
-    bool pipelined = false;          // records may carry "restarted" tags (Ptrs::pipelined): leave_pipelined() before anything else runs
-    int pipe_every = 1, pipe_count = 0;   // ... one restart launch behind every pipe_every-th rollout launch (auto_reset = -pipe_every); launches into the interval
-    hipStream_t side = nullptr;
-    hipEvent_t ev_launch = nullptr, ev_reset[2] = {nullptr, nullptr};
-    bool reset_in_flight[2] = {false, false};
-    size_t step_lds = 0, reset_lds = 0;
-    KernelSet k{};                 // kernels chosen at create (pick_kernels): shape-specialised when compiled for these counts
-    size_t image_wave_bytes = 0;   // per-environment LDS slice of the row-image rollout (k.image), else of the plain one
-    int64_t cus = 256;             // compute units of the device
-    int split_on = 0;              // launch_step uses k.split (MATE_STEP_SPLIT, or the batch is one resident generation)
-    int last_flow = 0;
-    std::vector<void *> allocs;
-    // on-device rule-based policies (mate_engine_step_greedy)
-    bool policy_ready = false;
-    PolicyPtrs q{};
-    int greedy_team_bits = 0;  // during mate_engine_step_greedy / _step_versus_greedy: teams whose joint action the policy kernel wrote
-    // observation post-processing fused into the packer (set_obs_mode / set_obs_transform)
-    int cam_mode = 0, tgt_mode = 0;
-    bool xf_relative = false, xf_cam = false, xf_tgt = false;
-    std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
-    uint2 *d_xdesc = nullptr;
-    void *d_xab = nullptr;
-    // global state rows (mate_engine_enable_state_rows): the caller's [N][S] buffer every record-changing call refreshes, its type,
-    // its (scale, bias) table on the device (null: raw rows); and the table of the last on-demand call (mate_engine_state_rows)
-    void *state_dst = nullptr;
-    bool state_f64 = false;
-    void *d_state_ab = nullptr, *d_state_ab_demand = nullptr;
-    const void *state_ab = nullptr;
-    std::vector<double> state_demand_table;      // scale[S] | bias[S] | type, as uploaded to d_state_ab_demand
-    // shaped reward rows (mate_engine_enable_reward_rows): the attached launch's arguments (scalars, masks and mode are the launch's own),
-    // the row type, whether the soft-coverage launch goes in front, and the engine-owned buffers (kept across re-attachments)
-    bool reward_on = false, reward_f64 = false, reward_soft = false, reward_accumulate = false;
-    RewardArgs reward{};
-    int32_t *d_reward_snapshot = nullptr;
-    double *d_reward_matrix = nullptr, *d_reward_scores = nullptr;
-    // kernel timing (HIP events on the launch stream)
-    int timing = 0;            // 0 = off, k = time every k-th step launch
-    int64_t timing_tick = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t events_used = 0;
-};
 
 // The host-side accessors wait for the stream of the handle's most recent launch, not for the device.  Work the caller enqueued
 // through this handle on ANOTHER stream since the last wait, or a stream handle that has been destroyed since, falls back to
@@ -259,6 +176,7 @@ static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 constexpr int kSortGridCap = 1024;     // workgroups of a table-build launch when the sort arrays live in HBM (one scratch slice each)
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+
 // LDS carve of the reset kernel behind the wave-0 context: the four sort arrays of the occlusion-table build (keys, values,
 // compacted keys, compacted values: 4 x sort_cap doubles), the per-degree index, per-obstacle ray metadata, a scan buffer.
 // Up to 20 obstacles per camera table (360 + 185 * obstacles rays) the sort runs in the 160 KiB LDS; beyond, the same code
@@ -266,7 +184,7 @@ static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static void layout_reset_lds(const Params &p, ResetLds &rl, int sort_cap) {
     rl.sort_cap = sort_cap;
     const int fixed = 368 * 2 + round_up(8 * p.No * 8 + (2 * p.No + 4) * 4, 16) + 256 * 4;
-    rl.sort_in_hbm = (size_t)p.lds_wave_bytes + (size_t)4 * sort_cap * 8 + fixed > 160 * 1024;
+    rl.sort_in_hbm = (size_t)p.lds_wave_bytes + (size_t)4 * sort_cap * 8 + fixed > kLdsCeiling;
     const int in_lds = rl.sort_in_hbm ? 0 : sort_cap * 8;
     // (the placement phase borrows the start of the sort region for its list of placed circles: keep that much in the LDS)
     const int place_bytes = round_up(5 * (4 + p.Nc + p.No + p.Nt) * 8 + (p.Nc + p.No + 2 * p.Nt) * 4 + 64, 16);
@@ -431,7 +349,7 @@ extern "C" int mate_engine_create(const mate_config *cfg, int64_t num_envs, int3
     layout_reset_lds(p, rl, std::max(512, next_pow2(Nc > 0 ? 360 + No * 185 + 1 : 1)));
     e->reset_lds = (size_t)rl.total_bytes;
     setup_two_tier(e);
-    if (e->step_lds > 160 * 1024 || e->reset_lds > 160 * 1024) {
+    if (e->step_lds > kLdsCeiling || e->reset_lds > kLdsCeiling) {
         const size_t a = e->step_lds, b = e->reset_lds;
         delete e;
         return fail(MATE_EINVAL, "scenario too large for the 160 KiB LDS (%zu / %zu bytes)", a, b);
@@ -1019,6 +937,49 @@ static int leave_pipelined(mate_engine *e, hipStream_t stream) {
     note_stream(e, stream);
     return MATE_OK;
 }
+// Entering the mode (a call inside it changes nothing): the side stream and the events exist, both lists are empty, nothing is in flight.
+static int enter_pipelined(mate_engine *e, int pipe_every, hipStream_t stream) {
+    if (!e->side) {
+        {   // the LOWEST priority the device offers (MATE_PIPELINED_PRIORITY=0: default priority): the resets' latency-bound workgroups
+            // should take the slots the rollout launch leaves free -- its tail --, not displace its workgroups
+            int least = 0, greatest = 0;
+            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            if (!e->sw.pipelined_low_priority) HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+            else HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, least));
+        }
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_launch, hipEventDisableTiming));
+        for (int q = 0; q < 2; ++q) HIP_TRY(hipEventCreateWithFlags(&e->ev_reset[q], hipEventDisableTiming));
+    }
+    if (!e->pipelined) {
+        HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
+        e->reset_in_flight[0] = e->reset_in_flight[1] = false;
+        e->pipelined = true;
+        e->pipe_every = pipe_every; e->pipe_count = 0;
+    }
+    return MATE_OK;
+}
+// Behind a rollout launch of the mode, every pipe_every-th one: the reset of what this interval of launches finished (list `parity`) on the side
+// stream, behind the launch and under the next ones.  Inside an interval the following launches append to the same list; what has finished idles
+// (listed) until the interval's restart.
+static int pipelined_restart(mate_engine *e, hipStream_t stream) {
+    if (++e->pipe_count < e->pipe_every) return MATE_OK;
+    e->pipe_count = 0;
+    const bool serial = e->sw.pipelined_serial;
+    hipStream_t rs = serial ? stream : e->side;
+    if (!serial) { HIP_TRY(hipEventRecord(e->ev_launch, stream)); HIP_TRY(hipStreamWaitEvent(rs, e->ev_launch, 0)); }
+    Ptrs r = restart_ptrs(e);
+    r.pipelined = 1;
+    const bool multi_before = e->multi_stream;
+    int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, rs, true);
+    if (rc != MATE_OK) return rc;
+    HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), rs));      // (the list is consumed: the launch after next appends to it afresh)
+    if (!serial) { HIP_TRY(hipEventRecord(e->ev_reset[e->parity], rs)); e->reset_in_flight[e->parity] = true; }
+    // (launch_reset noted the side stream: the accessors order it through leave_pipelined's event waits, so it neither becomes
+    // the stream they wait for nor counts as a second stream of the CALLER's -- which would turn every accessor into a device-wide wait)
+    e->last_stream = stream; e->multi_stream = multi_before;
+    e->parity ^= 1;
+    return MATE_OK;
+}
 
 extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
@@ -1046,8 +1007,6 @@ extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *str
     if (!enable) return refresh_state_rows(e, flush_pending(e, 0, 0, stream), stream);      // (an open interval's finished environments restart here)
     return MATE_OK;
 }
-
-static int sub_wave_of_launch(const mate_engine *e, bool greedy);
 
 // Device-resident step counter: the auto-reset launch advances it, so every stepping call uses the interval it was enabled with, and
 // the launches of one reset interval all run the same number of frames (1: the per-step flows; K: FrameSkip launches).
@@ -1113,25 +1072,10 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     if (mode == MODE_OBSERVE || auto_reset == 0) g.done_count = nullptr;
     Timed t;
     { const int rc_ = take_timing_events(e, !e->dev_tick && mode != MODE_OBSERVE, &t); if (rc_ != MATE_OK) return rc_; }
-    // the kernel compiled for this launch's switches (enum Flow), when they are the common ones
-    int flow = FLOW_ANY;
-    if (!e->sw.flow_generic && !g.tape_ct && !g.tape_goal && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab &&
-        g.scratch_init && (g.cam_obs || e->p.Nc == 0) && g.tgt_obs && g.scalars) {
-        if (mode == MODE_STEP_RANDOM) flow = FLOW_RANDOM;
-        else if (mode == MODE_STEP) flow = FLOW_ACT_F32;      // caller-supplied real-valued actions, f32 or f64 per team
-    }
-    e->last_flow = flow;
-    // The small scenarios' steps on the sub-wave rollout kernel with ONE step (four environments per wave; Ptrs::per_step), where their fused flows run
-    // it: from 32 environments per CU on (sub_wave_of_launch).  Not for auto_reset = 0 in the device-counted mode... every mode but observe().
-    const int E = (mode != MODE_OBSERVE && e->sw.step_sub_wave && !e->p.obs_f64) ? sub_wave_of_launch(e, false) : 1;
-    if (E > 1) {      // (FLOW_ANY / FLOW_RANDOM / FLOW_ACT_F32: the same switches folded as in step_kernel)
-        g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0;
-        launch(e->k.rollout_sub[flow], dim3((unsigned)((e->N + 4 * E - 1) / (4 * E))), dim3(256), E * e->step_lds, stream, t, e->d_params, g);
-    } else if (e->split_on && e->k.split[flow]) {      // two waves per environment: one 128-thread workgroup each
-        launch(e->k.split[flow], dim3((unsigned)e->N), dim3(128), e->step_lds / 4, stream, t, e->d_params, g);
-    } else {
-        launch(e->k.step[flow], dim3((unsigned)((e->N + 3) / 4)), dim3(256), e->step_lds, stream, t, e->d_params, g);
-    }
+    const LaunchPlan pl = plan_step(e, mode, g);
+    e->last_flow = pl.last_flow;
+    if (pl.E > 1) { g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0; }      // (the sub-wave rollout kernel with ONE step)
+    launch(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g);
     HIP_TRY(hipGetLastError());
     if (mode == MODE_OBSERVE) return MATE_OK;
     if (!e->dev_tick) e->tick += 1;
@@ -1147,21 +1091,6 @@ extern "C" int mate_engine_step(mate_engine *e, const mate_step_io *io, int32_t 
 extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
     return refresh_state_rows(e, launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream), stream);
 }
-// Environments per wave of a fused launch (engine_kernels.hpp, Ctx<ObsT, L>): the shape's E = 4 where the sub-wave kernels exist and
-//   mode 1: always;
-//   mode 2: where they measured faster (profiles/r06_subwave_probe.txt) -- batches of at least 32 environments per CU (8192 on an MI355X:
-//           below that a launch has one wave per SIMD or less and is latency-bound whatever the lane use: x0.6 .. 1.1 at 4096), and,
-//           under the random policy, every shape but MATE-4v4-*, whose one-per-wave rollout (the register-resident row image) is as fast.
-//           Greedy flows x1.2 .. 3.3, random-policy flows x1.1 .. 2.9 there.
-static int sub_wave_of_launch(const mate_engine *e, bool greedy) {
-    const int mode = e->sw.sub_wave_mode;
-    if (mode == 0 || e->k.sub_wave <= 1 || !(greedy ? (const void *)e->k.rollout_greedy_sub : (const void *)e->k.rollout_sub[0])) return 1;
-    if (mode == 1) return e->k.sub_wave;
-    if (e->N < 32 * e->cus) return 1;
-    if (!greedy && e->p.Nc * e->p.Nt >= 16) return 1;      // MATE-4v4-*: the row-image kernel is as fast or faster (x0.72 .. 1.14)
-    return e->k.sub_wave;
-}
-
 static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
@@ -1177,17 +1106,12 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     g.tape_ct = nullptr; g.tape_goal = nullptr;
     g.rotate_prio = e->sw.rollout_rotate;
     if (auto_reset != 1) g.done_count = nullptr;     // no list: nothing restarts (0), or a batched reset finds the finished ones by their flag (k > 1)
-    const int E = sub_wave_of_launch(e, false);      // environments per wave (1, or the small scenarios' 4)
-    const unsigned blocks = (unsigned)((e->N + 4 * E - 1) / (4 * E));
     Timed t;
     { const int rc_ = take_timing_events(e, true, &t); if (rc_ != MATE_OK) return rc_; }
-    const int flow = (!e->sw.flow_generic && !g.act_discrete && g.obs_mode == 0 && !g.xdesc && !g.xab && g.scratch_init &&
-                      (g.cam_obs || e->p.Nc == 0) && g.tgt_obs && g.scalars) ? FLOW_RANDOM : FLOW_ANY;
-    e->last_flow = flow;
-    const StepFn fn = E > 1 ? e->k.rollout_sub[flow] : e->k.rollout[flow];
-    const size_t lds = E > 1 ? E * e->step_lds : (flow == FLOW_RANDOM && e->k.image) ? 4 * e->image_wave_bytes : e->step_lds;
+    const LaunchPlan pl = plan_rollout_random(e, g);
+    e->last_flow = pl.last_flow;
     // (this flow has always gone through the extended launch, timed or not -- null events: not through launch())
-    hipExtLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
+    hipExtLaunchKernelGGL(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
     { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
@@ -1198,15 +1122,6 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
 extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
     return refresh_state_rows(e, rollout_random_impl(e, io, steps, auto_reset, stream), stream);      // (the state after the launch's last frame)
 }
-
-// LDS per workgroup of the two one-launch forms of a step with the on-device agents
-// (the 1024 bytes behind the slices: the exchange area of the zoom solve the agents once shared -- nothing reads it since the solve became a table lookup; the
-// one-per-wave launches keep their size, the sub-wave launches, whose occupancy the LDS bounds, do without)
-static size_t fused_rollout_lds(const mate_engine *e, int E = 1) { return (size_t)E * (4 * (size_t)e->p.lds_wave_bytes + 4 * (size_t)policy_slice_bytes(e->q.PW, e->p.Nc, e->p.Nt)) + (E == 1 ? 1024 : 0); }
-static size_t step_greedy_lds(const mate_engine *e, bool cameras = true) {
-    return 4 * (size_t)e->p.lds_wave_bytes + 4 * (size_t)step_greedy_slice_bytes(e->q.PW, e->q.TW, e->p.Nc, e->p.Nt, e->p.MW, cameras);
-}
-static bool use_step_greedy(const mate_engine *e) { return e->k.step_greedy && !e->sw.step_greedy_rollout && step_greedy_lds(e) <= 160 * 1024; }
 
 static int policy_enable(mate_engine *e) {
     if (e->policy_ready) return MATE_OK;
@@ -1247,14 +1162,12 @@ static int policy_enable(mate_engine *e) {
         HIP_TRY(hipMemcpy(d_tab, tab.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         q.zoom_tab = d_tab; q.zoom_inv_h = kInvH; q.zoom_n = e->sw.zoom_iterate ? 0 : n;      // 0 entries: zoom_lookup iterates
     }
-    // dynamic LDS of the agents' kernel and of the one-launch forms that fit a workgroup (fused_rollout_lds, step_greedy_lds)
-    const KernelSet &k = e->k;
-    hipError_t err = hipSuccess;
-    auto opt_in = [&](PolicyFn fn, size_t bytes) { if (err == hipSuccess && bytes <= 160 * 1024) err = set_dynamic_lds(fn, bytes); };
-    err = set_dynamic_lds(k.policy, 4 * (size_t)q.lds_bytes + 1024);
-    opt_in(k.rollout_greedy, fused_rollout_lds(e));
-    opt_in(k.rollout_greedy_sub, fused_rollout_lds(e, k.sub_wave));
-    opt_in(k.step_greedy, step_greedy_lds(e));
+    // dynamic LDS of the agents' kernel and of everything plan_with_policies can return for this engine: the forms that fit a workgroup
+    hipError_t err = set_dynamic_lds(e->k.policy, 4 * (size_t)q.lds_bytes + 1024);
+    for (int form = 0; form < kPolicyForms; ++form) {
+        const LaunchPlan pl = policy_form(e, form, -1);      // (-1: step_greedy_kernel's larger workgroup, both teams' agents)
+        if (err == hipSuccess && pl.fits()) err = set_dynamic_lds(pl.policy, pl.lds);
+    }
     if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
     e->policy_ready = true;
     return MATE_OK;
@@ -1267,8 +1180,25 @@ extern "C" int mate_engine_policy_enable(mate_engine *e) {
     return policy_enable(e);
 }
 
-static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false);
+// What a call brings for the ONE-launch form with the on-device agents.  Both gates of that form read THIS: rollout_with_policies turns the first one
+// missing into its error; step_with_policies runs its two-launch form instead, whose checks then name what is wrong with the call itself.
+struct FusedCall {
+    bool reset, ready;      // an episode is in progress; mate_engine_policy_enable has run
+    bool outputs, plain;    // every observation and scalar output is there; no fused observation transform / team mode
+    bool action;            // the caller's team (if any) brought its joint action
+    bool complete() const { return reset && ready && outputs && plain && action; }
+};
+static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_step_io *io) {
+    return {e->was_reset, e->policy_ready, io && (io->camera_obs_dev || e->p.Nc == 0) && io->target_obs_dev && io->scalars_dev,
+            e->g.obs_mode == 0 && !e->g.xdesc, team_caller < 0 || (io && (team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev))};
+}
+// step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
+// recorded agent draws, tapes of the step itself, f64 observations
+static bool one_launch_step(const mate_engine *e, const FusedCall &c, const mate_step_io *io, const mate_policy_tape *tape) {
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64;
+}
 
+static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false);
 
 // team_caller: -1 = both teams are the on-device agents; 0 / 1 = the camera / target team's joint action is the caller's
 static int step_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, hipStream_t stream) {
@@ -1277,20 +1207,15 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     // two-launch form reads all three, so the mode is left HERE, not only in launch_step behind it)
     { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone)
-    // One launch (agents + step fused, rollout_greedy_kernel with one step) unless something needs the two-launch form: recorded
-    // agent draws, tapes of the step itself, fused observation post-processing, a missing output, a workgroup that does not fit
-    if (e->policy_ready && e->was_reset && !e->sw.policy_split && !tape && io && !io->tape_camera_target_dev && !io->tape_goal_dev &&
-        e->g.obs_mode == 0 && !e->g.xdesc && (io->camera_obs_dev || e->p.Nc == 0) && io->target_obs_dev && io->scalars_dev && !e->p.obs_f64 &&
-        (use_step_greedy(e) || fused_rollout_lds(e) <= 160 * 1024) &&
-        (team_caller < 0 || (team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev)))
+    const FusedCall c = fused_call(e, team_caller, io);
+    if (one_launch_step(e, c, io, tape) && plan_with_policies(e, true, team_caller).fits())
         return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true);
-    if (!e->was_reset) return fail(MATE_ESTATE, "step_greedy called before reset() (or import_state)");
+    if (!c.reset) return fail(MATE_ESTATE, "step_greedy called before reset() (or import_state)");
     // (works with a device-resident step counter too -- the agents take their tick from the environment record -- so the
     // learner-versus-greedy loop can be captured in a HIP graph like step(); launch_step checks the reset interval)
-    if (!e->policy_ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
+    if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
     if (team_caller == 0 && e->p.Nc == 0) return fail(MATE_EINVAL, "the scenario has no cameras to act for");
-    if (team_caller >= 0 && (!io || !(team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev)))
-        return fail(MATE_EINVAL, "step_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
+    if (!c.action) return fail(MATE_EINVAL, "step_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
     // the checks launch_step would make only after the policy launch below has advanced the agents' memory: a rejected call must leave it alone
     { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(hipSetDevice(e->device));
@@ -1329,117 +1254,77 @@ extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, cons
     return refresh_state_rows(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), stream);
 }
 
-// `per_step`: ONE fused (agents act, environment steps) launch with the semantics of the per-step flows -- outputs in the
-// caller's [N][...] buffers, immediate (auto_reset = 1) or batched (k > 1: finished environments idle, listed, and restart
-// together behind every k-th call) list-driven resets that write the restarted environments' first observations, and the
-// device-resident step counter (graph replay).  It is what step_greedy / step_versus_greedy run when nothing asks for
-// the two-launch form (a policy tape, a fused observation transform or team mode, a missing output buffer).
+// What differs between the two forms of rollout_with_policies, spelled once (after struct Restart):
+//   fused (rollout_greedy / rollout_versus_greedy): rollout-shaped outputs; restarts of state and the engine's own masks -- the agents of the next
+//     rollout act on the fresh view --, the interval's by flag, so the finished-episode list exists for the immediate and the pipelined restart only;
+//   per-step: ONE launch with the semantics of the per-step flows -- outputs in the caller's [N][...] buffers, immediate (auto_reset = 1) or batched
+//     (k > 1: finished environments idle, listed, and restart together behind every k-th call) list-driven restarts that write the restarted
+//     environments' first observations (not its actions' encoding; the immediate one, idle almost always, stays ONE launch, the interval's is split:
+//     placement / tables / view), and the device-resident step counter (graph replay).  What step_greedy / step_versus_greedy run (one_launch_step).
+struct PolicyFlow {
+    Restart restart;             // (its flow_tag is the interval tag of flush_pending too)
+    bool keep_list;              // this call's auto_reset restarts by the finished-episode list
+    bool may_pipeline;           // auto_reset = MATE_RESET_PIPELINED
+    bool may_count_on_device;    // mate_engine_device_tick: the per-step flows, and the K-frame launches of a learner against the greedy opponents --
+                                 // FrameSkip in a HIP graph; the auto-reset launch behind every auto_reset-th launch advances the counter by auto_reset * K
+};
+
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    if (!e->was_reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
-    // (device-resident counter: the per-step flows, and the K-frame launches of a learner against the greedy opponents -- FrameSkip in a
-    // HIP graph; the auto-reset launch behind every auto_reset-th launch advances the counter by auto_reset * K)
-    if (e->dev_tick && !per_step && team_caller < 0) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
+    const FusedCall c = fused_call(e, team_caller, io);
+    const bool pipelined = auto_reset < 0;          // MATE_RESET_PIPELINED (-1), or -m: one restart launch behind every m-th rollout launch
+    const int full = PH_PLACE | PH_LUT | PH_VIEW;
+    const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
+                                     : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow}, auto_reset == 1 || pipelined, true, team_caller >= 0};
+    if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
+    if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }
-    if (!e->policy_ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
+    if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(e->device));
-    const bool pipelined = auto_reset < 0;          // MATE_RESET_PIPELINED (-1), or -m: one restart launch behind every m-th rollout launch
     if (auto_reset < -(1 << 16)) return fail(MATE_EINVAL, "auto_reset = %d: pipelined restarts every -auto_reset launches take 1 .. 65536", auto_reset);
     const int pipe_every = pipelined ? -auto_reset : 1;
-    if (pipelined && (per_step || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
+    if (pipelined && (!flow.may_pipeline || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
     // (the restarts run on the engine's side stream UNDER the next launches: a state-row launch on the caller's stream would read records they rewrite)
     if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
     if (pipelined && e->reward_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while reward rows are attached (mate_engine_enable_reward_rows): detach them first");
     { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
-    { int rc = flush_pending(e, auto_reset, per_step ? kStepFlow : kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
-    if (pipelined && !e->side) {
-        {   // the LOWEST priority the device offers (MATE_PIPELINED_PRIORITY=0: default priority): the resets' latency-bound workgroups
-            // should take the slots the rollout launch leaves free -- its tail --, not displace its workgroups
-            int least = 0, greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            if (!e->sw.pipelined_low_priority) HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-            else HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, least));
-        }
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_launch, hipEventDisableTiming));
-        for (int q = 0; q < 2; ++q) HIP_TRY(hipEventCreateWithFlags(&e->ev_reset[q], hipEventDisableTiming));
-    }
-    if (pipelined && !e->pipelined) {                // entering the mode: both lists empty, nothing in flight
-        HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
-        e->reset_in_flight[0] = e->reset_in_flight[1] = false;
-        e->pipelined = true;
-        e->pipe_every = pipe_every; e->pipe_count = 0;
-    }
+    { int rc = flush_pending(e, auto_reset, flow.restart.flow_tag, stream); if (rc != MATE_OK) return rc; }
+    if (pipelined) { const int rc_ = enter_pipelined(e, pipe_every, stream); if (rc_ != MATE_OK) return rc_; }
     Ptrs g = e->g;
     apply_io(g, io);
     g.pipelined = pipelined ? 1 : 0;
-    if ((e->p.Nc > 0 && !g.cam_obs) || !g.tgt_obs || !g.scalars) return fail(MATE_EINVAL, "rollout_greedy needs the observation and scalar outputs");
-    if (g.obs_mode != 0 || g.xdesc) return fail(MATE_EINVAL, "rollout_greedy packs plain observations (no fused transform / team mode)");
+    if (!c.outputs) return fail(MATE_EINVAL, "rollout_greedy needs the observation and scalar outputs");
+    if (!c.plain) return fail(MATE_EINVAL, "rollout_greedy packs plain observations (no fused transform / team mode)");
     if (team_caller == 0 && e->p.Nc == 0) return fail(MATE_EINVAL, "the scenario has no cameras to act for");
-    if (team_caller >= 0 && !(team_caller == 0 ? g.cam_act : g.tgt_act))
-        return fail(MATE_EINVAL, "rollout_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
+    if (!c.action) return fail(MATE_EINVAL, "rollout_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
     if (team_caller >= 0 && (((g.act_discrete & 1) && team_caller == 0 && !g.cam_grid) || ((g.act_discrete & 2) && team_caller == 1 && !g.tgt_grid)))
         return fail(MATE_ESTATE, "discrete actions passed before mate_engine_set_action_grids");
-    // the per-step flows run step_greedy_kernel (step_kernel's sequence with the agents in front) where it exists; the fused
-    // rollouts -- and MATE_STEP_GREEDY_ROLLOUT=1 -- rollout_greedy_kernel
-    // E environments per wave: the fused launches of the small scenarios -- and their PER-STEP Greedy flows too (step_greedy / step_versus_greedy:
-    // the one-step form of the sub-wave rollout kernel instead of step_greedy_kernel: MATE-2v4-0 x 16 384 against the greedy cameras 38.2 -> 20.5 us
-    // per step, x1.2 .. 1.9 from 8192 environments on; same bytes; MATE_STEP_SUBWAVE=0 keeps step_greedy_kernel)
-    const int E = ((!per_step || e->sw.step_sub_wave) && fused_rollout_lds(e, e->k.sub_wave) <= 160 * 1024) ? sub_wave_of_launch(e, true) : 1;
-    const bool light = per_step && use_step_greedy(e) && E == 1;
-    const PolicyFn fn = light ? e->k.step_greedy : E > 1 ? e->k.rollout_greedy_sub : e->k.rollout_greedy;
-    // (the caller plays the cameras: step_greedy_kernel holds the target agents' section only -- a smaller slice, one more workgroup per CU)
-    const size_t lds = light ? step_greedy_lds(e, team_caller != 0) : fused_rollout_lds(e, E);
-    if (lds > 160 * 1024) return fail(MATE_EINVAL, "rollout_greedy: %zu bytes of LDS per workgroup do not fit", lds);
+    const LaunchPlan pl = plan_with_policies(e, per_step, team_caller);
+    if (!pl.fits()) return fail(MATE_EINVAL, "rollout_greedy: %zu bytes of LDS per workgroup do not fit", pl.lds);
     g.mode = MODE_STEP; g.reset_kind = -1; g.rollout_steps = steps;
     g.parity = e->dev_tick ? 0 : e->parity;
     g.tick = e->dev_tick ? (uint32_t)e->steps_since_reset * (uint32_t)steps : e->tick;     // device-resident counter: the offset inside the reset interval
     g.tape_ct = nullptr; g.tape_goal = nullptr; g.freeze_done = 0;
     g.rotate_prio = e->sw.rollout_rotate;
-    // the finished-episode list: the rollout flows keep it for the immediate restart only (a batched restart finds the finished
-    // ones by their flag); the per-step flow lists in both modes, like step()
-    if (per_step ? auto_reset == 0 : (auto_reset != 1 && !pipelined)) g.done_count = nullptr;
+    if (!flow.keep_list) g.done_count = nullptr;
     // pipelined restarts: this launch appends to list `parity`, which the reset launched two calls ago has consumed and cleared; the
     // environments that reset restarted carry this parity's tag and go live now
     if (pipelined && e->reset_in_flight[e->parity]) { HIP_TRY(hipStreamWaitEvent(stream, e->ev_reset[e->parity], 0)); e->reset_in_flight[e->parity] = false; }
     PolicyPtrs q = e->q;
     std::memset(&q.tape, 0, sizeof(q.tape));
     q.caller_team = team_caller;
-    const unsigned blocks = (unsigned)((e->N + 4 * E - 1) / (4 * E));
     Timed t;
     { const int rc_ = take_timing_events(e, !e->dev_tick, &t); if (rc_ != MATE_OK) return rc_; }
-    e->last_flow = light ? FLOW_STEP_GREEDY : FLOW_GREEDY;
-    launch(fn, dim3(blocks), dim3(256), lds, stream, t, e->d_params, g, q);
+    e->last_flow = pl.last_flow;
+    launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     if (!e->dev_tick) e->tick += (uint32_t)steps;
     { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
-    const int full = PH_PLACE | PH_LUT | PH_VIEW;
-    // per-step: list-driven restarts that write the restarted environments' first observations into the caller's buffers (not its
-    // actions' encoding); the immediate one, idle almost always, stays ONE launch, the interval's is split: placement / tables / view
-    if (per_step) return restart_finished(e, auto_reset, Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, stream);
-    // fused: state and the engine's own masks -- the agents of the next rollout act on the fresh view; the interval's restart by flag
-    if (!pipelined) return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow}, stream);
-    if (++e->pipe_count < e->pipe_every) return MATE_OK;      // inside a restart interval: the following launches append to the same list; what has finished idles (listed) until the interval's restart
-    e->pipe_count = 0;
-    // the reset of what THIS launch (this interval of launches) finishes (list `parity`): on the side stream, behind this launch, under the next ones
-    const bool serial = e->sw.pipelined_serial;
-    hipStream_t rs = serial ? stream : e->side;
-    if (!serial) { HIP_TRY(hipEventRecord(e->ev_launch, stream)); HIP_TRY(hipStreamWaitEvent(rs, e->ev_launch, 0)); }
-    Ptrs r = restart_ptrs(e);
-    r.pipelined = 1;
-    const bool multi_before = e->multi_stream;
-    int rc = launch_reset(e, r, RESET_DONE, full, rs, true);
-    if (rc != MATE_OK) return rc;
-    HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), rs));      // (the list is consumed: the launch after next appends to it afresh)
-    if (!serial) { HIP_TRY(hipEventRecord(e->ev_reset[e->parity], rs)); e->reset_in_flight[e->parity] = true; }
-    // (launch_reset noted the side stream: the accessors order it through leave_pipelined's event waits, so it neither becomes
-    // the stream they wait for nor counts as a second stream of the CALLER's -- which would turn every accessor into a device-wide wait)
-    e->last_stream = stream; e->multi_stream = multi_before;
-    e->parity ^= 1;
-    return MATE_OK;
+    return pipelined ? pipelined_restart(e, stream) : restart_finished(e, auto_reset, flow.restart, stream);
 }
 
 extern "C" int mate_engine_rollout_greedy(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
@@ -1859,7 +1744,7 @@ extern "C" int mate_engine_set_sub_wave(mate_engine *e, int32_t enable, int32_t 
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (enable > 2) return fail(MATE_EINVAL, "set_sub_wave: 0 (one per wave), 1 (the shape's number), 2 (where it measured faster) or negative (query)");
     if (enable >= 0) e->sw.sub_wave_mode = enable;      // (negative: a query)
-    if (in_use) { in_use[0] = sub_wave_of_launch(e, true); }
+    if (in_use) { in_use[0] = plan_with_policies(e, false, -1).E; }
     return MATE_OK;
 }
 
