@@ -439,6 +439,46 @@ typedef struct mate_reward_rows {
 } mate_reward_rows;
 int mate_engine_enable_reward_rows(mate_engine *engine, const mate_reward_rows *config);
 
+/* Target-selection camera actions: the per-frame part of the reference's HierarchicalCamera wrapper (examples/hrl/wrappers.py), the
+ * wrapper every hierarchical camera trainer (examples/hrl/<algorithm>/camera) goes through.  The learner emits a selection of targets per camera;
+ * a fixed executor (HierarchicalCamera.track, wrappers.py:183-220) turns it into the camera team's continuous joint action on EVERY
+ * frame, from the camera's true state, the selected targets' true positions and the camera's view of the previous frame.  Attached
+ * launches of one kernel (csrc/selection_rows.hpp); no stepping kernel changes.
+ *   mode MATE_SELECTION_SINGLE: selection_dev [N][Nc] int32, an index in [0, Nt]; Nt selects nothing (the wrapper's index2onehot)
+ *   mode MATE_SELECTION_MULTI:  selection_dev [N][Nc] uint32, bit t = target t selected (Nt <= 16)
+ * read at every mate_engine_step_selected; values are not validated (bits beyond Nt are ignored, an index outside [0, Nt) selects nothing).
+ * Optional outputs, caller-owned: metrics_dev [N][Nc][4] f64 = num_selected_targets, num_valid_selected_targets,
+ * num_invalid_selected_targets, invalid_target_selection_rate (= invalid / max(1, selected)) of wrappers.py:120-136, against the view of
+ * the step that has just run; frames_dev [N] int32 = frames that contributed; action_mask_dev = action_mask() (wrappers.py:166-175) of
+ * the observation the learner sees next: [N][Nc][2 Nt] u8 with the even entries 1 (multi) / [N][Nc][Nt + 1] u8 with the last entry 1.
+ * flags: MATE_SELECTION_ACCUMULATE -- metrics += and frames += 1 per frame instead of = (FrameSkip's mean is metrics / frames; the caller
+ * zeroes both when it consumes them); MATE_SELECTION_ACT_F32 -- the engine-owned joint action is f32 pairs (default f64).
+ * An environment whose scalar record says done = 2 (idling under a batched restart) contributes nothing: zero rows and count, or, accumulating,
+ * nothing added.  "View" is the opponent-flag column of the camera rows: the camera_target_view_mask bits, their OR over the cameras under
+ * MATE_OBS_SHARED, all ones under MATE_OBS_ENHANCED (camera team mode).
+ *
+ * mate_engine_step_selected enqueues, in this order: the executor; exactly what mate_engine_step_versus_greedy(MATE_TEAM_CAMERA) enqueues,
+ * reading the engine-owned joint action (io->camera_actions_dev is ignored); the reward launch when reward rows are attached; the metrics
+ * launch; the restart of finished episodes; the action-mask launch; state rows last.  The executor reads the engine's own mask words as the
+ * previous step, reset or restart launch left them: a restarted environment acts on its new episode's first view.  Every check, and
+ * whatever the stepping flow enqueues ahead of its launch, precedes the executor: a rejected call leaves the action buffer alone.  While
+ * selection is attached the action-mask launch also follows mate_engine_reset / _reset_tape / _observe and the other stepping calls
+ * (ahead of state rows), whenever the engine's mask words are current; mate_engine_enable_selection writes it once and returns with it
+ * complete.  io->scalars_dev is required.  No allocation, no synchronisation, identical arguments at every call: capturable under mate_engine_device_tick.
+ * MATE_ESTATE: before mate_engine_policy_enable / the first reset; auto_reset = MATE_RESET_PIPELINED (and the pipelined rollouts while
+ * attached); view masks older than the records (a fused random rollout restarted episodes, import_state: observe() first).
+ * MATE_EINVAL: a null selection buffer, an unknown mode or flag, no cameras, a misaligned buffer.
+ * mate_engine_selection_actions: the engine-owned joint action [N][Nc][2] and its MATE_ACT_F32 / MATE_ACT_F64 type (what the last
+ * mate_engine_step_selected executed). */
+enum { MATE_SELECTION_SINGLE = 0, MATE_SELECTION_MULTI = 1 };
+enum { MATE_SELECTION_ACCUMULATE = 1, MATE_SELECTION_ACT_F32 = 2 };
+#define MATE_SELECTION_METRICS 4
+int mate_engine_enable_selection(mate_engine *engine, int32_t mode, const void *selection_dev, double *metrics_dev, int32_t *frames_dev,
+                                 uint8_t *action_mask_dev, int32_t flags);
+int mate_engine_disable_selection(mate_engine *engine);
+int mate_engine_selection_actions(mate_engine *engine, void **actions_dev, int32_t *act_dtype);
+int mate_engine_step_selected(mate_engine *engine, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream);
+
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,
                          double *rhos_host, int32_t capacity, int32_t *count);

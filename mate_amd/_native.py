@@ -16,6 +16,7 @@ EXPORTED_SYMBOLS = (
     'mate_engine_get_layout', 'mate_engine_set_obs_transform', 'mate_engine_set_obs_mode', 'mate_engine_set_action_grids', 'mate_engine_seed', 'mate_engine_reset', 'mate_engine_reset_tape', 'mate_engine_step', 'mate_engine_device_tick', 'mate_engine_set_episode_stats', 'mate_engine_snapshot_episode_stats', 'mate_engine_step_random',
     'mate_engine_rollout_random', 'mate_engine_policy_enable', 'mate_engine_step_greedy', 'mate_engine_step_versus_greedy', 'mate_engine_rollout_greedy', 'mate_engine_rollout_versus_greedy', 'mate_engine_policy_actions',
     'mate_engine_observe', 'mate_engine_export_state', 'mate_engine_import_state', 'mate_engine_enable_state_rows', 'mate_engine_state_rows', 'mate_engine_enable_reward_rows', 'mate_engine_lut_read',
+    'mate_engine_enable_selection', 'mate_engine_disable_selection', 'mate_engine_selection_actions', 'mate_engine_step_selected',
     'mate_engine_block_alloc', 'mate_engine_block_free', 'mate_engine_block_probe', 'mate_engine_set_store_form',
     'mate_engine_memory_hold', 'mate_engine_memory_release', 'mate_engine_hbm_probe', 'mate_engine_set_sub_wave',
     'mate_engine_lut_write', 'mate_engine_enable_outer_boundary', 'mate_engine_lut_read_outer', 'mate_engine_lut_write_outer', 'mate_engine_soft_coverage', 'mate_engine_rebuild_luts', 'mate_engine_idle_steps', 'mate_engine_kernel_time', 'mate_engine_last_flow',
@@ -128,6 +129,10 @@ def load():
     handle.mate_engine_enable_state_rows.argtypes = [P, P, I32, P, P]
     handle.mate_engine_state_rows.argtypes = [P, P, I32, P, P, P]
     handle.mate_engine_enable_reward_rows.argtypes = [P, ctypes.POINTER(MateRewardRows)]
+    handle.mate_engine_enable_selection.argtypes = [P, I32, P, P, P, P, I32]
+    handle.mate_engine_disable_selection.argtypes = [P]
+    handle.mate_engine_selection_actions.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(I32)]
+    handle.mate_engine_step_selected.argtypes = [P, ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape), I32, P]
     handle.mate_engine_lut_read.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_lut_read_outer.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_enable_outer_boundary.argtypes = [P, ctypes.POINTER(I32)]

@@ -12,6 +12,7 @@
 #include "../../include/mate_engine.h"
 #include "reset_kernels.hpp"
 #include "reward_rows.hpp"
+#include "selection_rows.hpp"
 #include "shape_groups.hpp"
 
 using namespace mate;
@@ -93,6 +94,12 @@ struct mate_engine {
     RewardArgs reward{};
     int32_t *d_reward_snapshot = nullptr;
     double *d_reward_matrix = nullptr, *d_reward_scores = nullptr;
+    // target-selection camera actions (mate_engine_enable_selection): the attached launches' arguments (phase, masks and scalars are the
+    // launch's own) and the type of the engine-owned action buffer
+    bool selection_on = false, selection_act_f64 = true;
+    SelectionArgs selection{};
+    double *d_selection_actions = nullptr;       // [N][Nc][2] of f64 (or, in the same bytes, f32)
+    bool masks_stale = false;                    // a state-only restart ran since the view masks were last written (rollout_random's)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -182,4 +189,31 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
     const bool sub = (!per_step || e->sw.step_sub_wave) && sub_wave_of_launch(e, true) > 1 && policy_form(e, FORM_ROLLOUT_SUB, team_caller).fits();
     const bool light = per_step && !sub && e->k.step_greedy && !e->sw.step_greedy_rollout && policy_form(e, FORM_STEP_GREEDY, -1).fits();
     return policy_form(e, sub ? FORM_ROLLOUT_SUB : light ? FORM_STEP_GREEDY : FORM_ROLLOUT, team_caller);
+}
+
+// What a stepping call enqueues AROUND its stepping launch (the LaunchPlan above), in the order of the fields: the one place that order is
+// written down.  The entry points ask for the plan and launch what it names; none of them decides an order of its own.
+//   1 execute      selection_kernel, SELECTION_EXECUTE: the camera team's joint action of this frame        (mate_engine_step_selected)
+//   2              the stepping launch (and, two-launch form, the opponents' agents in front of it)
+//   3 reward       reward_rows_kernel (soft coverage in front): the rows of the step that has just run      (mate_engine_enable_reward_rows)
+//   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks
+//   5              the restart epilogue (restart_finished) and, with reward rows, its snapshot refresh
+//   6 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next, the restarted episodes' included
+//   7 state        state_rows_kernel, last                                                                  (mate_engine_enable_state_rows)
+struct AttachedPlan {
+    bool execute = false, reward = false, observe = false, action_mask = false, state = false;
+    unsigned selection_blocks = 0;
+    size_t selection_lds = 0;
+};
+// `selected`: the call is mate_engine_step_selected.  The action mask is the view the executor would act on next, so while selection is
+// attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
+static AttachedPlan plan_attached(const mate_engine *e, bool selected) {
+    AttachedPlan pl;
+    pl.execute = pl.observe = selected;
+    pl.action_mask = e->selection_on && e->selection.action_mask && !e->masks_stale;
+    pl.reward = e->reward_on;
+    pl.state = e->state_dst != nullptr;
+    pl.selection_blocks = blocks_of(e, kSelectionEnvsPerBlock);
+    pl.selection_lds = (size_t)selection_lds_bytes(e->p.DW);
+    return pl;
 }

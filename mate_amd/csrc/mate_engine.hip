@@ -22,6 +22,7 @@
 #include "aux_kernels.hpp"
 #include "state_rows.hpp"
 #include "reward_rows.hpp"
+#include "selection_rows.hpp"
 #include "engine_host.h"
 
 using namespace mate;
@@ -685,9 +686,12 @@ static int launch_state_rows(mate_engine *e, void *dst, bool f64, const void *ab
 
 // Behind every entry point that leaves new records: the attached rows, as the call's LAST launch on its stream -- behind the
 // auto-reset launch where the call has one, so that a restarted environment's row and observation rows show the same episode.
+static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream);
 static int refresh_state_rows(mate_engine *e, int rc, void *stream) {
-    if (rc != MATE_OK || !e || !e->state_dst) return rc;
-    return launch_state_rows(e, e->state_dst, e->state_f64, e->state_ab, (hipStream_t)stream);
+    if (rc != MATE_OK || !e) return rc;
+    const AttachedPlan pl = plan_attached(e, false);
+    if (pl.action_mask) { const int rc_ = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    return pl.state ? launch_state_rows(e, e->state_dst, e->state_f64, e->state_ab, (hipStream_t)stream) : MATE_OK;
 }
 
 // (scale, bias) host arrays -> the kernel's interleaved table in the row type
@@ -768,11 +772,28 @@ static int check_reward_io(const mate_engine *e, const mate_step_io *io) {
         return fail(MATE_EINVAL, "reward rows are attached (mate_engine_enable_reward_rows): the call needs io->scalars_dev and io->masks_dev");
     return MATE_OK;
 }
-// Behind a stepping launch, ahead of the restart of what it finished: the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers).
-static int reward_rows_of_step(mate_engine *e, const mate_step_io *io, int frames, hipStream_t stream) {
-    if (!e->reward_on) return MATE_OK;
+// ---- target-selection camera actions (csrc/selection_rows.hpp)
+// One selection_kernel launch of `phase`.  Capturable: no allocation, no synchronisation, the same arguments at every call.  The masks are
+// the engine's own copy (Ptrs::own_masks: every step, reset and restart launch that writes a view writes it there).
+static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream) {
+    SelectionArgs a = e->selection;
+    a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->cam_mode;
+    with_obs_type(e->selection_act_f64, [&](auto tag) {
+        hipLaunchKernelGGL(selection_kernel<decltype(tag)>, dim3(pl.selection_blocks), dim3(256), pl.selection_lds, stream, (const Params *)e->d_params, (const Ptrs)e->g, (const SelectionArgs)a);
+    });
+    HIP_TRY(hipGetLastError());
+    return MATE_OK;
+}
+// Behind a stepping launch, ahead of the restart of what it finished: the attached rows of the launch's last frame (`frames` > 1:
+// rollout-shaped buffers), as plan_attached orders them -- reward rows, then the selection metrics.
+static int attached_rows_of_step(mate_engine *e, const mate_step_io *io, int frames, bool selected, hipStream_t stream) {
+    const AttachedPlan pl = plan_attached(e, selected);
     const size_t last = (size_t)(frames - 1) * (size_t)e->N;
-    return launch_reward_rows(e, e->reward_accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
+    if (pl.reward) {
+        const int rc = launch_reward_rows(e, e->reward_accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
+        if (rc != MATE_OK) return rc;
+    }
+    return pl.observe ? launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream) : MATE_OK;
 }
 // Behind a restart launch, a reset or an import: the goals and episodes the next step's sparse_delivery is measured against.
 static int refresh_reward_snapshot(mate_engine *e, int rc, hipStream_t stream) {
@@ -838,7 +859,7 @@ static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_st
     g.reset_mask = env_mask_dev;
     int rc = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream);
     if (rc == MATE_OK && !env_mask_dev) {
-        e->was_reset = true;
+        e->was_reset = true; e->masks_stale = false;
         if (!e->dev_tick) {      // nothing is finished any more: the lists of a batched-reset interval in progress are void
             HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
             e->steps_since_reset = 0; e->pending_interval = 0;
@@ -863,7 +884,7 @@ static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const ma
     g.reset_mask = env_mask_dev;
     g.reset_tape = tape_dev; g.reset_tape_len = tape_len; g.reset_draws = draws_used_dev;
     int rc = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream);
-    if (rc == MATE_OK && !env_mask_dev) e->was_reset = true;
+    if (rc == MATE_OK && !env_mask_dev) { e->was_reset = true; e->masks_stale = false; }
     return rc;
 }
 
@@ -1052,7 +1073,7 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
     return refresh_reward_snapshot(e, MATE_OK, stream);      // (new episodes: their goals are what the next step's sparse_delivery compares with)
 }
 
-static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream) {
+static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream, bool selected = false) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
     if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
@@ -1077,9 +1098,10 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     if (pl.E > 1) { g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0; }      // (the sub-wave rollout kernel with ONE step)
     launch(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g);
     HIP_TRY(hipGetLastError());
+    e->masks_stale = false;
     if (mode == MODE_OBSERVE) return MATE_OK;
     if (!e->dev_tick) e->tick += 1;
-    { const int rc_ = reward_rows_of_step(e, io, 1, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
+    { const int rc_ = attached_rows_of_step(e, io, 1, selected, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
     // (the restart writes the caller's observation buffers and masks; the immediate one, idle almost always, stays ONE launch, and so
     // does the interval's unless the on-device agents play: their ~1.2 k-step episodes finish somewhere in the batch all the time)
     return restart_finished(e, auto_reset, Restart{io, true, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, false, e->greedy_team_bits != 0, 1u, kStepFlow}, stream);
@@ -1114,8 +1136,9 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     hipExtLaunchKernelGGL(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
-    { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = attached_rows_of_step(e, io, steps, false, stream); if (rc_ != MATE_OK) return rc_; }
     // (state only, placement and tables: the next rollout observes the fresh episode on its first step)
+    if (auto_reset >= 1) e->masks_stale = true;      // (... and until then the view masks of a restarted environment are its finished episode's)
     return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, PH_PLACE | PH_LUT, false, false, 0u, kRolloutFlow}, stream);
 }
 
@@ -1198,10 +1221,11 @@ static bool one_launch_step(const mate_engine *e, const FusedCall &c, const mate
     return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64;
 }
 
-static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false);
+static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 
 // team_caller: -1 = both teams are the on-device agents; 0 / 1 = the camera / target team's joint action is the caller's
-static int step_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, hipStream_t stream) {
+// selected: the call is mate_engine_step_selected (the camera team's joint action is the executor's; the metrics follow the step)
+static int step_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, hipStream_t stream, bool selected = false) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     // (pipelined restarts still in flight rewrite records, masks and `done` tags on the side stream: the agents' kernel of the
     // two-launch form reads all three, so the mode is left HERE, not only in launch_step behind it)
@@ -1209,7 +1233,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone)
     const FusedCall c = fused_call(e, team_caller, io);
     if (one_launch_step(e, c, io, tape) && plan_with_policies(e, true, team_caller).fits())
-        return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true);
+        return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true, selected);
     if (!c.reset) return fail(MATE_ESTATE, "step_greedy called before reset() (or import_state)");
     // (works with a device-resident step counter too -- the agents take their tick from the environment record -- so the
     // learner-versus-greedy loop can be captured in a HIP graph like step(); launch_step checks the reset interval)
@@ -1240,7 +1264,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (team_caller != 0) { io2.camera_actions_dev = q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
     if (team_caller != 1) { io2.target_actions_dev = q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
-    const int rc = launch_step(e, &io2, MODE_STEP, auto_reset, stream);
+    const int rc = launch_step(e, &io2, MODE_STEP, auto_reset, stream, selected);
     e->greedy_team_bits = 0;
     return rc;
 }
@@ -1252,6 +1276,77 @@ extern "C" int mate_engine_step_greedy(mate_engine *e, const mate_step_io *io, c
 extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
     return refresh_state_rows(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), stream);
+}
+
+// Target-selection camera actions (include/mate_engine.h).  The buffers are the caller's, but for the joint action the executor hands to
+// the stepping launch: engine-owned, f64 unless MATE_SELECTION_ACT_F32.
+extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const void *selection_dev, double *metrics_dev, int32_t *frames_dev,
+                                            uint8_t *action_mask_dev, int32_t flags) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!selection_dev) return fail(MATE_EINVAL, "enable_selection: null selection buffer");
+    if (mode != MATE_SELECTION_SINGLE && mode != MATE_SELECTION_MULTI) return fail(MATE_EINVAL, "enable_selection: mode must be MATE_SELECTION_SINGLE or MATE_SELECTION_MULTI");
+    if (flags & ~(MATE_SELECTION_ACCUMULATE | MATE_SELECTION_ACT_F32)) return fail(MATE_EINVAL, "enable_selection: unknown flag bits");
+    if (e->p.Nc == 0) return fail(MATE_EINVAL, "enable_selection: the scenario has no cameras to act for");
+    if ((reinterpret_cast<uintptr_t>(selection_dev) & 3u) || (reinterpret_cast<uintptr_t>(metrics_dev) & 7u) || (reinterpret_cast<uintptr_t>(frames_dev) & 3u))
+        return fail(MATE_EINVAL, "enable_selection: a buffer is not aligned to its element size");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "enable_selection: call mate_engine_policy_enable() first (the opponents, and the engine's own view masks)");
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_selection called before reset() (or import_state)");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (no launch reads the arguments while they change)
+    int rc = MATE_OK;
+    if (!e->d_selection_actions && (rc = dev_alloc(e, &e->d_selection_actions, (size_t)e->N * e->p.Nc * 2))) return rc;
+    mate_layout layout;
+    if ((rc = mate_engine_get_layout(e, &layout))) return rc;
+    SelectionArgs a{};
+    a.selection = selection_dev; a.actions = e->d_selection_actions;
+    a.metrics = metrics_dev; a.frames = frames_dev; a.action_mask = action_mask_dev;
+    a.multi = mode == MATE_SELECTION_MULTI; a.accumulate = (flags & MATE_SELECTION_ACCUMULATE) != 0;
+    a.bit_ct = layout.bit_camera_target;
+    e->selection = a; e->selection_act_f64 = !(flags & MATE_SELECTION_ACT_F32);
+    e->selection_on = true;
+    const AttachedPlan pl = plan_attached(e, false);
+    if (!pl.action_mask) return MATE_OK;
+    // action_mask() of the observation rows as they are, complete when the call returns (the caller need not know the stream)
+    if ((rc = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, e->last_stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->last_stream));
+    return MATE_OK;
+}
+extern "C" int mate_engine_disable_selection(mate_engine *e) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    e->selection_on = false;
+    return MATE_OK;
+}
+extern "C" int mate_engine_selection_actions(mate_engine *e, void **actions_dev, int32_t *act_dtype) {
+    if (!e || !actions_dev) return fail(MATE_EINVAL, "null argument");
+    if (!e->selection_on) return fail(MATE_ESTATE, "selection_actions: mate_engine_enable_selection has not run");
+    *actions_dev = e->d_selection_actions;
+    if (act_dtype) *act_dtype = e->selection_act_f64 ? MATE_ACT_F64 : MATE_ACT_F32;
+    return MATE_OK;
+}
+
+// The launches of plan_attached around exactly what mate_engine_step_versus_greedy(team = camera) enqueues, with the engine-owned joint action.
+extern "C" int mate_engine_step_selected(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream_) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!e->selection_on) return fail(MATE_ESTATE, "step_selected: call mate_engine_enable_selection() first");
+    if (auto_reset < 0) return fail(MATE_ESTATE, "step_selected is not available under pipelined restarts (auto_reset = MATE_RESET_PIPELINED)");
+    if (!io || !io->scalars_dev) return fail(MATE_EINVAL, "step_selected needs io->scalars_dev (the metrics skip environments whose record says done = 2)");
+    if (e->masks_stale) return fail(MATE_ESTATE, "step_selected: the view masks are older than the records (a fused random rollout restarted episodes, or import_state): call observe() first");
+    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }      // (a rejected call launches nothing)
+    // the state checks of the stepping flows and what they enqueue ahead of their launch, all AHEAD of the executor: a rejected call
+    // leaves the action buffer alone; pipelined restarts in flight are joined before the executor reads the mask words; an open
+    // reset interval of another flow restarts what it finished before the executor looks at it
+    { const int rc_ = enter(e, stream, "step_selected"); if (rc_ != MATE_OK) return rc_; }
+    if (!e->policy_ready) return fail(MATE_ESTATE, "step_selected: call mate_engine_policy_enable() before the reset whose observations the policies act on");
+    note_stream(e, stream);
+    { const int rc_ = flush_pending(e, auto_reset, kStepFlow, stream); if (rc_ != MATE_OK) return rc_; }
+    mate_step_io io2 = *io;
+    io2.camera_actions_dev = e->d_selection_actions;
+    io2.act_dtype = (io->act_dtype & ~(0xff | MATE_ACT_CAMERA_DISCRETE)) | (e->selection_act_f64 ? MATE_ACT_F64 : MATE_ACT_F32);
+    int rc = launch_selection(e, plan_attached(e, true), SELECTION_EXECUTE, nullptr, stream);
+    if (rc == MATE_OK) rc = step_with_policies(e, MATE_TEAM_CAMERA, &io2, tape, auto_reset, stream, true);
+    return refresh_state_rows(e, rc, stream_);
 }
 
 // What differs between the two forms of rollout_with_policies, spelled once (after struct Restart):
@@ -1269,7 +1364,7 @@ struct PolicyFlow {
                                  // FrameSkip in a HIP graph; the auto-reset launch behind every auto_reset-th launch advances the counter by auto_reset * K
 };
 
-static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step) {
+static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step, bool selected) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     const FusedCall c = fused_call(e, team_caller, io);
     const bool pipelined = auto_reset < 0;          // MATE_RESET_PIPELINED (-1), or -m: one restart launch behind every m-th rollout launch
@@ -1289,6 +1384,8 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     // (the restarts run on the engine's side stream UNDER the next launches: a state-row launch on the caller's stream would read records they rewrite)
     if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
     if (pipelined && e->reward_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while reward rows are attached (mate_engine_enable_reward_rows): detach them first");
+    // (... and the view masks the selection executor reads)
+    if (pipelined && e->selection_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while target selection is attached (mate_engine_enable_selection): detach it first");
     { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
@@ -1322,8 +1419,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     e->last_flow = pl.last_flow;
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
+    e->masks_stale = false;
     if (!e->dev_tick) e->tick += (uint32_t)steps;
-    { const int rc_ = reward_rows_of_step(e, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = attached_rows_of_step(e, io, steps, selected, stream); if (rc_ != MATE_OK) return rc_; }
     return pipelined ? pipelined_restart(e, stream) : restart_finished(e, auto_reset, flow.restart, stream);
 }
 
@@ -1373,7 +1471,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     int32_t tick = 0;
     HIP_TRY(hipMemcpy(&tick, reinterpret_cast<const int32_t *>(e->g.dyn + e->p.DF) + e->p.Nt * TI_STRIDE + EI_TICK, sizeof(tick), hipMemcpyDeviceToHost));
     e->tick = (uint32_t)tick;
-    e->was_reset = true;
+    e->was_reset = true; e->masks_stale = true;      // (records only: the view masks are whatever ran before)
     return refresh_state_rows(e, refresh_reward_snapshot(e, MATE_OK, (hipStream_t)stream), stream);
 }
 

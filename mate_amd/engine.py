@@ -12,7 +12,8 @@ import torch
 from mate_amd import _native
 from mate_amd._native import MateConfig, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 
-__all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'SCALAR_NAMES', 'REWARD_REDUCTIONS']
+__all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'encode_selection', 'decode_selection',
+           'SCALAR_NAMES', 'REWARD_REDUCTIONS']
 
 SCALAR_NAMES = ('camera_team_reward', 'target_team_reward', 'done', 'coverage_rate', 'real_coverage_rate',
                 'mean_transport_rate', 'num_delivered_cargoes', 'normalized_target_team_reward')
@@ -38,6 +39,31 @@ def export_layout(Nc, Nt, No):
 
 
 REWARD_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2, 'max': 3, 'min': 4}      # MATE_REDUCE_* (include/mate_engine.h)
+
+
+def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
+    """The reference's HierarchicalCamera action (examples/hrl/wrappers.py) -> the int32 words [N, Nc] mate_engine_enable_selection reads:
+    multi-selection [N, Nc, Nt] of 0 / 1 -> bit t of the word (already packed [N, Nc] words pass through); single selection [N, Nc]
+    indices in [0, Nt] (Nt: none) as they are.  Shape and dtype are checked, values are not.  Runs where `selection` lives."""
+    selection = torch.as_tensor(selection, device=device)
+    assert not selection.dtype.is_floating_point and not selection.dtype.is_complex, f'selections are integers (got {selection.dtype})'
+    if multi and selection.dim() == 3:
+        assert selection.shape == (num_envs, num_cameras, num_targets), tuple(selection.shape)
+        weights = 1 << torch.arange(num_targets, device=selection.device, dtype=torch.int64)
+        return ((selection != 0).to(torch.int64) * weights).sum(-1).to(torch.int32)
+    assert selection.shape == (num_envs, num_cameras), tuple(selection.shape)
+    return selection.to(torch.int32)
+
+
+def decode_selection(words, multi, num_targets):
+    """The words of encode_selection -> [..., Nt] bool, the targets the executor takes as selected (selection_kernel reads them the same
+    way): bit t of a multi-selection word, bits beyond Nt ignored; the one-hot row of a single selection's index (the wrapper's
+    index2onehot), all zero for Nt -- and for any index outside [0, Nt)."""
+    words = torch.as_tensor(words).to(torch.int64)
+    t = torch.arange(num_targets, device=words.device, dtype=torch.int64)
+    if multi:
+        return ((words[..., None] >> t) & 1).bool()
+    return words[..., None] == t
 
 
 def reward_term_keys(team):
@@ -141,6 +167,10 @@ class Engine:
         # and the two coefficient tables on the device ({'camera': [7], 'target': [10]} f64)
         self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
         self.reward_coefficients = None
+        # while target selection is attached (enable_selection): the learner's selection [N, Nc] int32, the executor's joint action
+        # [N, Nc, 2] (engine-owned), the metrics [N, Nc, 4] f64, the contributing frames [N] int32 and action_mask() [N, Nc, 2 Nt | Nt + 1] u8
+        self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
+        self.multi_selection = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -641,7 +671,7 @@ class Engine:
         check(self.lib.mate_engine_enable_reward_rows(self._h, ctypes.byref(cfg)))
         self.camera_reward_rows, self.target_reward_rows = rows.get('camera'), rows.get('target')
         self.camera_reward_terms, self.target_reward_terms = term_rows.get('camera'), term_rows.get('target')
-        self.reward_coefficients = coefficients
+        self.reward_coefficients, self.reward_accumulate = coefficients, bool(accumulate)
         self.__dict__.pop('_random_io', None)
         return self.camera_reward_rows, self.target_reward_rows
 
@@ -650,6 +680,62 @@ class Engine:
         check(self.lib.mate_engine_enable_reward_rows(self._h, None))
         self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
         self.reward_coefficients = None
+
+    # ------------------------------------------------------------------ target-selection camera actions (HierarchicalCamera)
+    SELECTION_METRICS = ('num_selected_targets', 'num_valid_selected_targets', 'num_invalid_selected_targets', 'invalid_target_selection_rate')
+
+    def encode_selection(self, selection, multi_selection=None):
+        """encode_selection() of this module for this engine's shape, on its device."""
+        multi = self.multi_selection if multi_selection is None else bool(multi_selection)
+        return encode_selection(selection, multi, self.num_envs, self.num_cameras, self.num_targets, device=self.device)
+
+    def enable_selection(self, multi_selection=True, selection=None, accumulate=False, act_dtype=torch.float64):
+        """Attach the executor of the reference's HierarchicalCamera wrapper (examples/hrl/wrappers.py): from now on step_selected()
+        turns `Engine.selection` ([N, Nc] int32: bit t = target t selected, or -- single selection -- an index in [0, Nt], Nt = none)
+        into the camera team's joint action on the device (`selection_actions` [N, Nc, 2]), steps against the greedy targets, and
+        leaves the wrapper's four metrics in `selection_metrics` [N, Nc, 4] f64 (SELECTION_METRICS), the frames that contributed in
+        `selection_frames` [N] int32 and action_mask() of the next observation in `action_mask` ([N, Nc, 2 Nt] / [N, Nc, Nt + 1] u8).
+        `accumulate`: metrics and frames add up over calls (FrameSkip: mean = metrics / frames; zero both when consumed).  `selection`: a
+        caller-owned int32 [N, Nc] tensor to read instead of a new one.  Needs enable_policies() and a reset() since.  Returns the
+        selection tensor."""
+        N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
+        assert act_dtype in (torch.float32, torch.float64)
+        with torch.cuda.device(self.device):
+            if selection is None:
+                selection = torch.full((N, Nc), 0 if multi_selection else Nt, dtype=torch.int32, device=self.device)
+            assert selection.dtype == torch.int32 and selection.shape == (N, Nc) and selection.is_contiguous() and selection.device == self.device, \
+                'selection: a contiguous int32 [num_envs, num_cameras] tensor on the engine device'
+            metrics = torch.zeros((N, Nc, 4), dtype=torch.float64, device=self.device)
+            frames = torch.zeros(N, dtype=torch.int32, device=self.device)
+            action_mask = torch.zeros((N, Nc, 2 * Nt if multi_selection else Nt + 1), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        flags = (1 if accumulate else 0) | (2 if act_dtype == torch.float32 else 0)
+        check(self.lib.mate_engine_enable_selection(self._h, int(bool(multi_selection)), ctypes.c_void_p(selection.data_ptr()), ctypes.c_void_p(metrics.data_ptr()),
+                                                    ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(action_mask.data_ptr()), flags))
+        ptr, code = ctypes.c_void_p(), ctypes.c_int32()
+        check(self.lib.mate_engine_selection_actions(self._h, ctypes.byref(ptr), ctypes.byref(code)))
+
+        class _Owned:      # the engine-owned joint action as a zero-copy tensor (the engine outlives it: the tensor keeps `self`)
+            def __init__(view, owner):
+                view.owner = owner
+                view.__cuda_array_interface__ = {'shape': (N * Nc * 2,), 'typestr': '<f8' if code.value == 1 else '<f4', 'data': (ptr.value, False), 'version': 2}
+        self.selection_actions = torch.as_tensor(_Owned(self), device=self.device).view(N, Nc, 2)
+        self.selection, self.selection_metrics, self.selection_frames, self.action_mask = selection, metrics, frames, action_mask
+        self.multi_selection, self.selection_accumulate = bool(multi_selection), bool(accumulate)
+        return selection
+
+    def disable_selection(self):
+        check(self.lib.mate_engine_disable_selection(self._h))
+        self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
+        self.multi_selection = None
+
+    def step_selected(self, policy_tape=None, tape_ct=None, tape_goal=None, auto_reset=True):
+        """One frame of HierarchicalCamera over MultiCamera(target_agent=GreedyTargetAgent()): the executor turns `Engine.selection` into
+        the cameras' joint action, the greedy targets act, the environment steps; metrics, action mask and the attached rows follow
+        (mate_engine_step_selected).  Returns (camera_obs, target_obs, scalars)."""
+        io, keep = self._io(tape_ct=tape_ct, tape_goal=tape_goal)
+        check(self.lib.mate_engine_step_selected(self._h, ctypes.byref(io), self._policy_tape(policy_tape, keep), int(auto_reset), self._stream()))
+        return self.camera_obs, self.target_obs, self.scalars
 
     # One copy per step for the N = 1 NumPy API (mate_amd.environment): the output tensors and an export_state buffer become views of
     # ONE device allocation, and fetch_host() brings a step's results over in a single transfer (five blocking copies of a few KB each
@@ -843,6 +929,20 @@ class Stepper:
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
         # versus = 'camera' / 'target': the caller's team (MultiCamera / MultiTarget); the other team is played by the on-device
         # greedy agents (Engine.step_versus_greedy) and its tensor argument is ignored
+        # versus = 'selection': the camera learner emits target selections (Engine.enable_selection first); every step of this stepper is
+        # one FRAGMENT of HierarchicalCamera: frame_skip x (executor, greedy targets + step, reward rows, metrics) with the selection held.
+        # A finished environment must execute no further frame of its fragment and restart behind it: the frames run under the engine's
+        # batched restart with the interval frame_skip (finished environments idle, done = 2; the restart, the action mask and the state
+        # rows follow the fragment's LAST frame), and fragments stay aligned with that interval because (a) a fragment is only ever run
+        # whole (_one), (b) the constructor closes whatever interval was open (device_tick on / off: what had finished restarts, the
+        # count starts at 0) and (c) `auto_reset` must be 1 fragment.  Metrics, frames and accumulating reward rows are zeroed at the
+        # head of every fragment, inside the graph too.
+        self.selection = versus == 'selection'
+        if self.selection:
+            assert eng.selection is not None, 'Engine.enable_selection() first'
+            assert self.auto_reset == 1, "versus='selection': finished environments restart behind their fragment (auto_reset = True)"
+            assert self.frame_skip == 1 or eng.selection_accumulate, 'frame_skip > 1 sums the metrics over the frames: enable_selection(accumulate=True)'
+            versus, cam_act, tgt_act = None, None, None
         self.versus = {'camera': 0, 'target': 1, None: None}.get(versus, versus)
         assert self.versus in (None, 0, 1)
         if self.versus == 0:
@@ -855,7 +955,7 @@ class Stepper:
             (cam_act is None or eng.num_cameras == 0 or self.io.camera_actions_dev == cam_act.data_ptr()), \
             'action tensors must be contiguous f32/f64 (or int32 grid indices) on the engine device'
         self.outputs = None
-        if self.frame_skip > 1:
+        if self.frame_skip > 1 and not self.selection:
             shaped = eng.reward_coefficients is not None      # (the reward launch reads the last frame's masks)
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
             self.io.camera_obs_dev = buf['camera_obs'].data_ptr() if eng.num_cameras else None
@@ -868,10 +968,14 @@ class Stepper:
         self.graph = None
         self._phase = 0                                   # steps into the current reset interval (graphs hold whole intervals)
         self.warmup_steps = self.auto_reset if self.graph_steps > 0 else 0      # real steps the constructor runs (see the class note)
+        if self.selection and self.frame_skip > 1:
+            eng.device_tick(self.frame_skip)              # (closes an open reset interval: fragments start on an interval boundary)
+            if self.graph_steps == 0:
+                eng.device_tick(False)
         if self.graph_steps > 0:
             assert self.auto_reset >= 1 and self.graph_steps % self.auto_reset == 0, \
                 'graph replay needs auto_reset >= 1 (the auto-reset launch advances the device step counter) and whole reset intervals per graph'
-            eng.device_tick(self.auto_reset)
+            eng.device_tick(self.frame_skip if self.selection else self.auto_reset)
             for _ in range(self.auto_reset):
                 self._one()                               # code objects loaded before the capture (one whole reset interval)
             torch.cuda.synchronize(eng.device)
@@ -884,7 +988,18 @@ class Stepper:
         if self.between is not None:
             self.between()
         eng = self.eng
-        if self.versus is None:
+        if self.selection:
+            if eng.selection_accumulate:
+                eng.selection_metrics.zero_()
+                eng.selection_frames.zero_()
+                if eng.reward_coefficients is not None and getattr(eng, 'reward_accumulate', False):
+                    for rows in (eng.camera_reward_rows, eng.target_reward_rows):
+                        if rows is not None:
+                            rows.zero_()
+            status = 0
+            for _ in range(self.frame_skip):
+                status = status or eng.lib.mate_engine_step_selected(eng._h, self.ref, None, self.frame_skip if self.frame_skip > 1 else self.auto_reset, eng._stream())
+        elif self.versus is None:
             status = eng.lib.mate_engine_step(eng._h, self.ref, self.auto_reset, eng._stream())
         elif self.frame_skip > 1:
             status = eng.lib.mate_engine_rollout_versus_greedy(eng._h, self.versus, self.ref, self.frame_skip, self.auto_reset, eng._stream())

@@ -638,7 +638,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
-                 camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, **kwargs):
+                 camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
@@ -675,6 +675,13 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         for team, spec in self._reward_shaping.items():
             reward_coefficient_table(team, *spec)
         self._reward_dtype = reward_dtype
+        # HierarchicalCamera(MultiCamera(env, GreedyTargetAgent()), multi_selection) of the reference's hierarchical camera trainers
+        # (examples/hrl/wrappers.py), one frame per call: 'multi' / 'single'; attached behind the first reset() (Engine.enable_selection)
+        assert camera_selection in (None, 'multi', 'single'), f"camera_selection = {camera_selection!r}: None, 'multi' or 'single'"
+        self.camera_selection = camera_selection
+        if camera_selection:
+            assert self.num_cameras > 0, 'camera_selection needs cameras'
+            self.enable_greedy_policies()
 
     def seed(self, seed):
         self.engine.seed(int(seed))
@@ -700,6 +707,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self.engine.enable_state_rows(normalize=self.state_rows == 'normalized')
         if self._reward_shaping and self.engine.reward_coefficients is None:
             self.engine.enable_reward_rows(camera=self._reward_shaping.get('camera'), target=self._reward_shaping.get('target'), dtype=self._reward_dtype)
+        if self.camera_selection and self.engine.selection is None:
+            self.engine.enable_selection(self.camera_selection == 'multi')
         for shaper in self.__dict__.get('_target_shapers', {}).values():
             shaper.observe_reset()
         return out
@@ -759,6 +768,35 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if not getattr(self, '_policies_on', False):
             raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
         return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
+
+    def step_selected(self, selection, **replay):
+        """One frame of HierarchicalCamera.step (examples/hrl/wrappers.py:93-152) for every environment: `selection` is [num_envs,
+        num_cameras, num_targets] of 0 / 1 (camera_selection='multi'; or the packed [num_envs, num_cameras] words) or [num_envs,
+        num_cameras] indices in [0, num_targets] ('single'; num_targets = none), integers, checked for shape and dtype only.  The
+        executor and the greedy targets act on the device.  Returns step()'s result; `selection_info()` and `action_mask()` follow it.
+        The wrapper's frame_skip = K is K calls with the selection held, in an environment built with auto_reset = K: an environment
+        that finishes inside the fragment idles for the rest of it (done stays set, selection_info()['frames'] is 0: add neither its
+        rewards nor its metrics) and restarts behind the fragment's last call.  (In a graph: Engine.make_stepper(versus='selection',
+        frame_skip=K).)  `replay`: recorded draws, as Engine.step_selected takes them (policy_tape, tape_ct, tape_goal)."""
+        assert self.camera_selection, "built without camera_selection='multi' | 'single'"
+        eng = self.engine
+        assert eng.selection is not None, 'reset() first'
+        eng.selection.copy_(eng.encode_selection(selection))
+        eng.step_selected(auto_reset=self.auto_reset, **replay)
+        return self._result()
+
+    def selection_info(self):
+        """The wrapper's infos of the frame step_selected last ran, {name: [num_envs, num_cameras] f64} for the four SELECTION_METRICS,
+        and 'frames': [num_envs] int32 -- 1, or 0 for an environment that idles behind its terminal frame (its metrics are zero)."""
+        eng = self.engine
+        info = {name: eng.selection_metrics[:, :, k] for k, name in enumerate(eng.SELECTION_METRICS)}
+        info['frames'] = eng.selection_frames
+        return info
+
+    def action_mask(self):
+        """action_mask() (examples/hrl/wrappers.py:166-175) of the camera rows the learner sees next: [num_envs, num_cameras, 2 num_targets]
+        ('multi': even entries 1) or [num_envs, num_cameras, num_targets + 1] ('single': last entry 1) u8, the same tensor every time."""
+        return self.engine.action_mask
 
     def masks(self):
         return self.engine.unpack_masks()
