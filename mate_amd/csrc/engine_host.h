@@ -1,6 +1,6 @@
-// engine_host.h -- the host's state of one engine (struct mate_engine, the environment switches) and the launch plans: the pure decisions over
-// that state of which kernel a stepping entry point runs, on how many workgroups, with how much LDS.  Host only: included by mate_engine.hip, never
-// by the shape-group translation units; nothing here calls HIP.
+// engine_host.h -- the host's state of one engine (struct mate_engine, the environment switches, one struct per attached feature) and the launch plans: the pure
+// decisions over that state of which kernel a stepping entry point runs, on how many workgroups, with how much LDS (LaunchPlan), and of what is enqueued around it
+// in which order (AttachedPlan: the ONE place that order is written).  Host only: included by mate_engine.hip, never by the shape-group units; nothing here calls HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "reset_kernels.hpp"
 #include "reward_rows.hpp"
 #include "selection_rows.hpp"
+#include "state_rows.hpp"
 #include "shape_groups.hpp"
 
 using namespace mate;
@@ -36,6 +37,23 @@ struct Switches {
     bool step_greedy_rollout = false;   // MATE_STEP_GREEDY_ROLLOUT=1: the one-launch form of step_greedy / step_versus_greedy on rollout_greedy_kernel with one step (round 3) instead of step_greedy_kernel
     bool pipelined_low_priority = true; // MATE_PIPELINED_PRIORITY=0: the side stream of the pipelined restarts at the default priority instead of the device's lowest
     bool pipelined_serial = false;      // MATE_PIPELINED_SERIAL=1: the pipelined-restart protocol with the resets on the CALLER's stream (the tests' reference)
+};
+// ---- attached state, one struct per feature: the launch's arguments, the engine-owned buffers (kept across re-attachments), whether it is on
+struct StateRows {       // mate_engine_enable_state_rows: the caller's [N][S] buffer, its type, its (scale, bias) table on the device (null: raw rows)
+    void *dst = nullptr; bool f64 = false; const void *ab = nullptr; void *d_ab = nullptr, *d_ab_demand = nullptr;
+    std::vector<double> demand_table;            // of the last on-demand call (mate_engine_state_rows): scale[S] | bias[S] | type, as uploaded to d_ab_demand
+    bool on() const { return dst != nullptr; }
+};
+struct RewardRows {      // mate_engine_enable_reward_rows: scalars, masks and mode of `args` are the launch's own
+    bool on = false, f64 = false, soft = false, accumulate = false;      // attached; the row type; the soft-coverage launch goes in front; rows += shaped
+    RewardArgs args{};
+    int32_t *d_snapshot = nullptr; double *d_matrix = nullptr, *d_scores = nullptr;
+};
+struct Selection {       // mate_engine_enable_selection: phase, masks and scalars of `args` are the launch's own
+    bool on = false, act_f64 = true;             // attached; the type of the engine-owned action buffer d_actions, [N][Nc][2]
+    SelectionArgs args{};
+    double *d_actions = nullptr;
+    bool masks_stale = false;                    // a state-only restart (rollout_random's) or import_state ran since the view masks were last written
 };
 struct mate_engine {
     Switches sw{};
@@ -81,25 +99,7 @@ struct mate_engine {
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
-    // global state rows (mate_engine_enable_state_rows): the caller's [N][S] buffer every record-changing call refreshes, its type,
-    // its (scale, bias) table on the device (null: raw rows); and the table of the last on-demand call (mate_engine_state_rows)
-    void *state_dst = nullptr;
-    bool state_f64 = false;
-    void *d_state_ab = nullptr, *d_state_ab_demand = nullptr;
-    const void *state_ab = nullptr;
-    std::vector<double> state_demand_table;      // scale[S] | bias[S] | type, as uploaded to d_state_ab_demand
-    // shaped reward rows (mate_engine_enable_reward_rows): the attached launch's arguments (scalars, masks and mode are the launch's own),
-    // the row type, whether the soft-coverage launch goes in front, and the engine-owned buffers (kept across re-attachments)
-    bool reward_on = false, reward_f64 = false, reward_soft = false, reward_accumulate = false;
-    RewardArgs reward{};
-    int32_t *d_reward_snapshot = nullptr;
-    double *d_reward_matrix = nullptr, *d_reward_scores = nullptr;
-    // target-selection camera actions (mate_engine_enable_selection): the attached launches' arguments (phase, masks and scalars are the
-    // launch's own) and the type of the engine-owned action buffer
-    bool selection_on = false, selection_act_f64 = true;
-    SelectionArgs selection{};
-    double *d_selection_actions = nullptr;       // [N][Nc][2] of f64 (or, in the same bytes, f32)
-    bool masks_stale = false;                    // a state-only restart ran since the view masks were last written (rollout_random's)
+    StateRows state; RewardRows reward; Selection selection;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -108,9 +108,9 @@ struct mate_engine {
 };
 
 // ---- launch plans
-// What a stepping entry point launches is decided HERE, as a value, by three pure functions of the engine (and of the call's record pointers where
-// the flow depends on them): no HIP call, no allocation, nothing written, no environment variable read.  Everything else reads the plan: the launch
-// sites launch it, policy_enable opts in what plan_with_policies can return, step_with_policies asks whether it fits, set_sub_wave reports its E.
+// What a stepping entry point launches is decided HERE, as a value, by pure functions of the engine (and of the call's record pointers where
+// the flow depends on them): no HIP call, no allocation, nothing written, no environment variable read.  Everything else reads the plan: the launch sites launch
+// it and compute no geometry, policy_enable opts in what plan_with_policies can return, step_with_policies asks whether it fits, set_sub_wave reports its E.
 struct LaunchPlan {
     StepFn step = nullptr; PolicyFn policy = nullptr;      // the kernel: of launch_step and rollout_random_impl, or of rollout_with_policies
     int E = 1;                                             // environments per wave (engine_kernels.hpp, Ctx<ObsT, L>)
@@ -191,29 +191,40 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
     return policy_form(e, sub ? FORM_ROLLOUT_SUB : light ? FORM_STEP_GREEDY : FORM_ROLLOUT, team_caller);
 }
 
-// What a stepping call enqueues AROUND its stepping launch (the LaunchPlan above), in the order of the fields: the one place that order is
-// written down.  The entry points ask for the plan and launch what it names; none of them decides an order of its own.
-//   1 execute      selection_kernel, SELECTION_EXECUTE: the camera team's joint action of this frame        (mate_engine_step_selected)
+// ---- the attached launches
+// What a call enqueues AROUND its stepping (or reset / import) launch, in the order of the fields: THE one place that order is written.  The "attached
+// launches" section of mate_engine.hip has one function per position; each reads this plan and launches what it names, with the geometry it carries.
+//   1 execute      selection_kernel, SELECTION_EXECUTE: the camera team's joint action of this frame       attached_ahead_of_step (step_selected)
 //   2              the stepping launch (and, two-launch form, the opponents' agents in front of it)
-//   3 reward       reward_rows_kernel (soft coverage in front): the rows of the step that has just run      (mate_engine_enable_reward_rows)
-//   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks
-//   5              the restart epilogue (restart_finished) and, with reward rows, its snapshot refresh
-//   6 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next, the restarted episodes' included
-//   7 state        state_rows_kernel, last                                                                  (mate_engine_enable_state_rows)
+//   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
+//   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
+//   5              the restart epilogue, a reset or an import; with reward rows the snapshot-only launch    attached_behind_restart
+//   6 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
+//   7 state        state_rows_kernel, last                                                                  attached_last
+struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
     bool execute = false, reward = false, observe = false, action_mask = false, state = false;
-    unsigned selection_blocks = 0;
-    size_t selection_lds = 0;
+    Tiles soft_coverage, reward_rows, selection, state_rows;      // (selection: the three phases are one kernel on one grid)
 };
+static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
+// Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
+static Tiles plan_state_rows(const mate_engine *e, bool f64) {
+    const Params &p = e->p;
+    const int S = state_dim_of(p.Nc, p.Nt, p.No), sz = f64 ? 8 : 4;
+    int E = 16;
+    while (E > 4 && state_rows_lds_bytes(p.SW, p.DW, S, E, sz) > 40 * 1024) E /= 2;
+    return {blocks_of(e, E), 256, (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz), E};
+}
 // `selected`: the call is mate_engine_step_selected.  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
 static AttachedPlan plan_attached(const mate_engine *e, bool selected) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;
-    pl.action_mask = e->selection_on && e->selection.action_mask && !e->masks_stale;
-    pl.reward = e->reward_on;
-    pl.state = e->state_dst != nullptr;
-    pl.selection_blocks = blocks_of(e, kSelectionEnvsPerBlock);
-    pl.selection_lds = (size_t)selection_lds_bytes(e->p.DW);
+    pl.action_mask = e->selection.on && e->selection.args.action_mask && !e->selection.masks_stale;
+    pl.reward = e->reward.on;
+    pl.state = e->state.on();
+    if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
+    pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
+    pl.state_rows = plan_state_rows(e, e->state.f64);
     return pl;
 }

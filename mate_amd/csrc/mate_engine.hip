@@ -20,10 +20,7 @@
 #include "reset_kernels.hpp"
 #include "policy_kernels.hpp"
 #include "aux_kernels.hpp"
-#include "state_rows.hpp"
-#include "reward_rows.hpp"
-#include "selection_rows.hpp"
-#include "engine_host.h"
+#include "engine_host.h"      // (state_rows.hpp, reward_rows.hpp, selection_rows.hpp)
 
 using namespace mate;
 
@@ -665,35 +662,84 @@ static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_
 }
 
 
-// ---- global state rows (csrc/state_rows.hpp)
-// One state_rows_kernel launch: the rows of all environments into `dst`.  Capturable: no allocation, no synchronisation, the same
-// arguments at every call.  Environments per workgroup: 16, or fewer where the tile (records + rows) would take more than 40 KB of LDS.
-static int launch_state_rows(mate_engine *e, void *dst, bool f64, const void *ab, hipStream_t stream) {
-    const Params &p = e->p;
-    const int S = state_dim_of(p.Nc, p.Nt, p.No), sz = f64 ? 8 : 4;
-    int E = 16;
-    while (E > 4 && state_rows_lds_bytes(p.SW, p.DW, S, E, sz) > 40 * 1024) E /= 2;
-    const size_t lds = (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz);
-    const unsigned blocks = (unsigned)((e->N + E - 1) / E);
-    with_obs_type(f64, [&](auto tag) {
-        using T = decltype(tag);
-        hipLaunchKernelGGL(state_rows_kernel<T>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g,
-                           reinterpret_cast<T *>(dst), reinterpret_cast<const T *>(ab), (const int32_t)E);
-    });
+// ---- attached launches (csrc/state_rows.hpp, reward_rows.hpp, selection_rows.hpp)
+// Everything a call enqueues around its stepping, reset or import launch while something is attached, in AttachedPlan's order (engine_host.h): the launches it names,
+// each with the plan's geometry and capturable (no allocation, no synchronisation, the same arguments at every call); the one check; one function per position.
+template <class... P>
+static int launch_tiles(void (*fn)(P...), const Tiles &t, hipStream_t stream, std::common_type_t<P>... args) {
+    hipLaunchKernelGGL(fn, dim3(t.blocks), dim3(t.threads), t.lds, stream, args...);
     HIP_TRY(hipGetLastError());
     return MATE_OK;
 }
-
-// Behind every entry point that leaves new records: the attached rows, as the call's LAST launch on its stream -- behind the
-// auto-reset launch where the call has one, so that a restarted environment's row and observation rows show the same episode.
-static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream);
-static int refresh_state_rows(mate_engine *e, int rc, void *stream) {
-    if (rc != MATE_OK || !e) return rc;
-    const AttachedPlan pl = plan_attached(e, false);
-    if (pl.action_mask) { const int rc_ = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
-    return pl.state ? launch_state_rows(e, e->state_dst, e->state_f64, e->state_ab, (hipStream_t)stream) : MATE_OK;
+static int launch_state_rows(mate_engine *e, const Tiles &t, void *dst, bool f64, const void *ab, hipStream_t stream) {
+    return with_obs_type(f64, [&](auto tag) {
+        using T = decltype(tag);
+        return launch_tiles(state_rows_kernel<T>, t, stream, e->d_params, e->g, reinterpret_cast<T *>(dst), reinterpret_cast<const T *>(ab), t.E);
+    });
 }
+static void launch_soft_coverage(mate_engine *e, const Tiles &t, const uint32_t *masks, double *matrix, double *scores, hipStream_t stream) {
+    hipLaunchKernelGGL(soft_coverage_kernel, dim3(t.blocks), dim3(t.threads), t.lds, stream, (const Params *)e->d_params, (const Ptrs)e->g, masks, matrix, scores);
+}
+static int launch_reward_rows(mate_engine *e, const AttachedPlan &pl, int mode, const float *scalars, const uint32_t *masks, hipStream_t stream) {
+    RewardArgs a = e->reward.args;
+    a.mode = mode; a.scalars = scalars; a.masks = masks;
+    if (mode != REWARD_SNAPSHOT && pl.soft_coverage.blocks)      // (in front where the term exists: every mode but the snapshot)
+        launch_soft_coverage(e, pl.soft_coverage, masks, e->reward.d_matrix, e->reward.d_scores, stream);
+    return with_obs_type(e->reward.f64, [&](auto tag) { return launch_tiles(reward_rows_kernel<decltype(tag)>, pl.reward_rows, stream, e->d_params, e->g, a); });
+}
+// (the masks are the engine's own copy, Ptrs::own_masks: every step, reset and restart launch that writes a view writes it there)
+static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream) {
+    SelectionArgs a = e->selection.args;
+    a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->cam_mode;
+    return with_obs_type(e->selection.act_f64, [&](auto tag) { return launch_tiles(selection_kernel<decltype(tag)>, pl.selection, stream, e->d_params, e->g, a); });
+}
+// What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
+// `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own).
+static int check_attached_call(const mate_engine *e, const mate_step_io *io, bool pipelined, bool selected, int auto_reset = 0) {
+    const char *const no_pipeline = "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while %s attached (mate_engine_enable_%s): detach %s first";
+    if (selected && !e->selection.on) return fail(MATE_ESTATE, "step_selected: call mate_engine_enable_selection() first");
+    if (selected && auto_reset < 0) return fail(MATE_ESTATE, "step_selected is not available under pipelined restarts (auto_reset = MATE_RESET_PIPELINED)");
+    if (selected && (!io || !io->scalars_dev)) return fail(MATE_EINVAL, "step_selected needs io->scalars_dev (the metrics skip environments whose record says done = 2)");
+    if (selected && e->selection.masks_stale) return fail(MATE_ESTATE, "step_selected: the view masks are older than the records (a fused random rollout restarted episodes, or import_state): call observe() first");
+    // (the restarts run on the engine's side stream UNDER the next launches: an attached launch on the caller's stream would read records and view masks they rewrite)
+    if (pipelined && e->state.on()) return fail(MATE_ESTATE, no_pipeline, "state rows are", "state_rows", "them");
+    if (pipelined && e->reward.on) return fail(MATE_ESTATE, no_pipeline, "reward rows are", "reward_rows", "them");
+    if (pipelined && e->selection.on) return fail(MATE_ESTATE, no_pipeline, "target selection is", "selection", "it");
+    if (e->reward.on && (!io || !io->scalars_dev || !io->masks_dev))      // (the reward launch reads the step's scalar record and masks)
+        return fail(MATE_EINVAL, "reward rows are attached (mate_engine_enable_reward_rows): the call needs io->scalars_dev and io->masks_dev");
+    return MATE_OK;
+}
+// 1: ahead of the stepping launch (and of the opponents' agents) -- the executor's joint action of this frame
+static int attached_ahead_of_step(mate_engine *e, bool selected, hipStream_t stream) {
+    const AttachedPlan pl = plan_attached(e, selected);
+    return pl.execute ? launch_selection(e, pl, SELECTION_EXECUTE, nullptr, stream) : MATE_OK;
+}
+// 3, 4: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers)
+static int attached_behind_step(mate_engine *e, bool selected, const mate_step_io *io, int frames, hipStream_t stream) {
+    const AttachedPlan pl = plan_attached(e, selected);
+    const size_t last = (size_t)(frames - 1) * (size_t)e->N;
+    if (pl.reward) {
+        const int rc = launch_reward_rows(e, pl, e->reward.accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
+        if (rc != MATE_OK) return rc;
+    }
+    return pl.observe ? launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream) : MATE_OK;
+}
+// 5: behind a restart launch, a reset or an import -- the goals and episodes the next step's sparse_delivery is measured against
+static int attached_behind_restart(mate_engine *e, hipStream_t stream) {
+    const AttachedPlan pl = plan_attached(e, false);
+    return pl.reward ? launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream) : MATE_OK;
+}
+// 6, 7: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
+static int attached_last(mate_engine *e, int rc, hipStream_t stream) {
+    if (rc != MATE_OK) return rc;
+    const AttachedPlan pl = plan_attached(e, false);
+    if (pl.action_mask) { const int rc_ = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, stream); if (rc_ != MATE_OK) return rc_; }
+    return pl.state ? launch_state_rows(e, pl.state_rows, e->state.dst, e->state.f64, e->state.ab, stream) : MATE_OK;
+}
+// 5 .. 7 behind reset, reset_tape and import_state: new records without a step
+static int attached_behind_new_records(mate_engine *e, hipStream_t stream) { return attached_last(e, attached_behind_restart(e, stream), stream); }
 
+// ---- global state rows: attaching, and the on-demand launch
 // (scale, bias) host arrays -> the kernel's interleaved table in the row type
 static int upload_state_table(mate_engine *e, void **table, const double *scale, const double *bias, bool f64) {
     const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
@@ -716,13 +762,13 @@ static int check_state_rows_args(const mate_engine *e, const void *dst, int32_t 
 
 extern "C" int mate_engine_enable_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias) {
     { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
-    if (!dst_dev) { e->state_dst = nullptr; e->state_ab = nullptr; return MATE_OK; }
+    if (!dst_dev) { e->state.dst = nullptr; e->state.ab = nullptr; return MATE_OK; }
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_state_rows called before reset() (or import_state)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the table while it is rewritten)
     const bool f64 = out_dtype == MATE_OBS_F64;
-    if (scale) { const int rc = upload_state_table(e, &e->d_state_ab, scale, bias, f64); if (rc != MATE_OK) return rc; }
-    e->state_dst = dst_dev; e->state_f64 = f64; e->state_ab = scale ? e->d_state_ab : nullptr;
+    if (scale) { const int rc = upload_state_table(e, &e->state.d_ab, scale, bias, f64); if (rc != MATE_OK) return rc; }
+    e->state.dst = dst_dev; e->state.f64 = f64; e->state.ab = scale ? e->state.d_ab : nullptr;
     return MATE_OK;
 }
 
@@ -735,75 +781,22 @@ extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out
         const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
         std::vector<double> table((size_t)2 * S + 1);
         std::copy(scale, scale + S, table.begin()); std::copy(bias, bias + S, table.begin() + S); table[(size_t)2 * S] = f64 ? 1.0 : 0.0;
-        if (table.size() != e->state_demand_table.size() || std::memcmp(table.data(), e->state_demand_table.data(), table.size() * 8) != 0) {
+        if (table.size() != e->state.demand_table.size() || std::memcmp(table.data(), e->state.demand_table.data(), table.size() * 8) != 0) {
             HIP_TRY(wait_for_launches(e));      // (an earlier on-demand launch may still read the old table)
-            e->state_demand_table.clear();
-            const int rc = upload_state_table(e, &e->d_state_ab_demand, scale, bias, f64);
+            e->state.demand_table.clear();
+            const int rc = upload_state_table(e, &e->state.d_ab_demand, scale, bias, f64);
             if (rc != MATE_OK) return rc;
-            e->state_demand_table = table;
+            e->state.demand_table = table;
         }
     }
     note_stream(e, (hipStream_t)stream);
-    return launch_state_rows(e, dst_dev, f64, scale ? e->d_state_ab_demand : nullptr, (hipStream_t)stream);
+    return launch_state_rows(e, plan_state_rows(e, f64), dst_dev, f64, scale ? e->state.d_ab_demand : nullptr, (hipStream_t)stream);
 }
 
-// ---- shaped reward rows (csrc/reward_rows.hpp)
-// One reward_rows_kernel launch (the soft-coverage launch in front where that term exists).  Capturable: no allocation, no
-// synchronisation, the same arguments at every call.
-static int launch_reward_rows(mate_engine *e, int mode, const float *scalars, const uint32_t *masks, hipStream_t stream) {
-    RewardArgs a = e->reward;
-    a.mode = mode; a.scalars = scalars; a.masks = masks;
-    if (mode != REWARD_SNAPSHOT && e->reward_soft) {
-        const int64_t items = e->N * e->p.Nc;
-        hipLaunchKernelGGL(soft_coverage_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream,
-                           (const Params *)e->d_params, (const Ptrs)e->g, masks, e->d_reward_matrix, e->d_reward_scores);
-    }
-    const unsigned blocks = (unsigned)((e->N + kRewardEnvsPerBlock - 1) / kRewardEnvsPerBlock);
-    const size_t lds = (size_t)reward_rows_lds_bytes(e->p.DW);
-    with_obs_type(e->reward_f64, [&](auto tag) {
-        hipLaunchKernelGGL(reward_rows_kernel<decltype(tag)>, dim3(blocks), dim3(256), lds, stream, (const Params *)e->d_params, (const Ptrs)e->g, (const RewardArgs)a);
-    });
-    HIP_TRY(hipGetLastError());
-    return MATE_OK;
-}
-// Ahead of a stepping launch: the reward launch behind it reads the step's scalar record and masks.
-static int check_reward_io(const mate_engine *e, const mate_step_io *io) {
-    if (e->reward_on && (!io || !io->scalars_dev || !io->masks_dev))
-        return fail(MATE_EINVAL, "reward rows are attached (mate_engine_enable_reward_rows): the call needs io->scalars_dev and io->masks_dev");
-    return MATE_OK;
-}
-// ---- target-selection camera actions (csrc/selection_rows.hpp)
-// One selection_kernel launch of `phase`.  Capturable: no allocation, no synchronisation, the same arguments at every call.  The masks are
-// the engine's own copy (Ptrs::own_masks: every step, reset and restart launch that writes a view writes it there).
-static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream) {
-    SelectionArgs a = e->selection;
-    a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->cam_mode;
-    with_obs_type(e->selection_act_f64, [&](auto tag) {
-        hipLaunchKernelGGL(selection_kernel<decltype(tag)>, dim3(pl.selection_blocks), dim3(256), pl.selection_lds, stream, (const Params *)e->d_params, (const Ptrs)e->g, (const SelectionArgs)a);
-    });
-    HIP_TRY(hipGetLastError());
-    return MATE_OK;
-}
-// Behind a stepping launch, ahead of the restart of what it finished: the attached rows of the launch's last frame (`frames` > 1:
-// rollout-shaped buffers), as plan_attached orders them -- reward rows, then the selection metrics.
-static int attached_rows_of_step(mate_engine *e, const mate_step_io *io, int frames, bool selected, hipStream_t stream) {
-    const AttachedPlan pl = plan_attached(e, selected);
-    const size_t last = (size_t)(frames - 1) * (size_t)e->N;
-    if (pl.reward) {
-        const int rc = launch_reward_rows(e, e->reward_accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
-        if (rc != MATE_OK) return rc;
-    }
-    return pl.observe ? launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream) : MATE_OK;
-}
-// Behind a restart launch, a reset or an import: the goals and episodes the next step's sparse_delivery is measured against.
-static int refresh_reward_snapshot(mate_engine *e, int rc, hipStream_t stream) {
-    if (rc != MATE_OK || !e || !e->reward_on) return rc;
-    return launch_reward_rows(e, REWARD_SNAPSHOT, nullptr, nullptr, stream);
-}
-
+// ---- shaped reward rows: attaching
 extern "C" int mate_engine_enable_reward_rows(mate_engine *e, const mate_reward_rows *cfg) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    if (!cfg) { e->reward_on = false; return MATE_OK; }
+    if (!cfg) { e->reward.on = false; return MATE_OK; }
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_reward_rows called before reset() (or import_state)");
     const Params &p = e->p;
     const bool f64 = cfg->out_dtype == MATE_OBS_F64;
@@ -828,53 +821,50 @@ extern "C" int mate_engine_enable_reward_rows(mate_engine *e, const mate_reward_
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the arguments while they change)
     int rc = MATE_OK;
-    if (!e->d_reward_snapshot && (rc = dev_alloc(e, &e->d_reward_snapshot, (size_t)e->N * (p.Nt + 1)))) return rc;
-    if (cfg->soft_coverage && !e->d_reward_matrix) {
-        if ((rc = dev_alloc(e, &e->d_reward_matrix, (size_t)e->N * p.Nc * p.Nt))) return rc;
-        if ((rc = dev_alloc(e, &e->d_reward_scores, (size_t)e->N * p.Nc))) return rc;
+    RewardRows &r = e->reward;
+    if (!r.d_snapshot && (rc = dev_alloc(e, &r.d_snapshot, (size_t)e->N * (p.Nt + 1)))) return rc;
+    if (cfg->soft_coverage && !r.d_matrix) {
+        if ((rc = dev_alloc(e, &r.d_matrix, (size_t)e->N * p.Nc * p.Nt))) return rc;
+        if ((rc = dev_alloc(e, &r.d_scores, (size_t)e->N * p.Nc))) return rc;
     }
     mate_layout layout;
     if ((rc = mate_engine_get_layout(e, &layout))) return rc;
     RewardArgs a{};
-    a.snapshot = e->d_reward_snapshot;
+    a.snapshot = r.d_snapshot;
     a.cam_rows = cfg->camera_rows_dev; a.tgt_rows = cfg->target_rows_dev;
     a.cam_terms = cfg->camera_terms_dev; a.tgt_terms = cfg->target_terms_dev;
     a.cam_coef = cfg->camera_coefficients_dev; a.tgt_coef = cfg->target_coefficients_dev;
-    a.soft_matrix = cfg->soft_coverage ? e->d_reward_matrix : nullptr; a.soft_scores = cfg->soft_coverage ? e->d_reward_scores : nullptr;
+    a.soft_matrix = cfg->soft_coverage ? r.d_matrix : nullptr; a.soft_scores = cfg->soft_coverage ? r.d_scores : nullptr;
     a.cam_reduction = cfg->camera_reduction; a.tgt_reduction = cfg->target_reduction;
     a.bit_ct = layout.bit_camera_target;
-    e->reward = a; e->reward_f64 = f64; e->reward_soft = cfg->soft_coverage != 0; e->reward_accumulate = cfg->accumulate != 0;
-    e->reward_on = true;
+    r.args = a; r.f64 = f64; r.soft = cfg->soft_coverage != 0; r.accumulate = cfg->accumulate != 0;
+    r.on = true;
     // the goals and episodes of the records as they are: the first step's sparse_delivery is measured against them
     note_stream(e, e->last_stream);
-    return refresh_reward_snapshot(e, MATE_OK, e->last_stream);
+    return attached_behind_restart(e, e->last_stream);
 }
 
-static int reset_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
+extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     Ptrs g = e->g;
     apply_io(g, io);
     g.tape_ct = nullptr; g.tape_goal = nullptr;
     g.reset_mask = env_mask_dev;
-    int rc = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream);
-    if (rc == MATE_OK && !env_mask_dev) {
-        e->was_reset = true; e->masks_stale = false;
+    { const int rc_ = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    if (!env_mask_dev) {
+        e->was_reset = true; e->selection.masks_stale = false;
         if (!e->dev_tick) {      // nothing is finished any more: the lists of a batched-reset interval in progress are void
             HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
             e->steps_since_reset = 0; e->pending_interval = 0;
         }
     }
-    return rc;
-}
-
-extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
-    return refresh_state_rows(e, refresh_reward_snapshot(e, reset_impl(e, env_mask_dev, io, stream), (hipStream_t)stream), stream);
+    return attached_behind_new_records(e, (hipStream_t)stream);
 }
 
 // reset() with every random draw taken from a tape recorded from the reference (parity runs).
-static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
-                           int32_t tape_len, int32_t *draws_used_dev, void *stream) {
+extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
+                                      int32_t tape_len, int32_t *draws_used_dev, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     if (!tape_dev || tape_len < 1) return fail(MATE_EINVAL, "reset_tape needs a tape");
@@ -883,14 +873,9 @@ static int reset_tape_impl(mate_engine *e, const uint8_t *env_mask_dev, const ma
     g.tape_goal = nullptr;                  // io->tape_camera_target_dev: see-through uniforms of the first view
     g.reset_mask = env_mask_dev;
     g.reset_tape = tape_dev; g.reset_tape_len = tape_len; g.reset_draws = draws_used_dev;
-    int rc = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream);
-    if (rc == MATE_OK && !env_mask_dev) { e->was_reset = true; e->masks_stale = false; }
-    return rc;
-}
-
-extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
-                                      int32_t tape_len, int32_t *draws_used_dev, void *stream) {
-    return refresh_state_rows(e, refresh_reward_snapshot(e, reset_tape_impl(e, env_mask_dev, io, tape_dev, tape_len, draws_used_dev, stream), (hipStream_t)stream), stream);
+    { const int rc_ = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    if (!env_mask_dev) { e->was_reset = true; e->selection.masks_stale = false; }
+    return attached_behind_new_records(e, (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_rebuild_luts(mate_engine *e, void *stream) {
@@ -931,7 +916,7 @@ static int flush_pending(mate_engine *e, int auto_reset, int flow_tag, hipStream
     if (rc != MATE_OK) return rc;
     HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
     e->steps_since_reset = 0; e->pending_interval = 0;
-    return refresh_reward_snapshot(e, MATE_OK, stream);
+    return attached_behind_restart(e, stream);
 }
 
 // Device-resident step counter: see Params::dev_tick.  enable = k >= 1: the host's tick goes to the device and stays there,
@@ -1025,8 +1010,9 @@ extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *str
     }
     HIP_TRY(hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
     e->dev_tick = enable != 0;
-    if (!enable) return refresh_state_rows(e, flush_pending(e, 0, 0, stream), stream);      // (an open interval's finished environments restart here)
-    return MATE_OK;
+    if (enable) return MATE_OK;
+    const int rc = flush_pending(e, 0, 0, stream);      // (an open interval's finished environments restart here)
+    return attached_last(e, rc, stream);
 }
 
 // Device-resident step counter: the auto-reset launch advances it, so every stepping call uses the interval it was enabled with, and
@@ -1070,14 +1056,11 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
     const int rc = launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate);
     if (rc != MATE_OK) return rc;
     if (kind == RESET_DONE && !e->dev_tick) e->parity ^= 1;      // (the list is consumed: the next launches append to the other one)
-    return refresh_reward_snapshot(e, MATE_OK, stream);      // (new episodes: their goals are what the next step's sparse_delivery compares with)
+    return attached_behind_restart(e, stream);      // (new episodes: their goals are what the next step's sparse_delivery compares with)
 }
 
-static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream, bool selected = false) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
-    if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
-    if (mode != MODE_OBSERVE) { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
+// The per-step launch and what follows it, behind the state checks of the call: launch_step's, or those step_with_policies makes ahead of its agents' launch
+static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream, bool selected) {
     note_stream(e, stream);
     if (mode != MODE_OBSERVE) { int rc = flush_pending(e, auto_reset, kStepFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
@@ -1098,20 +1081,28 @@ static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int aut
     if (pl.E > 1) { g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0; }      // (the sub-wave rollout kernel with ONE step)
     launch(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g);
     HIP_TRY(hipGetLastError());
-    e->masks_stale = false;
+    e->selection.masks_stale = false;
     if (mode == MODE_OBSERVE) return MATE_OK;
     if (!e->dev_tick) e->tick += 1;
-    { const int rc_ = attached_rows_of_step(e, io, 1, selected, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
+    { const int rc_ = attached_behind_step(e, selected, io, 1, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
     // (the restart writes the caller's observation buffers and masks; the immediate one, idle almost always, stays ONE launch, and so
     // does the interval's unless the on-device agents play: their ~1.2 k-step episodes finish somewhere in the batch all the time)
     return restart_finished(e, auto_reset, Restart{io, true, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, false, e->greedy_team_bits != 0, 1u, kStepFlow}, stream);
 }
 
+static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
+    if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
+    if (mode != MODE_OBSERVE) { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }
+    return step_launches(e, io, mode, auto_reset, stream, false);
+}
+
 extern "C" int mate_engine_step(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
-    return refresh_state_rows(e, launch_step(e, io, MODE_STEP, auto_reset, (hipStream_t)stream), stream);
+    return attached_last(e, launch_step(e, io, MODE_STEP, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
 extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
-    return refresh_state_rows(e, launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream), stream);
+    return attached_last(e, launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
 static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
@@ -1119,7 +1110,7 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     { const int rc_ = enter(e, stream, "rollout"); if (rc_ != MATE_OK) return rc_; }
     if (e->dev_tick) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
-    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset, kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
     Ptrs g = e->g;
@@ -1136,14 +1127,14 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     hipExtLaunchKernelGGL(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
-    { const int rc_ = attached_rows_of_step(e, io, steps, false, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = attached_behind_step(e, false, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
     // (state only, placement and tables: the next rollout observes the fresh episode on its first step)
-    if (auto_reset >= 1) e->masks_stale = true;      // (... and until then the view masks of a restarted environment are its finished episode's)
+    if (auto_reset >= 1) e->selection.masks_stale = true;      // (... and until then the view masks of a restarted environment are its finished episode's)
     return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, PH_PLACE | PH_LUT, false, false, 0u, kRolloutFlow}, stream);
 }
 
 extern "C" int mate_engine_rollout_random(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
-    return refresh_state_rows(e, rollout_random_impl(e, io, steps, auto_reset, stream), stream);      // (the state after the launch's last frame)
+    return attached_last(e, rollout_random_impl(e, io, steps, auto_reset, stream), (hipStream_t)stream);      // (the state after the launch's last frame)
 }
 
 static int policy_enable(mate_engine *e) {
@@ -1230,7 +1221,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     // (pipelined restarts still in flight rewrite records, masks and `done` tags on the side stream: the agents' kernel of the
     // two-launch form reads all three, so the mode is left HERE, not only in launch_step behind it)
     { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
-    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone)
+    if (!selected) { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone; step_selected has made it)
     const FusedCall c = fused_call(e, team_caller, io);
     if (one_launch_step(e, c, io, tape) && plan_with_policies(e, true, team_caller).fits())
         return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true, selected);
@@ -1240,7 +1231,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
     if (team_caller == 0 && e->p.Nc == 0) return fail(MATE_EINVAL, "the scenario has no cameras to act for");
     if (!c.action) return fail(MATE_EINVAL, "step_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
-    // the checks launch_step would make only after the policy launch below has advanced the agents' memory: a rejected call must leave it alone
+    // (with the checks above, everything launch_step checks: made here, ahead of the policy launch that advances the agents' memory -- a rejected call must leave it alone)
     { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, stream);
@@ -1264,18 +1255,18 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (team_caller != 0) { io2.camera_actions_dev = q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
     if (team_caller != 1) { io2.target_actions_dev = q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
-    const int rc = launch_step(e, &io2, MODE_STEP, auto_reset, stream, selected);
+    const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
     e->greedy_team_bits = 0;
     return rc;
 }
 
 extern "C" int mate_engine_step_greedy(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
-    return refresh_state_rows(e, step_with_policies(e, -1, io, tape, auto_reset, (hipStream_t)stream), stream);
+    return attached_last(e, step_with_policies(e, -1, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    return refresh_state_rows(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), stream);
+    return attached_last(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 // Target-selection camera actions (include/mate_engine.h).  The buffers are the caller's, but for the joint action the executor hands to
@@ -1294,16 +1285,16 @@ extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const 
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (no launch reads the arguments while they change)
     int rc = MATE_OK;
-    if (!e->d_selection_actions && (rc = dev_alloc(e, &e->d_selection_actions, (size_t)e->N * e->p.Nc * 2))) return rc;
+    if (!e->selection.d_actions && (rc = dev_alloc(e, &e->selection.d_actions, (size_t)e->N * e->p.Nc * 2))) return rc;
     mate_layout layout;
     if ((rc = mate_engine_get_layout(e, &layout))) return rc;
     SelectionArgs a{};
-    a.selection = selection_dev; a.actions = e->d_selection_actions;
+    a.selection = selection_dev; a.actions = e->selection.d_actions;
     a.metrics = metrics_dev; a.frames = frames_dev; a.action_mask = action_mask_dev;
     a.multi = mode == MATE_SELECTION_MULTI; a.accumulate = (flags & MATE_SELECTION_ACCUMULATE) != 0;
     a.bit_ct = layout.bit_camera_target;
-    e->selection = a; e->selection_act_f64 = !(flags & MATE_SELECTION_ACT_F32);
-    e->selection_on = true;
+    e->selection.args = a; e->selection.act_f64 = !(flags & MATE_SELECTION_ACT_F32);
+    e->selection.on = true;
     const AttachedPlan pl = plan_attached(e, false);
     if (!pl.action_mask) return MATE_OK;
     // action_mask() of the observation rows as they are, complete when the call returns (the caller need not know the stream)
@@ -1313,26 +1304,22 @@ extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const 
 }
 extern "C" int mate_engine_disable_selection(mate_engine *e) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    e->selection_on = false;
+    e->selection.on = false;
     return MATE_OK;
 }
 extern "C" int mate_engine_selection_actions(mate_engine *e, void **actions_dev, int32_t *act_dtype) {
     if (!e || !actions_dev) return fail(MATE_EINVAL, "null argument");
-    if (!e->selection_on) return fail(MATE_ESTATE, "selection_actions: mate_engine_enable_selection has not run");
-    *actions_dev = e->d_selection_actions;
-    if (act_dtype) *act_dtype = e->selection_act_f64 ? MATE_ACT_F64 : MATE_ACT_F32;
+    if (!e->selection.on) return fail(MATE_ESTATE, "selection_actions: mate_engine_enable_selection has not run");
+    *actions_dev = e->selection.d_actions;
+    if (act_dtype) *act_dtype = e->selection.act_f64 ? MATE_ACT_F64 : MATE_ACT_F32;
     return MATE_OK;
 }
 
-// The launches of plan_attached around exactly what mate_engine_step_versus_greedy(team = camera) enqueues, with the engine-owned joint action.
+// The attached launches around exactly what mate_engine_step_versus_greedy(team = camera) enqueues, with the engine-owned joint action.
 extern "C" int mate_engine_step_selected(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
-    if (!e->selection_on) return fail(MATE_ESTATE, "step_selected: call mate_engine_enable_selection() first");
-    if (auto_reset < 0) return fail(MATE_ESTATE, "step_selected is not available under pipelined restarts (auto_reset = MATE_RESET_PIPELINED)");
-    if (!io || !io->scalars_dev) return fail(MATE_EINVAL, "step_selected needs io->scalars_dev (the metrics skip environments whose record says done = 2)");
-    if (e->masks_stale) return fail(MATE_ESTATE, "step_selected: the view masks are older than the records (a fused random rollout restarted episodes, or import_state): call observe() first");
-    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = check_attached_call(e, io, false, true, auto_reset); if (rc_ != MATE_OK) return rc_; }
     { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }      // (a rejected call launches nothing)
     // the state checks of the stepping flows and what they enqueue ahead of their launch, all AHEAD of the executor: a rejected call
     // leaves the action buffer alone; pipelined restarts in flight are joined before the executor reads the mask words; an open
@@ -1342,11 +1329,11 @@ extern "C" int mate_engine_step_selected(mate_engine *e, const mate_step_io *io,
     note_stream(e, stream);
     { const int rc_ = flush_pending(e, auto_reset, kStepFlow, stream); if (rc_ != MATE_OK) return rc_; }
     mate_step_io io2 = *io;
-    io2.camera_actions_dev = e->d_selection_actions;
-    io2.act_dtype = (io->act_dtype & ~(0xff | MATE_ACT_CAMERA_DISCRETE)) | (e->selection_act_f64 ? MATE_ACT_F64 : MATE_ACT_F32);
-    int rc = launch_selection(e, plan_attached(e, true), SELECTION_EXECUTE, nullptr, stream);
+    io2.camera_actions_dev = e->selection.d_actions;
+    io2.act_dtype = (io->act_dtype & ~(0xff | MATE_ACT_CAMERA_DISCRETE)) | (e->selection.act_f64 ? MATE_ACT_F64 : MATE_ACT_F32);
+    int rc = attached_ahead_of_step(e, true, stream);
     if (rc == MATE_OK) rc = step_with_policies(e, MATE_TEAM_CAMERA, &io2, tape, auto_reset, stream, true);
-    return refresh_state_rows(e, rc, stream_);
+    return attached_last(e, rc, stream);
 }
 
 // What differs between the two forms of rollout_with_policies, spelled once (after struct Restart):
@@ -1381,12 +1368,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (auto_reset < -(1 << 16)) return fail(MATE_EINVAL, "auto_reset = %d: pipelined restarts every -auto_reset launches take 1 .. 65536", auto_reset);
     const int pipe_every = pipelined ? -auto_reset : 1;
     if (pipelined && (!flow.may_pipeline || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
-    // (the restarts run on the engine's side stream UNDER the next launches: a state-row launch on the caller's stream would read records they rewrite)
-    if (pipelined && e->state_dst) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while state rows are attached (mate_engine_enable_state_rows): detach them first");
-    if (pipelined && e->reward_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while reward rows are attached (mate_engine_enable_reward_rows): detach them first");
-    // (... and the view masks the selection executor reads)
-    if (pipelined && e->selection_on) return fail(MATE_ESTATE, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while target selection is attached (mate_engine_enable_selection): detach it first");
-    { const int rc_ = check_reward_io(e, io); if (rc_ != MATE_OK) return rc_; }
+    if (!per_step) { const int rc_ = check_attached_call(e, io, pipelined, false); if (rc_ != MATE_OK) return rc_; }      // (per_step: step_with_policies has made it)
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset, flow.restart.flow_tag, stream); if (rc != MATE_OK) return rc; }
@@ -1419,19 +1401,19 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     e->last_flow = pl.last_flow;
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
-    e->masks_stale = false;
+    e->selection.masks_stale = false;
     if (!e->dev_tick) e->tick += (uint32_t)steps;
-    { const int rc_ = attached_rows_of_step(e, io, steps, selected, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = attached_behind_step(e, selected, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
     return pipelined ? pipelined_restart(e, stream) : restart_finished(e, auto_reset, flow.restart, stream);
 }
 
 extern "C" int mate_engine_rollout_greedy(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
-    return refresh_state_rows(e, rollout_with_policies(e, -1, io, steps, auto_reset, stream), stream);
+    return attached_last(e, rollout_with_policies(e, -1, io, steps, auto_reset, stream), (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_rollout_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    return refresh_state_rows(e, rollout_with_policies(e, team, io, steps, auto_reset, stream), stream);
+    return attached_last(e, rollout_with_policies(e, team, io, steps, auto_reset, stream), (hipStream_t)stream);
 }
 
 // Copy the joint actions the last mate_engine_step_greedy produced into caller buffers ([N][Nc][2], [N][Nt][2] f64).
@@ -1447,7 +1429,7 @@ extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions
 }
 
 extern "C" int mate_engine_observe(mate_engine *e, const mate_step_io *io, void *stream) {
-    return refresh_state_rows(e, launch_step(e, io, MODE_OBSERVE, 0, (hipStream_t)stream), stream);
+    return attached_last(e, launch_step(e, io, MODE_OBSERVE, 0, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *stream) {
@@ -1471,8 +1453,8 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     int32_t tick = 0;
     HIP_TRY(hipMemcpy(&tick, reinterpret_cast<const int32_t *>(e->g.dyn + e->p.DF) + e->p.Nt * TI_STRIDE + EI_TICK, sizeof(tick), hipMemcpyDeviceToHost));
     e->tick = (uint32_t)tick;
-    e->was_reset = true; e->masks_stale = true;      // (records only: the view masks are whatever ran before)
-    return refresh_state_rows(e, refresh_reward_snapshot(e, MATE_OK, (hipStream_t)stream), stream);
+    e->was_reset = true; e->selection.masks_stale = true;      // (records only: the view masks are whatever ran before)
+    return attached_behind_new_records(e, (hipStream_t)stream);
 }
 
 // One camera's knot table (inner or outer boundary) to the host / from the host.  `who`: the entry point's name in the messages.
@@ -1561,10 +1543,8 @@ extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_d
     if (e->p.Nt > kAuxMaxTargets) return fail(MATE_EINVAL, "soft_coverage: at most %d targets", kAuxMaxTargets);
     if (!e->g.lut_knots_outer) return fail(MATE_ESTATE, "outer boundary not enabled (mate_engine_enable_outer_boundary)");
     { const int rc_ = enter(e, (hipStream_t)stream, "soft_coverage"); if (rc_ != MATE_OK) return rc_; }
-    const int64_t items = e->N * e->p.Nc;
     note_stream(e, (hipStream_t)stream);
-    hipLaunchKernelGGL(soft_coverage_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const Params *)e->d_params, (const Ptrs)e->g, masks_dev, matrix_dev, scores_dev);
+    launch_soft_coverage(e, plan_soft_coverage(e), masks_dev, matrix_dev, scores_dev, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return MATE_OK;
 }

@@ -13,17 +13,15 @@
 //                normalized_goal_distance | sparse_delivery | soft_coverage_score | is_tracked | is_colliding | baseline
 // The four shared terms are the f32 step record widened to f64; the sum runs in that order, product then add (-ffp-contract=off).
 //
-// Mapping: a group of 16 lanes per environment, sixteen environments per 256-thread workgroup; lane j of a group is target j
-// AND camera j (the engine takes at most sixteen of each).  The tile's dynamic records are one contiguous stretch of HBM,
-// staged in LDS with whole-wave loads; the scalar record and the camera->target mask words arrive with one load per group and
-// are handed round by shuffles / LDS; the reductions over an environment's agents are four-stage butterflies inside the group.
+// Mapping: the tile of attached_tile.hpp; lane j of a group is target j AND camera j (the engine takes at most sixteen of each).
+// The scalar record is handed round by shuffles, the mask words through LDS; the reductions over an environment's agents are
+// four-stage butterflies inside the group.
 #pragma once
-#include "engine_kernels.hpp"
+#include "attached_tile.hpp"
 
 namespace mate {
 
 constexpr int kRewardCameraTerms = 7, kRewardTargetTerms = 10;
-constexpr int kRewardEnvsPerBlock = 16;
 enum RewardMode : int32_t { REWARD_OVERWRITE = 0, REWARD_ACCUMULATE = 1, REWARD_SNAPSHOT = 2 };
 enum RewardReduction : int32_t { REDUCE_NONE = 0, REDUCE_MEAN = 1, REDUCE_SUM = 2, REDUCE_MAX = 3, REDUCE_MIN = 4 };
 
@@ -39,8 +37,6 @@ struct RewardArgs {
     int32_t mode;
     int32_t bit_ct;               // mate_layout.bit_camera_target
 };
-
-__host__ __device__ constexpr int reward_rows_lds_bytes(int DW) { return kRewardEnvsPerBlock * DW * 8; }
 
 // over the sixteen lanes of an environment's group; lanes that hold no agent carry the identity
 __device__ __forceinline__ double group16_reduce(double v, int how) {
@@ -66,26 +62,22 @@ __device__ __forceinline__ void reward_store(OutT *row, double shaped, int mode)
 template <typename OutT>
 __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restrict__ pp, const Ptrs g, const RewardArgs a) {
     extern __shared__ __align__(16) unsigned char reward_lds[];
-    __shared__ uint32_t mask_words[kRewardEnvsPerBlock][16];
+    __shared__ uint32_t mask_words[kAttachedEnvsPerBlock][16];
     const Params &p = *pp;
     const int Nc = p.Nc, Nt = p.Nt, DW = p.DW;
     const int tid = threadIdx.x, el = tid >> 4, j = tid & 15;
-    const int64_t e0 = (int64_t)blockIdx.x * kRewardEnvsPerBlock;
+    const int64_t e0 = (int64_t)blockIdx.x * kAttachedEnvsPerBlock;
     if (e0 >= g.N) return;
-    const int ne = (int)(g.N - e0 < (int64_t)kRewardEnvsPerBlock ? g.N - e0 : (int64_t)kRewardEnvsPerBlock);
+    const int ne = (int)(g.N - e0 < (int64_t)kAttachedEnvsPerBlock ? g.N - e0 : (int64_t)kAttachedEnvsPerBlock);
     double *dy = reinterpret_cast<double *>(reward_lds);
-    {   // the tile's dynamic records: one contiguous stretch, 512 bytes per wave and load
-        const double *gd = g.dyn + e0 * DW;
-        for (int i = tid; i < ne * DW; i += 256) dy[i] = gd[i];
-    }
+    stage_records(dy, g.dyn + e0 * DW, ne * DW, tid);
     const int64_t env = e0 + el;
     const bool live = el < ne, step = a.mode != REWARD_SNAPSHOT;
-    // camera_target_view_mask: bit(c, t) = bit_ct + c * Nt + t -- up to 256 bits from any origin: at most nine words
-    const int first_word = a.bit_ct >> 5, n_words = Nc * Nt > 0 ? ((a.bit_ct & 31) + Nc * Nt + 31) >> 5 : 0;
+    const ViewWords vw = view_words(a.bit_ct, Nc, Nt);
     float scalar = 0.f;
     if (live && step) {
         scalar = a.scalars[env * 8 + (j & 7)];
-        if (j < n_words) mask_words[el][j] = a.masks[env * p.MW + first_word + j];
+        load_view_words(mask_words[el], vw, a.masks, env, p.MW, j);
     }
     __syncthreads();
     if (!live) return;
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restri
     }
     const double s_cam = (double)__shfl(scalar, 0, 16), s_tgt = (double)__shfl(scalar, 1, 16), s_cov = (double)__shfl(scalar, 3, 16),
                  s_real = (double)__shfl(scalar, 4, 16), s_mtr = (double)__shfl(scalar, 5, 16);
-    const bool idle = __shfl(scalar, 2, 16) == 2.0f;               // waiting for a batched restart: no step ran
+    const bool idle = tile_idle(scalar);
     OutT *cam_row = reinterpret_cast<OutT *>(a.cam_rows), *tgt_row = reinterpret_cast<OutT *>(a.tgt_rows);
     if (idle) {                                                    // contributes nothing; its snapshot stays
         if (a.mode == REWARD_OVERWRITE) {
@@ -123,8 +115,7 @@ __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restri
     const uint32_t *mw = mask_words[el];
     for (int k = 0; k < (Nc > Nt ? Nc : Nt); ++k) {
         if (is_tgt && k < Nc) {
-            const int bit = (a.bit_ct & 31) + k * Nt + j;
-            const bool seen = (mw[bit >> 5] >> (bit & 31)) & 1u;
+            const bool seen = view_bit(mw, vw, k, j, Nt);
             seen_by += seen;
             if (soft_t) {                                          // auxiliary_target_rewards.py:146-158
                 const double m = a.soft_matrix[(env * Nc + k) * Nt + j];
@@ -132,10 +123,7 @@ __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restri
                 soft_max = m > soft_max ? m : soft_max;
             }
         }
-        if (is_cam && k < Nt) {
-            const int bit = (a.bit_ct & 31) + j * Nt + k;
-            sees += (mw[bit >> 5] >> (bit & 31)) & 1u;
-        }
+        if (is_cam && k < Nt) sees += view_bit(mw, vw, j, k, Nt);
     }
 
     if (tgt_row) {

@@ -13,18 +13,14 @@
 // view[c] is the opponent-flag column of camera c's observation row as the packer writes it: the camera_target_view_mask bits in
 // plain mode, their OR over the cameras under SharedFieldOfView, all ones under EnhancedObservation.
 //
-// Mapping (reward_rows_kernel's): a group of 16 lanes per environment, sixteen environments per 256-thread workgroup, lane j of a
-// group is camera j.  The tile's dynamic records are one contiguous stretch of HBM staged in LDS with whole-wave loads, the camera
-// locations of the static records next to them; the mask words arrive with one load per group.  f64 throughout, product then add
-// (-ffp-contract=off); fused where the Greedy agents' code fuses (norm2).
+// Mapping: the tile of attached_tile.hpp, lane j of a group is camera j; the camera locations of the static records are staged next
+// to the dynamic records.  f64 throughout, product then add (-ffp-contract=off); fused where the Greedy agents' code fuses (norm2).
 #pragma once
-#include "engine_kernels.hpp"
+#include "attached_tile.hpp"
 #include "policy_kernels.hpp"
-#include "reward_rows.hpp"
 
 namespace mate {
 
-constexpr int kSelectionEnvsPerBlock = kRewardEnvsPerBlock;
 constexpr int kSelectionMetrics = 4;      // num_selected_targets | num_valid_selected_targets | num_invalid_selected_targets | invalid_target_selection_rate
 enum SelectionPhase : int32_t { SELECTION_EXECUTE = 0, SELECTION_OBSERVE = 1, SELECTION_ACTION_MASK = 2 };
 
@@ -40,8 +36,6 @@ struct SelectionArgs {
     int32_t bit_ct;               // mate_layout.bit_camera_target
     int32_t phase;
 };
-
-__host__ __device__ constexpr int selection_lds_bytes(int DW) { return kSelectionEnvsPerBlock * DW * 8; }
 
 // The viewing angle that puts `distance` at the rim of the sector (wrappers.py:207-210): best <- area_product / (distance (1 +
 // sin(min(best / 2, 90))))^2, 20 times from 180 -- the reference's operations in the reference's order (zoom_fixed_point of the Greedy
@@ -59,46 +53,37 @@ __device__ __forceinline__ double selection_zoom(double area_product, double dis
 template <typename ActT>
 __global__ __launch_bounds__(256) void selection_kernel(const Params *__restrict__ pp, const Ptrs g, const SelectionArgs a) {
     extern __shared__ __align__(16) unsigned char selection_lds[];
-    __shared__ uint32_t mask_words[kSelectionEnvsPerBlock][16];
-    __shared__ double cam_xy[kSelectionEnvsPerBlock][32];
+    __shared__ uint32_t mask_words[kAttachedEnvsPerBlock][16];
+    __shared__ double cam_xy[kAttachedEnvsPerBlock][32];
     const Params &p = *pp;
     const int Nc = p.Nc, Nt = p.Nt, DW = p.DW;
     const int tid = threadIdx.x, el = tid >> 4, j = tid & 15;
-    const int64_t e0 = (int64_t)blockIdx.x * kSelectionEnvsPerBlock;
+    const int64_t e0 = (int64_t)blockIdx.x * kAttachedEnvsPerBlock;
     if (e0 >= g.N) return;
-    const int ne = (int)(g.N - e0 < (int64_t)kSelectionEnvsPerBlock ? g.N - e0 : (int64_t)kSelectionEnvsPerBlock);
+    const int ne = (int)(g.N - e0 < (int64_t)kAttachedEnvsPerBlock ? g.N - e0 : (int64_t)kAttachedEnvsPerBlock);
     double *dy = reinterpret_cast<double *>(selection_lds);
-    if (a.phase == SELECTION_EXECUTE) {      // the tile's dynamic records: one contiguous stretch; the camera locations: 2 Nc words per record
-        const double *gd = g.dyn + e0 * DW;
-        for (int i = tid; i < ne * DW; i += 256) dy[i] = gd[i];
+    if (a.phase == SELECTION_EXECUTE) {      // the camera locations: 2 Nc words per static record
+        stage_records(dy, g.dyn + e0 * DW, ne * DW, tid);
         for (int i = tid; i < ne * 32; i += 256) { const int e = i >> 5, k = i & 31; if (k < 2 * Nc) cam_xy[e][k] = g.stat[(e0 + e) * p.SW + k]; }
     }
     const int64_t env = e0 + el;
     const bool live = el < ne, is_cam = j < Nc;
-    // camera_target_view_mask: bit(c, t) = bit_ct + c * Nt + t -- up to 256 bits from any origin: at most nine words
-    const int first_word = a.bit_ct >> 5, n_words = ((a.bit_ct & 31) + Nc * Nt + 31) >> 5;
+    const ViewWords vw = view_words(a.bit_ct, Nc, Nt);
     float scalar = 0.f;
     if (live) {
         if (a.phase == SELECTION_OBSERVE) scalar = a.scalars[env * 8 + (j & 7)];
-        if (j < n_words) mask_words[el][j] = a.masks[env * p.MW + first_word + j];
+        load_view_words(mask_words[el], vw, a.masks, env, p.MW, j);
     }
     __syncthreads();
     if (!live) return;
 
     const uint32_t all = (1u << Nt) - 1u;      // (Nt <= 16)
-    uint32_t row = 0u;
-    if (is_cam) {
-        const int b = (a.bit_ct & 31) + j * Nt;
-        const uint32_t *mw = mask_words[el];
-        const uint64_t w = (uint64_t)mw[b >> 5] | ((b >> 5) + 1 < n_words ? (uint64_t)mw[(b >> 5) + 1] << 32 : 0ull);
-        row = (uint32_t)(w >> (b & 31)) & all;
-    }
-    uint32_t view = row;
+    uint32_t view = is_cam ? view_row(mask_words[el], vw, j, Nt) : 0u;
     if (a.cam_mode == 2) {                     // SharedFieldOfView: what any camera sees
 #pragma unroll
         for (int off = 8; off > 0; off >>= 1) view |= (uint32_t)__shfl_xor((int)view, off, 16);
     } else if (a.cam_mode == 1) view = all;    // EnhancedObservation: every flag is set
-    const bool idle = a.phase == SELECTION_OBSERVE && __shfl(scalar, 2, 16) == 2.0f;      // waiting for a batched restart: no step ran
+    const bool idle = a.phase == SELECTION_OBSERVE && tile_idle(scalar);
     if (!is_cam) return;
 
     if (a.phase == SELECTION_ACTION_MASK) {

@@ -20,7 +20,7 @@
 // fill_scratch in engine_kernels.hpp: the same device_math.hpp functions on the same record words, the same casts), so that a
 // raw row's camera / target blocks are bit-identical to elements [13:22] / [13:27] of that agent's plain observation row of the same type.
 #pragma once
-#include "engine_kernels.hpp"
+#include "attached_tile.hpp"
 
 namespace mate {
 
@@ -65,11 +65,8 @@ __global__ __launch_bounds__(256) void state_rows_kernel(const Params *__restric
     double *dy = st + E * SW;
     OutT *tile = reinterpret_cast<OutT *>(state_lds + state_rows_record_bytes(SW, DW, E));
 
-    {   // the tile's records: two contiguous stretches, 512 bytes per wave and load
-        const double *gs = g.stat + e0 * SW, *gd = g.dyn + e0 * DW;
-        for (int i = tid; i < ne * SW; i += 256) st[i] = gs[i];
-        for (int i = tid; i < ne * DW; i += 256) dy[i] = gd[i];
-    }
+    stage_records(st, g.stat + e0 * SW, ne * SW, tid);      // the tile's records: two contiguous stretches
+    stage_records(dy, g.dyn + e0 * DW, ne * DW, tid);
     __syncthreads();
 
     for (int item = tid; item < ne * Nc; item += 256) {           // Camera.state(private=True), entities.py:313-321

@@ -5,9 +5,18 @@ the environments per wave the Greedy rollouts run with (Engine.sub_wave), or the
 python tools/launch_matrix.py [<shape> [<batch>]]      (default: every shape at both batches)
 Under `rocprofv3 --kernel-trace -- python tools/launch_matrix.py ...` the ordered (kernel, grid, workgroup, LDS) list of two builds of
 the library (MATE_ENGINE_LIB) must be the same; tests/test_gpu_launch_matrix.py runs the 8-environment part against recorded values.
-The environment switches are read when an engine is created: a column under one of SWITCH_COLUMNS is run with the variable set."""
+The environment switches are read when an engine is created: a column under one of SWITCH_COLUMNS is run with the variable set.
+python tools/launch_matrix.py attached [<shape>]      the ATTACHED column set: every call that leaves new records under every combination of
+attached launches (state rows, reward rows, target selection), and the calls the engine refuses, each on an engine of its own;
+`attached --record PATH` writes the record (status, error text, SHA-256 of every attached output and of export_state() per call) as JSON:
+the record of two builds of the library (MATE_ENGINE_LIB) must be the same bytes.
+python tools/launch_matrix.py host-cost [<batch>]     microseconds of host time and per graph-replayed step of step_versus_greedy and
+step_selected with all three attached (default: 4096 environments of MATE-4v8-9)."""
+import hashlib
+import json
 import os
 import sys
+import time
 
 import torch
 
@@ -141,7 +150,196 @@ def in_use_record(shape):
     return record
 
 
+# ---- the attached column set
+ATTACHED_SHAPES = ('MATE-2v4-0', 'MATE-4v8-9')      # (the 32 camera->target bits of MATE-4v8-9 straddle mask words)
+ATTACHED_BATCH = 17                                  # one full 16-environment tile and a second tile holding one environment
+ATTACHED = ('state', 'reward', 'reward_soft', 'selection_multi', 'selection_single', 'all')
+STEPPING = ('step', 'step_random', 'step_greedy', 'step_versus_greedy_camera', 'step_versus_greedy_target', 'step_selected',
+            'rollout_random', 'rollout_greedy', 'rollout_versus_greedy_camera', 'rollout_versus_greedy_target')
+# (auto_reset = 3 is issued four times: the third call ends the interval, the fourth opens one the next flow has to flush)
+ATTACHED_CALLS = ([('reset', 0), ('reset_masked', 0), ('observe', 0)] +
+                  [(name, k) for k in AUTO_RESETS for name in STEPPING for _ in range(4 if k == 3 else 1)] +
+                  [('import_state', 0), ('step_selected', 1), ('observe', 0), ('device_tick_on', 3), ('step_random', 3), ('device_tick_off', 0)])
+ATTACHED_OUTPUTS = ('camera_reward_rows', 'target_reward_rows', 'camera_reward_terms', 'target_reward_terms', 'selection_actions',
+                    'selection_metrics', 'selection_frames', 'action_mask', 'state')
+CAMERA_TERMS = {'coverage_rate': 1.0, 'num_tracked': 0.25, 'baseline': -0.5}
+TARGET_TERMS = {'raw_reward': 1.0, 'normalized_goal_distance': -1.0, 'sparse_delivery': 10.0, 'is_tracked': -0.5, 'is_colliding': -1.0}
+SOFT_TERM = {'soft_coverage_score': 0.125}
+# the calls the engine refuses: (id, what is attached, the calls in front, the refused call)
+REFUSED = ([('pipelined under ' + combo, combo, (), 'rollout_greedy_pipelined') for combo in ('state', 'reward', 'selection_multi', 'all')] +
+           [('%s under reward' % call, 'reward', (), call) for call in ('step_random_no_masks', 'step_random_no_scalars', 'rollout_random_no_masks',
+                                                                         'rollout_greedy_no_masks', 'step_greedy_no_masks')] +
+           [('step_selected behind rollout_random', 'selection_multi', (('rollout_random', 1),), 'step_selected'),
+            ('step_selected behind import_state', 'selection_multi', (('import_state', 0),), 'step_selected'),
+            ('step_selected without policies', 'none', (), 'step_selected_no_policies'),
+            ('step_selected without masks under reward', 'all', (), 'step_selected_no_masks')])
+
+
+def attach(eng, combo):
+    """Attaches `combo` to a reset engine with policies on; 'all' turns every option the other columns leave off."""
+    everything = combo == 'all'
+    gen = torch.Generator().manual_seed(5)
+    if combo.startswith('reward') or everything:
+        soft = SOFT_TERM if combo == 'reward_soft' or everything else {}
+        eng.enable_reward_rows(camera=(dict(CAMERA_TERMS, **soft), 'mean'), target=(dict(TARGET_TERMS, **soft), 'none'), terms=True,
+                               dtype=torch.float32 if everything else torch.float64, accumulate=everything)
+    if combo.startswith('selection') or everything:
+        multi = combo != 'selection_single'
+        high = (1 << eng.num_targets) if multi else eng.num_targets + 1
+        selection = torch.randint(0, high, (eng.num_envs, eng.num_cameras), generator=gen).to(dtype=torch.int32, device=eng.device)
+        eng.enable_selection(multi_selection=multi, selection=selection, accumulate=everything, act_dtype=torch.float32 if everything else torch.float64)
+    if combo == 'state' or everything:
+        eng.enable_state_rows(normalize=everything, dtype=torch.float64 if everything else None)
+
+
+def attached_engine(shape, combo, batch=ATTACHED_BATCH, policies=True):
+    eng = Engine(config_of(shape), batch, seed=11, first_env_index=2)
+    if policies:
+        eng.enable_policies()
+    eng.reset()
+    eng.reserve_rollout(ROLLOUT_STEPS, want_masks=True, search='none')
+    attach(eng, combo)
+    return eng
+
+
+def issue_attached(eng, name, k, acts):
+    """One call of ATTACHED_CALLS or REFUSED."""
+    import ctypes
+    from mate_amd._native import check
+    if name in CALLS or name == 'observe':
+        return issue(eng, name, k, acts)
+    if name == 'reset':
+        return eng.reset()
+    if name == 'reset_masked':
+        return eng.reset(env_mask=(torch.arange(eng.num_envs, device=eng.device) % 3 == 1))
+    if name == 'step_selected':
+        return eng.step_selected(auto_reset=k)
+    if name == 'import_state':
+        return eng.import_state(eng.export_state().roll(1, 0))
+    if name == 'device_tick_on':
+        return eng.device_tick(k)
+    if name == 'device_tick_off':
+        return eng.device_tick(False)
+    if name == 'rollout_greedy_pipelined':
+        return eng.rollout_greedy(ROLLOUT_STEPS, auto_reset='pipelined', want_masks=True)
+    if name == 'step_selected_no_policies':
+        return eng.step_selected(auto_reset=1)
+    base, _, missing = name.rpartition('_no_')
+    if base.startswith('rollout'):
+        return getattr(eng, base)(ROLLOUT_STEPS, auto_reset=1, want_masks=False)
+    io, _ = eng._io(want_masks=missing != 'masks')
+    if missing == 'scalars':
+        io.scalars_dev = None
+    entry = getattr(eng.lib, 'mate_engine_' + base)
+    args = (eng._h, ctypes.byref(io)) + ((None,) if base in ('step_greedy', 'step_selected') else ()) + (1, eng._stream())
+    return check(entry(*args))
+
+
+def digest(tensor):
+    return hashlib.sha256(tensor.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+
+
+def attached_row(eng, name, k, acts):
+    """[status code, error text, {attached output: sha256 of its bytes behind the call}, sha256 of export_state()]"""
+    code, text = 0, ''
+    try:
+        issue_attached(eng, name, k, acts)
+    except EngineError as err:
+        code, text = err.code, str(err)
+    outputs = {key: digest(getattr(eng, key)) for key in ATTACHED_OUTPUTS if getattr(eng, key, None) is not None}
+    return [code, text, outputs, digest(eng.export_state())]
+
+
+def attached_record(shape):
+    """{'columns': {combination: [attached_row of every call of ATTACHED_CALLS]}, 'refused': {id: attached_row of the refused call}}"""
+    record = {'columns': {}, 'refused': {}}
+    for combo in ATTACHED:
+        eng = attached_engine(shape, combo)
+        acts = actions_of(eng)
+        record['columns'][combo] = [attached_row(eng, name, k, acts) for name, k in ATTACHED_CALLS]
+        eng.close()
+    for what, combo, before, name in REFUSED:
+        eng = attached_engine(shape, combo, policies=name != 'step_selected_no_policies')
+        acts = actions_of(eng)
+        for earlier, k in before:
+            issue_attached(eng, earlier, k, acts)
+        record['refused'][what] = attached_row(eng, name, 1, acts)
+        eng.close()
+    return record
+
+
+def attached_main(argv):
+    """Every dispatch of the column set in order (the rocprofv3 --kernel-trace target); --record PATH: the record of every shape as JSON."""
+    record_to = argv[argv.index('--record') + 1] if '--record' in argv else None
+    shapes = [a for a in argv if a in ATTACHED_SHAPES] or ATTACHED_SHAPES
+    record = {shape: attached_record(shape) for shape in shapes}
+    for shape in shapes:
+        for combo, rows in record[shape]['columns'].items():
+            print(shape, combo, 'batch', ATTACHED_BATCH)
+            for (name, k), row in zip(ATTACHED_CALLS, rows):
+                print('  %-32s status %d %s' % ('%s/%d' % (name, k), row[0], row[1]))
+        for what, row in record[shape]['refused'].items():
+            print(shape, 'refused:', what, 'status', row[0], row[1])
+    if record_to:
+        with open(record_to, 'w') as fh:
+            json.dump(record, fh, indent=0, sort_keys=True)
+    print('done', sum(len(ATTACHED) * len(ATTACHED_CALLS) + len(REFUSED) for _ in shapes), 'calls')
+
+
+# ---- host cost per step with everything attached
+def host_cost_main(argv):
+    """One row per (call, form): step_versus_greedy (camera learner) and step_selected on MATE-4v8-9 with all three attached, direct (host
+    microseconds per call of 512 enqueued back to back, and wall microseconds per step with the stream drained at the end) and as replays
+    of a 16-step HIP graph under the device-resident step counter; five repeats each, every repeat printed."""
+    batch = int(argv[0]) if argv else 4096
+    eng = attached_engine('MATE-4v8-9', 'all', batch)
+    import ctypes
+    from mate_amd._native import check
+    cam_io, keep = eng._io(cam_act=actions_of(eng)[0])
+    sel_io, _ = eng._io()
+    cam_ref, sel_ref = ctypes.byref(cam_io), ctypes.byref(sel_io)
+    calls = {'step_versus_greedy': lambda: check(eng.lib.mate_engine_step_versus_greedy(eng._h, 0, cam_ref, None, 1, eng._stream())),
+             'step_selected': lambda: check(eng.lib.mate_engine_step_selected(eng._h, sel_ref, None, 1, eng._stream()))}
+    print('host-cost: MATE-4v8-9 x %d, state + reward (soft) + selection attached, auto_reset = 1' % batch)
+    for name, call in calls.items():
+        for _ in range(64):
+            call()
+        torch.cuda.synchronize()
+        for rep in range(5):
+            t0 = time.perf_counter()
+            for _ in range(512):
+                call()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            print('  %-20s direct rep %d: host %.2f us per call, %.2f us per step' % (name, rep, (t1 - t0) / 512 * 1e6, (t2 - t0) / 512 * 1e6), flush=True)
+    eng.device_tick(1)
+    for name, call in calls.items():
+        call()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(16):
+                call()
+        for _ in range(8):
+            graph.replay()
+        torch.cuda.synchronize()
+        for rep in range(5):
+            t0 = time.perf_counter()
+            for _ in range(32):
+                graph.replay()
+            torch.cuda.synchronize()
+            print('  %-20s graph  rep %d: %.2f us per step' % (name, rep, (time.perf_counter() - t0) / 512 * 1e6), flush=True)
+        del graph
+    eng.device_tick(False)
+    eng.close()
+
+
 def main(argv):
+    if argv[1:2] == ['attached']:
+        return attached_main(argv[2:])
+    if argv[1:2] == ['host-cost']:
+        return host_cost_main(argv[2:])
     shapes = argv[1:2] or SHAPES
     batches = [int(argv[2])] if len(argv) > 2 else [SMALL_BATCH, threshold_batch()]
     calls = 0
