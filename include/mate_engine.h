@@ -85,7 +85,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -478,6 +478,58 @@ int mate_engine_enable_selection(mate_engine *engine, int32_t mode, const void *
 int mate_engine_disable_selection(mate_engine *engine);
 int mate_engine_selection_actions(mate_engine *engine, void **actions_dev, int32_t *act_dtype);
 int mate_engine_step_selected(mate_engine *engine, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream);
+
+/* FrameSkip fragments: what the reference's FrameSkip wrapper (examples/utils/wrappers.py:301-323) at the end of every example trainer's chain
+ *   ... -> RelativeCoordinates -> RescaledObservation -> RepeatedRewardIndividualDone -> [AuxiliaryCameraRewards | AuxiliaryTargetRewards] -> FrameSkip(K)
+ * hands the learner, as ONE launch (csrc/fragment_rows.hpp) over the rollout-shaped buffers of a K-frame launch: scalars [K][N][8], masks
+ * [K][N][mask_words], the learner team's PLAIN observation rows [K][N][A][D].  live(f): the scalar record of frame f does not say done = 2.
+ *   frames_dev  [N] int32: live frames; `last` is the greatest live f
+ *   done_dev    [N] u8: 1 if a live frame says done = 1
+ *   rewards_dev [N][4] f64: the frame-order sums over the live frames of the camera team reward, the target team reward, the normalised target team
+ *               reward (scalar columns 0, 1, 7 widened to f64) and the negated third (the camera side's, environment.py:621-624)
+ *   info_dev    [N][4] f64: the means over the live frames of coverage_rate and real_coverage_rate (frame-order sum / frames), mean_transport_rate and
+ *               num_delivered_cargoes of frame `last` (FrameSkip.INFO_KEYS' 'mean' and 'last' entries; its 'sum' entries are rewards_dev)
+ *   shaped_dev  [N][A] of `out_dtype`: the sum over the live frames of that frame's AuxiliaryCameraRewards / AuxiliaryTargetRewards row, exactly what
+ *               `frames` accumulating launches of mate_engine_enable_reward_rows leave (same weighted sum, zero-coefficient skip, team `reduction`
+ *               inside each frame).  `coefficients`: a HOST array [7] (camera) / [10] (target) in the order of mate_reward_rows, copied into an
+ *               engine-owned device table the launch reads every time; mate_engine_fragment_coefficients returns that table, a schedule rewrites it
+ *               in place between the replays of a captured graph.  Only the terms that are functions of the scalar record and the masks exist:
+ *               soft_coverage_score, normalized_goal_distance, sparse_delivery and is_colliding need every frame's state, read NaN in the launch and a
+ *               non-zero coefficient for one of them is refused (MATE_EINVAL, the message names the term).  num_tracked / is_tracked read that
+ *               frame's camera -> target bits; the call must bring masks when one of them has a non-zero coefficient at enable (without masks they read 0).
+ *   obs_dev     [N][A][D] of the engine's obs_dtype: frame `last`'s rows, through the optional column table (HOST arrays [D]; all four or none):
+ *               out = ((v - own x) if column_sub = 1, (v - own y) if 2, v if 0; +0 where column_flag >= 0 and that column of the row reads 0)
+ *               * column_scale + column_bias -- the operations and the order of the packer's fused transform (mate_engine_set_obs_transform) on the
+ *               values the plain packer wrote: the rows equal the per-step flows' transformed rows bit for bit.
+ * Any output may be NULL.  An environment without a live frame: frames 0, done 0, zero rewards / info / shaped; its observation row is not written.
+ *
+ * mate_engine_enable_fragment_rows (NULL `config` detaches): while attached, mate_engine_rollout_versus_greedy for `team` enqueues the launch BEHIND
+ * the stepping launch (and the reward launch, if attached) and AHEAD of the restart of finished episodes, over the call's own buffers and its `steps`.
+ * The call then needs io->scalars_dev 16-byte aligned and, where a mask term had a non-zero coefficient at enable, io->masks_dev (MATE_EINVAL).  No
+ * allocation, no synchronisation, identical arguments at every call: capturable under mate_engine_device_tick.  Pipelined restarts return
+ * MATE_ESTATE while attached.  No other call enqueues it.  A fused launch restarts finished episodes behind the launch WITHOUT packing their first
+ * observation into caller buffers: a restarted environment hands the learner its terminal row, done set, for one fragment, as FrameSkip does before
+ * the trainer's reset(), and its next action is chosen on that row.
+ * mate_engine_fragment_rows: the on-demand form over any caller buffers (`rows`: camera_obs_dev or target_obs_dev of `team`, scalars_dev, masks_dev;
+ * `frames` = K >= 1); uploads its tables (waits for the handle's launches).  frames = 1 over the per-step buffers gives the transformed reset() rows.
+ * MATE_EINVAL: an unknown team, out_dtype or reduction, a camera team in a scenario without cameras, shaped rows without coefficients, a partial
+ * column table, a refused term, misaligned buffers.  MATE_ESTATE: before the first reset / import_state. */
+typedef struct mate_fragment_rows {
+    int32_t team;                      /* MATE_TEAM_CAMERA / MATE_TEAM_TARGET: the learner's */
+    void *obs_dev;
+    double *rewards_dev, *info_dev;
+    uint8_t *done_dev;
+    int32_t *frames_dev;
+    void *shaped_dev;
+    int32_t out_dtype;                 /* of shaped_dev: MATE_OBS_F32 / MATE_OBS_F64 */
+    int32_t reduction;                 /* MATE_REDUCE_* (MATE_REDUCE_MIN: the camera team's alone) */
+    const double *coefficients;        /* host [7] / [10]; required with shaped_dev */
+    const int32_t *column_sub, *column_flag;       /* host [D] */
+    const double *column_scale, *column_bias;      /* host [D] */
+} mate_fragment_rows;
+int mate_engine_enable_fragment_rows(mate_engine *engine, const mate_fragment_rows *config);
+int mate_engine_fragment_coefficients(mate_engine *engine, double **coefficients_dev, int32_t *count);
+int mate_engine_fragment_rows(mate_engine *engine, const mate_fragment_rows *config, const mate_step_io *rows, int32_t frames, void *stream);
 
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,

@@ -12,6 +12,7 @@
 #include "../../include/mate_engine.h"
 #include "reset_kernels.hpp"
 #include "reward_rows.hpp"
+#include "fragment_rows.hpp"
 #include "selection_rows.hpp"
 #include "state_rows.hpp"
 #include "shape_groups.hpp"
@@ -54,6 +55,12 @@ struct Selection {       // mate_engine_enable_selection: phase, masks and scala
     SelectionArgs args{};
     double *d_actions = nullptr;
     bool masks_stale = false;                    // a state-only restart (rollout_random's) or import_state ran since the view masks were last written
+};
+struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
+    bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
+    FragmentArgs args{};
+    double *d_coef = nullptr, *d_coef_demand = nullptr;    // [10] each
+    void *d_columns = nullptr, *d_columns_demand = nullptr;      // [max(Dc, Dt)] FragmentColumn<double>-sized entries each
 };
 struct mate_engine {
     Switches sw{};
@@ -99,7 +106,7 @@ struct mate_engine {
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
-    StateRows state; RewardRows reward; Selection selection;      // what is attached around the stepping launches (plan_attached)
+    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -198,13 +205,14 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   2              the stepping launch (and, two-launch form, the opponents' agents in front of it)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
-//   5              the restart epilogue, a reset or an import; with reward rows the snapshot-only launch    attached_behind_restart
-//   6 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
-//   7 state        state_rows_kernel, last                                                                  attached_last
+//   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
+//   6              the restart epilogue, a reset or an import; with reward rows the snapshot-only launch    attached_behind_restart
+//   7 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
+//   8 state        state_rows_kernel, last                                                                  attached_last
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
-    bool execute = false, reward = false, observe = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, state_rows;      // (selection: the three phases are one kernel on one grid)
+    bool execute = false, reward = false, observe = false, fragment = false, action_mask = false, state = false;
+    Tiles soft_coverage, reward_rows, selection, fragment_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
 };
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
 // Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
@@ -215,16 +223,19 @@ static Tiles plan_state_rows(const mate_engine *e, bool f64) {
     while (E > 4 && state_rows_lds_bytes(p.SW, p.DW, S, E, sz) > 40 * 1024) E /= 2;
     return {blocks_of(e, E), 256, (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz), E};
 }
-// `selected`: the call is mate_engine_step_selected.  The action mask is the view the executor would act on next, so while selection is
+static Tiles plan_fragment_rows(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
+// `selected`: the call is mate_engine_step_selected; `fused_team`: the call is mate_engine_rollout_versus_greedy for that team (-1: any other).  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
-static AttachedPlan plan_attached(const mate_engine *e, bool selected) {
+static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;
     pl.action_mask = e->selection.on && e->selection.args.action_mask && !e->selection.masks_stale;
     pl.reward = e->reward.on;
+    pl.fragment = e->fragment.on && fused_team == e->fragment.args.team;
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
     pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
+    pl.fragment_rows = plan_fragment_rows(e);
     pl.state_rows = plan_state_rows(e, e->state.f64);
     return pl;
 }

@@ -662,7 +662,7 @@ static int launch_reset(mate_engine *e, Ptrs g, int kind, int phases, hipStream_
 }
 
 
-// ---- attached launches (csrc/state_rows.hpp, reward_rows.hpp, selection_rows.hpp)
+// ---- attached launches (csrc/state_rows.hpp, reward_rows.hpp, selection_rows.hpp, fragment_rows.hpp)
 // Everything a call enqueues around its stepping, reset or import launch while something is attached, in AttachedPlan's order (engine_host.h): the launches it names,
 // each with the plan's geometry and capturable (no allocation, no synchronisation, the same arguments at every call); the one check; one function per position.
 template <class... P>
@@ -693,9 +693,16 @@ static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, c
     a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->cam_mode;
     return with_obs_type(e->selection.act_f64, [&](auto tag) { return launch_tiles(selection_kernel<decltype(tag)>, pl.selection, stream, e->d_params, e->g, a); });
 }
+// `a`: complete arguments (the attached ones with the call's buffers and frames, or the on-demand form's)
+static int launch_fragment_rows(mate_engine *e, const Tiles &t, const FragmentArgs &a, bool shaped_f64, hipStream_t stream) {
+    return with_obs_type(e->p.obs_f64 != 0, [&](auto obs) {
+        return with_obs_type(shaped_f64, [&](auto out) { return launch_tiles(fragment_rows_kernel<decltype(obs), decltype(out)>, t, stream, e->d_params, a); });
+    });
+}
 // What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
-// `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own).
-static int check_attached_call(const mate_engine *e, const mate_step_io *io, bool pipelined, bool selected, int auto_reset = 0) {
+// `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own);
+// `fused_team`: it is mate_engine_rollout_versus_greedy for that team (-1: any other call).
+static int check_attached_call(const mate_engine *e, const mate_step_io *io, bool pipelined, bool selected, int auto_reset = 0, int fused_team = -1) {
     const char *const no_pipeline = "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) are not available while %s attached (mate_engine_enable_%s): detach %s first";
     if (selected && !e->selection.on) return fail(MATE_ESTATE, "step_selected: call mate_engine_enable_selection() first");
     if (selected && auto_reset < 0) return fail(MATE_ESTATE, "step_selected is not available under pipelined restarts (auto_reset = MATE_RESET_PIPELINED)");
@@ -707,6 +714,14 @@ static int check_attached_call(const mate_engine *e, const mate_step_io *io, boo
     if (pipelined && e->selection.on) return fail(MATE_ESTATE, no_pipeline, "target selection is", "selection", "it");
     if (e->reward.on && (!io || !io->scalars_dev || !io->masks_dev))      // (the reward launch reads the step's scalar record and masks)
         return fail(MATE_EINVAL, "reward rows are attached (mate_engine_enable_reward_rows): the call needs io->scalars_dev and io->masks_dev");
+    if (pipelined && e->fragment.on) return fail(MATE_ESTATE, no_pipeline, "fragment rows are", "fragment_rows", "them");
+    if (plan_attached(e, selected, fused_team).fragment) {      // (the fragment launch reads the K scalar records, 16 bytes at a time, the learner's rows and, for a mask term, the masks)
+        const void *rows = io ? (fused_team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev) : nullptr;
+        if (!io || !io->scalars_dev || (reinterpret_cast<uintptr_t>(io->scalars_dev) & 15u) || (e->fragment.args.obs && !rows))
+            return fail(MATE_EINVAL, "fragment rows are attached (mate_engine_enable_fragment_rows): the call needs io->scalars_dev, 16-byte aligned, and the learner team's observation rows");
+        if (e->fragment.need_masks && !io->masks_dev)
+            return fail(MATE_EINVAL, "fragment rows are attached with a mask term (num_tracked / is_tracked): the call needs io->masks_dev");
+    }
     return MATE_OK;
 }
 // 1: ahead of the stepping launch (and of the opponents' agents) -- the executor's joint action of this frame
@@ -714,29 +729,36 @@ static int attached_ahead_of_step(mate_engine *e, bool selected, hipStream_t str
     const AttachedPlan pl = plan_attached(e, selected);
     return pl.execute ? launch_selection(e, pl, SELECTION_EXECUTE, nullptr, stream) : MATE_OK;
 }
-// 3, 4: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers)
-static int attached_behind_step(mate_engine *e, bool selected, const mate_step_io *io, int frames, hipStream_t stream) {
-    const AttachedPlan pl = plan_attached(e, selected);
+// 3, 4, 5: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers), the fragment of all of them
+static int attached_behind_step(mate_engine *e, bool selected, const mate_step_io *io, int frames, hipStream_t stream, int fused_team = -1) {
+    const AttachedPlan pl = plan_attached(e, selected, fused_team);
     const size_t last = (size_t)(frames - 1) * (size_t)e->N;
     if (pl.reward) {
         const int rc = launch_reward_rows(e, pl, e->reward.accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
         if (rc != MATE_OK) return rc;
     }
-    return pl.observe ? launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream) : MATE_OK;
+    if (pl.observe) { const int rc = launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream); if (rc != MATE_OK) return rc; }
+    if (pl.fragment) {
+        FragmentArgs a = e->fragment.args;
+        a.scalars = io->scalars_dev; a.masks = io->masks_dev; a.K = frames;
+        a.rows = a.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev;
+        return launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream);
+    }
+    return MATE_OK;
 }
-// 5: behind a restart launch, a reset or an import -- the goals and episodes the next step's sparse_delivery is measured against
+// 6: behind a restart launch, a reset or an import -- the goals and episodes the next step's sparse_delivery is measured against
 static int attached_behind_restart(mate_engine *e, hipStream_t stream) {
     const AttachedPlan pl = plan_attached(e, false);
     return pl.reward ? launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream) : MATE_OK;
 }
-// 6, 7: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
+// 7, 8: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
 static int attached_last(mate_engine *e, int rc, hipStream_t stream) {
     if (rc != MATE_OK) return rc;
     const AttachedPlan pl = plan_attached(e, false);
     if (pl.action_mask) { const int rc_ = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, stream); if (rc_ != MATE_OK) return rc_; }
     return pl.state ? launch_state_rows(e, pl.state_rows, e->state.dst, e->state.f64, e->state.ab, stream) : MATE_OK;
 }
-// 5 .. 7 behind reset, reset_tape and import_state: new records without a step
+// 6 .. 8 behind reset, reset_tape and import_state: new records without a step
 static int attached_behind_new_records(mate_engine *e, hipStream_t stream) { return attached_last(e, attached_behind_restart(e, stream), stream); }
 
 // ---- global state rows: attaching, and the on-demand launch
@@ -842,6 +864,110 @@ extern "C" int mate_engine_enable_reward_rows(mate_engine *e, const mate_reward_
     // the goals and episodes of the records as they are: the first step's sparse_delivery is measured against them
     note_stream(e, e->last_stream);
     return attached_behind_restart(e, e->last_stream);
+}
+
+// ---- FrameSkip fragments: attaching, the coefficient table, and the on-demand launch
+// Validates `cfg`, uploads its tables into the given engine-owned buffers (allocated on first use) and fills the launch's arguments but the call's own.
+static int fragment_args_of(mate_engine *e, const mate_fragment_rows *cfg, double **d_coef, void **d_columns, FragmentArgs *out, bool *shaped_f64, bool *need_masks) {
+    const Params &p = e->p;
+    static const char *const kCameraKeys[kRewardCameraTerms] = {"raw_reward", "coverage_rate", "real_coverage_rate", "mean_transport_rate", "soft_coverage_score", "num_tracked", "baseline"};
+    static const char *const kTargetKeys[kRewardTargetTerms] = {"raw_reward", "coverage_rate", "real_coverage_rate", "mean_transport_rate", "normalized_goal_distance",
+                                                                "sparse_delivery", "soft_coverage_score", "is_tracked", "is_colliding", "baseline"};
+    if (cfg->team != MATE_TEAM_CAMERA && cfg->team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "fragment rows: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    const bool camera = cfg->team == MATE_TEAM_CAMERA;
+    if (camera && p.Nc == 0) return fail(MATE_EINVAL, "fragment rows: the scenario has no cameras to learn for");
+    const bool f64 = cfg->out_dtype == MATE_OBS_F64;
+    if (cfg->out_dtype != MATE_OBS_F32 && !f64) return fail(MATE_EINVAL, "fragment rows: out_dtype must be MATE_OBS_F32 or MATE_OBS_F64");
+    if (cfg->reduction < MATE_REDUCE_NONE || cfg->reduction > (camera ? MATE_REDUCE_MIN : MATE_REDUCE_MAX))
+        return fail(MATE_EINVAL, "fragment rows: reduction must be one of MATE_REDUCE_NONE .. %s", camera ? "MATE_REDUCE_MIN" : "MATE_REDUCE_MAX");
+    if (cfg->shaped_dev && !cfg->coefficients) return fail(MATE_EINVAL, "fragment rows: shaped rows without the coefficient table");
+    const int have = (cfg->column_sub != nullptr) + (cfg->column_flag != nullptr) + (cfg->column_scale != nullptr) + (cfg->column_bias != nullptr);
+    if (have != 0 && have != 4) return fail(MATE_EINVAL, "fragment rows: a partial column table (column_sub, column_flag, column_scale and column_bias go together)");
+    const int terms = camera ? kRewardCameraTerms : kRewardTargetTerms, D = camera ? p.Dc : p.Dt;
+    const char *const *keys = camera ? kCameraKeys : kTargetKeys;
+    bool masks = false;
+    for (int k = 0; cfg->coefficients && k < terms; ++k) {
+        const bool state_term = camera ? k == 4 : (k == 4 || k == 5 || k == 6 || k == 8);
+        if (state_term && cfg->coefficients[k] != 0.0)
+            return fail(MATE_EINVAL, "fragment rows: the term %s needs the state of every frame and is not available in a fragment (its coefficient must be 0)", keys[k]);
+        if (k == (camera ? 5 : 7) && cfg->coefficients[k] != 0.0) masks = true;
+    }
+    const uintptr_t obs_align = p.obs_f64 ? 7u : 3u, row_align = f64 ? 7u : 3u;
+    auto misaligned = [](const void *ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; };
+    if (misaligned(cfg->obs_dev, obs_align) || misaligned(cfg->rewards_dev, 7u) || misaligned(cfg->info_dev, 7u) || misaligned(cfg->frames_dev, 3u) || misaligned(cfg->shaped_dev, row_align))
+        return fail(MATE_EINVAL, "fragment rows: a buffer is not aligned to its element size");
+    for (int k = 0; have && k < D; ++k)
+        if (cfg->column_sub[k] < 0 || cfg->column_sub[k] > 2 || cfg->column_flag[k] < -1 || cfg->column_flag[k] >= D)
+            return fail(MATE_EINVAL, "fragment rows: column %d of the table is out of range (sub 0 .. 2, flag -1 .. D - 1)", k);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the tables while they are rewritten)
+    int rc = MATE_OK;
+    if (!*d_coef && (rc = dev_alloc(e, d_coef, (size_t)kRewardTargetTerms))) return rc;
+    if (!*d_columns) {
+        unsigned char *buf = nullptr;
+        if ((rc = dev_alloc(e, &buf, (size_t)(p.Dc > p.Dt ? p.Dc : p.Dt) * sizeof(FragmentColumn<double>)))) return rc;
+        *d_columns = buf;
+    }
+    if (cfg->coefficients) HIP_TRY(hipMemcpy(*d_coef, cfg->coefficients, sizeof(double) * terms, hipMemcpyHostToDevice));
+    if (have) {
+        rc = with_obs_type(p.obs_f64 != 0, [&](auto tag) -> int {
+            using T = decltype(tag);
+            std::vector<FragmentColumn<T>> table((size_t)D);
+            for (int k = 0; k < D; ++k) table[k] = {cfg->column_sub[k], cfg->column_flag[k], (T)cfg->column_scale[k], (T)cfg->column_bias[k]};
+            HIP_TRY(hipMemcpy(*d_columns, table.data(), table.size() * sizeof(table[0]), hipMemcpyHostToDevice));
+            return MATE_OK;
+        });
+        if (rc != MATE_OK) return rc;
+    }
+    mate_layout layout;
+    if ((rc = mate_engine_get_layout(e, &layout))) return rc;
+    FragmentArgs a{};
+    a.obs = cfg->obs_dev; a.columns = have ? *d_columns : nullptr;
+    a.rewards = cfg->rewards_dev; a.info = cfg->info_dev; a.done = cfg->done_dev; a.frames = cfg->frames_dev;
+    a.shaped = cfg->shaped_dev; a.coef = *d_coef;
+    a.N = e->N; a.K = 1; a.team = cfg->team; a.A = camera ? p.Nc : p.Nt; a.D = D; a.reduction = cfg->reduction;
+    a.bit_ct = layout.bit_camera_target;
+    *out = a; *shaped_f64 = f64; *need_masks = masks && cfg->shaped_dev;
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_enable_fragment_rows(mate_engine *e, const mate_fragment_rows *cfg) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!cfg) { e->fragment.on = false; return MATE_OK; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_fragment_rows called before reset() (or import_state)");
+    FragmentRows &f = e->fragment;
+    FragmentArgs a{};
+    bool f64 = false, masks = false;
+    { const int rc = fragment_args_of(e, cfg, &f.d_coef, &f.d_columns, &a, &f64, &masks); if (rc != MATE_OK) return rc; }
+    f.args = a; f.f64 = f64; f.need_masks = masks;
+    f.on = true;
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_fragment_coefficients(mate_engine *e, double **coefficients_dev, int32_t *count) {
+    if (!e || !coefficients_dev) return fail(MATE_EINVAL, "null argument");
+    if (!e->fragment.on) return fail(MATE_ESTATE, "fragment_coefficients: mate_engine_enable_fragment_rows has not run");
+    *coefficients_dev = e->fragment.d_coef;
+    if (count) *count = e->fragment.args.team == MATE_TEAM_CAMERA ? kRewardCameraTerms : kRewardTargetTerms;
+    return MATE_OK;
+}
+
+extern "C" int mate_engine_fragment_rows(mate_engine *e, const mate_fragment_rows *cfg, const mate_step_io *rows, int32_t frames, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!cfg || !rows) return fail(MATE_EINVAL, "fragment_rows: null config or buffers");
+    if (frames < 1) return fail(MATE_EINVAL, "fragment_rows: frames must be at least 1");
+    { const int rc_ = enter(e, (hipStream_t)stream, "fragment_rows"); if (rc_ != MATE_OK) return rc_; }
+    FragmentRows &f = e->fragment;
+    FragmentArgs a{};
+    bool f64 = false, masks = false;
+    { const int rc = fragment_args_of(e, cfg, &f.d_coef_demand, &f.d_columns_demand, &a, &f64, &masks); if (rc != MATE_OK) return rc; }
+    a.rows = cfg->team == MATE_TEAM_CAMERA ? rows->camera_obs_dev : rows->target_obs_dev;
+    a.scalars = rows->scalars_dev; a.masks = rows->masks_dev; a.K = frames;
+    if (!a.scalars || (reinterpret_cast<uintptr_t>(a.scalars) & 15u)) return fail(MATE_EINVAL, "fragment_rows: scalars_dev must be there and 16-byte aligned");
+    if (a.obs && !a.rows) return fail(MATE_EINVAL, "fragment_rows: the learner team's observation rows are missing");
+    if (masks && !a.masks) return fail(MATE_EINVAL, "fragment_rows: a mask term (num_tracked / is_tracked) needs masks_dev");
+    note_stream(e, (hipStream_t)stream);
+    return launch_fragment_rows(e, plan_fragment_rows(e), a, f64, (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
@@ -1368,7 +1494,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (auto_reset < -(1 << 16)) return fail(MATE_EINVAL, "auto_reset = %d: pipelined restarts every -auto_reset launches take 1 .. 65536", auto_reset);
     const int pipe_every = pipelined ? -auto_reset : 1;
     if (pipelined && (!flow.may_pipeline || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
-    if (!per_step) { const int rc_ = check_attached_call(e, io, pipelined, false); if (rc_ != MATE_OK) return rc_; }      // (per_step: step_with_policies has made it)
+    if (!per_step) { const int rc_ = check_attached_call(e, io, pipelined, false, 0, team_caller); if (rc_ != MATE_OK) return rc_; }      // (per_step: step_with_policies has made it)
     if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, stream);
     { int rc = flush_pending(e, auto_reset, flow.restart.flow_tag, stream); if (rc != MATE_OK) return rc; }
@@ -1403,7 +1529,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
     if (!e->dev_tick) e->tick += (uint32_t)steps;
-    { const int rc_ = attached_behind_step(e, selected, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
+    { const int rc_ = attached_behind_step(e, selected, io, steps, stream, per_step ? -1 : team_caller); if (rc_ != MATE_OK) return rc_; }
     return pipelined ? pipelined_restart(e, stream) : restart_finished(e, auto_reset, flow.restart, stream);
 }
 

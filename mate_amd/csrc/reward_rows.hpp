@@ -54,6 +54,15 @@ __device__ __forceinline__ double reward_reduce(double mine, bool agent, int age
     return how == REDUCE_MEAN ? all / (double)agents : all;
 }
 
+// A frame's shaped value ahead of the team reduction: the terms in the order of the coefficient table, product then add; a term whose coefficient
+// is exactly 0 is not added.  ONE text for reward_rows_kernel and fragment_rows_kernel (fragment_rows.hpp); a macro, not a function, so that
+// reward_rows_kernel compiles to the instructions it had before the loop was shared (as an inlined function the adds came out with swapped operands).
+#define MATE_REWARD_WEIGHTED_SUM(shaped, coef, term, K)          \
+    _Pragma("unroll") for (int k = 0; k < (K); ++k) {            \
+        const double c = (coef)[k];                              \
+        if (c != 0.0) shaped = shaped + c * (term)[k];           \
+    }
+
 template <typename OutT>
 __device__ __forceinline__ void reward_store(OutT *row, double shaped, int mode) {
     *row = mode == REWARD_ACCUMULATE ? (OutT)(*row + (OutT)shaped) : (OutT)shaped;
@@ -152,11 +161,7 @@ __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restri
         term[8] = (double)((gw >> 24) & 1);
         term[9] = 1.0;
         double shaped = 0.0;
-#pragma unroll
-        for (int k = 0; k < kRewardTargetTerms; ++k) {
-            const double c = a.tgt_coef[k];
-            if (c != 0.0) shaped = shaped + c * term[k];
-        }
+        MATE_REWARD_WEIGHTED_SUM(shaped, a.tgt_coef, term, kRewardTargetTerms)
         shaped = reward_reduce(shaped, is_tgt, Nt, a.tgt_reduction);
         if (is_tgt) {
             reward_store(tgt_row + env * Nt + j, shaped, a.mode);
@@ -173,11 +178,7 @@ __global__ __launch_bounds__(256) void reward_rows_kernel(const Params *__restri
         term[5] = (double)sees;
         term[6] = 1.0;
         double shaped = 0.0;
-#pragma unroll
-        for (int k = 0; k < kRewardCameraTerms; ++k) {
-            const double c = a.cam_coef[k];
-            if (c != 0.0) shaped = shaped + c * term[k];
-        }
+        MATE_REWARD_WEIGHTED_SUM(shaped, a.cam_coef, term, kRewardCameraTerms)
         shaped = reward_reduce(shaped, is_cam, Nc, a.cam_reduction);
         if (is_cam) {
             reward_store(cam_row + env * Nc + j, shaped, a.mode);

@@ -94,6 +94,29 @@ def reward_coefficient_table(team, coefficients, reduction='none'):
     return [float(coefficients.get(key, 0.0)) for key in keys], REWARD_REDUCTIONS[reduction]
 
 
+FRAGMENT_REFUSED_KEYS = ('soft_coverage_score', 'normalized_goal_distance', 'sparse_delivery', 'is_colliding')
+
+
+def fragment_coefficient_table(team, coefficients, reduction='none'):
+    """reward_coefficient_table() for the shaped rows of a FrameSkip fragment (Engine.enable_fragment_rows): the same keys, order and
+    assertions, but the four terms that need the state of every frame -- FRAGMENT_REFUSED_KEYS -- must be absent or 0; the
+    fragment launch sees the scalar records and the masks only (the engine refuses them too, MATE_EINVAL)."""
+    table = reward_coefficient_table(team, coefficients, reduction)
+    for key in FRAGMENT_REFUSED_KEYS:
+        assert not coefficients.get(key), (
+            f'The term {key!r} needs the state of every frame and is not available in a fused fragment (got coefficient {coefficients[key]!r}); '
+            f'use per-step launches with Engine.enable_reward_rows(accumulate=True) for it.')
+    return table
+
+
+class _EngineOwned:
+    """Engine-owned device memory as a zero-copy tensor source (the tensor keeps `owner`, the Engine, alive)."""
+
+    def __init__(self, owner, ptr, count, typestr):
+        self.owner = owner
+        self.__cuda_array_interface__ = {'shape': (count,), 'typestr': typestr, 'data': (ptr, False), 'version': 2}
+
+
 class Engine:
     """N environments of one scenario on one GPU."""
 
@@ -171,6 +194,10 @@ class Engine:
         # [N, Nc, 2] (engine-owned), the metrics [N, Nc, 4] f64, the contributing frames [N] int32 and action_mask() [N, Nc, 2 Nt | Nt + 1] u8
         self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
         self.multi_selection = None
+        # while fragment rows are attached (enable_fragment_rows): what FrameSkip hands the learner per K-frame launch
+        self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
+        self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
+        self.fragment_frame_skip, self._fragment_masks = 0, False
 
     def close(self):
         if getattr(self, '_h', None):
@@ -338,6 +365,7 @@ class Engine:
         assert team in (0, 1)
         auto_reset = self._auto_reset_code(auto_reset)
         steps = int(steps)
+        want_masks = want_masks or (self._fragment_masks and self.fragment_team == team)
         buf = self.reserve_rollout(steps, want_masks)
         io, keep = self._io(cam_act=joint_action if team == 0 else None, tgt_act=joint_action if team == 1 else None)
         io.camera_obs_dev = buf['camera_obs'].data_ptr() if self.num_cameras else None
@@ -681,6 +709,124 @@ class Engine:
         self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
         self.reward_coefficients = None
 
+    # ------------------------------------------------------------------ FrameSkip fragments behind the fused K-frame launch
+    FRAGMENT_REWARDS = ('camera_team_reward', 'target_team_reward', 'normalized_target_team_reward', 'normalized_camera_team_reward')
+    FRAGMENT_INFO = ('coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'num_delivered_cargoes')
+
+    def _fragment_config(self, team, shaping, relative_coordinates, rescaled_observation, dtype, out):
+        """(MateFragmentRows, what must stay alive during the call, a mask term has a non-zero coefficient) for `out`: the dict of output tensors."""
+        from mate_amd._native import MateFragmentRows
+        from mate_amd.spaces import fragment_column_table
+        code = {'camera': 0, 'target': 1}.get(team, team)
+        assert code in (0, 1), f"team = {team!r}: 'camera' or 'target'"
+        assert dtype in (torch.float32, torch.float64)
+        name = ('camera', 'target')[code]
+        cfg, keep = MateFragmentRows(), []
+        cfg.team, cfg.out_dtype = code, int(dtype == torch.float64)
+        for key in ('obs', 'rewards', 'info', 'done', 'frames', 'shaped'):
+            tensor = out.get(key)
+            if tensor is not None:
+                assert tensor.is_contiguous() and tensor.device == self.device
+                setattr(cfg, key + '_dev', tensor.data_ptr())
+        masks = False
+        if shaping is not None:
+            table, cfg.reduction = reward_coefficient_table(name, *shaping)
+            coefficients = np.ascontiguousarray(table, dtype=np.float64)
+            cfg.coefficients = coefficients.ctypes.data
+            keep.append(coefficients)
+            masks = coefficients[5 if code == 0 else 7] != 0.0
+        columns = fragment_column_table(name, self.num_cameras, self.num_targets, self.num_obstacles, relative_coordinates, rescaled_observation)
+        if columns is not None:
+            columns = [np.ascontiguousarray(c) for c in columns]
+            cfg.column_sub, cfg.column_flag, cfg.column_scale, cfg.column_bias = (c.ctypes.data for c in columns)
+            keep.append(columns)
+        return cfg, keep, bool(masks)
+
+    def _fragment_outputs(self, team, shaped, dtype):
+        code = {'camera': 0, 'target': 1}.get(team, team)
+        N, A, D = self.num_envs, (self.num_cameras, self.num_targets)[code], (self.camera_obs_dim, self.target_obs_dim)[code]
+        with torch.cuda.device(self.device):
+            return {
+                'obs': torch.zeros((N, A, D), dtype=self.obs_dtype, device=self.device),
+                'rewards': torch.zeros((N, 4), dtype=torch.float64, device=self.device), 'info': torch.zeros((N, 4), dtype=torch.float64, device=self.device),
+                'done': torch.zeros(N, dtype=torch.uint8, device=self.device), 'frames': torch.zeros(N, dtype=torch.int32, device=self.device),
+                'shaped': torch.zeros((N, A), dtype=dtype, device=self.device) if shaped else None,
+            }
+
+    def enable_fragment_rows(self, team, frame_skip, shaping=None, relative_coordinates=False, rescaled_observation=False, dtype=torch.float64):
+        """Attach the tail of the example trainers' wrapper chain -- RelativeCoordinates -> RescaledObservation ->
+        RepeatedRewardIndividualDone -> [AuxiliaryCameraRewards | AuxiliaryTargetRewards] -> FrameSkip(frame_skip) -- to the fused
+        K-frame launch: from now on rollout_versus_greedy(team, ...) (and a Stepper(versus=team, frame_skip=K) built afterwards)
+        enqueues ONE more launch behind the stepping launch and ahead of the restart, which reduces the launch's K frames to what
+        FrameSkip hands the learner, in engine-owned tensors:
+          fragment_obs [N, A, D] (obs_dtype): the rows of the last frame that ran, through RelativeCoordinates / RescaledObservation
+            when asked for (the fused launch itself packs plain rows: do NOT call set_obs_transform), bit-identical to the per-step
+            flows' transformed rows;
+          fragment_rewards [N, 4] f64 (FRAGMENT_REWARDS), fragment_done [N] u8, fragment_frames [N] int32 (frames that ran),
+          fragment_info [N, 4] f64 (FRAGMENT_INFO: means of the two coverage rates, the last frame's transport rate and deliveries),
+          fragment_shaped [N, A] (`dtype`) with `shaping` = (coefficients dict, reduction): the sum over the frames of the shaped
+            rows, equal to per-step launches with enable_reward_rows(accumulate=True); FRAGMENT_REFUSED_KEYS are refused,
+          fragment_coefficients [7] / [10] f64: the engine's device table, rewritten in place by a schedule (between graph replays too).
+        An environment that ran no frame (idle under a batched restart) keeps its fragment_obs row; its other rows are 0.  A fused launch
+        restarts finished episodes behind the launch without packing their first observation: a restarted environment hands the
+        learner its terminal row, done set, for one fragment (as FrameSkip does before the trainer's reset()), and the next action
+        is chosen on that row.  Call after the first reset().  Returns fragment_obs."""
+        frame_skip = int(frame_skip)
+        assert frame_skip >= 1
+        out = self._fragment_outputs(team, shaping is not None, dtype)
+        cfg, keep, masks = self._fragment_config(team, shaping, relative_coordinates, rescaled_observation, dtype, out)
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.mate_engine_enable_fragment_rows(self._h, ctypes.byref(cfg)))
+        ptr, count = ctypes.c_void_p(), ctypes.c_int32()
+        check(self.lib.mate_engine_fragment_coefficients(self._h, ctypes.byref(ptr), ctypes.byref(count)))
+        self.fragment_coefficients = torch.as_tensor(_EngineOwned(self, ptr.value, count.value, '<f8'), device=self.device) if shaping is not None else None
+        self.fragment_obs, self.fragment_rewards, self.fragment_done = out['obs'], out['rewards'], out['done']
+        self.fragment_frames, self.fragment_info, self.fragment_shaped = out['frames'], out['info'], out['shaped']
+        self.fragment_team, self.fragment_frame_skip, self._fragment_masks = cfg.team, frame_skip, masks
+        self.reserve_rollout(frame_skip, want_masks=masks)
+        return self.fragment_obs
+
+    def disable_fragment_rows(self):
+        """Detach the fragment launch: rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
+        check(self.lib.mate_engine_enable_fragment_rows(self._h, None))
+        self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
+        self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
+        self.fragment_frame_skip, self._fragment_masks = 0, False
+
+    @property
+    def fragment(self):
+        """The fragment tensors by name (None while detached)."""
+        if self.fragment_team is None:
+            return None
+        return {'obs': self.fragment_obs, 'rewards': self.fragment_rewards, 'done': self.fragment_done, 'frames': self.fragment_frames,
+                'info': self.fragment_info, 'shaped': self.fragment_shaped, 'coefficients': self.fragment_coefficients}
+
+    def fragment_rows(self, team, rows, scalars, masks=None, shaping=None, relative_coordinates=False, rescaled_observation=False,
+                      dtype=torch.float64, out=None):
+        """The fragment launch on demand over caller buffers: `rows` [K, N, A, D] (obs_dtype) the team's PLAIN observation rows,
+        `scalars` [K, N, 8] f32, `masks` [K, N, mask_words] int32 (needed by num_tracked / is_tracked).  K = 1 over the engine's
+        per-step tensors gives the transformed reset() observation.  `out`: a dict of tensors to write (as returned); default: new
+        ones.  Returns {'obs', 'rewards', 'info', 'done', 'frames', 'shaped'}."""
+        code = {'camera': 0, 'target': 1}.get(team, team)
+        if rows.dim() == 3:
+            rows, scalars, masks = rows[None], scalars[None], (masks[None] if masks is not None else None)
+        K = int(rows.shape[0])
+        N, A, D = self.num_envs, (self.num_cameras, self.num_targets)[code], (self.camera_obs_dim, self.target_obs_dim)[code]
+        assert rows.shape == (K, N, A, D) and rows.dtype == self.obs_dtype and rows.is_contiguous() and rows.device == self.device
+        assert scalars.shape == (K, N, 8) and scalars.dtype == torch.float32 and scalars.is_contiguous() and scalars.device == self.device
+        if out is None:
+            out = self._fragment_outputs(code, shaping is not None, dtype)
+        cfg, keep, _ = self._fragment_config(code, shaping, relative_coordinates, rescaled_observation, dtype, out)
+        io = MateStepIO()
+        setattr(io, ('camera_obs_dev', 'target_obs_dev')[code], rows.data_ptr())
+        io.scalars_dev = scalars.data_ptr()
+        if masks is not None:
+            assert masks.shape == (K, N, self.layout.mask_words) and masks.dtype == torch.int32 and masks.is_contiguous() and masks.device == self.device
+            io.masks_dev = masks.data_ptr()
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.mate_engine_fragment_rows(self._h, ctypes.byref(cfg), ctypes.byref(io), K, self._stream()))
+        return out
+
     # ------------------------------------------------------------------ target-selection camera actions (HierarchicalCamera)
     SELECTION_METRICS = ('num_selected_targets', 'num_valid_selected_targets', 'num_invalid_selected_targets', 'invalid_target_selection_rate')
 
@@ -956,7 +1102,8 @@ class Stepper:
             'action tensors must be contiguous f32/f64 (or int32 grid indices) on the engine device'
         self.outputs = None
         if self.frame_skip > 1 and not self.selection:
-            shaped = eng.reward_coefficients is not None      # (the reward launch reads the last frame's masks)
+            # (the reward launch reads the last frame's masks; the fragment launch every frame's, for a mask term)
+            shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus)
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
             self.io.camera_obs_dev = buf['camera_obs'].data_ptr() if eng.num_cameras else None
             self.io.target_obs_dev = buf['target_obs'].data_ptr()
@@ -1039,6 +1186,9 @@ class Stepper:
     camera_reward_terms = property(lambda self: self.eng.camera_reward_terms)
     target_reward_terms = property(lambda self: self.eng.target_reward_terms)
     reward_coefficients = property(lambda self: self.eng.reward_coefficients)
+    # The engine's fragment tensors (Engine.enable_fragment_rows BEFORE the stepper is built: versus = that team, frame_skip = K): a dict
+    # {'obs', 'rewards', 'done', 'frames', 'info', 'shaped', 'coefficients'}, rewritten by every K-frame launch and every replay.
+    fragment = property(lambda self: self.eng.fragment)
 
     def close(self):
         if self.graph is not None:

@@ -621,6 +621,32 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         return out
 
 
+def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, target_reward_shaping=None, enhanced_observation=None,
+                       shared_field_of_view=None, camera_selection=None):
+    """The argument rules of BatchedMultiAgentTracking(frame_skip=K, learner=...), checked ahead of everything that needs a GPU.
+    Returns None without `frame_skip`, else {'frame_skip', 'learner', 'shaping'}: the learner's (coefficients, reduction) or None."""
+    if frame_skip is None:
+        assert learner is None, "learner = ... belongs to frame_skip = K (the fused learner-versus-greedy fragments)"
+        return None
+    from mate_amd.engine import fragment_coefficient_table
+    assert isinstance(frame_skip, (int, np.integer)) and not isinstance(frame_skip, bool) and frame_skip >= 1, \
+        f'frame_skip = {frame_skip!r}: a positive number of frames (examples/utils/wrappers.py FrameSkip)'
+    assert learner in ('camera', 'target'), f"frame_skip needs learner = 'camera' or 'target' (got {learner!r}): the other team is the greedy agents"
+    cameras = config.get('camera', {})
+    assert learner != 'camera' or len(cameras.get('location', [])) + len(cameras.get('location_random_range', [])) > 0, \
+        "learner = 'camera' needs cameras"
+    for name, value in (('enhanced_observation', enhanced_observation), ('shared_field_of_view', shared_field_of_view)):
+        assert value in (None, False, 'none'), f'{name} is not available with frame_skip: the fused launch packs plain rows'
+    assert not camera_selection, 'camera_selection steps one frame per call: it does not combine with frame_skip'
+    other = target_reward_shaping if learner == 'camera' else camera_reward_shaping
+    assert other is None, f"frame_skip with learner = {learner!r} shapes the learner's rewards only (the other team is the greedy agents)"
+    shaping = camera_reward_shaping if learner == 'camera' else target_reward_shaping
+    if shaping is not None:
+        shaping = (dict(shaping[0]), shaping[1])
+        fragment_coefficient_table(learner, *shaping)
+    return {'frame_skip': int(frame_skip), 'learner': learner, 'shaping': shaping}
+
+
 class BatchedMultiAgentTracking(_ScenarioMixin):
     """N independent environments stepped by one kernel launch; every array is a torch tensor on the GPU.
 
@@ -633,14 +659,31 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     `camera_reward_shaping` / `target_reward_shaping` = (coefficients, reduction): the reference's AuxiliaryCameraRewards /
     AuxiliaryTargetRewards wrappers as one device launch behind every stepping call; `shaped_rewards()`
-    returns the two tensors ([num_envs, agents], `reward_dtype`).  What step() and the rest return does not change."""
+    returns the two tensors ([num_envs, agents], `reward_dtype`).  What step() and the rest return does not change.
+
+    `frame_skip` = K with `learner` = 'camera' | 'target': the tail of the example trainers' chain -- MultiCamera | MultiTarget against
+    the greedy opponents -> RelativeCoordinates -> RescaledObservation -> RepeatedRewardIndividualDone -> Auxiliary*Rewards ->
+    FrameSkip(K) -- on the fused K-frame launch with the fragment launch behind it.  `relative_coordinates` /
+    `rescaled_observation` then go to the fragment launch's column table instead of the packer (the fused launch packs plain rows),
+    the learner's `*_reward_shaping` to its coefficients (the four terms that need every frame's state are refused).  reset() returns the
+    learner's transformed rows [num_envs, agents, D]; step_fragment(joint_action) returns (obs, rewards [num_envs, agents], done
+    [num_envs], info).  LIMIT: a fused launch restarts finished episodes behind the launch without packing their first observation into
+    caller buffers, so a restarted environment hands the learner its TERMINAL row with done set for one fragment -- as FrameSkip does
+    before the trainer calls reset() -- and its next action is chosen on that row.  Without `frame_skip` nothing about the class changes."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
-                 camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, **kwargs):
+                 camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
+                 learner=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
+        self._fragment = fragment_arguments(self.config, frame_skip, learner, camera_reward_shaping, target_reward_shaping, enhanced_observation,
+                                            shared_field_of_view, camera_selection)
+        if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
+            self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype)
+            relative_coordinates = rescaled_observation = False
+            camera_reward_shaping = target_reward_shaping = None
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
         self.engine = Engine(self.config, self.num_envs, device=device, seed=seed, first_env_index=first_env_index, obs_dtype=obs_dtype)
         self.num_cameras, self.num_targets, self.num_obstacles = self.engine.num_cameras, self.engine.num_targets, self.engine.num_obstacles
@@ -682,6 +725,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
+        if self._fragment:
+            self.enable_greedy_policies()
 
     def seed(self, seed):
         self.engine.seed(int(seed))
@@ -711,7 +756,48 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self.engine.enable_selection(self.camera_selection == 'multi')
         for shaper in self.__dict__.get('_target_shapers', {}).values():
             shaper.observe_reset()
+        if self._fragment:
+            return self._fragment_reset(env_mask)
         return out
+
+    def _fragment_reset(self, env_mask=None):
+        """The learner's transformed rows of the observation reset() has just packed: the fragment launch on demand, one frame.  A masked
+        reset repacks the listed environments only: the others' one-frame record says done = 2, so their fragment rows stay as they are."""
+        spec, eng = self._fragment, self.engine
+        transform = {'relative_coordinates': spec['relative_coordinates'], 'rescaled_observation': spec['rescaled_observation']}
+        if eng.fragment_team is None:
+            eng.enable_fragment_rows(spec['learner'], spec['frame_skip'], shaping=spec['shaping'], dtype=spec['dtype'], **transform)
+        rows = eng.camera_obs if spec['learner'] == 'camera' else eng.target_obs
+        if '_live' not in spec:      # (a scalar record that says "this frame ran": the step's own may be older than the reset)
+            spec['_live'] = torch.zeros((self.num_envs, 8), dtype=torch.float32, device=self.device)
+        if env_mask is None:
+            spec['_live'][:, 2] = 0.0
+        else:
+            spec['_live'][:, 2] = torch.where(env_mask.to(device=self.device).bool().reshape(-1), 0.0, 2.0)
+        eng.fragment_rows(spec['learner'], rows, spec['_live'], out={'obs': eng.fragment_obs}, **transform)
+        return eng.fragment_obs
+
+    def step_fragment(self, joint_action):
+        """One fragment: `joint_action` ([num_envs, agents, 2] or grid indices) held for frame_skip frames against the greedy opponents in
+        one launch, reduced by the fragment launch.  Returns (obs [num_envs, agents, D], rewards [num_envs, agents], done [num_envs],
+        info): `rewards` is the shaped sum with `*_reward_shaping`, else the learner's team reward repeated per agent
+        (RepeatedRewardIndividualDone); `info` holds FrameSkip's reduced keys ('sum': the raw and normalised rewards; 'mean': the two
+        coverage rates; 'last': mean_transport_rate, num_delivered_cargoes) and 'frames' [num_envs], the frames that ran.  The tensors are
+        the engine's own, rewritten by the next call.  See the class docstring for the row a restarted environment shows."""
+        assert self._fragment, 'built without frame_skip = K, learner = ...'
+        spec, eng = self._fragment, self.engine
+        assert eng.fragment_team is not None, 'reset() first'
+        eng.rollout_versus_greedy(spec['learner'], joint_action, spec['frame_skip'], auto_reset=int(self.auto_reset))
+        camera = spec['learner'] == 'camera'
+        sums, means = eng.fragment_rewards, eng.fragment_info
+        if eng.fragment_shaped is not None:
+            rewards = eng.fragment_shaped
+        else:
+            rewards = sums[:, 0 if camera else 1, None].expand(-1, eng.fragment_obs.shape[1])
+        info = {'raw_reward': sums[:, 0 if camera else 1], 'normalized_raw_reward': sums[:, 3 if camera else 2],
+                'coverage_rate': means[:, 0], 'real_coverage_rate': means[:, 1], 'mean_transport_rate': means[:, 2],
+                'num_delivered_cargoes': means[:, 3], 'frames': eng.fragment_frames}
+        return eng.fragment_obs, rewards, eng.fragment_done > 0, info
 
     def _result(self):
         s = self.engine.scalars

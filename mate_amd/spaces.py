@@ -100,6 +100,51 @@ def rescale_affine(space):
     return np.ascontiguousarray(scale), np.ascontiguousarray(bias)
 
 
+def fragment_column_table(team, num_cameras, num_targets, num_obstacles, relative_coordinates=False, rescaled_observation=False):
+    """The per-column table of the fragment launch (mate_engine_enable_fragment_rows) for one team's observation row [D]:
+    `(sub, flag, scale, bias)` with out = ((v - own x) where sub = 1, (v - own y) where 2, v where 0; +0 where flag >= 0 and that
+    column of the row reads 0) * scale + bias -- RelativeCoordinates then RescaledObservation (mate/agents/utils.py:40-137 of the
+    reference) on a PLAIN row, with the packer's visible / invisible rule: the entries of an entity the agent does not see stay 0
+    through the subtraction.  The row owner's (x, y) are columns 13 and 14 (the head of its own state, behind the 13 preserved
+    entries).  Coordinates: the four warehouse centres of the preserved block (columns 4 .. 11, never gated) and x, y at the head
+    of every opponent / obstacle / teammate entry, gated by that entry's flag (its last column).  None when neither wrapper is asked for."""
+    from mate_amd import constants as consts
+    assert team in ('camera', 'target')
+    if not relative_coordinates and not rescaled_observation:
+        return None
+    nums = (num_cameras, num_targets, num_obstacles)
+    camera = team == 'camera'
+    space = consts.camera_observation_space_of(*nums) if camera else consts.target_observation_space_of(*nums)
+    D = int(np.prod(space.shape))
+    self_dim = 9 if camera else 14
+    blocks = ((num_targets, 5), (num_obstacles, 4), (num_cameras, 7)) if camera else ((num_cameras, 7), (num_obstacles, 4), (num_targets, 5))
+    assert D == 13 + self_dim + sum(count * width for count, width in blocks), (D, team, nums)
+    sub, flag = np.zeros(D, dtype=np.int32), np.full(D, -1, dtype=np.int32)
+    if relative_coordinates:
+        sub[4:12:2], sub[5:12:2] = 1, 2
+    start = 13 + self_dim
+    for count, width in blocks:
+        for entry in range(count):
+            flag[start:start + width] = start + width - 1
+            if relative_coordinates:
+                sub[start], sub[start + 1] = 1, 2
+            start += width
+    scale, bias = rescale_affine(space) if rescaled_observation else (np.ones(D), np.zeros(D))
+    return sub, flag, np.ascontiguousarray(scale, dtype=np.float64), np.ascontiguousarray(bias, dtype=np.float64)
+
+
+def apply_fragment_column_table(rows, table):
+    """`fragment_column_table` applied to plain rows [..., D] in NumPy, in the launch's order of operations (the tests' restatement)."""
+    rows = np.asarray(rows)
+    if table is None:
+        return rows.copy()
+    sub, flag, scale, bias = table
+    own = np.stack([np.zeros_like(rows[..., 0]), rows[..., 13], rows[..., 14]], axis=-1)[..., sub]
+    visible = np.where(flag >= 0, rows[..., np.maximum(flag, 0)] != 0, True)
+    gated = np.where(visible, rows - own, np.zeros_like(rows))
+    return gated * scale.astype(rows.dtype) + bias.astype(rows.dtype)
+
+
 def _square_grid(levels):
     """`levels` x `levels` grid on [-1, 1]^2, x fastest (np.meshgrid of two linspaces, discrete_action_spaces.py:107-113)."""
     if not (isinstance(levels, (int, np.integer)) and levels >= 3 and levels % 2 == 1):
