@@ -243,19 +243,64 @@ struct Ptrs {
     int32_t obs_mode;             // bits 0-1 camera team, bits 2-3 target team: 0 plain, 1 EnhancedObservation, 2 SharedFieldOfView
     int32_t rotate_prio;          // rollout kernel: rotate the wave priorities (fair SIMD shares, see rollout_kernel)
     int32_t store_shifted;        // row-image rollouts: the line-aligned form of the row stores (image_store_form; mate_engine_set_store_form)
-    // Pipelined restarts of the fused Greedy rollouts (mate_engine_rollout_greedy, auto_reset = MATE_RESET_PIPELINED): the reset of
-    // what launch n finished runs on a side stream UNDER launch n + 1, and a restarted environment joins launch n + 2.  The
-    // record's `done` word carries the hand-over: kDoneTag | parity << 3 = "restarted, live from the next launch of this list
-    // parity on"; any launch of the other parity -- the one the reset runs under -- leaves such an environment alone (no step, no
-    // store), so what a launch does never depends on how far the concurrent reset has come.
+    // Pipelined restarts of the fused Greedy rollouts (mate_engine_rollout_greedy, auto_reset = MATE_RESET_PIPELINED): the reset of what launch n
+    // finished runs on a side stream UNDER launch n + 1, and a restarted environment joins launch n + 2 (its `done` word: kDoneTag | parity << 3); a launch
+    // of the other parity -- the one the reset runs under -- leaves it alone (no step, no store): what a launch does never depends on how far that reset has come.
     int32_t pipelined;
     // The sub-wave rollout kernel as ONE step of the per-step flows (mate_engine_step / _step_random of the small scenarios, launch_step): step()'s
     // semantics instead of a rollout's -- a finished environment idles only under a batched restart (freeze_done), the tick and the list parity
     // may live on the device (mate_engine_device_tick).
     int32_t per_step;
 };
-constexpr int32_t kDoneTag = 4;
 
+// ---------------------------------------------------------------------------------------------
+// The restart list: how a finished environment reaches the reset launch; one protocol for every stepping kernel (here and in
+// policy_kernels.hpp), reset_kernels.hpp and the host (mate_engine.hip: restart_finished, pipelined_restart).  `done_count[2]` /
+// `done_list[2][N]` are used in turn: a stepping launch appends to list `parity` (Ctx::list_parity; host-counted, or Params::dev_group
+// with a device-resident step counter) and its first thread clears the other list's counter; the reset launch behind it consumes
+// list `parity`; without a list (`done_count` == NULL: auto_reset = 0, observe, flag-driven restarts) nothing is appended.  Who writes which EI_DONE value (non-zero = "not live"):
+//   0                      live: every executed step that does not end the episode, reset_state, untag_kernel, and the entry of a
+//                          pipelined rollout_greedy_kernel launch for an environment tagged for its parity.
+//   kDoneFinished (1)      ended, on NO list: the step that ended it in a launch without a list, or import_kernel.
+//   kDoneListed (3)        ended AND on the next reset launch's list (nobody lists it twice): the step that ended it in a launch with
+//                          a list; or, finished under auto_reset = 0 earlier, the entry of a later launch with a list (in the LDS
+//                          record, stored at the launch's end; the pipelined entry: in device memory) or its idle path (step_kernel,
+//                          step_split_kernel, step_greedy_kernel: in device memory, done_word_of -- they store nothing else).
+//   kDoneTag | parity << 3 restarted by a pipelined reset, live from the next launch of that parity on (Ptrs::pipelined): reset_state.
+constexpr int32_t kDoneFinished = 1, kDoneListed = 3, kDoneTag = 4;
+// the scalar row of an idle step (finished, waiting for the reset launch): done = 2, the rest 0 -- the whole row, so that every form of a step writes the same bytes
+__device__ __forceinline__ void write_idle_row(float *o) { o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+// the EI_DONE word of an environment's record in device memory (`dyn`: Ptrs::dyn)
+__device__ __forceinline__ int32_t *done_word_of(const Params &p, double *dyn, int64_t env) { return &reinterpret_cast<int32_t *>(dyn + env * p.DW + p.DF)[p.Nt * TI_STRIDE + EI_DONE]; }
+// `env` goes on list `parity` of the restart list; returns its slot.  The three launch arguments BY REFERENCE, so that each is read
+// where the sites this replaced read it -- the list and N behind the atomic.  Measured: by value (loaded ahead of the atomic) the
+// figures of 11 kernels move, e.g. step_split_kernel<0v8-32> 49 -> 45 VGPRs, rollout_greedy_kernel<double, 4v2-9> SGPR spills 34 -> 44.
+__device__ __forceinline__ int list_finished(int32_t *const &done_count, int32_t *const &done_list, const int64_t &N, int parity, int64_t env) {
+    const int slot = atomicAdd(done_count + parity, 1);
+    done_list[(int64_t)parity * N + slot] = (int32_t)env;
+    return slot;
+}
+
+// Which warehouse holds a target at (x, y), or -1 (constants.py:70-72: 0 (+,+), 1 (-,+), 2 (-,-), 3 (+,-), Chebyshev radius 75 around (+-925, +-925); environment.py:1283).
+// Only the warehouse of the target's own quadrant can hold it (any other centre is >= 925 away in one coordinate): one test is the reference's loop over the four.
+__device__ __forceinline__ int warehouse_of(double x, double y) {
+    const bool px = x > 0.0, py = y > 0.0;
+    const double wx = px ? kWarehouseCenter : -kWarehouseCenter, wy = py ? kWarehouseCenter : -kWarehouseCenter;
+    const double sup = fmax(fabs(x - wx), fabs(y - wy));
+    return sup <= kWarehouseRadius ? (px ? (py ? 0 : 3) : (py ? 1 : 2)) : -1;
+}
+// tracked_bits = camera_target_view_mask.any(axis=0) (environment.py:1388) from the ballot of the only round of sector pairs (pair cam * Nt + t on that bit)
+__device__ __forceinline__ unsigned long long tracked_from_ballot(const Params &p, unsigned long long sector_ballot) {
+    unsigned long long any = 0ull;
+    for (int cam = 0; cam < p.Nc; ++cam) any |= sector_ballot >> (cam * p.Nt);
+    return any;
+}
+// A target's action cut to its step size (entities.py:649-650).  `step.norm = step_size` goes through the polar form in the reference; rescaling the
+// vector is the same quantity to within the last-place noise a device atan2 / sincos would add anyway, at a tenth of the instructions.
+__device__ __forceinline__ void clamp_step(double ax, double ay, double step_size, double &vx, double &vy, double &n) {
+    vx = ax; vy = ay; n = norm2(ax, ay);
+    if (n > step_size) { const double k = div_nz(step_size, n); vx = ax * k; vy = ay * k; n = step_size; }
+}
 // Phase-keyed issue priority.  The SIMD arbiter serves its oldest wave first, so the four co-resident
 // environment-waves of a SIMD finish one after the other and the last one runs its tail alone, with nobody
 // to hide its LDS/HBM round trips (measured: wave lifetimes 27k..41k cycles by wave slot).  Lowering a
@@ -724,15 +769,7 @@ __device__ __forceinline__ void simulate_targets(Ctx<ObsT, L> &c, const StepDraw
         }
         const double step_size = ((c.capword() >> t) & 1ull) ? p.tgt_step * 0.5 : p.tgt_step;   // entities.py:612-615
         ox = c.tx(t); oy = c.ty(t);
-        vx = ax; vy = ay;
-        n = norm2(ax, ay);
-        if (n > step_size) {
-            // `step.norm = step_size` (entities.py:649-650) goes through the polar form in the reference
-            // (s*(cos, sin) of atan2(a)); rescaling the vector is the same quantity to within the
-            // last-place noise a device atan2/sincos would add anyway, at a tenth of the instructions.
-            const double k = div_nz(step_size, n);
-            vx = ax * k; vy = ay * k; n = step_size;
-        }
+        clamp_step(ax, ay, step_size, vx, vy, n);
         desx = ox + vx; desy = oy + vy;
         if (!carried) { c.snorm(t) = n; if (!ballot_screen && !group_screen) { c.near(t) = 0; c.near(p.Nt + t) = 0; } }
     }
@@ -1487,14 +1524,7 @@ __device__ __forceinline__ void update_view(Ctx<ObsT, L> &c, uint32_t tick, uint
         int any = 0;
         for (int cam = 0; cam < p.Nc; ++cam) any |= (int)c.mask_bit(cam * p.Nt + lane);
         c.tracked(lane) = any;
-        // warehouses (constants.py:70-72): 0 (+,+), 1 (-,+), 2 (-,-), 3 (+,-), Chebyshev radius 75 around (+-925, +-925)
-        // (environment.py:1283).  Only the warehouse of the target's own quadrant can hold it (any other centre is at
-        // least 925 away in one coordinate), so one test with that centre is the reference's loop over the four.
-        const double x = c.tx(lane), y = c.ty(lane);
-        const bool px = x > 0.0, py = y > 0.0;
-        const double wx = px ? kWarehouseCenter : -kWarehouseCenter, wy = py ? kWarehouseCenter : -kWarehouseCenter;
-        const double sup = fmax(fabs(x - wx), fabs(y - wy));
-        c.inside(lane) = sup <= kWarehouseRadius ? (px ? (py ? 0 : 3) : (py ? 1 : 2)) : -1;
+        c.inside(lane) = warehouse_of(c.tx(lane), c.ty(lane));
     }
     wave_sync();
 #undef MATE_N_SR
@@ -1569,22 +1599,16 @@ __device__ __forceinline__ void goal_logistics(Ctx<ObsT, L> &c, uint32_t tick, d
     }
 }
 
-// update_view's tail for lanes [0, Nt) from the ballot of the (only) sector round: tracked_bits = camera_target_view_mask.any(axis=0)
-// (environment.py:1388), and which warehouse holds the target (see update_view)
+// update_view's tail for lanes [0, Nt) from the ballot of the (only) sector round: tracked bit and warehouse
 template <typename ObsT>
 __device__ __forceinline__ void view_tail_regs(Ctx<ObsT> &c, unsigned long long sector_ballot, int &tracked, int &inside) {
     const Params &p = c.p;
     const int lane = c.lane;
-    unsigned long long any = 0ull;
-    for (int cam = 0; cam < p.Nc; ++cam) any |= sector_ballot >> (cam * p.Nt);
+    const unsigned long long any = tracked_from_ballot(p, sector_ballot);
     tracked = lane < p.Nt ? (int)((any >> (lane & 63)) & 1ull) : 0;
     inside = -1;
     if (lane < p.Nt) {
-        const double x = c.tx(lane), y = c.ty(lane);
-        const bool px = x > 0.0, py = y > 0.0;
-        const double wx = px ? kWarehouseCenter : -kWarehouseCenter, wy = py ? kWarehouseCenter : -kWarehouseCenter;
-        const double sup = fmax(fabs(x - wx), fabs(y - wy));
-        inside = sup <= kWarehouseRadius ? (px ? (py ? 0 : 3) : (py ? 1 : 2)) : -1;
+        inside = warehouse_of(c.tx(lane), c.ty(lane));
     }
 }
 
@@ -1645,8 +1669,7 @@ __device__ __forceinline__ void assign_and_score(Ctx<ObsT, L> &c, uint32_t tick,
         c.ei(EI_EPSTEP) = ep_step;
         const bool awaiting = c.ei(EI_AWAITING) || c.ei(EI_AWAITING + 1) || c.ei(EI_AWAITING + 2) || c.ei(EI_AWAITING + 3);
         const int done = !(ep_step <= p.max_episode_steps && awaiting);
-        // 1 = finished; 3 = finished AND on the list of the next reset launch (so that nobody lists it twice)
-        c.ei(EI_DONE) = done ? (c.g.done_count ? 3 : 1) : 0;
+        c.ei(EI_DONE) = done ? (c.g.done_count ? kDoneListed : kDoneFinished) : 0;
         c.ei(EI_TICK) = (int)(tick + 1u);
         if (c.has_scalars() && scalars_out) {
             float *o = scalars_out + c.out * 8;
@@ -1654,9 +1677,7 @@ __device__ __forceinline__ void assign_and_score(Ctx<ObsT, L> &c, uint32_t tick,
             o[4] = (float)real_cov; o[5] = (float)transport; o[6] = (float)delivered; o[7] = (float)div_nz(r, p.max_team_reward);
         }
         if (done && c.g.done_count) {
-            const int parity = c.list_parity();
-            const int slot = atomicAdd(c.g.done_count + parity, 1);
-            c.g.done_list[(int64_t)parity * c.g.N + slot] = (int32_t)c.env;
+            list_finished(c.g.done_count, c.g.done_list, c.g.N, c.list_parity(), c.env);
         }
         if (done && c.g.ep_stats) {      // episode statistics for logging (the record SURVEY.md 8e all-gathers); rare
             double *es = c.g.ep_stats;
@@ -2326,9 +2347,8 @@ __device__ __forceinline__ void simulate_targets_held(Ctx<ObsT> &c, const StepDr
         const double ax = draws.a0, ay = draws.a1;
         const double step_size = ((c.capword() >> t) & 1ull) ? p.tgt_step * 0.5 : p.tgt_step;   // entities.py:612-615
         const double ox = h.x, oy = h.y;
-        double vx = ax, vy = ay;
-        double n = norm2(ax, ay);
-        if (n > step_size) { const double k = div_nz(step_size, n); vx = ax * k; vy = ay * k; n = step_size; }      // entities.py:649-650
+        double vx, vy, n;
+        clamp_step(ax, ay, step_size, vx, vy, n);
         const double desx = ox + vx, desy = oy + vy;
         uint64_t todo = near_field(p, carried, t);
         bool n_known = true;
@@ -2359,8 +2379,7 @@ template <typename ObsT>
 __device__ __forceinline__ void view_tail_held(const Ctx<ObsT> &c, unsigned long long sector_ballot, const HeldState &h, bool &tracked, int &inside) {
     const Params &p = c.p;
     const int t = c.lane - p.Nc;
-    unsigned long long any = 0ull;                       // tracked_bits = camera_target_view_mask.any(axis=0), environment.py:1388
-    for (int cam = 0; cam < p.Nc; ++cam) any |= sector_ballot >> (cam * p.Nt);
+    const unsigned long long any = tracked_from_ballot(p, sector_ballot);
     tracked = t >= 0 && t < p.Nt && ((any >> (t & 63)) & 1ull);
     const bool px = h.x > 0.0, py = h.y > 0.0;           // (see update_view: only the warehouse of the target's quadrant can hold it)
     const double wx = px ? kWarehouseCenter : -kWarehouseCenter, wy = py ? kWarehouseCenter : -kWarehouseCenter;
@@ -2433,11 +2452,9 @@ __device__ __forceinline__ int assign_and_score_held(Ctx<ObsT> &c, uint32_t tick
             o[4] = (float)real_cov; o[5] = (float)transport; o[6] = (float)delivered; o[7] = (float)div_nz(r, p.max_team_reward);
         }
         if (done) {                                            // rare: the record's flag, the restart list, the statistics
-            c.ei(EI_DONE) = c.g.done_count ? 3 : 1;            // (3: on the list of the next reset launch, see assign_and_score)
+            c.ei(EI_DONE) = c.g.done_count ? kDoneListed : kDoneFinished;
             if (c.g.done_count) {
-                const int parity = c.list_parity();
-                const int slot = atomicAdd(c.g.done_count + parity, 1);
-                c.g.done_list[(int64_t)parity * c.g.N + slot] = (int32_t)c.env;
+                list_finished(c.g.done_count, c.g.done_list, c.g.N, c.list_parity(), c.env);
             }
             if (c.g.ep_stats) {
                 double *es = c.g.ep_stats;
@@ -2514,13 +2531,11 @@ void step_kernel(const Params *__restrict__ pp, const Ptrs g) {
         wave_sync();
         if (c.ei(EI_DONE) != 0) {     // waiting for the next batched reset: no step, no new observation
             // (the whole row, like the idle rows of the fused kernels: the one-launch and the two-launch form of a step write the same bytes)
-            if (lane == 0 && g.scalars) { float *o = g.scalars + c.out * 8; o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+            if (lane == 0 && g.scalars) write_idle_row(g.scalars + c.out * 8);
             if (lane == 0 && g.idle_steps) g.idle_steps[env] += 1;
-            if (lane == 0 && g.done_count && c.ei(EI_DONE) == 1) {      // finished under auto_reset = 0 earlier: not on the list yet
-                const int parity = c.list_parity();
-                const int slot = atomicAdd(g.done_count + parity, 1);
-                g.done_list[(int64_t)parity * g.N + slot] = (int32_t)env;
-                reinterpret_cast<int32_t *>(g.dyn + env * p.DW + p.DF)[p.Nt * TI_STRIDE + EI_DONE] = 3;
+            if (lane == 0 && g.done_count && c.ei(EI_DONE) == kDoneFinished) {      // finished under auto_reset = 0 earlier: not on the list yet
+                list_finished(g.done_count, g.done_list, g.N, c.list_parity(), env);
+                *done_word_of(p, g.dyn, env) = kDoneListed;
             }
             return;
         }
@@ -2658,11 +2673,7 @@ __device__ __forceinline__ void split_view_sector(Ctx<ObsT> &c, uint32_t tick) {
     }
     // ... and which warehouse holds a target (the second half of update_view's tail)
     if (lane < p.Nt) {
-        const double x = c.tx(lane), y = c.ty(lane);
-        const bool px = x > 0.0, py = y > 0.0;
-        const double wx = px ? kWarehouseCenter : -kWarehouseCenter, wy = py ? kWarehouseCenter : -kWarehouseCenter;
-        const double sup = fmax(fabs(x - wx), fabs(y - wy));
-        c.inside(lane) = sup <= kWarehouseRadius ? (px ? (py ? 0 : 3) : (py ? 1 : 2)) : -1;
+        c.inside(lane) = warehouse_of(c.tx(lane), c.ty(lane));
     }
     unsigned long long b = 0ull;
     if (last >= 0) {
@@ -2791,13 +2802,11 @@ void step_split_kernel(const Params *__restrict__ pp, const Ptrs g) {
     }
     if (c.freeze_done() && done_word != 0) {
         if (role == 0 && lane == 0) {
-            if (g.scalars) { float *o = g.scalars + c.out * 8; o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+            if (g.scalars) write_idle_row(g.scalars + c.out * 8);
             if (g.idle_steps) g.idle_steps[env] += 1;
-            if (g.done_count && done_word == 1) {      // finished under auto_reset = 0 earlier: not on the list yet
-                const int parity = c.list_parity();
-                const int slot = atomicAdd(g.done_count + parity, 1);
-                g.done_list[(int64_t)parity * g.N + slot] = (int32_t)env;
-                reinterpret_cast<int32_t *>(g.dyn + env * p.DW + p.DF)[p.Nt * TI_STRIDE + EI_DONE] = 3;
+            if (g.done_count && done_word == kDoneFinished) {      // finished under auto_reset = 0 earlier: not on the list yet
+                list_finished(g.done_count, g.done_list, g.N, c.list_parity(), env);
+                *done_word_of(p, g.dyn, env) = kDoneListed;
             }
         }
         return;
@@ -2872,16 +2881,11 @@ void step_split_kernel(const Params *__restrict__ pp, const Ptrs g) {
     SPLIT_STAMP(7);
 }
 
-// An environment whose episode had ended BEFORE a fused rollout began (a step or rollout with auto_reset = 0, or an
-// imported done flag) is skipped by every step of the launch, so the step that would have listed it for the reset
-// launch never runs: list it here, or it would idle forever.
-template <typename ObsT, int L>
+template <typename ObsT, int L>      // finished BEFORE a fused rollout began: every step of the launch skips it, so no step lists it -- list it here, or it idles forever
 __device__ __forceinline__ void list_finished_at_entry(Ctx<ObsT, L> &c) {
-    if (c.lane == 0 && c.g.done_count && c.ei(EI_DONE) == 1) {     // (3: a batched-reset step listed it already)
-        const int parity = c.list_parity();
-        const int slot = atomicAdd(c.g.done_count + parity, 1);
-        c.g.done_list[(int64_t)parity * c.g.N + slot] = (int32_t)c.env;
-        c.ei(EI_DONE) = 3;      // listed (stored with the record at the end of the launch): the one-step launches of a batched-reset interval meet it again
+    if (c.lane == 0 && c.g.done_count && c.ei(EI_DONE) == kDoneFinished) {     // (kDoneListed: a batched-reset step listed it already)
+        list_finished(c.g.done_count, c.g.done_list, c.g.N, c.list_parity(), c.env);
+        c.ei(EI_DONE) = kDoneListed;      // listed (stored with the record at the end of the launch): the one-step launches of a batched-reset interval meet it again
     }
 }
 
@@ -2890,8 +2894,7 @@ __device__ __forceinline__ void list_finished_at_entry(Ctx<ObsT, L> &c) {
 // the environment's records resident in LDS for the whole launch.  Outputs of step r go to row r*N + env
 // of the (rollout-shaped) output buffers.  Waves drift apart freely, so the launch takes about the MEAN
 // wave time per step instead of the slowest wave's, and there is no kernel boundary between steps.
-// An environment whose episode ends stops stepping (rows of the remaining steps carry done = 2 in the
-// scalar record) and is reset by the host-launched reset kernel after the rollout.
+// An environment whose episode ends stops stepping (idle rows from there on) and is reset by the host-launched reset kernel after the rollout.
 // `E` environments per wave (Ctx: L = 64 / E lanes each; policy_kernels.hpp, rollout_greedy_kernel says what that means): E > 1 runs
 // the phase functions written for any L -- the descriptor packer, no held roles, no row image, no register-resident state.
 template <typename ObsT, typename Shape, int FLOW = FLOW_ANY, int E = 1>
@@ -3018,7 +3021,7 @@ __global__ __launch_bounds__(256, 4) void rollout_kernel(const Params *__restric
         c.pivots = Shape::kGreedyHeld;      // (the compiled shapes; the generic kernel has no registers to spare)
         // (E > 1 as one step of the per-step flows: step()'s rule -- a finished environment idles only while a batched restart is pending)
         if (HELDSTATE ? finished != 0 : (c.ei(EI_DONE) != 0 && (E == 1 || !g.per_step || g.freeze_done))) {
-            if (lane_r == 0 && g.scalars) { float *o = g.scalars + c.out * 8; o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+            if (lane_r == 0 && g.scalars) write_idle_row(g.scalars + c.out * 8);
             if (lane_r == 0 && g.idle_steps) g.idle_steps[env_r] += 1;      // a slot of the rollout, not an executed step
             continue;
         }

@@ -601,11 +601,10 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : 4) void rollou
     double *act_cam = a.f + (q.PW + policy_staging_words(p.Nc, p.Nt)), *act_tgt = act_cam + 2 * p.Nc;
     {
         Ctx<ObsT, L> c(p, gk, smem + slot * p.lds_wave_bytes, lane, env, FLOW_GREEDY, shift);
-        // pipelined restarts (Ptrs::pipelined): an environment tagged for this launch's list parity goes live; one that is not
-        // live at entry -- tagged for the other parity, or finished and in the hands of the reset running under this launch --
-        // is left alone: no step and, at the end, no store (the reset may be rewriting its records right now).  Whether it is
-        // live is decided from ONE 4-byte load of the record's `done` word, ahead of everything else: every value the concurrent
-        // reset can leave there (finished, listed, tagged for the other parity) reads "not mine", so the verdict does not depend
+        // pipelined restarts (Ptrs::pipelined): an environment tagged for this launch's list parity goes live; one that is not live at entry -- tagged for
+        // the other parity, or finished and in the hands of the reset running under this launch -- is left alone: no step and, at the end, no store (the reset
+        // may be rewriting its records right now).  Whether it is live is decided from ONE 4-byte load of the record's `done` word, ahead of everything else:
+        // every value the concurrent reset can leave there (finished, listed, tagged for the other parity) reads "not mine", so the verdict does not depend
         // on how far that reset has come, and nothing else of such an environment -- records, masks, agents' memory -- is read.
         int d_entry = 0;
         bool mine = false;
@@ -636,10 +635,9 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : 4) void rollou
             if (lane == 0) c.ei(EI_DONE) = d_entry;                  // (all the step loop reads of it: "not live")
         }
         if (g.pipelined) {
-            if (d_entry == 1 && in_batch && lane == 0 && g.done_count) {      // finished under auto_reset = 0 earlier, never listed: list it, and say so in the record itself
-                const int slot = atomicAdd(g.done_count + parity, 1);
-                g.done_list[(int64_t)parity * g.N + slot] = (int32_t)env;
-                reinterpret_cast<int32_t *>(g.dyn + env * p.DW + p.DF)[p.Nt * TI_STRIDE + EI_DONE] = 3;
+            if (d_entry == kDoneFinished && in_batch && lane == 0 && g.done_count) {      // finished under auto_reset = 0 earlier, never listed: list it, and say so in the record itself
+                list_finished(g.done_count, g.done_list, g.N, parity, env);
+                *done_word_of(p, g.dyn, env) = kDoneListed;
             }
             wave_sync();
             if (mine && lane == 0) c.ei(EI_DONE) = 0;
@@ -702,7 +700,7 @@ __global__ __launch_bounds__(256, E == 1 ? Shape::kGreedyBlocks : 4) void rollou
         GREEDY_STAMP(7);
         if (!active) {                                             // past the end of the batch, or the episode has ended: no agents, no step
             if (in_batch && lane_r == 0) {
-                if (g.scalars) { float *o = g.scalars + c.out * 8; o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+                if (g.scalars) write_idle_row(g.scalars + c.out * 8);
                 if (g.idle_steps) g.idle_steps[env_r] += 1;
             }
             continue;
@@ -834,13 +832,11 @@ void step_greedy_kernel(const Params *__restrict__ pp, const Ptrs g, const Polic
     if (lane == 0) mk[p.MW] = 0u;                                        // (seen_mask reads two words)
     wave_sync();
     if (c.ei(EI_DONE) != 0) {        // finished: waiting for the reset launch (immediate: behind this one; batched: at the interval's end) -- no agents, no step
-        if (lane == 0 && g.scalars) { float *o = g.scalars + c.out * 8; o[0] = 0.f; o[1] = 0.f; o[2] = 2.f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; }
+        if (lane == 0 && g.scalars) write_idle_row(g.scalars + c.out * 8);
         if (lane == 0 && g.idle_steps) g.idle_steps[env] += 1;
-        if (lane == 0 && g.done_count && c.ei(EI_DONE) == 1) {          // finished under auto_reset = 0 earlier: not on the list yet
-            const int parity = c.list_parity();
-            const int slot = atomicAdd(g.done_count + parity, 1);
-            g.done_list[(int64_t)parity * g.N + slot] = (int32_t)env;
-            reinterpret_cast<int32_t *>(g.dyn + env * p.DW + p.DF)[p.Nt * TI_STRIDE + EI_DONE] = 3;
+        if (lane == 0 && g.done_count && c.ei(EI_DONE) == kDoneFinished) {          // finished under auto_reset = 0 earlier: not on the list yet
+            list_finished(g.done_count, g.done_list, g.N, c.list_parity(), env);
+            *done_word_of(p, g.dyn, env) = kDoneListed;
         }
         return;
     }

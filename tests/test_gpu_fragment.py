@@ -1,6 +1,6 @@
 """FrameSkip fragments on the device (Engine.enable_fragment_rows / fragment_rows; csrc/fragment_rows.hpp): the reference fixtures
 through the on-demand form, the fused K-frame flow with the attached launch against K per-step launches of the same Philox streams,
-graph replay, the refusals, the kernels' resources, a generic shape.
+graph replay, the refusals, a generic shape (the kernels' resources: tests/test_kernel_resources.py).
 
 Bars.  done, frames, num_delivered_cargoes and the last-frame info: exact.  Against the FIXTURES, reward sums and means:
 K * 2^-24 * sum|term| (the scalar record is f32) + K * 2^-53 * sum|term| (np.mean / np.sum add pairwise, the launch in frame order);
@@ -8,7 +8,6 @@ observation rows: 1e-9 absolute for f64 (the packer's order of operations differ
 Against the PER-STEP FLOW everything is bit-identical (same operations, same order), f32 rows included; where the issue allows the
 project's f32 bar, 1e-5 * max(1, |ref|), it is kept as the bound."""
 import ctypes
-import json
 import os
 
 import numpy as np
@@ -321,23 +320,6 @@ def test_error_paths_and_detach():
     torch.cuda.synchronize()
     assert int(frames.max()) == -1
     assert eng.last_flow == flow_before                  # the same kernel form as before anything was attached
-
-
-def test_kernel_resources():
-    """lib/kernel_resources.json of this build: every kernel of the parent commit (tests/golden/kernel_resources_fragment_parent.json)
-    keeps its figures; fragment_rows_kernel (obs type x row type) has no scratch and spills nothing."""
-    from mate_amd import build
-    with open(build.RESOURCES) as fh:
-        now = json.load(fh)
-    with open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_fragment_parent.json')) as fh:
-        parent = json.load(fh)
-    assert len(parent) == 281
-    for kernel, figures in parent.items():
-        assert now.get(kernel) == figures, kernel
-    fragment = [k for k in now if 'fragment_rows_kernel' in k]
-    assert len(fragment) == 4 and len(now) == len(parent) + 4
-    for k in fragment:
-        assert now[k]['ScratchSize'] == 0 and now[k]['Dynamic Stack'] == 'False' and now[k]['VGPRs Spill'] == 0 and now[k]['SGPRs Spill'] == 0
 
 
 # ------------------------------------------------------------------ 5. a generic shape, rows that are no multiple of 16 bytes

@@ -1,10 +1,9 @@
 """Target-selection camera actions on the device (Engine.enable_selection / step_selected; csrc/selection_rows.hpp) against the
 reference's HierarchicalCamera wrapper (examples/hrl/wrappers.py): the recorded fixtures replayed with their tapes, the fragment that
 ends an episode, batches that do not fill their tiles, graph replay, the launch order with state and reward rows attached, the team
-observation modes, the error paths, the kernels' resources.  Executor actions: 1e-9 absolute (the project's bar for f64 positions
+observation modes, the error paths (the kernels' resources: tests/test_kernel_resources.py).  Executor actions: 1e-9 absolute (the project's bar for f64 positions
 and angles); masks, rewards, done, integer metrics, the rate (one IEEE division of small integers) and the
 action mask: exact."""
-import json
 import os
 
 import numpy as np
@@ -446,22 +445,3 @@ def test_error_paths():
     eng.step_selected()                               # the engine still steps
     eng.disable_selection()
     assert eng.selection is None
-
-
-def test_kernel_resources_of_the_parent_are_unchanged():
-    """lib/kernel_resources.json of this build: every kernel of the parent commit (tests/golden/kernel_resources_parent.json) and
-    reward_rows_kernel keep their figures; selection_kernel has no scratch."""
-    from mate_amd import build
-    with open(build.RESOURCES) as fh:
-        now = json.load(fh)
-    with open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json')) as fh:
-        parent = json.load(fh)
-    for kernel, figures in parent.items():
-        assert now.get(kernel) == figures, kernel
-    rewards = [k for k in now if 'reward_rows_kernel' in k]
-    selection = [k for k in now if 'selection_kernel' in k]
-    assert len(rewards) == 2 and len(selection) == 2
-    for k in rewards:
-        assert now[k]['VGPRs'] == 48 and now[k]['ScratchSize'] == 0
-    for k in selection:
-        assert now[k]['ScratchSize'] == 0 and now[k]['Dynamic Stack'] == 'False' and now[k]['VGPRs Spill'] == 0 and now[k]['SGPRs Spill'] == 0

@@ -1,7 +1,6 @@
-"""Host side of the shaped reward rows (no GPU): the coefficient tables' order, the shapers' assertions, the C header and its binding,
-and the register / scratch figures of the kernels that existed before the reward launch was added."""
+"""Host side of the shaped reward rows (no GPU): the coefficient tables' order, the shapers' assertions, the C header and its binding.
+(The kernels' register / scratch figures: tests/test_kernel_resources.py.)"""
 import ctypes
-import json
 import os
 import re
 
@@ -61,23 +60,3 @@ def test_header_declares_the_entry_point_and_the_binding_matches():
         handle = _native.load()
         assert len(handle.mate_engine_enable_reward_rows.argtypes) == 2
         assert handle.mate_engine_enable_reward_rows(None, None) == -1         # MATE_EINVAL: null engine
-
-
-def test_kernels_of_the_parent_commit_keep_their_resources():
-    """The reward launch is a kernel of its own: registers, scratch and occupancy of every kernel that existed before it are what
-    they were (tests/golden/kernel_resources_parent.json: the compiler's figures for the parent commit's build), and the new kernel
-    needs no private scratch."""
-    path = os.path.join(ROOT, 'mate_amd', 'lib', 'kernel_resources.json')
-    if not os.path.exists(path):
-        pytest.fail('mate_amd/lib/kernel_resources.json is missing: build the engine (python -m mate_amd.build --force)')
-    with open(path) as fh:
-        now = json.load(fh)
-    with open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json')) as fh:
-        parent = json.load(fh)
-    assert len(parent) > 200
-    changed = {name: (figures, now.get(name)) for name, figures in parent.items() if now.get(name) != figures}
-    assert not changed, changed
-    new = {name: figures for name, figures in now.items() if 'reward_rows_kernel' in name}
-    assert len(new) == 2      # <float>, <double>
-    for name, figures in new.items():
-        assert figures['ScratchSize'] == 0 and figures['Dynamic Stack'] == 'False' and figures['VGPRs Spill'] == 0, (name, figures)
