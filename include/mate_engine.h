@@ -85,7 +85,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -509,7 +509,7 @@ int mate_engine_step_selected(mate_engine *engine, const mate_step_io *io, const
  * allocation, no synchronisation, identical arguments at every call: capturable under mate_engine_device_tick.  Pipelined restarts return
  * MATE_ESTATE while attached.  No other call enqueues it.  A fused launch restarts finished episodes behind the launch WITHOUT packing their first
  * observation into caller buffers: a restarted environment hands the learner its terminal row, done set, for one fragment, as FrameSkip does before
- * the trainer's reset(), and its next action is chosen on that row.
+ * the trainer's reset(), and its next action is chosen on that row -- unless mate_engine_enable_first_rows (below) is on.
  * mate_engine_fragment_rows: the on-demand form over any caller buffers (`rows`: camera_obs_dev or target_obs_dev of `team`, scalars_dev, masks_dev;
  * `frames` = K >= 1); uploads its tables (waits for the handle's launches).  frames = 1 over the per-step buffers gives the transformed reset() rows.
  * MATE_EINVAL: an unknown team, out_dtype or reduction, a camera team in a scenario without cameras, shaped rows without coefficients, a partial
@@ -530,6 +530,35 @@ typedef struct mate_fragment_rows {
 int mate_engine_enable_fragment_rows(mate_engine *engine, const mate_fragment_rows *config);
 int mate_engine_fragment_coefficients(mate_engine *engine, double **coefficients_dev, int32_t *count);
 int mate_engine_fragment_rows(mate_engine *engine, const mate_fragment_rows *config, const mate_step_io *rows, int32_t frames, void *stream);
+
+/* First rows of restarted episodes, for the attached fragment rows (opt-in; off, nothing above changes): the row every example trainer of the reference
+ * gets from env.reset() once an episode has ended, and the per-step flows of this engine hand over in the call that restarts.  No kernel of its own and no
+ * stepping kernel involved: the restart launch mate_engine_rollout_versus_greedy enqueues anyway (placement, occlusion tables, FIRST VIEW) already computes and
+ * packs that row -- it now gets `rows_dev` as the attached team's observation pointer and `scalars_dev` as its scalar record -- and two more launches of the
+ * fragment kernel with one frame move it into place.  While on, every mate_engine_rollout_versus_greedy for the attached team also enqueues
+ *   behind the fragment launch: a memset node, every word of scalars_dev = 2.0f (no environment claims a restart this call did not make);
+ *   its restart launch (immediate, or the interval's k-th under auto_reset = k > 1) with the two pointers: same episodes, records, masks and draws;
+ *   behind that restart and ahead of the reward snapshot launch, only where the call enqueues the restart: obs_dev -> final_obs_dev (a plain copy; if set),
+ *   then rows_dev -> obs_dev through the attached column table -- both only for the environments whose record the restart wrote.
+ * After such a call, for an environment the call restarted (scalars_dev[env][2] != 2.0):
+ *   obs_dev[env]        the new episode's first row through the fragment's transform: the per-step flows' row of the restarting call, bit for bit;
+ *   final_obs_dev[env]  what obs_dev[env] would have shown without the feature: the terminal row, or, under a batched interval, the row it kept while
+ *                       idling -- also where the environment ran no frame in this fragment (frames = 0: its obs_dev row, otherwise left unwritten, is replaced);
+ *   done, frames, rewards, info, shaped: unchanged.  scalars_dev[env] is otherwise the restart's own record (done 0, the first view's coverage rates).
+ * For every other environment obs_dev[env] is as without the feature and final_obs_dev[env] is untouched.  No allocation, no synchronisation, identical
+ * arguments at every call: capturable under mate_engine_device_tick (the immediate restart is enqueued at every call, idle almost always, and so are the
+ * two launches behind it).  A restart that closes an interval because the caller changed auto_reset or the flow (at the head of a LATER call, or in
+ * mate_engine_device_tick) delivers no first rows: that call's own frames overwrite the rows.
+ * A and D are the attached team's; the three buffers are caller-owned and distinct from obs_dev.  NULL `config` detaches; so does detaching the fragment rows,
+ * or attaching them again for the other team or without obs_dev.
+ * MATE_ESTATE: no fragment rows attached, or attached without obs_dev.  MATE_EINVAL: rows_dev or scalars_dev null or not 16-byte aligned, final_obs_dev not
+ * aligned to its element, two of the buffers the same. */
+typedef struct mate_first_rows {
+    void  *rows_dev;       /* [N][A][D] obs_dtype: the learner team's PLAIN first rows (working buffer, caller-owned) */
+    float *scalars_dev;    /* [N][8], 16-byte aligned: column 2 reads 2.0 unless the last attached call restarted the environment */
+    void  *final_obs_dev;  /* [N][A][D] obs_dtype or NULL: the row obs_dev held before the first row replaced it */
+} mate_first_rows;
+int mate_engine_enable_first_rows(mate_engine *engine, const mate_first_rows *config);   /* NULL detaches */
 
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,

@@ -7,7 +7,7 @@ module raises, and every engine call that returns a non-zero status raises
 import ctypes
 import os
 
-__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'MateRewardRows', 'MateFragmentRows', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
+__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'MateRewardRows', 'MateFragmentRows', 'MateFirstRows', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
 
 LIB_PATH = os.environ.get('MATE_ENGINE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libmate_engine.so')
 
@@ -17,7 +17,7 @@ EXPORTED_SYMBOLS = (
     'mate_engine_rollout_random', 'mate_engine_policy_enable', 'mate_engine_step_greedy', 'mate_engine_step_versus_greedy', 'mate_engine_rollout_greedy', 'mate_engine_rollout_versus_greedy', 'mate_engine_policy_actions',
     'mate_engine_observe', 'mate_engine_export_state', 'mate_engine_import_state', 'mate_engine_enable_state_rows', 'mate_engine_state_rows', 'mate_engine_enable_reward_rows', 'mate_engine_lut_read',
     'mate_engine_enable_selection', 'mate_engine_disable_selection', 'mate_engine_selection_actions', 'mate_engine_step_selected',
-    'mate_engine_enable_fragment_rows', 'mate_engine_fragment_coefficients', 'mate_engine_fragment_rows',
+    'mate_engine_enable_fragment_rows', 'mate_engine_fragment_coefficients', 'mate_engine_fragment_rows', 'mate_engine_enable_first_rows',
     'mate_engine_block_alloc', 'mate_engine_block_free', 'mate_engine_block_probe', 'mate_engine_set_store_form',
     'mate_engine_memory_hold', 'mate_engine_memory_release', 'mate_engine_hbm_probe', 'mate_engine_set_sub_wave',
     'mate_engine_lut_write', 'mate_engine_enable_outer_boundary', 'mate_engine_lut_read_outer', 'mate_engine_lut_write_outer', 'mate_engine_soft_coverage', 'mate_engine_rebuild_luts', 'mate_engine_idle_steps', 'mate_engine_kernel_time', 'mate_engine_last_flow',
@@ -94,6 +94,11 @@ class MateFragmentRows(ctypes.Structure):
     ]
 
 
+class MateFirstRows(ctypes.Structure):
+    """mate_first_rows: first rows of restarted episodes behind the attached fragment rows (mate_engine_enable_first_rows)."""
+    _fields_ = [('rows_dev', ctypes.c_void_p), ('scalars_dev', ctypes.c_void_p), ('final_obs_dev', ctypes.c_void_p)]
+
+
 lib = None
 
 
@@ -147,6 +152,7 @@ def load():
     handle.mate_engine_enable_fragment_rows.argtypes = [P, ctypes.POINTER(MateFragmentRows)]
     handle.mate_engine_fragment_coefficients.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(I32)]
     handle.mate_engine_fragment_rows.argtypes = [P, ctypes.POINTER(MateFragmentRows), ctypes.POINTER(MateStepIO), I32, P]
+    handle.mate_engine_enable_first_rows.argtypes = [P, ctypes.POINTER(MateFirstRows)]
     handle.mate_engine_lut_read.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_lut_read_outer.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
     handle.mate_engine_enable_outer_boundary.argtypes = [P, ctypes.POINTER(I32)]

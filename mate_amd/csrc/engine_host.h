@@ -62,6 +62,12 @@ struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, ro
     double *d_coef = nullptr, *d_coef_demand = nullptr;    // [10] each
     void *d_columns = nullptr, *d_columns_demand = nullptr;      // [max(Dc, Dt)] FragmentColumn<double>-sized entries each
 };
+struct FirstRows {       // mate_engine_enable_first_rows: the caller's buffers; lives and dies with the fragment rows it completes (team, A, D, obs and column table are theirs)
+    bool on = false;
+    void *rows = nullptr;                        // [N][A][D] obs_dtype: the restart launch packs the restarted environments' PLAIN first rows here
+    float *scalars = nullptr;                    // [N][8]: 2.0f everywhere behind the fragment launch, then the restart's own record (column 2 = 0) where it restarted
+    void *final_obs = nullptr;                   // [N][A][D] obs_dtype or null: what the fragment's obs held before the first row replaced it
+};
 struct mate_engine {
     Switches sw{};
     hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
@@ -106,7 +112,7 @@ struct mate_engine {
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
-    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment;      // what is attached around the stepping launches (plan_attached)
+    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -206,12 +212,17 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
-//   6              the restart epilogue, a reset or an import; with reward rows the snapshot-only launch    attached_behind_restart
+//   5b first_rows  a memset node: every record of the first-row scalars reads 2.0f, "not restarted"          attached_behind_step
+//   6              the restart epilogue, a reset or an import (first_rows: the fused call's own restart      restart_finished
+//                  stores the learner team's plain first rows and its record into the first-row buffers)
+//   6b first_rows  behind THAT restart only: fragment_rows_kernel, K = 1, twice over the restart's records   attached_behind_restart
+//                  -- obs -> final_obs (plain copy; where asked for), then first rows -> obs (column table)
+//   6c             with reward rows the snapshot-only launch                                                attached_behind_restart
 //   7 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
 //   8 state        state_rows_kernel, last                                                                  attached_last
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
-    bool execute = false, reward = false, observe = false, fragment = false, action_mask = false, state = false;
+    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, action_mask = false, state = false;
     Tiles soft_coverage, reward_rows, selection, fragment_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
 };
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
@@ -232,6 +243,7 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.action_mask = e->selection.on && e->selection.args.action_mask && !e->selection.masks_stale;
     pl.reward = e->reward.on;
     pl.fragment = e->fragment.on && fused_team == e->fragment.args.team;
+    pl.first_rows = pl.fragment && e->first.on;
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
     pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};

@@ -729,7 +729,9 @@ static int attached_ahead_of_step(mate_engine *e, bool selected, hipStream_t str
     const AttachedPlan pl = plan_attached(e, selected);
     return pl.execute ? launch_selection(e, pl, SELECTION_EXECUTE, nullptr, stream) : MATE_OK;
 }
-// 3, 4, 5: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers), the fragment of all of them
+// 3, 4, 5, 5b: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers), the fragment of all
+// of them, and, with first rows, their scalar records back to "not restarted" (2.0f in every word: only column 2 is read, so no template buffer) -- on EVERY such call, so that no
+// environment claims a restart this call did not make
 static int attached_behind_step(mate_engine *e, bool selected, const mate_step_io *io, int frames, hipStream_t stream, int fused_team = -1) {
     const AttachedPlan pl = plan_attached(e, selected, fused_team);
     const size_t last = (size_t)(frames - 1) * (size_t)e->N;
@@ -742,13 +744,31 @@ static int attached_behind_step(mate_engine *e, bool selected, const mate_step_i
         FragmentArgs a = e->fragment.args;
         a.scalars = io->scalars_dev; a.masks = io->masks_dev; a.K = frames;
         a.rows = a.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev;
-        return launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream);
+        const int rc = launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream);
+        if (rc != MATE_OK) return rc;
     }
+    if (pl.first_rows) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->first.scalars), 0x40000000 /* 2.0f */, 8 * (size_t)e->N, stream));
     return MATE_OK;
 }
-// 6: behind a restart launch, a reset or an import -- the goals and episodes the next step's sparse_delivery is measured against
-static int attached_behind_restart(mate_engine *e, hipStream_t stream) {
-    const AttachedPlan pl = plan_attached(e, false);
+// One K = 1 launch of the fragment kernel over the first-row records: the rows of `src` through `columns` into `dst`, for exactly the environments whose record the restart
+// launch has just written (column 2 = 0; everywhere else the memset's 2.0f: "no live frame", row not written).  No other output.
+static int launch_first_rows(mate_engine *e, const Tiles &t, const void *src, void *dst, const void *columns, hipStream_t stream) {
+    FragmentArgs a = e->fragment.args;
+    a.scalars = e->first.scalars; a.masks = nullptr; a.rows = src; a.obs = dst; a.columns = columns; a.K = 1;
+    a.rewards = a.info = nullptr; a.done = nullptr; a.frames = nullptr; a.shaped = nullptr;
+    return launch_fragment_rows(e, t, a, e->fragment.f64, stream);
+}
+// 6b, 6c: behind a restart launch, a reset or an import.  6b (`fused_team`: the restart is the one mate_engine_rollout_versus_greedy for that team has just enqueued, -1: any
+// other) -- the restarted environments' fragment row moves to final_obs where asked for, then their first row goes through the fragment's transform into its place.
+// 6c -- the goals and episodes the next step's sparse_delivery is measured against
+static int attached_behind_restart(mate_engine *e, hipStream_t stream, int fused_team = -1) {
+    const AttachedPlan pl = plan_attached(e, false, fused_team);
+    if (pl.first_rows) {
+        void *const obs = e->fragment.args.obs;
+        if (e->first.final_obs) { const int rc = launch_first_rows(e, pl.fragment_rows, obs, e->first.final_obs, nullptr, stream); if (rc != MATE_OK) return rc; }
+        const int rc = launch_first_rows(e, pl.fragment_rows, e->first.rows, obs, e->fragment.args.columns, stream);
+        if (rc != MATE_OK) return rc;
+    }
     return pl.reward ? launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream) : MATE_OK;
 }
 // 7, 8: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
@@ -933,14 +953,32 @@ static int fragment_args_of(mate_engine *e, const mate_fragment_rows *cfg, doubl
 
 extern "C" int mate_engine_enable_fragment_rows(mate_engine *e, const mate_fragment_rows *cfg) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    if (!cfg) { e->fragment.on = false; return MATE_OK; }
+    if (!cfg) { e->fragment.on = false; e->first = FirstRows{}; return MATE_OK; }
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_fragment_rows called before reset() (or import_state)");
     FragmentRows &f = e->fragment;
     FragmentArgs a{};
     bool f64 = false, masks = false;
     { const int rc = fragment_args_of(e, cfg, &f.d_coef, &f.d_columns, &a, &f64, &masks); if (rc != MATE_OK) return rc; }
+    if (!f.on || a.team != f.args.team || !a.obs) e->first = FirstRows{};      // (first rows complete the rows of ONE team's fragment: another team, or no rows, detaches them)
     f.args = a; f.f64 = f64; f.need_masks = masks;
     f.on = true;
+    return MATE_OK;
+}
+
+// First rows of restarted episodes: see include/mate_engine.h.  Host state only -- the launches read it when they are enqueued.
+extern "C" int mate_engine_enable_first_rows(mate_engine *e, const mate_first_rows *cfg) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!cfg) { e->first = FirstRows{}; return MATE_OK; }
+    if (!e->fragment.on || !e->fragment.args.obs)
+        return fail(MATE_ESTATE, "enable_first_rows: fragment rows with obs_dev must be attached first (mate_engine_enable_fragment_rows)");
+    auto misaligned = [](const void *ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; };
+    if (!cfg->rows_dev || !cfg->scalars_dev || misaligned(cfg->rows_dev, 15u) || misaligned(cfg->scalars_dev, 15u))
+        return fail(MATE_EINVAL, "first rows: rows_dev and scalars_dev must be there and 16-byte aligned");
+    if (misaligned(cfg->final_obs_dev, e->p.obs_f64 ? 7u : 3u)) return fail(MATE_EINVAL, "first rows: final_obs_dev is not aligned to its element size");
+    if (cfg->rows_dev == e->fragment.args.obs || cfg->final_obs_dev == e->fragment.args.obs || cfg->final_obs_dev == cfg->rows_dev)
+        return fail(MATE_EINVAL, "first rows: rows_dev, final_obs_dev and the fragment's obs_dev must be three buffers");
+    e->first.rows = cfg->rows_dev; e->first.scalars = cfg->scalars_dev; e->first.final_obs = cfg->final_obs_dev;
+    e->first.on = true;
     return MATE_OK;
 }
 
@@ -1034,6 +1072,7 @@ extern "C" int mate_engine_snapshot_episode_stats(mate_engine *e, double *dst_de
 // A batched-reset interval (auto_reset = k > 1) is in progress and the caller changes the mode: restart what has finished
 // so far now, by flag, and forget the lists.
 // `auto_reset`, `flow_tag`: of the call that is about to run -- an interval belongs to one k and one flow (kStepFlow / kRolloutFlow).
+// It delivers NO first rows (mate_engine_enable_first_rows): it runs at the head of a later call, whose own frames then overwrite the rows.
 constexpr int kStepFlow = 0x10000, kRolloutFlow = 0x20000;
 static int flush_pending(mate_engine *e, int auto_reset, int flow_tag, hipStream_t stream) {
     if (e->steps_since_reset == 0 || (auto_reset > 1 ? (auto_reset | flow_tag) : auto_reset) == e->pending_interval) return MATE_OK;
@@ -1166,6 +1205,7 @@ struct Restart {
     bool split_immediate, split_batched;   // launch_reset's split_done: a list-driven restart as placement / tables / view launches
     uint32_t frames;             // steps per launch: the restart advances a device-resident counter by frames * auto_reset (0: the flow has none)
     int flow_tag;                // kStepFlow / kRolloutFlow
+    int fused_team = -1;         // the call is mate_engine_rollout_versus_greedy for this team (plan_attached: its restart may carry the first rows)
 };
 static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, hipStream_t stream) {
     if (auto_reset < 1) return MATE_OK;
@@ -1177,12 +1217,16 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
     e->steps_since_reset = 0; e->pending_interval = 0;
     Ptrs r = restart_ptrs(e, how.io);
     if (!how.keep_actions) { r.cam_act = r.tgt_act = nullptr; r.act_f64 = 0; r.act_discrete = 0; }
+    if (plan_attached(e, false, how.fused_team).first_rows) {      // (the view launch computes the first view and packs it anyway: now it also stores -- the learner team's rows, its own record)
+        (e->fragment.args.team == MATE_TEAM_CAMERA ? r.cam_obs : r.tgt_obs) = e->first.rows;
+        r.scalars = e->first.scalars;
+    }
     r.tick_advance = how.frames * (uint32_t)auto_reset;
     const int kind = batched ? how.kind_batched : RESET_DONE;
     const int rc = launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate);
     if (rc != MATE_OK) return rc;
     if (kind == RESET_DONE && !e->dev_tick) e->parity ^= 1;      // (the list is consumed: the next launches append to the other one)
-    return attached_behind_restart(e, stream);      // (new episodes: their goals are what the next step's sparse_delivery compares with)
+    return attached_behind_restart(e, stream, how.fused_team);      // (new episodes: their first rows; their goals are what the next step's sparse_delivery compares with)
 }
 
 // The per-step launch and what follows it, behind the state checks of the call: launch_step's, or those step_with_policies makes ahead of its agents' launch
@@ -1483,7 +1527,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     const bool pipelined = auto_reset < 0;          // MATE_RESET_PIPELINED (-1), or -m: one restart launch behind every m-th rollout launch
     const int full = PH_PLACE | PH_LUT | PH_VIEW;
     const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
-                                     : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow}, auto_reset == 1 || pipelined, true, team_caller >= 0};
+                                     : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow, team_caller}, auto_reset == 1 || pipelined, true, team_caller >= 0};
     if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
     if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }

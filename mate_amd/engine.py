@@ -197,6 +197,7 @@ class Engine:
         # while fragment rows are attached (enable_fragment_rows): what FrameSkip hands the learner per K-frame launch
         self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
         self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
+        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None      # (enable_fragment_rows(first_rows=True))
         self.fragment_frame_skip, self._fragment_masks = 0, False
 
     def close(self):
@@ -753,7 +754,8 @@ class Engine:
                 'shaped': torch.zeros((N, A), dtype=dtype, device=self.device) if shaped else None,
             }
 
-    def enable_fragment_rows(self, team, frame_skip, shaping=None, relative_coordinates=False, rescaled_observation=False, dtype=torch.float64):
+    def enable_fragment_rows(self, team, frame_skip, shaping=None, relative_coordinates=False, rescaled_observation=False, dtype=torch.float64,
+                             first_rows=False, final_obs=False):
         """Attach the tail of the example trainers' wrapper chain -- RelativeCoordinates -> RescaledObservation ->
         RepeatedRewardIndividualDone -> [AuxiliaryCameraRewards | AuxiliaryTargetRewards] -> FrameSkip(frame_skip) -- to the fused
         K-frame launch: from now on rollout_versus_greedy(team, ...) (and a Stepper(versus=team, frame_skip=K) built afterwards)
@@ -770,9 +772,20 @@ class Engine:
         An environment that ran no frame (idle under a batched restart) keeps its fragment_obs row; its other rows are 0.  A fused launch
         restarts finished episodes behind the launch without packing their first observation: a restarted environment hands the
         learner its terminal row, done set, for one fragment (as FrameSkip does before the trainer's reset()), and the next action
-        is chosen on that row.  Call after the first reset().  Returns fragment_obs."""
+        is chosen on that row -- unless `first_rows` is on (mate_engine_enable_first_rows).  Then, after every such call, for the
+        environments it restarted (fragment_restarted [N] bool = fragment_first_scalars[:, 2] != 2): their fragment_obs row is the new
+        episode's FIRST row through the same transform -- env.reset()'s row of the reference's trainers, what the per-step flows hand
+        over in the restarting call, bit for bit -- also where the environment ran no frame in this fragment; with `final_obs`,
+        fragment_final_obs [N, A, D] holds for them what fragment_obs would have shown without the feature (the terminal row, or the row
+        kept while idling under a batched interval).  done, frames, rewards, info and shaped are unchanged, and so is every row of an
+        environment that was not restarted (its fragment_final_obs row is untouched).  fragment_first_rows [N, A, D] is the working
+        buffer of the plain first rows, fragment_first_scalars [N, 8] f32 the restart's own records (2.0 where nothing restarted).
+        Costs one memset node and one or two K = 1 launches of the fragment kernel per call; no stepping kernel changes.  A restart that
+        closes an interval because auto_reset or the flow changed (at the head of a later call) delivers no first rows.
+        Call after the first reset().  Returns fragment_obs."""
         frame_skip = int(frame_skip)
         assert frame_skip >= 1
+        assert first_rows or not final_obs, 'final_obs belongs to first_rows = True'
         out = self._fragment_outputs(team, shaping is not None, dtype)
         cfg, keep, masks = self._fragment_config(team, shaping, relative_coordinates, rescaled_observation, dtype, out)
         torch.cuda.current_stream(self.device).synchronize()
@@ -783,23 +796,46 @@ class Engine:
         self.fragment_obs, self.fragment_rewards, self.fragment_done = out['obs'], out['rewards'], out['done']
         self.fragment_frames, self.fragment_info, self.fragment_shaped = out['frames'], out['info'], out['shaped']
         self.fragment_team, self.fragment_frame_skip, self._fragment_masks = cfg.team, frame_skip, masks
+        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None
+        check(self.lib.mate_engine_enable_first_rows(self._h, None))
+        if first_rows:
+            from mate_amd._native import MateFirstRows
+            with torch.cuda.device(self.device):
+                rows, scalars = torch.zeros_like(out['obs']), torch.full((self.num_envs, 8), 2.0, dtype=torch.float32, device=self.device)
+                final = torch.zeros_like(out['obs']) if final_obs else None
+            first = MateFirstRows(rows.data_ptr(), scalars.data_ptr(), final.data_ptr() if final_obs else None)
+            torch.cuda.current_stream(self.device).synchronize()
+            check(self.lib.mate_engine_enable_first_rows(self._h, ctypes.byref(first)))
+            self.fragment_first_rows, self.fragment_first_scalars, self.fragment_final_obs = rows, scalars, final
         self.reserve_rollout(frame_skip, want_masks=masks)
         return self.fragment_obs
 
     def disable_fragment_rows(self):
-        """Detach the fragment launch: rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
+        """Detach the fragment launch (and the first rows with it): rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
         check(self.lib.mate_engine_enable_fragment_rows(self._h, None))
         self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
         self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
+        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None
         self.fragment_frame_skip, self._fragment_masks = 0, False
+
+    @property
+    def fragment_restarted(self):
+        """[N] bool: the environments the last rollout_versus_greedy of the attached team restarted -- whose fragment_obs row is the new
+        episode's first row (enable_fragment_rows(first_rows=True)); None while first rows are off.  A new tensor at every read."""
+        if self.fragment_first_scalars is None:
+            return None
+        return self.fragment_first_scalars[:, 2] != 2
 
     @property
     def fragment(self):
         """The fragment tensors by name (None while detached)."""
         if self.fragment_team is None:
             return None
-        return {'obs': self.fragment_obs, 'rewards': self.fragment_rewards, 'done': self.fragment_done, 'frames': self.fragment_frames,
-                'info': self.fragment_info, 'shaped': self.fragment_shaped, 'coefficients': self.fragment_coefficients}
+        out = {'obs': self.fragment_obs, 'rewards': self.fragment_rewards, 'done': self.fragment_done, 'frames': self.fragment_frames,
+               'info': self.fragment_info, 'shaped': self.fragment_shaped, 'coefficients': self.fragment_coefficients}
+        if self.fragment_first_scalars is not None:      # (first rows on: the keys exist only then)
+            out.update(first_rows=self.fragment_first_rows, first_scalars=self.fragment_first_scalars, final_obs=self.fragment_final_obs)
+        return out
 
     def fragment_rows(self, team, rows, scalars, masks=None, shaping=None, relative_coordinates=False, rescaled_observation=False,
                       dtype=torch.float64, out=None):
@@ -1187,7 +1223,8 @@ class Stepper:
     target_reward_terms = property(lambda self: self.eng.target_reward_terms)
     reward_coefficients = property(lambda self: self.eng.reward_coefficients)
     # The engine's fragment tensors (Engine.enable_fragment_rows BEFORE the stepper is built: versus = that team, frame_skip = K): a dict
-    # {'obs', 'rewards', 'done', 'frames', 'info', 'shaped', 'coefficients'}, rewritten by every K-frame launch and every replay.
+    # {'obs', 'rewards', 'done', 'frames', 'info', 'shaped', 'coefficients'} (+ 'first_rows', 'first_scalars', 'final_obs' with first_rows=True: the memset
+    # node and the two launches behind the restart are captured with the rest), rewritten by every K-frame launch and every replay.
     fragment = property(lambda self: self.eng.fragment)
 
     def close(self):

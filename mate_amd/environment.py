@@ -667,21 +667,28 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     `rescaled_observation` then go to the fragment launch's column table instead of the packer (the fused launch packs plain rows),
     the learner's `*_reward_shaping` to its coefficients (the four terms that need every frame's state are refused).  reset() returns the
     learner's transformed rows [num_envs, agents, D]; step_fragment(joint_action) returns (obs, rewards [num_envs, agents], done
-    [num_envs], info).  LIMIT: a fused launch restarts finished episodes behind the launch without packing their first observation into
-    caller buffers, so a restarted environment hands the learner its TERMINAL row with done set for one fragment -- as FrameSkip does
-    before the trainer calls reset() -- and its next action is chosen on that row.  Without `frame_skip` nothing about the class changes."""
+    [num_envs], info).  The row a restarted environment shows: by default a fused launch restarts finished episodes behind the launch
+    without packing their first observation into caller buffers, so a restarted environment hands the learner its TERMINAL row with done
+    set for one fragment -- as FrameSkip does before the trainer calls reset() -- and its next action is chosen on that row.  With
+    `first_rows` = True (Engine.enable_fragment_rows(first_rows=True, final_obs=True)) the returned row of an environment the call
+    restarted is instead the new episode's FIRST row, through the same transform -- the row env.reset() hands the reference's trainers --
+    and `info` additionally holds 'restarted' [num_envs] bool and 'final_observation' [num_envs, agents, D], whose rows hold, for the
+    restarted environments only, what the returned row would have been without it (the terminal row); rewards, done and the other
+    info keys do not change.  Without `frame_skip` nothing about the class changes."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
-                 learner=None, **kwargs):
+                 learner=None, first_rows=False, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._fragment = fragment_arguments(self.config, frame_skip, learner, camera_reward_shaping, target_reward_shaping, enhanced_observation,
                                             shared_field_of_view, camera_selection)
+        assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
-            self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype)
+            self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype,
+                                  first_rows=bool(first_rows))
             relative_coordinates = rescaled_observation = False
             camera_reward_shaping = target_reward_shaping = None
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
@@ -766,7 +773,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         spec, eng = self._fragment, self.engine
         transform = {'relative_coordinates': spec['relative_coordinates'], 'rescaled_observation': spec['rescaled_observation']}
         if eng.fragment_team is None:
-            eng.enable_fragment_rows(spec['learner'], spec['frame_skip'], shaping=spec['shaping'], dtype=spec['dtype'], **transform)
+            eng.enable_fragment_rows(spec['learner'], spec['frame_skip'], shaping=spec['shaping'], dtype=spec['dtype'], first_rows=spec['first_rows'],
+                                     final_obs=spec['first_rows'], **transform)
         rows = eng.camera_obs if spec['learner'] == 'camera' else eng.target_obs
         if '_live' not in spec:      # (a scalar record that says "this frame ran": the step's own may be older than the reset)
             spec['_live'] = torch.zeros((self.num_envs, 8), dtype=torch.float32, device=self.device)
@@ -782,7 +790,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         one launch, reduced by the fragment launch.  Returns (obs [num_envs, agents, D], rewards [num_envs, agents], done [num_envs],
         info): `rewards` is the shaped sum with `*_reward_shaping`, else the learner's team reward repeated per agent
         (RepeatedRewardIndividualDone); `info` holds FrameSkip's reduced keys ('sum': the raw and normalised rewards; 'mean': the two
-        coverage rates; 'last': mean_transport_rate, num_delivered_cargoes) and 'frames' [num_envs], the frames that ran.  The tensors are
+        coverage rates; 'last': mean_transport_rate, num_delivered_cargoes) and 'frames' [num_envs], the frames that ran; built with
+        first_rows=True also 'restarted' [num_envs] bool and 'final_observation' [num_envs, agents, D].  The tensors are
         the engine's own, rewritten by the next call.  See the class docstring for the row a restarted environment shows."""
         assert self._fragment, 'built without frame_skip = K, learner = ...'
         spec, eng = self._fragment, self.engine
@@ -797,6 +806,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         info = {'raw_reward': sums[:, 0 if camera else 1], 'normalized_raw_reward': sums[:, 3 if camera else 2],
                 'coverage_rate': means[:, 0], 'real_coverage_rate': means[:, 1], 'mean_transport_rate': means[:, 2],
                 'num_delivered_cargoes': means[:, 3], 'frames': eng.fragment_frames}
+        if spec['first_rows']:
+            info.update(restarted=eng.fragment_restarted, final_observation=eng.fragment_final_obs)
         return eng.fragment_obs, rewards, eng.fragment_done > 0, info
 
     def _result(self):

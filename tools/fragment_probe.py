@@ -6,8 +6,10 @@ fragment of
       points that predate the launch only, its outputs are its own tensors and its column table is host-side NumPy (mate_amd.spaces),
   (b) rollout_versus_greedy + the attached fragment launch,
   (c) K x step_versus_greedy with the packer's fused transform and accumulating reward rows -- the only way to shaped FrameSkip before,
+  (d) (b) with the first rows of restarted episodes on (enable_fragment_rows(first_rows=True, final_obs=True)): one memset node and two
+      one-frame launches of the fragment kernel more per fragment; (d) - (b) is the feature's cost, (b) itself is the feature off,
 on MATE-4v8-9 (camera learner, {'coverage_rate': 1.0} 'mean', K = 5) and MATE-2v4-0 (target learner, unshaped, K = 10), each at 4096 and
-16 384 environments, all three in one process, interleaved; `--series` repeated series of `--rounds` timed blocks give the run-to-run
+16 384 environments, all four in one process, interleaved; `--series` repeated series of `--rounds` timed blocks give the run-to-run
 spread next to the medians.  Prints the table; `--out` also writes it (profiles/fragment_probe.txt).
 
     python tools/fragment_probe.py --out profiles/fragment_probe.txt
@@ -25,6 +27,7 @@ from mate_amd.config import read_config  # noqa: E402
 from mate_amd.engine import Engine  # noqa: E402
 from mate_amd.spaces import fragment_column_table  # noqa: E402
 
+LEGS = 'abcd'
 WORKLOADS = (('MATE-4v8-9.yaml', 'camera', 5, ({'coverage_rate': 1.0}, 'mean')), ('MATE-2v4-0.yaml', 'target', 10, None))
 
 
@@ -77,8 +80,8 @@ def build(kind, cfg, n, team, K, shaping):
             eng.enable_reward_rows(**{team: shaping}, accumulate=True)
         return eng, eng.make_stepper(*acts, auto_reset=K, graph_steps=2 * K, versus=team), K
     between = None
-    if kind == 'b':
-        eng.enable_fragment_rows(team, K, shaping=shaping, relative_coordinates=True, rescaled_observation=True)
+    if kind in 'bd':
+        eng.enable_fragment_rows(team, K, shaping=shaping, relative_coordinates=True, rescaled_observation=True, first_rows=kind == 'd', final_obs=kind == 'd')
     if kind == 'a':
         table = fragment_column_table(team, eng.num_cameras, eng.num_targets, eng.num_obstacles, True, True)
         D = eng.camera_obs_dim if team == 'camera' else eng.target_obs_dim
@@ -100,17 +103,17 @@ def main():
     ap.add_argument('--out')
     args = ap.parse_args()
     lines = ['graph-replayed, us per fragment: median over %d series x %d blocks of %d fragments [min .. max of the series medians]' % (args.series, args.rounds, args.fragments),
-             '| scenario | learner | K | envs | (a) fused + torch reduction | (b) fused + fragment launch | (c) K per-step launches | (a) - (b) | (c) / (b) |', '|---|---|---|---|---|---|---|---|---|']
+             '| scenario | learner | K | envs | (a) fused + torch reduction | (b) fused + fragment launch | (c) K per-step launches | (d) (b) + first rows | (a) - (b) | (c) / (b) | (d) - (b) |', '|---|---|---|---|---|---|---|---|---|---|---|']
     for config, team, K, shaping in WORKLOADS:
         cfg = read_config(config)
         for n in (4096, 16384):
-            flows = {kind: build(kind, cfg, n, team, K, shaping) for kind in 'abc'}
+            flows = {kind: build(kind, cfg, n, team, K, shaping) for kind in LEGS}
             for eng, stepper, per in flows.values():
                 stepper.run(args.fragments * per)      # warm-up
             torch.cuda.synchronize()
-            medians = {kind: [] for kind in 'abc'}
+            medians = {kind: [] for kind in LEGS}
             for _ in range(args.series):
-                times = {kind: [] for kind in 'abc'}
+                times = {kind: [] for kind in LEGS}
                 for _ in range(args.rounds):
                     for kind, (eng, stepper, per) in flows.items():
                         torch.cuda.synchronize()
@@ -118,11 +121,12 @@ def main():
                         stepper.run(args.fragments * per)
                         torch.cuda.synchronize()
                         times[kind].append((time.perf_counter() - t0) / args.fragments * 1e6)
-                for kind in 'abc':
+                for kind in LEGS:
                     medians[kind].append(statistics.median(times[kind]))
             med = {kind: statistics.median(v) for kind, v in medians.items()}
             cell = lambda kind: '%.2f [%.2f .. %.2f]' % (med[kind], min(medians[kind]), max(medians[kind]))  # noqa: E731
-            lines.append('| %s | %s | %d | %d | %s | %s | %s | %.2f | %.2f |' % (config[:-5], team, K, n, cell('a'), cell('b'), cell('c'), med['a'] - med['b'], med['c'] / med['b']))
+            lines.append('| %s | %s | %d | %d | %s | %s | %s | %s | %.2f | %.2f | %.2f |' % (config[:-5], team, K, n, cell('a'), cell('b'), cell('c'), cell('d'), med['a'] - med['b'], med['c'] / med['b'],
+                                                                                      med['d'] - med['b']))
             for eng, stepper, per in flows.values():
                 stepper.close()
                 eng.close()
