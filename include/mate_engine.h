@@ -85,7 +85,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows, the target opponent) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -315,8 +315,36 @@ int mate_engine_rollout_greedy(mate_engine *engine, const mate_step_io *io, int3
 int mate_engine_rollout_versus_greedy(mate_engine *engine, int32_t team, const mate_step_io *io, int32_t steps,
                                       int32_t auto_reset, void *stream);
 
-/* copies the joint actions of the last step_greedy into caller buffers [N][Nc][2] / [N][Nt][2] f64 (either may be NULL) */
+/* copies the joint actions of the last step_greedy into caller buffers [N][Nc][2] / [N][Nt][2] f64 (either may be NULL): what the step
+ * consumed -- with the Heuristic target opponent (below) the FINAL target actions.  mate_engine_policy_greedy_target_actions: the Greedy
+ * target agents' joint action of the same step, ahead of the drift (the same array while the opponent is Greedy). */
 int mate_engine_policy_actions(mate_engine *engine, double *camera_actions_dev, double *target_actions_dev, void *stream);
+int mate_engine_policy_greedy_target_actions(mate_engine *engine, double *target_actions_dev, void *stream);
+
+/* Which scripted agent plays the TARGET team where the engine plays it (the reference's opponent_agent_factory of
+ * camera configurations under examples/, mate.evaluate's --target-agent):
+ *   MATE_OPPONENT_GREEDY     GreedyTargetAgent (mate/agents/greedy.py:229-365), the default; nothing changes while it is selected
+ *   MATE_OPPONENT_HEURISTIC  HeuristicTargetAgent (mate/agents/heuristic.py:290-337): the Greedy target's action, then a drift away from the
+ *                            incentre of the nearest camera sector the target senses and lies in or near -- reached through the sector's SIGNED
+ *                            angle test, as the reference writes it (:308-311) --, applied where it does not oppose the action (:332-335).
+ *                            The agent draws nothing, remembers nothing and sends nothing of its own: ONE launch (csrc/opponent_rows.hpp) over the
+ *                            Greedy agents' joint action, out of place, into an engine-owned [N][Nt][2] f64 buffer allocated at the first switch.
+ * Needs mate_engine_policy_enable (MATE_ESTATE); may change at any call boundary (waits for the handle's launches; no agent memory to migrate).
+ * While Heuristic is selected:
+ *   - mate_engine_step_greedy, mate_engine_step_versus_greedy(MATE_TEAM_CAMERA) and mate_engine_step_selected take the TWO-launch form with the
+ *     drift launch in it: [executor,] agents' launch, drift launch, stepping launch reading the final buffer, then what follows a step as before.
+ *     The drift launch has identical arguments at every call, allocates nothing and does not synchronise: capturable under
+ *     mate_engine_device_tick, with tapes or Philox draws.  Environments the agents' launch skips (done = 2 under a batched restart) keep
+ *     their Greedy row; a scenario without cameras makes it a copy (bit-identical results to the Greedy opponent).
+ *   - mate_engine_step_versus_greedy(MATE_TEAM_TARGET) and mate_engine_rollout_versus_greedy(MATE_TEAM_TARGET) are unaffected: the caller plays
+ *     the targets.
+ *   - mate_engine_rollout_greedy and mate_engine_rollout_versus_greedy(MATE_TEAM_CAMERA) return MATE_ESTATE: the fused K-frame kernels hold the
+ *     Greedy agents.  (FrameSkip against this opponent is K per-step calls in one graph.)
+ *   - mate_engine_set_obs_mode with a non-plain TARGET team mode returns MATE_EINVAL, and selecting Heuristic under such a mode does: the
+ *     opponents' `sensed` is the flag column of their plain rows.
+ * MATE_EINVAL: an unknown opponent. */
+enum { MATE_OPPONENT_GREEDY = 0, MATE_OPPONENT_HEURISTIC = 1 };
+int mate_engine_set_target_opponent(mate_engine *engine, int32_t opponent);
 
 /* joint_observation() (environment.py:908-983) without advancing the simulation: recomputes
  * the view masks from the current state (see-through draws from io tape or Philox) and packs. */

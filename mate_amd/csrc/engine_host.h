@@ -14,6 +14,7 @@
 #include "reward_rows.hpp"
 #include "fragment_rows.hpp"
 #include "selection_rows.hpp"
+#include "opponent_rows.hpp"
 #include "state_rows.hpp"
 #include "shape_groups.hpp"
 
@@ -55,6 +56,11 @@ struct Selection {       // mate_engine_enable_selection: phase, masks and scala
     SelectionArgs args{};
     double *d_actions = nullptr;
     bool masks_stale = false;                    // a state-only restart (rollout_random's) or import_state ran since the view masks were last written
+};
+struct Opponent {        // mate_engine_set_target_opponent: which scripted agent plays the target team where the engine plays it
+    int kind = MATE_OPPONENT_GREEDY;
+    double *d_final = nullptr;                   // [N][Nt][2] f64, engine-owned, allocated at the first switch to Heuristic: the drift launch's output, the stepping launch's target actions
+    bool drifted = false;                        // the last call with the on-device agents ran the drift launch: d_final is what its step consumed (mate_engine_policy_actions)
 };
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
@@ -112,6 +118,7 @@ struct mate_engine {
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
+    Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -209,6 +216,9 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 // launches" section of mate_engine.hip has one function per position; each reads this plan and launches what it names, with the geometry it carries.
 //   1 execute      selection_kernel, SELECTION_EXECUTE: the camera team's joint action of this frame       attached_ahead_of_step (step_selected)
 //   2              the stepping launch (and, two-launch form, the opponents' agents in front of it)
+//   2a drift       heuristic_drift_kernel between the agents' launch and the stepping launch: the Heuristic   step_with_policies
+//                  target opponents' final joint action (opponent_rows.hpp); two-launch form only, where the
+//                  engine plays the targets (heuristic_targets: a property of the call, like `selected`, not of the plan)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
@@ -223,7 +233,7 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
     bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, fragment_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
+    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
 };
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
 // Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
@@ -237,6 +247,9 @@ static Tiles plan_state_rows(const mate_engine *e, bool f64) {
 static Tiles plan_fragment_rows(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
 // `selected`: the call is mate_engine_step_selected; `fused_team`: the call is mate_engine_rollout_versus_greedy for that team (-1: any other).  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
+// The engine plays the target team of this call (`team_caller`: -1 both teams are the agents, else the caller's) with the Heuristic agent: the call takes the two-launch
+// form with the drift launch in it (one_launch_step), the fused K-frame launches refuse (rollout_with_policies: their kernels hold the Greedy agents)
+static bool heuristic_targets(const mate_engine *e, int team_caller) { return e->opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_TARGET; }
 static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;
@@ -247,6 +260,7 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
     pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
+    if (e->opponent.kind == MATE_OPPONENT_HEURISTIC) pl.drift_rows = pl.reward_rows;      // (launched by the two-launch form where the engine plays the targets: heuristic_targets)
     pl.fragment_rows = plan_fragment_rows(e);
     pl.state_rows = plan_state_rows(e, e->state.f64);
     return pl;

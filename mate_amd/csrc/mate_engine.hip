@@ -63,6 +63,7 @@ static int fail(int code, const char *fmt, ...) {
 #define MATE_SHAPE_GROUP 5
 #include "shape_group.inc"
 #undef MATE_SHAPE_GROUP
+#include "opponent_kernels.inc"
 #endif
 
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
@@ -538,6 +539,8 @@ extern "C" int mate_engine_set_obs_transform(mate_engine *e, int32_t relative, c
 extern "C" int mate_engine_set_obs_mode(mate_engine *e, int32_t camera_mode, int32_t target_mode) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (camera_mode < 0 || camera_mode > 2 || target_mode < 0 || target_mode > 2) return fail(MATE_EINVAL, "observation mode must be 0 (plain), 1 (enhanced) or 2 (shared field of view)");
+    if (target_mode != 0 && e->opponent.kind == MATE_OPPONENT_HEURISTIC)
+        return fail(MATE_EINVAL, "set_obs_mode: the heuristic target opponent (mate_engine_set_target_opponent) senses the cameras of its plain rows: the target team mode must stay 0");
     { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     e->cam_mode = camera_mode; e->tgt_mode = target_mode;
     return apply_obs_tables(e);
@@ -1377,9 +1380,16 @@ static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_st
             e->g.obs_mode == 0 && !e->g.xdesc, team_caller < 0 || (io && (team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev))};
 }
 // step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
-// recorded agent draws, tapes of the step itself, f64 observations
-static bool one_launch_step(const mate_engine *e, const FusedCall &c, const mate_step_io *io, const mate_policy_tape *tape) {
-    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64;
+// recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two)
+static bool one_launch_step(const mate_engine *e, const FusedCall &c, int team_caller, const mate_step_io *io, const mate_policy_tape *tape) {
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller);
+}
+// 2a: between the agents' launch and the stepping launch -- the Heuristic opponents' final joint action from the Greedy one (`freeze_done`: of the agents' launch)
+static int launch_drift(mate_engine *e, const AttachedPlan &pl, int freeze_done, hipStream_t stream) {
+    if (!pl.drift_rows.blocks) return MATE_OK;
+    const DriftArgs a{e->q.tgt_act, e->opponent.d_final, e->g.own_masks, e->q.noise_scale, e->p.bit_range, freeze_done};
+    HIP_TRY(launch_heuristic_drift(pl.drift_rows.blocks, pl.drift_rows.lds, stream, e->d_params, e->g, a));
+    return MATE_OK;
 }
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
@@ -1393,7 +1403,7 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
     if (!selected) { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone; step_selected has made it)
     const FusedCall c = fused_call(e, team_caller, io);
-    if (one_launch_step(e, c, io, tape) && plan_with_policies(e, true, team_caller).fits())
+    if (one_launch_step(e, c, team_caller, io, tape) && plan_with_policies(e, true, team_caller).fits())
         return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true, selected);
     if (!c.reset) return fail(MATE_ESTATE, "step_greedy called before reset() (or import_state)");
     // (works with a device-resident step counter too -- the agents take their tick from the environment record -- so the
@@ -1419,11 +1429,14 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     gp.freeze_done = auto_reset > 1;
     launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
     HIP_TRY(hipGetLastError());
+    const bool drift = heuristic_targets(e, team_caller);      // (the caller plays the targets: no opponent of that team acts)
+    if (drift) { const int rc_ = launch_drift(e, plan_attached(e, selected), gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
+    e->opponent.drifted = drift;
     mate_step_io io2;
     if (io) io2 = *io; else std::memset(&io2, 0, sizeof(io2));
     // the caller's team keeps its own pointer and encoding (f32 / f64 / grid indices); the agents' joint action is f64 pairs
     if (team_caller != 0) { io2.camera_actions_dev = q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
-    if (team_caller != 1) { io2.target_actions_dev = q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
+    if (team_caller != 1) { io2.target_actions_dev = drift ? e->opponent.d_final : q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
     const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
     e->greedy_team_bits = 0;
@@ -1529,6 +1542,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
                                      : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow, team_caller}, auto_reset == 1 || pipelined, true, team_caller >= 0};
     if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
+    if (heuristic_targets(e, team_caller))      // (a per-step call never arrives here with it: one_launch_step)
+        return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the target opponent is the heuristic one (mate_engine_set_target_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
+                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
     if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }
     if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
@@ -1569,6 +1585,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     Timed t;
     { const int rc_ = take_timing_events(e, !e->dev_tick, &t); if (rc_ != MATE_OK) return rc_; }
     e->last_flow = pl.last_flow;
+    e->opponent.drifted = false;      // (the target team's joint action of this launch is in q.tgt_act: the Greedy agents', or the caller's)
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
@@ -1593,8 +1610,33 @@ extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions
     note_stream(e, (hipStream_t)stream);
     if (camera_actions_dev && e->p.Nc > 0)
         HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (target_actions_dev)
-        HIP_TRY(hipMemcpyAsync(target_actions_dev, e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (target_actions_dev)      // what the step consumed: behind a call that ran the drift launch, its output
+        HIP_TRY(hipMemcpyAsync(target_actions_dev, e->opponent.drifted ? e->opponent.d_final : e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MATE_OK;
+}
+extern "C" int mate_engine_policy_greedy_target_actions(mate_engine *e, double *target_actions_dev, void *stream) {
+    if (!e || !e->policy_ready) return fail(MATE_ESTATE, "policies are not enabled");
+    if (!target_actions_dev) return fail(MATE_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    note_stream(e, (hipStream_t)stream);
+    HIP_TRY(hipMemcpyAsync(target_actions_dev, e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MATE_OK;
+}
+
+// Which scripted agent plays the target team where the engine plays it (include/mate_engine.h).  No agent memory differs between the two, so the
+// switch is a flag and, once, the final-action buffer.
+extern "C" int mate_engine_set_target_opponent(mate_engine *e, int32_t opponent) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_target_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "set_target_opponent: call mate_engine_policy_enable() first (the Greedy agents the heuristic opponent builds on, and the engine's own view masks)");
+    if (opponent == MATE_OPPONENT_HEURISTIC && e->tgt_mode != 0)
+        return fail(MATE_EINVAL, "set_target_opponent: the heuristic target opponent senses the cameras of its plain rows, the target team's observation mode is %d (mate_engine_set_obs_mode)", e->tgt_mode);
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the buffer the getters switch between)
+    if (opponent == MATE_OPPONENT_HEURISTIC && !e->opponent.d_final) {
+        const int rc = dev_alloc(e, &e->opponent.d_final, (size_t)e->N * e->p.Nt * 2);
+        if (rc != MATE_OK) return rc;
+    }
+    e->opponent.kind = opponent;
     return MATE_OK;
 }
 

@@ -13,7 +13,7 @@ from mate_amd import _native
 from mate_amd._native import MateConfig, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 
 __all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'encode_selection', 'decode_selection',
-           'SCALAR_NAMES', 'REWARD_REDUCTIONS']
+           'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS']
 
 SCALAR_NAMES = ('camera_team_reward', 'target_team_reward', 'done', 'coverage_rate', 'real_coverage_rate',
                 'mean_transport_rate', 'num_delivered_cargoes', 'normalized_target_team_reward')
@@ -38,6 +38,7 @@ def export_layout(Nc, Nt, No):
     return layout, off
 
 
+TARGET_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* (include/mate_engine.h): the scripted agents that can play the target team
 REWARD_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2, 'max': 3, 'min': 4}      # MATE_REDUCE_* (include/mate_engine.h)
 
 
@@ -186,6 +187,7 @@ class Engine:
         check(self.lib.mate_engine_set_episode_stats(self._h, ctypes.c_void_p(self.episode_stats.data_ptr())))
         self.state_dim = layout.state_dim
         self.state = None                 # [N, state_dim] while state rows are attached (enable_state_rows)
+        self.target_agent = 'greedy'      # the scripted agent of the target team (set_target_opponent)
         # while reward rows are attached (enable_reward_rows): [N, Nc] / [N, Nt] shaped rewards, [N, Nc, 7] / [N, Nt, 10] f64 terms,
         # and the two coefficient tables on the device ({'camera': [7], 'target': [10]} f64)
         self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
@@ -551,9 +553,23 @@ class Engine:
         With graph_steps > 0 the constructor runs `auto_reset` REAL steps before it captures (Stepper.warmup_steps)."""
         return Stepper(self, cam_act, tgt_act, auto_reset, graph_steps, between, versus, frame_skip)
 
-    def enable_policies(self):
-        """Allocate the on-device policy state (call before the reset whose observations the agents act on)."""
+    def enable_policies(self, target_agent='greedy'):
+        """Allocate the on-device policy state (call before the reset whose observations the agents act on).  `target_agent`:
+        the scripted agent that plays the target team where the engine plays it (set_target_opponent)."""
         check(self.lib.mate_engine_policy_enable(self._h))
+        if target_agent != 'greedy' or self.target_agent != 'greedy':
+            self.set_target_opponent(target_agent)
+
+    def set_target_opponent(self, target_agent):
+        """'greedy' (GreedyTargetAgent, the default) or 'heuristic' (HeuristicTargetAgent, mate/agents/heuristic.py:290-337: the
+        Greedy action plus a drift away from the nearest camera sector's incentre) as the target team of step_greedy,
+        step_versus_greedy('camera') and step_selected (mate_engine_set_target_opponent).  Any call boundary; enable_policies first.
+        While 'heuristic' those calls are three launches (agents, drift, step), the fused rollouts against the engine's targets and a
+        non-plain target observation mode are refused."""
+        if target_agent not in TARGET_AGENTS:
+            raise ValueError(f"target_agent must be one of {TARGET_AGENTS}, got {target_agent!r}")
+        check(self.lib.mate_engine_set_target_opponent(self._h, TARGET_AGENTS.index(target_agent)))
+        self.target_agent = target_agent
 
     def _policy_tape(self, policy_tape, keep):
         if policy_tape is None:
@@ -588,14 +604,20 @@ class Engine:
                                                       int(auto_reset), self._stream()))
         return self.camera_obs, self.target_obs, self.scalars
 
-    def policy_actions(self):
-        """(camera_actions [N,Nc,2], target_actions [N,Nt,2]) f64: the joint actions of the last step_greedy."""
+    def policy_actions(self, greedy_targets=False):
+        """(camera_actions [N,Nc,2], target_actions [N,Nt,2]) f64: the joint actions of the last step_greedy, as the step consumed
+        them -- with the heuristic target opponent the final target actions.  greedy_targets=True: a third tensor, the Greedy
+        target agents' joint action of the same step ahead of the drift (equal to the second while the opponent is 'greedy')."""
         N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
         cam = torch.zeros((N, Nc, 2), dtype=torch.float64, device=self.device)
         tgt = torch.zeros((N, Nt, 2), dtype=torch.float64, device=self.device)
         check(self.lib.mate_engine_policy_actions(self._h, ctypes.c_void_p(cam.data_ptr()) if Nc else None,
                                                   ctypes.c_void_p(tgt.data_ptr()), self._stream()))
-        return cam, tgt
+        if not greedy_targets:
+            return cam, tgt
+        greedy = torch.zeros((N, Nt, 2), dtype=torch.float64, device=self.device)
+        check(self.lib.mate_engine_policy_greedy_target_actions(self._h, ctypes.c_void_p(greedy.data_ptr()), self._stream()))
+        return cam, tgt, greedy
 
     def observe(self, tape_ct=None):
         io, keep = self._io(tape_ct=tape_ct)
@@ -1102,12 +1124,16 @@ class Stepper:
 
     def __init__(self, eng, cam_act, tgt_act, auto_reset=True, graph_steps=0, between=None, versus=None, frame_skip=1):
         self.eng, self.between, self.graph_steps = eng, between, int(graph_steps)
+        self.graph = None                                 # (set first: close() reads it, also of a stepper whose construction was refused)
         # frame_skip = K > 1 (with `versus`): FrameSkip(K) over MultiCamera / MultiTarget, the example trainers' flow -- every "step" of
         # this stepper is ONE K-frame launch (Engine.rollout_versus_greedy: the caller's action repeated, the greedy opponents acting
         # anew on every frame), `auto_reset` and `graph_steps` count launches, and run() returns the rollout-shaped tensors
         # ([K, N, ...]: the caller sums the reward rows, reads the last frame's observation) instead of the engine's per-step ones
         self.frame_skip = int(frame_skip)
         assert self.frame_skip >= 1 and (self.frame_skip == 1 or versus is not None), 'frame_skip belongs to the learner-versus-greedy flow'
+        if self.frame_skip > 1 and versus in ('camera', 0) and eng.target_agent != 'greedy':
+            raise ValueError(f"make_stepper(versus='camera', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the target opponent is "
+                             f"{eng.target_agent!r} (Engine.set_target_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
         # versus = 'camera' / 'target': the caller's team (MultiCamera / MultiTarget); the other team is played by the on-device
         # greedy agents (Engine.step_versus_greedy) and its tensor argument is ignored

@@ -98,6 +98,8 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--episodes', type=int, default=1)
     ap.add_argument('--policy', choices=['greedy', 'random'], default='greedy')
+    ap.add_argument('--target-agent', choices=['greedy', 'heuristic'], default='greedy',
+                    help="the scripted agent of the target team under --policy greedy (mate.evaluate's --target-agent)")
     ap.add_argument('--max-episode-steps', type=int, default=None)
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args()
@@ -105,7 +107,7 @@ def main():
     overrides = {} if args.max_episode_steps is None else {'max_episode_steps': args.max_episode_steps}
     env = mate_amd.MultiAgentTracking(args.config, **overrides)
     if args.policy == 'greedy':
-        env.enable_greedy_policies()
+        env.enable_greedy_policies(target_agent=args.target_agent)
     env.seed(args.seed)
     rows = []
     for episode in range(args.episodes):
