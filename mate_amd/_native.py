@@ -11,19 +11,6 @@ __all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO
 
 LIB_PATH = os.environ.get('MATE_ENGINE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libmate_engine.so')
 
-EXPORTED_SYMBOLS = (
-    'mate_engine_last_error', 'mate_engine_abi_version', 'mate_engine_create', 'mate_engine_destroy',
-    'mate_engine_get_layout', 'mate_engine_set_obs_transform', 'mate_engine_set_obs_mode', 'mate_engine_set_action_grids', 'mate_engine_seed', 'mate_engine_reset', 'mate_engine_reset_tape', 'mate_engine_step', 'mate_engine_device_tick', 'mate_engine_set_episode_stats', 'mate_engine_snapshot_episode_stats', 'mate_engine_step_random',
-    'mate_engine_rollout_random', 'mate_engine_policy_enable', 'mate_engine_step_greedy', 'mate_engine_step_versus_greedy', 'mate_engine_rollout_greedy', 'mate_engine_rollout_versus_greedy', 'mate_engine_policy_actions', 'mate_engine_policy_greedy_target_actions', 'mate_engine_set_target_opponent',
-    'mate_engine_observe', 'mate_engine_export_state', 'mate_engine_import_state', 'mate_engine_enable_state_rows', 'mate_engine_state_rows', 'mate_engine_enable_reward_rows', 'mate_engine_lut_read',
-    'mate_engine_enable_selection', 'mate_engine_disable_selection', 'mate_engine_selection_actions', 'mate_engine_step_selected',
-    'mate_engine_enable_fragment_rows', 'mate_engine_fragment_coefficients', 'mate_engine_fragment_rows', 'mate_engine_enable_first_rows',
-    'mate_engine_block_alloc', 'mate_engine_block_free', 'mate_engine_block_probe', 'mate_engine_set_store_form',
-    'mate_engine_memory_hold', 'mate_engine_memory_release', 'mate_engine_hbm_probe', 'mate_engine_set_sub_wave',
-    'mate_engine_lut_write', 'mate_engine_enable_outer_boundary', 'mate_engine_lut_read_outer', 'mate_engine_lut_write_outer', 'mate_engine_soft_coverage', 'mate_engine_rebuild_luts', 'mate_engine_idle_steps', 'mate_engine_kernel_time', 'mate_engine_last_flow',
-)
-
-
 class EngineError(RuntimeError):
     """A C-ABI call failed (status code + message from the engine)."""
 
@@ -99,6 +86,72 @@ class MateFirstRows(ctypes.Structure):
     _fields_ = [('rows_dev', ctypes.c_void_p), ('scalars_dev', ctypes.c_void_p), ('final_obs_dev', ctypes.c_void_p)]
 
 
+P, I32, I64, U64, INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
+F64P, IO, TAPE = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape)
+
+# The C ABI of include/mate_engine.h, once: name -> (restype, argtypes).  load() applies it; tests/test_host_logic.py holds every
+# entry's arity and every structure's member names against the header.
+PROTOTYPES = {
+    'mate_engine_last_error': (ctypes.c_char_p, []),
+    'mate_engine_abi_version': (INT, []),
+    'mate_engine_create': (INT, [ctypes.POINTER(MateConfig), I64, I32, U64, U64, ctypes.POINTER(P)]),
+    'mate_engine_destroy': (INT, [P]),
+    'mate_engine_get_layout': (INT, [P, ctypes.POINTER(MateLayout)]),
+    'mate_engine_seed': (INT, [P, U64]),
+    'mate_engine_set_obs_transform': (INT, [P, I32, P, P, P, P]),
+    'mate_engine_set_obs_mode': (INT, [P, I32, I32]),
+    'mate_engine_set_action_grids': (INT, [P, P, I32, P, I32]),
+    'mate_engine_reset': (INT, [P, P, IO, P]),
+    'mate_engine_reset_tape': (INT, [P, P, IO, P, I32, P, P]),
+    'mate_engine_step': (INT, [P, IO, I32, P]),
+    'mate_engine_device_tick': (INT, [P, I32, P]),
+    'mate_engine_set_episode_stats': (INT, [P, P]),
+    'mate_engine_snapshot_episode_stats': (INT, [P, P, P]),
+    'mate_engine_step_random': (INT, [P, IO, I32, P]),
+    'mate_engine_rollout_random': (INT, [P, IO, I32, I32, P]),
+    'mate_engine_policy_enable': (INT, [P]),
+    'mate_engine_step_greedy': (INT, [P, IO, TAPE, I32, P]),
+    'mate_engine_step_versus_greedy': (INT, [P, I32, IO, TAPE, I32, P]),
+    'mate_engine_policy_actions': (INT, [P, P, P, P]),
+    'mate_engine_policy_greedy_target_actions': (INT, [P, P, P]),
+    'mate_engine_set_target_opponent': (INT, [P, I32]),
+    'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
+    'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
+    'mate_engine_observe': (INT, [P, IO, P]),
+    'mate_engine_export_state': (INT, [P, P, P]),
+    'mate_engine_import_state': (INT, [P, P, P]),
+    'mate_engine_enable_state_rows': (INT, [P, P, I32, P, P]),
+    'mate_engine_state_rows': (INT, [P, P, I32, P, P, P]),
+    'mate_engine_enable_reward_rows': (INT, [P, ctypes.POINTER(MateRewardRows)]),
+    'mate_engine_enable_selection': (INT, [P, I32, P, P, P, P, I32]),
+    'mate_engine_disable_selection': (INT, [P]),
+    'mate_engine_selection_actions': (INT, [P, ctypes.POINTER(P), ctypes.POINTER(I32)]),
+    'mate_engine_step_selected': (INT, [P, IO, TAPE, I32, P]),
+    'mate_engine_enable_fragment_rows': (INT, [P, ctypes.POINTER(MateFragmentRows)]),
+    'mate_engine_fragment_coefficients': (INT, [P, ctypes.POINTER(P), ctypes.POINTER(I32)]),
+    'mate_engine_fragment_rows': (INT, [P, ctypes.POINTER(MateFragmentRows), IO, I32, P]),
+    'mate_engine_enable_first_rows': (INT, [P, ctypes.POINTER(MateFirstRows)]),
+    'mate_engine_lut_read': (INT, [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]),
+    'mate_engine_lut_read_outer': (INT, [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]),
+    'mate_engine_enable_outer_boundary': (INT, [P, ctypes.POINTER(I32)]),
+    'mate_engine_lut_write': (INT, [P, I64, I32, P, P, I32]),
+    'mate_engine_lut_write_outer': (INT, [P, I64, I32, P, P, I32]),
+    'mate_engine_soft_coverage': (INT, [P, P, P, P, P]),
+    'mate_engine_rebuild_luts': (INT, [P, P]),
+    'mate_engine_idle_steps': (INT, [P, ctypes.POINTER(I64)]),
+    'mate_engine_kernel_time': (INT, [P, I32, F64P, ctypes.POINTER(I64)]),
+    'mate_engine_last_flow': (INT, [P]),
+    'mate_engine_block_alloc': (INT, [I32, I64, ctypes.POINTER(P)]),
+    'mate_engine_block_free': (INT, [P]),
+    'mate_engine_block_probe': (INT, [I32, P, I64, I32, I32, P, F64P]),
+    'mate_engine_set_store_form': (INT, [P, I32]),
+    'mate_engine_memory_hold': (INT, [I32, I64, ctypes.POINTER(P)]),
+    'mate_engine_memory_release': (INT, [P]),
+    'mate_engine_hbm_probe': (INT, [I32, P, P, I64, I32, P, F64P]),
+    'mate_engine_set_sub_wave': (INT, [P, I32, ctypes.POINTER(I32)]),
+}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
 lib = None
 
 
@@ -115,69 +168,9 @@ def load():
     # process; loading ROCm's copy before torch's leaves the later one without a device).
     import torch  # noqa: F401
     handle = ctypes.CDLL(LIB_PATH)
-    P, I32, I64, U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    handle.mate_engine_last_error.restype = ctypes.c_char_p
-    handle.mate_engine_last_error.argtypes = []
-    handle.mate_engine_abi_version.restype = ctypes.c_int
-    handle.mate_engine_create.argtypes = [ctypes.POINTER(MateConfig), I64, I32, U64, U64, ctypes.POINTER(P)]
-    handle.mate_engine_destroy.argtypes = [P]
-    handle.mate_engine_get_layout.argtypes = [P, ctypes.POINTER(MateLayout)]
-    handle.mate_engine_seed.argtypes = [P, U64]
-    handle.mate_engine_set_obs_transform.argtypes = [P, I32, P, P, P, P]
-    handle.mate_engine_set_obs_mode.argtypes = [P, I32, I32]
-    handle.mate_engine_set_action_grids.argtypes = [P, P, I32, P, I32]
-    handle.mate_engine_reset.argtypes = [P, P, ctypes.POINTER(MateStepIO), P]
-    handle.mate_engine_reset_tape.argtypes = [P, P, ctypes.POINTER(MateStepIO), P, I32, P, P]
-    handle.mate_engine_step.argtypes = [P, ctypes.POINTER(MateStepIO), I32, P]
-    handle.mate_engine_device_tick.argtypes = [P, I32, P]
-    handle.mate_engine_set_episode_stats.argtypes = [P, P]
-    handle.mate_engine_step_random.argtypes = [P, ctypes.POINTER(MateStepIO), I32, P]
-    handle.mate_engine_rollout_random.argtypes = [P, ctypes.POINTER(MateStepIO), I32, I32, P]
-    handle.mate_engine_policy_enable.argtypes = [P]
-    handle.mate_engine_step_greedy.argtypes = [P, ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape), I32, P]
-    handle.mate_engine_step_versus_greedy.argtypes = [P, I32, ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape), I32, P]
-    handle.mate_engine_policy_actions.argtypes = [P, P, P, P]
-    handle.mate_engine_policy_greedy_target_actions.argtypes = [P, P, P]
-    handle.mate_engine_set_target_opponent.argtypes = [P, I32]
-    handle.mate_engine_rollout_greedy.argtypes = [P, ctypes.POINTER(MateStepIO), I32, I32, P]
-    handle.mate_engine_rollout_versus_greedy.argtypes = [P, I32, ctypes.POINTER(MateStepIO), I32, I32, P]
-    handle.mate_engine_observe.argtypes = [P, ctypes.POINTER(MateStepIO), P]
-    handle.mate_engine_export_state.argtypes = [P, P, P]
-    handle.mate_engine_import_state.argtypes = [P, P, P]
-    handle.mate_engine_enable_state_rows.argtypes = [P, P, I32, P, P]
-    handle.mate_engine_state_rows.argtypes = [P, P, I32, P, P, P]
-    handle.mate_engine_enable_reward_rows.argtypes = [P, ctypes.POINTER(MateRewardRows)]
-    handle.mate_engine_enable_selection.argtypes = [P, I32, P, P, P, P, I32]
-    handle.mate_engine_disable_selection.argtypes = [P]
-    handle.mate_engine_selection_actions.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(I32)]
-    handle.mate_engine_step_selected.argtypes = [P, ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape), I32, P]
-    handle.mate_engine_enable_fragment_rows.argtypes = [P, ctypes.POINTER(MateFragmentRows)]
-    handle.mate_engine_fragment_coefficients.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(I32)]
-    handle.mate_engine_fragment_rows.argtypes = [P, ctypes.POINTER(MateFragmentRows), ctypes.POINTER(MateStepIO), I32, P]
-    handle.mate_engine_enable_first_rows.argtypes = [P, ctypes.POINTER(MateFirstRows)]
-    handle.mate_engine_lut_read.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
-    handle.mate_engine_lut_read_outer.argtypes = [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]
-    handle.mate_engine_enable_outer_boundary.argtypes = [P, ctypes.POINTER(I32)]
-    handle.mate_engine_lut_write.argtypes = [P, I64, I32, P, P, I32]
-    handle.mate_engine_lut_write_outer.argtypes = [P, I64, I32, P, P, I32]
-    handle.mate_engine_soft_coverage.argtypes = [P, P, P, P, P]
-    handle.mate_engine_rebuild_luts.argtypes = [P, P]
-    handle.mate_engine_idle_steps.argtypes = [P, ctypes.POINTER(I64)]
-    handle.mate_engine_kernel_time.argtypes = [P, I32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I64)]
-    handle.mate_engine_last_flow.argtypes = [P]
-    handle.mate_engine_block_alloc.argtypes = [I32, I64, ctypes.POINTER(P)]
-    handle.mate_engine_block_free.argtypes = [P]
-    handle.mate_engine_set_store_form.argtypes = [P, I32]
-    handle.mate_engine_memory_hold.argtypes = [I32, I64, ctypes.POINTER(P)]
-    handle.mate_engine_memory_release.argtypes = [P]
-    handle.mate_engine_block_probe.argtypes = [I32, P, I64, I32, I32, P, ctypes.POINTER(ctypes.c_double)]
-    handle.mate_engine_snapshot_episode_stats.argtypes = [P, P, P]
-    handle.mate_engine_set_sub_wave.argtypes = [P, I32, ctypes.POINTER(I32)]
-    handle.mate_engine_hbm_probe.argtypes = [I32, P, P, I64, I32, P, ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTED_SYMBOLS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(handle, name)
-        if name not in ('mate_engine_last_error',):
-            fn.restype = ctypes.c_int
+        fn.restype, fn.argtypes = restype, argtypes
     lib = handle
     return lib
 

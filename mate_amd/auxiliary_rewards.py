@@ -21,27 +21,50 @@ import torch
 
 from mate_amd import constants as consts
 
-__all__ = ['AuxiliaryTargetRewards']
+__all__ = ['AuxiliaryTargetRewards', 'CAMERA_REWARD_KEYS', 'TARGET_REWARD_KEYS', 'REWARD_REDUCTIONS', 'reward_term_keys', 'reward_coefficient_table']
+
+# The terms of a team's shaped reward in the order of its coefficient table (mate_engine_enable_reward_rows): the reference's
+# AuxiliaryCameraRewards.ACCEPTABLE_KEYS / AuxiliaryTargetRewards.ACCEPTABLE_KEYS
+CAMERA_REWARD_KEYS = ('raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'soft_coverage_score',
+                      'num_tracked', 'baseline')
+TARGET_REWARD_KEYS = ('raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'normalized_goal_distance',
+                      'sparse_delivery', 'soft_coverage_score', 'is_tracked', 'is_colliding', 'baseline')
+REWARD_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2, 'max': 3, 'min': 4}      # MATE_REDUCE_* (include/mate_engine.h)
+
+
+def reward_term_keys(team):
+    """The key tuple of a team's shaped reward: BatchedMultiAgentTracking.AUXILIARY_REWARD_KEYS / AuxiliaryTargetRewards.ACCEPTABLE_KEYS."""
+    assert team in ('camera', 'target')
+    return CAMERA_REWARD_KEYS if team == 'camera' else TARGET_REWARD_KEYS
+
+
+def reward_coefficient_table(team, coefficients, reduction='none'):
+    """(coefficients in the order of the team's key tuple, absent keys 0.0; MATE_REDUCE_* code) of one team's (coefficients, reduction).
+    The one holder of the key, reduction and constant-coefficient assertions (the reference wrappers' messages): the engine's attached
+    launches and both torch shapers take their arguments through it."""
+    keys = reward_term_keys(team)
+    if team == 'camera':
+        assert reduction in ('mean', 'sum', 'max', 'min', 'none'), f'Invalid reduction method {reduction}.'
+    else:                                                # auxiliary_target_rewards.py:84-88 (no 'min' there)
+        assert reduction in ('mean', 'sum', 'max', 'none'), (
+            f'Invalid reduction method {reduction}. The reduction method should be one of ("mean", "sum", "max") (for shared reward), '
+            f'or "none" for no reduction (for individual reward).')
+    assert set(keys).issuperset(coefficients.keys()), (
+        f'The coefficient mapping only accepts keys in {keys}. Got list(coefficients.keys()) = {list(coefficients.keys())}.')
+    for key, coefficient in coefficients.items():
+        assert isinstance(coefficient, (int, float)), f'only constant coefficients are supported on the batched path (got {key!r}: {coefficient!r})'
+    return [float(coefficients.get(key, 0.0)) for key in keys], REWARD_REDUCTIONS[reduction]
 
 
 class AuxiliaryTargetRewards:
-    ACCEPTABLE_KEYS = ('raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'normalized_goal_distance',
-                       'sparse_delivery', 'soft_coverage_score', 'is_tracked', 'is_colliding', 'baseline')
+    ACCEPTABLE_KEYS = TARGET_REWARD_KEYS
 
     def __init__(self, engine, coefficients, reduction='none'):
-        assert reduction in ('mean', 'sum', 'max', 'none'), (          # auxiliary_target_rewards.py:84-88 (no 'min' there)
-            f'Invalid reduction method {reduction}. The reduction method should be one of ("mean", "sum", "max") (for shared reward), '
-            f'or "none" for no reduction (for individual reward).')
-        assert set(self.ACCEPTABLE_KEYS).issuperset(coefficients.keys()), (
-            f'The coefficient mapping only accepts keys in {self.ACCEPTABLE_KEYS}. Got list(coefficients.keys()) = {list(coefficients.keys())}.')
-        for key, coefficient in coefficients.items():
-            assert isinstance(coefficient, (int, float)), f'only constant coefficients are supported on the batched path (got {key!r}: {coefficient!r})'
+        reward_coefficient_table('target', coefficients, reduction)
         self.engine, self.coefficients, self.reduction = engine, {k: float(v) for k, v in coefficients.items()}, reduction
         if 'soft_coverage_score' in self.coefficients:
             assert engine.num_cameras > 0, 'soft_coverage_score needs cameras (the reference takes a max over them)'
-            if not getattr(engine, 'outer_capacity', 0):
-                engine.enable_outer_boundary()       # built at every reset from now on; once now for the running episodes
-                engine.rebuild_luts()
+            engine.need_outer_boundary()
         self._warehouses = torch.as_tensor(consts.WAREHOUSES, dtype=torch.float64, device=engine.device)
         self.terms = None
         self.observe_reset()

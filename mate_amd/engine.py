@@ -5,12 +5,16 @@ in the HIP kernels behind ``include/mate_engine.h``.
 """
 import ctypes
 import os
+import time
+import warnings
 
 import numpy as np
 import torch
 
-from mate_amd import _native
-from mate_amd._native import MateConfig, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
+from mate_amd import _native, constants as consts, spaces
+from mate_amd._native import MateConfig, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
+from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_table, reward_term_keys      # noqa: F401 (this module's names too)
+from mate_amd.config import scenario_tables
 
 __all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'encode_selection', 'decode_selection',
            'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS']
@@ -39,8 +43,6 @@ def export_layout(Nc, Nt, No):
 
 
 TARGET_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* (include/mate_engine.h): the scripted agents that can play the target team
-REWARD_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2, 'max': 3, 'min': 4}      # MATE_REDUCE_* (include/mate_engine.h)
-
 
 def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
     """The reference's HierarchicalCamera action (examples/hrl/wrappers.py) -> the int32 words [N, Nc] mate_engine_enable_selection reads:
@@ -67,34 +69,6 @@ def decode_selection(words, multi, num_targets):
     return words[..., None] == t
 
 
-def reward_term_keys(team):
-    """The terms of a team's shaped reward in the order of its coefficient table (mate_engine_enable_reward_rows): the key tuples of
-    the torch shapers, BatchedMultiAgentTracking.AUXILIARY_REWARD_KEYS and AuxiliaryTargetRewards.ACCEPTABLE_KEYS."""
-    assert team in ('camera', 'target')
-    if team == 'camera':
-        from mate_amd.environment import BatchedMultiAgentTracking
-        return BatchedMultiAgentTracking.AUXILIARY_REWARD_KEYS
-    from mate_amd.auxiliary_rewards import AuxiliaryTargetRewards
-    return AuxiliaryTargetRewards.ACCEPTABLE_KEYS
-
-
-def reward_coefficient_table(team, coefficients, reduction='none'):
-    """(coefficients in the order of the team's key tuple, absent keys 0.0; MATE_REDUCE_* code) of one team's (coefficients, reduction),
-    with the key and reduction assertions of the torch shapers (the reference wrappers' messages)."""
-    keys = reward_term_keys(team)
-    if team == 'camera':
-        assert reduction in ('mean', 'sum', 'max', 'min', 'none'), f'Invalid reduction method {reduction}.'
-    else:                                                # auxiliary_target_rewards.py:84-88 (no 'min' there)
-        assert reduction in ('mean', 'sum', 'max', 'none'), (
-            f'Invalid reduction method {reduction}. The reduction method should be one of ("mean", "sum", "max") (for shared reward), '
-            f'or "none" for no reduction (for individual reward).')
-    assert set(keys).issuperset(coefficients.keys()), (
-        f'The coefficient mapping only accepts keys in {keys}. Got list(coefficients.keys()) = {list(coefficients.keys())}.')
-    for key, coefficient in coefficients.items():
-        assert isinstance(coefficient, (int, float)), f'only constant coefficients are supported on the batched path (got {key!r}: {coefficient!r})'
-    return [float(coefficients.get(key, 0.0)) for key in keys], REWARD_REDUCTIONS[reduction]
-
-
 FRAGMENT_REFUSED_KEYS = ('soft_coverage_score', 'normalized_goal_distance', 'sparse_delivery', 'is_colliding')
 
 
@@ -118,6 +92,13 @@ class _EngineOwned:
         self.__cuda_array_interface__ = {'shape': (count,), 'typestr': typestr, 'data': (ptr, False), 'version': 2}
 
 
+def _team_code(team):
+    """'camera' / 0 -> 0, 'target' / 1 -> 1."""
+    code = {'camera': 0, 'target': 1}.get(team, team)
+    assert code in (0, 1), f"team = {team!r}: 'camera' or 'target'"
+    return code
+
+
 class Engine:
     """N environments of one scenario on one GPU."""
 
@@ -130,14 +111,9 @@ class Engine:
         self.device_index = int(device)
         self.device = torch.device('cuda', self.device_index)
         self.obs_dtype = obs_dtype
-        cam, tgt, obs = config.get('camera', {}), config['target'], config.get('obstacle', {})
-
-        def ranges(sub):
-            rows = [[x, x, y, y] for x, y in sub.get('location', [])] + [list(r) for r in sub.get('location_random_range', [])]
-            return np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, 4))
-
-        self._ranges = (ranges(cam), ranges(tgt), ranges(obs))
-        self.num_cameras, self.num_targets, self.num_obstacles = (len(r) for r in self._ranges)
+        tables = scenario_tables(config)
+        self._ranges = (tables['camera_ranges'], tables['target_ranges'], tables['obstacle_ranges'])      # (self._cfg points into them)
+        self.num_cameras, self.num_targets, self.num_obstacles = tables['num_cameras'], tables['num_targets'], tables['num_obstacles']
         c = MateConfig()
         c.num_cameras, c.num_targets, c.num_obstacles = self.num_cameras, self.num_targets, self.num_obstacles
         c.max_episode_steps = int(config['max_episode_steps'])
@@ -147,23 +123,14 @@ class Engine:
         c.targets_start_with_cargoes = int(bool(config['targets_start_with_cargoes']))
         c.high_capacity_target_split = float(config['high_capacity_target_split'])
         c.bounty_factor = float(config['bounty_factor'])
-        c.transmittance = float(obs.get('transmittance', 0.0))
-        c.camera_radius = float(cam.get('radius', 40.0))
-        c.camera_min_viewing_angle = float(cam.get('min_viewing_angle', 90.0))
-        c.camera_max_sight_range = float(cam.get('max_sight_range', 500.0))
-        c.camera_rotation_step = float(cam.get('rotation_step', 5.0))
-        c.camera_zooming_step = float(cam.get('zooming_step', 2.5))
-        c.target_step_size = float(tgt['step_size'])
-        c.target_sight_range = float(tgt['sight_range'])
-        if 'radius_random_range' in obs:
-            rr = list(obs['radius_random_range'])
-        else:
-            rr = [float(obs.get('radius', 0.0))] * 2
-        c.obstacle_radius_range[0], c.obstacle_radius_range[1] = float(rr[0]), float(rr[1])
+        c.transmittance = tables['transmittance']
+        for key, value in tables['camera'].items():
+            setattr(c, 'camera_' + key, value)
+        c.target_step_size = float(config['target']['step_size'])
+        c.target_sight_range = float(config['target']['sight_range'])
+        c.obstacle_radius_range[0], c.obstacle_radius_range[1] = tables['obstacle_radius_range']
         dp = ctypes.POINTER(ctypes.c_double)
-        c.camera_location_ranges = self._ranges[0].ctypes.data_as(dp)
-        c.target_location_ranges = self._ranges[1].ctypes.data_as(dp)
-        c.obstacle_location_ranges = self._ranges[2].ctypes.data_as(dp)
+        c.camera_location_ranges, c.target_location_ranges, c.obstacle_location_ranges = (r.ctypes.data_as(dp) for r in self._ranges)
         c.obs_dtype = 1 if obs_dtype == torch.float64 else 0
         self._cfg = c
         handle = ctypes.c_void_p()
@@ -186,21 +153,44 @@ class Engine:
             self.episode_stats = torch.zeros(5, dtype=torch.float64, device=self.device)
         check(self.lib.mate_engine_set_episode_stats(self._h, ctypes.c_void_p(self.episode_stats.data_ptr())))
         self.state_dim = layout.state_dim
-        self.state = None                 # [N, state_dim] while state rows are attached (enable_state_rows)
         self.target_agent = 'greedy'      # the scripted agent of the target team (set_target_opponent)
+        self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
+        self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
+        # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
+        self._rollout, self._block_search, self._reserve_t0 = None, None, None
+        self.block_rates, self.store_form, self.reserve_seconds = [], 0, 0.0
+        self._random_io = {}              # the cached argument blocks of step_random (_forget_calls)
+        self._staged = self._softcov = self._export_slices = None      # (stage_outputs, soft_coverage, state_dict_from)
+        self._clear_state_rows()
+        self._clear_reward_rows()
+        self._clear_selection()
+        self._clear_fragment_rows()
+
+    # The detached value of every attached feature, written once: __init__ and the feature's disable_* both come here.
+    def _clear_state_rows(self):
+        self.state, self.state_normalized = None, False      # [N, state_dim] while state rows are attached (enable_state_rows)
+
+    def _clear_reward_rows(self):
         # while reward rows are attached (enable_reward_rows): [N, Nc] / [N, Nt] shaped rewards, [N, Nc, 7] / [N, Nt, 10] f64 terms,
         # and the two coefficient tables on the device ({'camera': [7], 'target': [10]} f64)
         self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
-        self.reward_coefficients = None
+        self.reward_coefficients, self.reward_accumulate = None, False
+
+    def _clear_selection(self):
         # while target selection is attached (enable_selection): the learner's selection [N, Nc] int32, the executor's joint action
         # [N, Nc, 2] (engine-owned), the metrics [N, Nc, 4] f64, the contributing frames [N] int32 and action_mask() [N, Nc, 2 Nt | Nt + 1] u8
         self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
-        self.multi_selection = None
+        self.multi_selection, self.selection_accumulate = None, False
+
+    def _clear_fragment_rows(self):
         # while fragment rows are attached (enable_fragment_rows): what FrameSkip hands the learner per K-frame launch
         self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
         self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
-        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None      # (enable_fragment_rows(first_rows=True))
         self.fragment_frame_skip, self._fragment_masks = 0, False
+        self._clear_first_rows()
+
+    def _clear_first_rows(self):
+        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None      # (enable_fragment_rows(first_rows=True))
 
     def close(self):
         if getattr(self, '_h', None):
@@ -213,6 +203,29 @@ class Engine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _bind_outputs(self, io, camera_obs, target_obs, scalars, masks=None):
+        """The four output pointers of a MateStepIO, set here and nowhere else: no camera pointer without cameras, no mask pointer unless
+        the call wants its masks (`masks` = None otherwise).  A tensor that is None leaves its pointer null."""
+        io.camera_obs_dev = camera_obs.data_ptr() if self.num_cameras and camera_obs is not None else None
+        io.target_obs_dev = target_obs.data_ptr() if target_obs is not None else None
+        io.scalars_dev = scalars.data_ptr()
+        io.masks_dev = masks.data_ptr() if masks is not None else None
+        return io
+
+    def _forget_calls(self):
+        """Drop the cached argument blocks (step_random's, _run_rollout's): they hold raw pointers into the output tensors, so whatever
+        re-homes or replaces an output tensor comes here."""
+        self._random_io = {}
+        if self._rollout is not None:
+            self._rollout['_calls'] = {}
+
+    def _env_mask(self, env_mask):
+        """(uint8 pointer or None, the tensor to keep alive) of a reset's environment mask."""
+        if env_mask is None:
+            return None, None
+        env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        return ctypes.c_void_p(env_mask.data_ptr()), env_mask
+
     def _io(self, cam_act=None, tgt_act=None, tape_ct=None, tape_goal=None, want_masks=True):
         io = MateStepIO()
         keep = []
@@ -222,15 +235,15 @@ class Engine:
             ints = (torch.int32, torch.int64, torch.int16, torch.uint8)
             if self.num_cameras == 0:
                 cam_act = None
-            teams = [(name, act, agents) for name, act, agents in (('camera', cam_act, self.num_cameras), ('target', tgt_act, self.num_targets))
-                     if act is not None]
-            reals = [act.dtype for _, act, _ in teams if act.dtype not in ints]
+            teams = [team for team in (('camera', cam_act, self.num_cameras, self.camera_action_grid),
+                                       ('target', tgt_act, self.num_targets, self.target_action_grid)) if team[1] is not None]
+            reals = [act.dtype for _, act, _, _ in teams if act.dtype not in ints]
             act_dtype = reals[0] if reals else torch.float64
             assert act_dtype in (torch.float32, torch.float64)
             io.act_dtype = 1 if act_dtype == torch.float64 else 0
-            for name, act, agents in teams:
+            for name, act, agents, grid in teams:
                 if act.dtype in ints:
-                    assert getattr(self, name + '_action_grid', None) is not None, f'call set_action_grids({name}_levels=...) first'
+                    assert grid is not None, f'call set_action_grids({name}_levels=...) first'
                     act = act.to(torch.int32).contiguous()
                     assert act.numel() == self.num_envs * agents and act.device == self.device
                     io.act_dtype |= 0x100 if name == 'camera' else 0x200
@@ -249,25 +262,18 @@ class Engine:
             assert tape_goal.numel() == self.num_envs * self.num_targets
             io.tape_goal_dev = tape_goal.data_ptr()
             keep.append(tape_goal)
-        io.camera_obs_dev = self.camera_obs.data_ptr() if self.num_cameras else None
-        io.target_obs_dev = self.target_obs.data_ptr()
-        io.scalars_dev = self.scalars.data_ptr()
-        io.masks_dev = self.masks.data_ptr() if want_masks else None
-        return io, keep
+        return self._bind_outputs(io, self.camera_obs, self.target_obs, self.scalars, self.masks if want_masks else None), keep
 
     # ---------------------------------------------------------------------- API
     def set_obs_transform(self, relative_coordinates=False, rescaled_observation=False):
         """Fuse RelativeCoordinates / RescaledObservation (the reference's observation wrappers) into the
         kernel's packer.  The affine map of the rescale comes from the observation-space bounds
         (mate_amd.constants), exactly as `rescale_observation` derives it."""
-        from mate_amd import constants as consts
-        from mate_amd.spaces import rescale_affine as affine
-
         nums = (self.num_cameras, self.num_targets, self.num_obstacles)
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
         if rescaled_observation:
-            cs, cb = affine(consts.camera_observation_space_of(*nums))
-            ts, tb = affine(consts.target_observation_space_of(*nums))
+            cs, cb = spaces.rescale_affine(consts.camera_observation_space_of(*nums))
+            ts, tb = spaces.rescale_affine(consts.target_observation_space_of(*nums))
             check(self.lib.mate_engine_set_obs_transform(self._h, int(relative_coordinates), ptr(cs), ptr(cb), ptr(ts), ptr(tb)))
         else:
             check(self.lib.mate_engine_set_obs_transform(self._h, int(relative_coordinates), None, None, None, None))
@@ -284,9 +290,8 @@ class Engine:
         wrappers/discrete_action_spaces.py): actions passed as int32 indices into `levels**2` grids are decoded
         in the step kernel.  The normalised grids are computed here with the reference's own NumPy formulas
         and handed to the engine as tables."""
-        from mate_amd.spaces import camera_action_grid, target_action_grid
-        cg = np.ascontiguousarray(camera_action_grid(camera_levels), dtype=np.float64) if camera_levels else None
-        tg = np.ascontiguousarray(target_action_grid(target_levels), dtype=np.float64) if target_levels else None
+        cg = np.ascontiguousarray(spaces.camera_action_grid(camera_levels), dtype=np.float64) if camera_levels else None
+        tg = np.ascontiguousarray(spaces.target_action_grid(target_levels), dtype=np.float64) if target_levels else None
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
         check(self.lib.mate_engine_set_action_grids(self._h, ptr(cg), 0 if cg is None else len(cg), ptr(tg), 0 if tg is None else len(tg)))
         self.camera_action_grid, self.target_action_grid = cg, tg
@@ -296,10 +301,7 @@ class Engine:
 
     def reset(self, env_mask=None):
         io, keep = self._io()
-        mask_ptr = None
-        if env_mask is not None:
-            env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mask_ptr = ctypes.c_void_p(env_mask.data_ptr())
+        mask_ptr, env_mask = self._env_mask(env_mask)
         check(self.lib.mate_engine_reset(self._h, mask_ptr, ctypes.byref(io), self._stream()))
         return self.camera_obs, self.target_obs
 
@@ -311,10 +313,7 @@ class Engine:
         assert tape.dim() == 2 and tape.shape[0] == self.num_envs
         io, keep = self._io(tape_ct=tape_ct)
         used = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-        mask_ptr = None
-        if env_mask is not None:
-            env_mask = env_mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mask_ptr = ctypes.c_void_p(env_mask.data_ptr())
+        mask_ptr, env_mask = self._env_mask(env_mask)
         check(self.lib.mate_engine_reset_tape(self._h, mask_ptr, ctypes.byref(io), ctypes.c_void_p(tape.data_ptr()), int(tape.shape[1]),
                                               ctypes.c_void_p(used.data_ptr()), self._stream()))
         return self.camera_obs, self.target_obs, used
@@ -327,11 +326,10 @@ class Engine:
     def step_random(self, auto_reset=True, want_masks=False):
         # the argument structure of this call never changes: built once per (masks or not), the host cost per step
         # matters when the step kernel is a dozen microseconds
-        cache = self.__dict__.setdefault('_random_io', {})
-        ref = cache.get(want_masks)
+        ref = self._random_io.get(want_masks)
         if ref is None:
             io, _ = self._io(want_masks=want_masks)
-            ref = cache[want_masks] = (io, ctypes.byref(io))
+            ref = self._random_io[want_masks] = (io, ctypes.byref(io))
         status = self.lib.mate_engine_step_random(self._h, ref[1], int(auto_reset), self._stream())
         if status != 0:
             check(status)
@@ -364,17 +362,13 @@ class Engine:
         """FrameSkip(frame_skip=steps) over MultiCamera / MultiTarget (examples/utils/wrappers.py:301-323 over
         mate/wrappers/single_team.py:245-264) in ONE launch: the caller's `team` repeats `joint_action` for `steps` frames while
         the on-device greedy opponents act anew on every frame.  Rollout-shaped tensors; the caller sums the reward rows."""
-        team = {'camera': 0, 'target': 1}.get(team, team)
-        assert team in (0, 1)
+        team = _team_code(team)
         auto_reset = self._auto_reset_code(auto_reset)
         steps = int(steps)
         want_masks = want_masks or (self._fragment_masks and self.fragment_team == team)
         buf = self.reserve_rollout(steps, want_masks)
         io, keep = self._io(cam_act=joint_action if team == 0 else None, tgt_act=joint_action if team == 1 else None)
-        io.camera_obs_dev = buf['camera_obs'].data_ptr() if self.num_cameras else None
-        io.target_obs_dev = buf['target_obs'].data_ptr()
-        io.scalars_dev = buf['scalars'].data_ptr()
-        io.masks_dev = buf['masks'].data_ptr() if want_masks else None
+        self._bind_outputs(io, buf['camera_obs'], buf['target_obs'], buf['scalars'], buf['masks'] if want_masks else None)
         check(self.lib.mate_engine_rollout_versus_greedy(self._h, team, ctypes.byref(io), steps, int(auto_reset), self._stream()))
         return buf['camera_obs'][:steps], buf['target_obs'][:steps], buf['scalars'][:steps]
 
@@ -425,7 +419,7 @@ class Engine:
         # take what the target block's search left, at least one).  Everything but the winner is freed at the end
         # (mate_engine_block_free: the physical memory comes back, the address range stays reserved).
         row_bytes = nbytes // (shape[0] * shape[1])
-        search = getattr(self, '_block_search', None) or ('deep' if sw['deep'] else 'shallow')
+        search = self._block_search or ('deep' if sw['deep'] else 'shallow')
         tries = (sw['candidates'] or (6 if search == 'deep' else 3)) if nbytes >= (128 << 20) and row_bytes % 16 == 0 and search != 'none' else 1
         free = torch.cuda.mem_get_info(self.device)[0]
         deep = deep and tries > 1 and search == 'deep'
@@ -435,15 +429,13 @@ class Engine:
         if deep and sw['candidates'] is None:      # (an explicit count bounds the deep search too)
             tries = max(tries, int(budget // (nbytes + spacer_bytes)))
         tries = max(1, min(tries, int(free // (2 * nbytes))))
-        import time
-        t0 = getattr(self, '_reserve_t0', None) or time.perf_counter()      # (reserve_rollout's start: one time budget for both blocks)
+        t0 = self._reserve_t0 or time.perf_counter()      # (reserve_rollout's start: one time budget for both blocks)
         best, rates, held, spacers = None, [], [], []
         for _ in range(tries):
             try:
                 block = _native.ScatteredBlock(self.device_index, nbytes)
             except _native.EngineError as err:      # no virtual-memory management on this driver, or out of memory: plain memory works as well
                 if best is None:
-                    import warnings
                     warnings.warn(f'mate_engine_block_alloc failed ({err}); the rollout block comes from torch.zeros')
                     return torch.zeros(shape, dtype=self.obs_dtype, device=self.device), rates
                 break
@@ -487,14 +479,12 @@ class Engine:
             raise ValueError(f"reserve_rollout(search={search!r}): 'shallow', 'deep', 'none' or None (= the last explicit choice)")
         if search is not None:                       # an explicit choice stays for the (re)allocations that follow, the internal ones included
             self._block_search = search
-        buf = getattr(self, '_rollout', None)
+        buf = self._rollout
         depth = {'none': 0, 'shallow': 1, 'deep': 2}
         if buf is not None and search is not None and depth[search] > depth.get(buf.get('search'), 0) and buf['steps'] >= steps:
-            import warnings                          # (buffers that exist are kept: say that the deeper search was not run)
-            warnings.warn(f"reserve_rollout(search={search!r}): the rollout buffers exist (searched {buf.get('search')!r}); release them "
+            warnings.warn(f"reserve_rollout(search={search!r}): the rollout buffers exist (searched {buf.get('search')!r}); release them "      # (kept: the deeper search was not run)
                           '(Engine.close() or a longer reservation) to search again', RuntimeWarning, stacklevel=2)
         if buf is None or buf['steps'] < steps or (want_masks and buf['masks'] is None):     # a shorter rollout fills a prefix
-            import time
             t0 = self._reserve_t0 = time.perf_counter()
             N, Nc, Nt, L = self.num_envs, self.num_cameras, self.num_targets, self.layout
             self._rollout = None
@@ -502,13 +492,14 @@ class Engine:
                 target_block, target_rates = self._observation_block((steps, N, Nt, L.target_obs_dim), deep=True)      # (first: its search holds the most memory)
                 camera_block, camera_rates = self._observation_block((steps, N, Nc, L.camera_obs_dim))
                 buf = {
-                    'steps': steps, 'search': getattr(self, '_block_search', None) or ('deep' if self._block_switches['deep'] else 'shallow'),
+                    'steps': steps, 'search': self._block_search or ('deep' if self._block_switches['deep'] else 'shallow'),
                     'camera_obs': camera_block,
                     'target_obs': target_block,
                     'scalars': torch.zeros((steps, N, 8), dtype=torch.float32, device=self.device),
                     'masks': torch.zeros((steps, N, L.mask_words), dtype=torch.int32, device=self.device) if want_masks else None,
                 }
             self._rollout = buf
+            self._forget_calls()
             self.block_rates = [target_rates, camera_rates]
             # where even the best candidate takes the rows slowly the stores bound a launch, and the line-aligned form of the row
             # stores wins 3 %; elsewhere it costs 1.3-2 % (include/mate_engine.h).  MATE_STORE_FORM=0 / 1 forces a form.
@@ -526,14 +517,10 @@ class Engine:
         buf = self.reserve_rollout(steps, want_masks)
         # the argument block and the returned views of a (launch length, masks) combination never change while the buffers
         # live: built once -- a 20-step launch lasts 0.18 ms, and this call is what the GPU waits for before it starts
-        cache = buf.setdefault('_calls', {})
+        cache = buf['_calls']
         call = cache.get((steps, bool(want_masks)))
         if call is None:
-            io = MateStepIO()
-            io.camera_obs_dev = buf['camera_obs'].data_ptr() if self.num_cameras else None
-            io.target_obs_dev = buf['target_obs'].data_ptr()
-            io.scalars_dev = buf['scalars'].data_ptr()
-            io.masks_dev = buf['masks'].data_ptr() if want_masks else None
+            io = self._bind_outputs(MateStepIO(), buf['camera_obs'], buf['target_obs'], buf['scalars'], buf['masks'] if want_masks else None)
             call = cache[(steps, bool(want_masks))] = (io, ctypes.byref(io), (buf['camera_obs'][:steps], buf['target_obs'][:steps], buf['scalars'][:steps]))
         status = entry_point(self._h, call[1], steps, int(auto_reset), self._stream())
         if status != 0:
@@ -596,8 +583,7 @@ class Engine:
         """MultiCamera (team = 'camera' / 0) or MultiTarget (team = 'target' / 1), mate/wrappers/single_team.py:245-264:
         `joint_action` is the caller's team ([N, agents, 2] reals or [N, agents] grid indices), the opponents are the
         on-device greedy agents.  Returns (camera_obs, target_obs, scalars)."""
-        team = {'camera': 0, 'target': 1}.get(team, team)
-        assert team in (0, 1)
+        team = _team_code(team)
         io, keep = self._io(cam_act=joint_action if team == 0 else None, tgt_act=joint_action if team == 1 else None,
                             tape_ct=tape_ct, tape_goal=tape_goal)
         check(self.lib.mate_engine_step_versus_greedy(self._h, team, ctypes.byref(io), self._policy_tape(policy_tape, keep),
@@ -635,9 +621,7 @@ class Engine:
         """Host (scale, bias) of mate.normalize_observation over the state space, as ctypes pointers (+ the arrays, to keep alive)."""
         if not normalize:
             return None, None, ()
-        from mate_amd import constants as consts
-        from mate_amd.spaces import rescale_affine
-        scale, bias = rescale_affine(consts.state_space_of(self.num_cameras, self.num_targets, self.num_obstacles))
+        scale, bias = spaces.rescale_affine(consts.state_space_of(self.num_cameras, self.num_targets, self.num_obstacles))
         assert scale.shape == (self.state_dim,)
         return scale.ctypes.data_as(ctypes.c_void_p), bias.ctypes.data_as(ctypes.c_void_p), (scale, bias)
 
@@ -659,7 +643,7 @@ class Engine:
     def disable_state_rows(self):
         """Detach the state rows: the calls go back to their launch sequence without them; `Engine.state` becomes None."""
         check(self.lib.mate_engine_enable_state_rows(self._h, None, 0, None, None))
-        self.state = None
+        self._clear_state_rows()
 
     def state_rows(self, out=None, normalize=False, dtype=None):
         """The global state rows of the current records, written by one launch on the current stream into `out` ([N, state_dim],
@@ -698,9 +682,7 @@ class Engine:
         soft = any('soft_coverage_score' in spec[0] for spec in (camera, target) if spec is not None)
         if soft:
             assert self.num_cameras > 0, 'soft_coverage_score needs cameras (the reference takes a max over them)'
-            if not getattr(self, 'outer_capacity', 0):
-                self.enable_outer_boundary()         # built at every reset from now on; once now for the running episodes
-                self.rebuild_luts()
+            self.need_outer_boundary()
         N, agents, widths = self.num_envs, {'camera': self.num_cameras, 'target': self.num_targets}, {'camera': 7, 'target': 10}
         cfg = MateRewardRows()
         cfg.out_dtype, cfg.accumulate, cfg.soft_coverage = int(dtype == torch.float64), int(bool(accumulate)), int(soft)
@@ -723,14 +705,13 @@ class Engine:
         self.camera_reward_rows, self.target_reward_rows = rows.get('camera'), rows.get('target')
         self.camera_reward_terms, self.target_reward_terms = term_rows.get('camera'), term_rows.get('target')
         self.reward_coefficients, self.reward_accumulate = coefficients, bool(accumulate)
-        self.__dict__.pop('_random_io', None)
+        self._forget_calls()
         return self.camera_reward_rows, self.target_reward_rows
 
     def disable_reward_rows(self):
         """Detach the reward rows: the calls go back to their launch sequence without them; the tensors become None."""
         check(self.lib.mate_engine_enable_reward_rows(self._h, None))
-        self.camera_reward_rows = self.target_reward_rows = self.camera_reward_terms = self.target_reward_terms = None
-        self.reward_coefficients = None
+        self._clear_reward_rows()
 
     # ------------------------------------------------------------------ FrameSkip fragments behind the fused K-frame launch
     FRAGMENT_REWARDS = ('camera_team_reward', 'target_team_reward', 'normalized_target_team_reward', 'normalized_camera_team_reward')
@@ -738,10 +719,7 @@ class Engine:
 
     def _fragment_config(self, team, shaping, relative_coordinates, rescaled_observation, dtype, out):
         """(MateFragmentRows, what must stay alive during the call, a mask term has a non-zero coefficient) for `out`: the dict of output tensors."""
-        from mate_amd._native import MateFragmentRows
-        from mate_amd.spaces import fragment_column_table
-        code = {'camera': 0, 'target': 1}.get(team, team)
-        assert code in (0, 1), f"team = {team!r}: 'camera' or 'target'"
+        code = _team_code(team)
         assert dtype in (torch.float32, torch.float64)
         name = ('camera', 'target')[code]
         cfg, keep = MateFragmentRows(), []
@@ -758,7 +736,7 @@ class Engine:
             cfg.coefficients = coefficients.ctypes.data
             keep.append(coefficients)
             masks = coefficients[5 if code == 0 else 7] != 0.0
-        columns = fragment_column_table(name, self.num_cameras, self.num_targets, self.num_obstacles, relative_coordinates, rescaled_observation)
+        columns = spaces.fragment_column_table(name, self.num_cameras, self.num_targets, self.num_obstacles, relative_coordinates, rescaled_observation)
         if columns is not None:
             columns = [np.ascontiguousarray(c) for c in columns]
             cfg.column_sub, cfg.column_flag, cfg.column_scale, cfg.column_bias = (c.ctypes.data for c in columns)
@@ -766,7 +744,7 @@ class Engine:
         return cfg, keep, bool(masks)
 
     def _fragment_outputs(self, team, shaped, dtype):
-        code = {'camera': 0, 'target': 1}.get(team, team)
+        code = _team_code(team)
         N, A, D = self.num_envs, (self.num_cameras, self.num_targets)[code], (self.camera_obs_dim, self.target_obs_dim)[code]
         with torch.cuda.device(self.device):
             return {
@@ -818,10 +796,9 @@ class Engine:
         self.fragment_obs, self.fragment_rewards, self.fragment_done = out['obs'], out['rewards'], out['done']
         self.fragment_frames, self.fragment_info, self.fragment_shaped = out['frames'], out['info'], out['shaped']
         self.fragment_team, self.fragment_frame_skip, self._fragment_masks = cfg.team, frame_skip, masks
-        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None
+        self._clear_first_rows()
         check(self.lib.mate_engine_enable_first_rows(self._h, None))
         if first_rows:
-            from mate_amd._native import MateFirstRows
             with torch.cuda.device(self.device):
                 rows, scalars = torch.zeros_like(out['obs']), torch.full((self.num_envs, 8), 2.0, dtype=torch.float32, device=self.device)
                 final = torch.zeros_like(out['obs']) if final_obs else None
@@ -835,10 +812,7 @@ class Engine:
     def disable_fragment_rows(self):
         """Detach the fragment launch (and the first rows with it): rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
         check(self.lib.mate_engine_enable_fragment_rows(self._h, None))
-        self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
-        self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
-        self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None
-        self.fragment_frame_skip, self._fragment_masks = 0, False
+        self._clear_fragment_rows()
 
     @property
     def fragment_restarted(self):
@@ -865,7 +839,7 @@ class Engine:
         `scalars` [K, N, 8] f32, `masks` [K, N, mask_words] int32 (needed by num_tracked / is_tracked).  K = 1 over the engine's
         per-step tensors gives the transformed reset() observation.  `out`: a dict of tensors to write (as returned); default: new
         ones.  Returns {'obs', 'rewards', 'info', 'done', 'frames', 'shaped'}."""
-        code = {'camera': 0, 'target': 1}.get(team, team)
+        code = _team_code(team)
         if rows.dim() == 3:
             rows, scalars, masks = rows[None], scalars[None], (masks[None] if masks is not None else None)
         K = int(rows.shape[0])
@@ -875,12 +849,9 @@ class Engine:
         if out is None:
             out = self._fragment_outputs(code, shaping is not None, dtype)
         cfg, keep, _ = self._fragment_config(code, shaping, relative_coordinates, rescaled_observation, dtype, out)
-        io = MateStepIO()
-        setattr(io, ('camera_obs_dev', 'target_obs_dev')[code], rows.data_ptr())
-        io.scalars_dev = scalars.data_ptr()
         if masks is not None:
             assert masks.shape == (K, N, self.layout.mask_words) and masks.dtype == torch.int32 and masks.is_contiguous() and masks.device == self.device
-            io.masks_dev = masks.data_ptr()
+        io = self._bind_outputs(MateStepIO(), rows if code == 0 else None, rows if code == 1 else None, scalars, masks)
         torch.cuda.current_stream(self.device).synchronize()
         check(self.lib.mate_engine_fragment_rows(self._h, ctypes.byref(cfg), ctypes.byref(io), K, self._stream()))
         return out
@@ -918,20 +889,15 @@ class Engine:
                                                     ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(action_mask.data_ptr()), flags))
         ptr, code = ctypes.c_void_p(), ctypes.c_int32()
         check(self.lib.mate_engine_selection_actions(self._h, ctypes.byref(ptr), ctypes.byref(code)))
-
-        class _Owned:      # the engine-owned joint action as a zero-copy tensor (the engine outlives it: the tensor keeps `self`)
-            def __init__(view, owner):
-                view.owner = owner
-                view.__cuda_array_interface__ = {'shape': (N * Nc * 2,), 'typestr': '<f8' if code.value == 1 else '<f4', 'data': (ptr.value, False), 'version': 2}
-        self.selection_actions = torch.as_tensor(_Owned(self), device=self.device).view(N, Nc, 2)
+        # the engine-owned joint action as a zero-copy tensor (the engine outlives it: the tensor keeps `self`)
+        self.selection_actions = torch.as_tensor(_EngineOwned(self, ptr.value, N * Nc * 2, '<f8' if code.value == 1 else '<f4'), device=self.device).view(N, Nc, 2)
         self.selection, self.selection_metrics, self.selection_frames, self.action_mask = selection, metrics, frames, action_mask
         self.multi_selection, self.selection_accumulate = bool(multi_selection), bool(accumulate)
         return selection
 
     def disable_selection(self):
         check(self.lib.mate_engine_disable_selection(self._h))
-        self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
-        self.multi_selection = None
+        self._clear_selection()
 
     def step_selected(self, policy_tape=None, tape_ct=None, tape_goal=None, auto_reset=True):
         """One frame of HierarchicalCamera over MultiCamera(target_agent=GreedyTargetAgent()): the executor turns `Engine.selection` into
@@ -963,7 +929,7 @@ class Engine:
                 self._staged['state'] = view
             else:
                 setattr(self, name, view)
-        self.__dict__.pop('_random_io', None)
+        self._forget_calls()
 
     _NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32}
 
@@ -982,7 +948,7 @@ class Engine:
 
     def state_dict_from(self, flat):
         """state_dict() of an already fetched [N, export_width] f64 array."""
-        if getattr(self, '_export_slices', None) is None:
+        if self._export_slices is None:
             self._export_slices = [(name, off, int(np.prod(shape)) if shape else 1, (self.num_envs,) + tuple(shape))
                                    for name, (off, shape) in self.export_fields.items()]
         return {name: flat[:, off:off + n].reshape(shape) for name, off, n, shape in self._export_slices}
@@ -1015,6 +981,12 @@ class Engine:
         check(self.lib.mate_engine_enable_outer_boundary(self._h, ctypes.byref(cap)))
         self.outer_capacity = cap.value
 
+    def need_outer_boundary(self):
+        """enable_outer_boundary() unless it is on already: built at every reset from now on, and once now for the running episodes."""
+        if not self.outer_capacity:
+            self.enable_outer_boundary()
+            self.rebuild_luts()
+
     def lut_read(self, env, camera, outer=False):
         cap = self.outer_capacity if outer else self.layout.lut_capacity
         phis, rhos = np.zeros(cap), np.zeros(cap)
@@ -1036,7 +1008,7 @@ class Engine:
         rebuild_luts since."""
         masks = self.masks if masks is None else masks
         assert masks.dtype == torch.int32 and masks.is_contiguous() and masks.shape == (self.num_envs, self.layout.mask_words)
-        if getattr(self, '_softcov', None) is None:
+        if self._softcov is None:
             self._softcov = (torch.empty((self.num_envs, self.num_cameras, self.num_targets), dtype=torch.float64, device=self.device),
                              torch.empty((self.num_envs, self.num_cameras), dtype=torch.float64, device=self.device))
         matrix, scores = self._softcov
@@ -1151,8 +1123,7 @@ class Stepper:
             assert self.auto_reset == 1, "versus='selection': finished environments restart behind their fragment (auto_reset = True)"
             assert self.frame_skip == 1 or eng.selection_accumulate, 'frame_skip > 1 sums the metrics over the frames: enable_selection(accumulate=True)'
             versus, cam_act, tgt_act = None, None, None
-        self.versus = {'camera': 0, 'target': 1, None: None}.get(versus, versus)
-        assert self.versus in (None, 0, 1)
+        self.versus = None if versus is None else _team_code(versus)
         if self.versus == 0:
             tgt_act = None
         elif self.versus == 1:
@@ -1167,14 +1138,10 @@ class Stepper:
             # (the reward launch reads the last frame's masks; the fragment launch every frame's, for a mask term)
             shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus)
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
-            self.io.camera_obs_dev = buf['camera_obs'].data_ptr() if eng.num_cameras else None
-            self.io.target_obs_dev = buf['target_obs'].data_ptr()
-            self.io.scalars_dev = buf['scalars'].data_ptr()
-            self.io.masks_dev = buf['masks'].data_ptr() if shaped else None
+            eng._bind_outputs(self.io, buf['camera_obs'], buf['target_obs'], buf['scalars'], buf['masks'] if shaped else None)
             self.outputs = (buf['camera_obs'][:self.frame_skip], buf['target_obs'][:self.frame_skip], buf['scalars'][:self.frame_skip])
             self.keep = (self.keep, buf)
         self.ref = ctypes.byref(self.io)
-        self.graph = None
         self._phase = 0                                   # steps into the current reset interval (graphs hold whole intervals)
         self.warmup_steps = self.auto_reset if self.graph_steps > 0 else 0      # real steps the constructor runs (see the class note)
         if self.selection and self.frame_skip > 1:
@@ -1201,7 +1168,7 @@ class Stepper:
             if eng.selection_accumulate:
                 eng.selection_metrics.zero_()
                 eng.selection_frames.zero_()
-                if eng.reward_coefficients is not None and getattr(eng, 'reward_accumulate', False):
+                if eng.reward_coefficients is not None and eng.reward_accumulate:
                     for rows in (eng.camera_reward_rows, eng.target_reward_rows):
                         if rows is not None:
                             rows.zero_()
@@ -1264,7 +1231,6 @@ class Stepper:
         try:
             self.close()
         except Exception as exc:      # an engine left in device-tick mode refuses rollouts / seed / import_state: say so
-            import warnings
             warnings.warn(f'Stepper.close() failed while the stepper was collected: {exc!r}; the engine may still count steps on the device', RuntimeWarning)
 
 
@@ -1326,7 +1292,6 @@ class EngineGroups:
         or reset afterwards.  A group's engine moves to a stream that knows nothing of the work queued on its previous one (a
         reset, an import), so the device is synchronised before the first trial and at every change of stream; the engine's buffers
         were allocated on the first stream and live as long as the engine, so the caching allocator never hands them out again."""
-        import time
         times = []
         torch.cuda.synchronize(self.device)           # everything queued on the groups' present streams is complete before one of them changes
         for g in range(1, self.groups):

@@ -11,8 +11,9 @@ import torch
 
 from mate_amd import constants as consts
 from mate_amd import spaces
+from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
-from mate_amd.engine import Engine
+from mate_amd.engine import SCALAR_NAMES, TARGET_AGENTS, Engine, fragment_coefficient_table
 from mate_amd.utils import Message, Team, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
@@ -139,9 +140,8 @@ class CameraView(_EntityView):
 
     def _table(self, outer=False):
         engine = self._env.engine
-        if outer and not getattr(engine, 'outer_capacity', 0):
-            engine.enable_outer_boundary()      # built from now on at every reset; build it once for the running episode
-            engine.rebuild_luts()
+        if outer:
+            engine.need_outer_boundary()
         return engine.lut_read(0, self.index, outer=outer)
 
     def sight_range_at(self, angle, outer=False):
@@ -240,6 +240,10 @@ class _ScenarioMixin:
     camera_observation_dim = property(lambda self: self.camera_observation_space.shape[-1])
     target_observation_dim = property(lambda self: self.target_observation_space.shape[-1])
 
+    def _need_policies(self):
+        if not self._policies_on:      # (enable_greedy_policies sets it)
+            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+
     def _setup_spaces(self):
         Nc, Nt, No = self.num_cameras, self.num_targets, self.num_obstacles
 
@@ -313,9 +317,10 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self.coverage_rate = self.real_coverage_rate = self.mean_transport_rate = 0.0
         self.num_delivered_cargoes = 0
         self.episode_step = 0
-        self._cache = None
-        self._masks = None
-        self._np_random = None
+        self._cache = self._masks = self._np_random = None
+        self._policies_on = False                         # (enable_greedy_policies)
+        self.target_dones, self._last_goals = np.zeros(Nt, dtype=bool), None                  # (reset, _finish_step)
+        self._last_episode_rewards = self._last_step_rewards = (0.0, 0.0)
         self.seed(0)
 
     # ------------------------------------------------------------------ state access
@@ -442,13 +447,12 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         whose observations the agents first act on.  target_agent='heuristic': HeuristicTargetAgent plays the targets
         (Engine.set_target_opponent)."""
         self.engine.enable_policies(target_agent=target_agent)
-        self._greedy = True
+        self._policies_on = True
 
     def step_greedy(self):
         """`env.step(mate.group_step(...))` of both teams with the reference's Greedy agents computed on the device
         (mate/agents/greedy.py through Engine.step_greedy); same return value as step()."""
-        if not getattr(self, '_greedy', False):
-            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+        self._need_policies()
         tape_ct, tape_goal = self._tapes()
         self.engine.step_greedy(tape_ct=tape_ct, tape_goal=tape_goal, auto_reset=False)
         return self._finish_step()
@@ -457,8 +461,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         """`mate.MultiCamera(env, target_agent=GreedyTargetAgent()).step(joint_action)` for team = 'camera' (or mate_amd.Team.CAMERA),
         `mate.MultiTarget(env, camera_agent=GreedyCameraAgent()).step(...)` for 'target' (mate/wrappers/single_team.py:245-264): the
         caller's team acts, the greedy opponents act on the device.  Same return value as step() (both teams' halves)."""
-        if not getattr(self, '_greedy', False):
-            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+        self._need_policies()
         team = getattr(team, 'name', team)
         team = team.lower() if isinstance(team, str) else ('camera', 'target')[int(team)]
         assert team in ('camera', 'target'), f'Invalid team {team!r}.'
@@ -520,7 +523,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         f = self._fields()
         Nc, Nt, No = self.num_cameras, self.num_targets, self.num_obstacles
         area = self.config['camera']['min_viewing_angle'] * self.config['camera']['max_sight_range'] ** 2 if Nc else 0.0
-        last = getattr(self, '_last_step_rewards', (0.0, 0.0))
+        last = self._last_step_rewards
         snap = {
             'cam_xy': np.stack([f['cam_x'], f['cam_y']], axis=-1).reshape(Nc, 2), 'cam_phi': f['cam_phi'].copy(), 'cam_theta': f['cam_theta'].copy(),
             'cam_sight': np.sqrt(area / f['cam_theta']) if Nc else np.zeros(0),
@@ -626,12 +629,10 @@ def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, 
                        shared_field_of_view=None, camera_selection=None, target_agent='greedy'):
     """The argument rules of BatchedMultiAgentTracking(frame_skip=K, learner=...), checked ahead of everything that needs a GPU.
     Returns None without `frame_skip`, else {'frame_skip', 'learner', 'shaping'}: the learner's (coefficients, reduction) or None."""
-    from mate_amd.engine import TARGET_AGENTS
     assert target_agent in TARGET_AGENTS, f'target_agent = {target_agent!r}: one of {TARGET_AGENTS}'
     if frame_skip is None:
         assert learner is None, "learner = ... belongs to frame_skip = K (the fused learner-versus-greedy fragments)"
         return None
-    from mate_amd.engine import fragment_coefficient_table
     assert isinstance(frame_skip, (int, np.integer)) and not isinstance(frame_skip, bool) and frame_skip >= 1, \
         f'frame_skip = {frame_skip!r}: a positive number of frames (examples/utils/wrappers.py FrameSkip)'
     assert learner in ('camera', 'target'), f"frame_skip needs learner = 'camera' or 'target' (got {learner!r}): the other team is the greedy agents"
@@ -688,6 +689,9 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  learner=None, first_rows=False, target_agent='greedy', **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
+        self._policies_on = False                         # (enable_greedy_policies)
+        self._target_shapers = {}                         # (auxiliary_target_rewards: one shaper per (coefficients, reduction))
+        self._fragment_live = None                        # (_fragment_reset: the scalar record that says which environments were reset)
         self._fragment = fragment_arguments(self.config, frame_skip, learner, camera_reward_shaping, target_reward_shaping, enhanced_observation,
                                             shared_field_of_view, camera_selection, target_agent)
         assert target_agent == 'greedy' or not any(team in ('both', 'target') for team in (enhanced_observation, shared_field_of_view)), \
@@ -727,7 +731,6 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self.state_space = consts.normalized_state_space_of(self.num_cameras, self.num_targets, self.num_obstacles)
         # AuxiliaryCameraRewards / AuxiliaryTargetRewards (the last wrapper of the example trainers' chains) as a launch attached to the
         # engine: (coefficients, reduction) per team, checked now, attached behind the first reset() (Engine.enable_reward_rows)
-        from mate_amd.engine import reward_coefficient_table
         self._reward_shaping = {team: (dict(spec[0]), spec[1]) for team, spec in (('camera', camera_reward_shaping), ('target', target_reward_shaping))
                                 if spec is not None}
         for team, spec in self._reward_shaping.items():
@@ -769,7 +772,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self.engine.enable_reward_rows(camera=self._reward_shaping.get('camera'), target=self._reward_shaping.get('target'), dtype=self._reward_dtype)
         if self.camera_selection and self.engine.selection is None:
             self.engine.enable_selection(self.camera_selection == 'multi')
-        for shaper in self.__dict__.get('_target_shapers', {}).values():
+        for shaper in self._target_shapers.values():
             shaper.observe_reset()
         if self._fragment:
             return self._fragment_reset(env_mask)
@@ -784,13 +787,13 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             eng.enable_fragment_rows(spec['learner'], spec['frame_skip'], shaping=spec['shaping'], dtype=spec['dtype'], first_rows=spec['first_rows'],
                                      final_obs=spec['first_rows'], **transform)
         rows = eng.camera_obs if spec['learner'] == 'camera' else eng.target_obs
-        if '_live' not in spec:      # (a scalar record that says "this frame ran": the step's own may be older than the reset)
-            spec['_live'] = torch.zeros((self.num_envs, 8), dtype=torch.float32, device=self.device)
+        if self._fragment_live is None:      # (a scalar record that says "this frame ran": the step's own may be older than the reset)
+            self._fragment_live = torch.zeros((self.num_envs, 8), dtype=torch.float32, device=self.device)
         if env_mask is None:
-            spec['_live'][:, 2] = 0.0
+            self._fragment_live[:, 2] = 0.0
         else:
-            spec['_live'][:, 2] = torch.where(env_mask.to(device=self.device).bool().reshape(-1), 0.0, 2.0)
-        eng.fragment_rows(spec['learner'], rows, spec['_live'], out={'obs': eng.fragment_obs}, **transform)
+            self._fragment_live[:, 2] = torch.where(env_mask.to(device=self.device).bool().reshape(-1), 0.0, 2.0)
+        eng.fragment_rows(spec['learner'], rows, self._fragment_live, out={'obs': eng.fragment_obs}, **transform)
         return eng.fragment_obs
 
     def step_fragment(self, joint_action):
@@ -818,11 +821,17 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             info.update(restarted=eng.fragment_restarted, final_observation=eng.fragment_final_obs)
         return eng.fragment_obs, rewards, eng.fragment_done > 0, info
 
+    @staticmethod
+    def _columns(s):
+        """(rewards, done column, info) of scalar records [..., 8], by SCALAR_NAMES."""
+        col = dict(zip(SCALAR_NAMES, s.unbind(-1)))
+        info = {key: col[key] for key in ('coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'num_delivered_cargoes')}
+        info['normalized_raw_reward'] = col['normalized_target_team_reward']
+        return (col['camera_team_reward'], col['target_team_reward']), col['done'], info
+
     def _result(self):
-        s = self.engine.scalars
-        info = {'coverage_rate': s[:, 3], 'real_coverage_rate': s[:, 4], 'mean_transport_rate': s[:, 5],
-                'num_delivered_cargoes': s[:, 6], 'normalized_raw_reward': s[:, 7]}
-        return (self.engine.camera_obs, self.engine.target_obs), (s[:, 0], s[:, 1]), s[:, 2] > 0, info
+        rewards, done, info = self._columns(self.engine.scalars)
+        return (self.engine.camera_obs, self.engine.target_obs), rewards, done > 0, info
 
     def step(self, action):
         cam_act, tgt_act = action
@@ -836,10 +845,9 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def _rollout_result(self, out):
         cam, tgt, s = out
-        info = {'coverage_rate': s[..., 3], 'real_coverage_rate': s[..., 4], 'mean_transport_rate': s[..., 5],
-                'num_delivered_cargoes': s[..., 6], 'normalized_raw_reward': s[..., 7],
-                'skipped': s[..., 2] == 2}          # slots after the end of an episode inside the launch (no step, stale rows)
-        return (cam, tgt), (s[..., 0], s[..., 1]), s[..., 2] == 1, info
+        rewards, done, info = self._columns(s)
+        info['skipped'] = done == 2          # slots after the end of an episode inside the launch (no step, stale rows)
+        return (cam, tgt), rewards, done == 1, info
 
     def rollout_random(self, steps):
         """`steps` env.step(random action) iterations in ONE launch (the fastest flow, profiles/HISTORY.md 3.1b): every tensor of
@@ -849,8 +857,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     def rollout_greedy(self, steps):
         """`steps` iterations of mate.group_step with the reference's Greedy camera / target agents + env.step in ONE
         launch (agents on the device, profiles/HISTORY.md 3.1c)."""
-        if not getattr(self, '_policies_on', False):
-            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+        self._need_policies()
         return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def enable_greedy_policies(self):
@@ -862,16 +869,14 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         camera_agent=GreedyCameraAgent()) for team = 'target' (mate/wrappers/single_team.py:281-306): the caller acts for
         `team`, the greedy agents of the other team act on the device.  step()'s full result (both teams' observations
         and rewards; a single-team learner reads its own half)."""
-        if not getattr(self, '_policies_on', False):
-            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+        self._need_policies()
         self.engine.step_versus_greedy(team, joint_action, auto_reset=self.auto_reset)
         return self._result()
 
     def rollout_versus_greedy(self, team, joint_action, frame_skip):
         """FrameSkip(MultiCamera | MultiTarget, frame_skip) in one launch (examples/utils/wrappers.py:301-323): rollout-shaped
         result; `rewards.sum(0)` is the wrapper's reward, `done.any(0)` its done."""
-        if not getattr(self, '_policies_on', False):
-            raise RuntimeError('enable_greedy_policies() must precede the reset() the agents first act on')
+        self._need_policies()
         return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def step_selected(self, selection, **replay):
@@ -906,8 +911,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     def masks(self):
         return self.engine.unpack_masks()
 
-    AUXILIARY_REWARD_KEYS = ('raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'soft_coverage_score',
-                             'num_tracked', 'baseline')
+    AUXILIARY_REWARD_KEYS = CAMERA_REWARD_KEYS
 
     def auxiliary_camera_rewards(self, coefficients, reduction='none'):
         """Per-camera shaped rewards of the last step, the reference's AuxiliaryCameraRewards wrapper
@@ -917,9 +921,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         Returns a [num_envs, num_cameras] tensor on the GPU (a handful of elementwise ops on the [N, 8] step record
         and the packed masks: nothing here touches the observation bytes).  `soft_coverage_score` (:181-239) is one more
         small kernel over the outer occlusion boundary, which the engine builds from the first request on."""
-        assert set(self.AUXILIARY_REWARD_KEYS).issuperset(coefficients.keys()), (
-            f'The coefficient mapping only accepts keys in {self.AUXILIARY_REWARD_KEYS}. Got list(coefficients.keys()) = {list(coefficients.keys())}.')
-        assert reduction in ('mean', 'sum', 'max', 'min', 'none'), f'Invalid reduction method {reduction}.'
+        reward_coefficient_table('camera', coefficients, reduction)
         s = self.engine.scalars.double()
         N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
         bits = torch.arange(Nc * Nt, device=self.device)
@@ -929,13 +931,10 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  'real_coverage_rate': s[:, 4:5].expand(N, Nc), 'mean_transport_rate': s[:, 5:6].expand(N, Nc),
                  'num_tracked': seen.sum(dim=2).double(), 'baseline': torch.ones((N, Nc), dtype=torch.float64, device=self.device)}
         if 'soft_coverage_score' in coefficients:
-            if not getattr(self.engine, 'outer_capacity', 0):
-                self.engine.enable_outer_boundary()     # built at every reset from now on; once now for the running episodes
-                self.engine.rebuild_luts()
+            self.engine.need_outer_boundary()
             terms['soft_coverage_score'] = self.engine.soft_coverage()[1]
         reward = torch.zeros((N, Nc), dtype=torch.float64, device=self.device)
         for key, coefficient in coefficients.items():
-            assert isinstance(coefficient, (int, float)), 'only constant coefficients are supported on the batched path'
             reward = reward + float(coefficient) * terms[key]
         if reduction != 'none':
             shared = {'mean': reward.mean(dim=1), 'sum': reward.sum(dim=1), 'max': reward.max(dim=1).values, 'min': reward.min(dim=1).values}[reduction]
@@ -948,11 +947,9 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         it after every step (its `sparse_delivery` term compares the goals with those of the previous call; see
         mate_amd/auxiliary_rewards.py)."""
         key = (tuple(sorted(coefficients.items())), reduction)
-        shapers = self.__dict__.setdefault('_target_shapers', {})
-        if key not in shapers:
-            from mate_amd.auxiliary_rewards import AuxiliaryTargetRewards
-            shapers[key] = AuxiliaryTargetRewards(self.engine, coefficients, reduction)
-        return shapers[key]()
+        if key not in self._target_shapers:
+            self._target_shapers[key] = AuxiliaryTargetRewards(self.engine, coefficients, reduction)
+        return self._target_shapers[key]()
 
     def state_dict(self):
         return self.engine.state_dict()

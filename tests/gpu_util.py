@@ -3,7 +3,7 @@ import numpy as np
 import torch
 
 import golden_util as G
-from mate_amd.config import read_config
+from mate_amd.config import read_config, scenario_tables
 from mate_amd.engine import Engine
 
 STATE_KEYS = ['cam_x', 'cam_y', 'obs_x', 'obs_y', 'obs_radius', 'tgt_capacity', 'camera_obstacle_view_mask', 'cam_phi',
@@ -52,18 +52,11 @@ def load_fixture_state(eng, fx):
 
 def oracle_proto_from_config(cfg, O):
     """Oracle prototype env carrying the scenario (ranges, reward scales, ...)."""
-    cam, tgt, obs = cfg.get('camera', {}), cfg['target'], cfg.get('obstacle', {})
-
-    def ranges(sub):
-        rows = [[x, x, y, y] for x, y in sub.get('location', [])] + [list(r) for r in sub.get('location_random_range', [])]
-        return np.asarray(rows, dtype=np.float64).reshape(-1, 4)
-
-    rc, rt, ro = ranges(cam), ranges(tgt), ranges(obs)
-    env = O.OracleEnv(len(rc), len(rt), len(ro))
-    env.set('cam_range', rc); env.set('tgt_range', rt); env.set('obs_range', ro)
-    rr = obs.get('radius_random_range', [obs.get('radius', 0.0)] * 2)
-    env.set('obs_radius_range', rr)
-    env.set('transmittance', obs.get('transmittance', 0.0))
+    tgt, tables = cfg['target'], scenario_tables(cfg)
+    env = O.OracleEnv(tables['num_cameras'], tables['num_targets'], tables['num_obstacles'])
+    env.set('cam_range', tables['camera_ranges']); env.set('tgt_range', tables['target_ranges']); env.set('obs_range', tables['obstacle_ranges'])
+    env.set('obs_radius_range', tables['obstacle_radius_range'])
+    env.set('transmittance', tables['transmittance'])
     env.set('max_episode_steps', cfg['max_episode_steps'])
     env.set('sparse_reward', cfg['reward_type'] == 'sparse')
     env.set('num_cargoes_per_target', cfg['num_cargoes_per_target'])
@@ -74,27 +67,23 @@ def oracle_proto_from_config(cfg, O):
     freight = np.ceil(2000.0 / tgt['step_size'])
     bounty = np.ceil(freight * max(0.0, cfg['bounty_factor']))
     env.set('freight_scale', freight); env.set('bounty_scale', bounty); env.set('reward_scale', freight + bounty)
-    env.set('max_target_team_episode_reward', (freight + bounty) * cfg['num_cargoes_per_target'] * len(rt))
-    env.set('cfg_cam_radius', cam.get('radius', 40.0)); env.set('cfg_cam_min_viewing_angle', cam.get('min_viewing_angle', 90.0))
-    env.set('cfg_cam_max_sight_range', cam.get('max_sight_range', 500.0)); env.set('cfg_cam_rotation_step', cam.get('rotation_step', 5.0))
-    env.set('cfg_cam_zooming_step', cam.get('zooming_step', 2.5))
+    env.set('max_target_team_episode_reward', (freight + bounty) * cfg['num_cargoes_per_target'] * tables['num_targets'])
+    for key, value in tables['camera'].items():      # radius, min_viewing_angle, max_sight_range, rotation_step, zooming_step
+        env.set('cfg_cam_' + key, value)
     return env
 
 
 def oracle_load_engine_state(oenv, sd, i, cfg):
     """Copy environment i of an Engine.state_dict() into an oracle env."""
-    cam = cfg.get('camera', {})
+    cam = scenario_tables(cfg)['camera']
     Nc = oenv.Nc
     for k in STATE_KEYS:
         oenv.set(k, sd[k][i])
-    oenv.set('cam_radius', np.full(Nc, cam.get('radius', 40.0)))
-    oenv.set('cam_min_viewing_angle', np.full(Nc, cam.get('min_viewing_angle', 90.0)))
-    oenv.set('cam_max_sight_range', np.full(Nc, cam.get('max_sight_range', 500.0)))
-    oenv.set('cam_rotation_step', np.full(Nc, cam.get('rotation_step', 5.0)))
-    oenv.set('cam_zooming_step', np.full(Nc, cam.get('zooming_step', 2.5)))
+    for key, value in cam.items():      # radius, min_viewing_angle, max_sight_range, rotation_step, zooming_step
+        oenv.set('cam_' + key, np.full(Nc, value))
     oenv.set('tgt_step_size', cfg['target']['step_size'] / sd['tgt_capacity'][i])
     oenv.set('tgt_sight_range', np.full(oenv.Nt, cfg['target']['sight_range']))
-    theta_min, rmax = cam.get('min_viewing_angle', 90.0), cam.get('max_sight_range', 500.0)
+    theta_min, rmax = cam['min_viewing_angle'], cam['max_sight_range']
     if Nc:
         oenv.set('cam_sight', np.sqrt(theta_min * rmax * rmax / sd['cam_theta'][i]))
     oenv.set('tick', sd['tick'][i]); oenv.set('episode', sd['episode'][i])

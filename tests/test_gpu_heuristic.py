@@ -86,8 +86,8 @@ def test_multi_camera_versus_heuristic_targets_closed_loop(name):
 def _restatement_inputs(eng, cfg):
     """What the agents of the NEXT step act on, from the engine: the state and the engine's mask words as the last call left them."""
     sd = eng.state_dict()
-    cam = cfg.get('camera', {})
-    theta_min, rmax = cam.get('min_viewing_angle', 90.0), cam.get('max_sight_range', 500.0)
+    cam = U.scenario_tables(cfg)['camera']
+    theta_min, rmax = cam['min_viewing_angle'], cam['max_sight_range']
     sensed = eng.unpack_masks()['target_camera_view_mask']
     with np.errstate(divide='ignore'):
         sight = np.sqrt(theta_min * rmax * rmax / sd['cam_theta'])

@@ -258,10 +258,8 @@ def _track_batch(sd, view, sel, c):
 
 
 def _constants_of(eng):
-    cam = eng.config.get('camera', {})
-    mva, msr = float(cam.get('min_viewing_angle', 90.0)), float(cam.get('max_sight_range', 500.0))
-    return dict(min_viewing_angle=mva, max_sight_range=msr, rotation_step=float(cam.get('rotation_step', 5.0)),
-                zooming_step=float(cam.get('zooming_step', 2.5)), area=mva * np.square(msr))
+    cam = {key: value for key, value in U.scenario_tables(eng.config)['camera'].items() if key != 'radius'}
+    return dict(cam, area=cam['min_viewing_angle'] * np.square(cam['max_sight_range']))
 
 
 def _bits_of(words, Nt):

@@ -227,9 +227,7 @@ def host_state(eng, cfg):
     """state() re-assembled on the host from Engine.state_dict() (f64), in the reference's order (environment.py:894-906)."""
     sd = eng.state_dict()
     N, Nc, Nt, No = eng.num_envs, eng.num_cameras, eng.num_targets, eng.num_obstacles
-    cam = cfg.get('camera', {})
-    radius, theta_min, rmax = cam.get('radius', 40.0), cam.get('min_viewing_angle', 90.0), cam.get('max_sight_range', 500.0)
-    rot, zoom = cam.get('rotation_step', 5.0), cam.get('zooming_step', 2.5)
+    radius, theta_min, rmax, rot, zoom = U.scenario_tables(cfg)['camera'].values()      # (the order of CAMERA_DEFAULTS)
     rows = np.zeros((N, eng.state_dim))
     rows[:, 0:3] = (Nc, Nt, No)
     rows[:, 4:12] = 925.0 * np.array([1, 1, -1, 1, -1, -1, 1, -1])

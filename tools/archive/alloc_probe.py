@@ -36,7 +36,7 @@ for i, t in enumerate(times):
 a, b = engines[0], engines[-1]
 a._rollout, b._rollout = b._rollout, a._rollout
 for e in (a, b):
-    e._rollout.pop('_calls', None)
+    e._forget_calls()
 times = [[] for _ in engines]
 for _ in range(10):
     for i, eng in enumerate(engines):

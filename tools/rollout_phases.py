@@ -5,7 +5,7 @@ import ctypes, os, sys
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mate_amd.config import read_config  # noqa: E402
+from mate_amd.config import read_config, scenario_tables  # noqa: E402
 from mate_amd.engine import Engine  # noqa: E402
 workload = sys.argv[1] if len(sys.argv) > 1 else 'MATE-4v8-9.yaml'
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
@@ -51,8 +51,8 @@ sd = eng.state_dict()
 cx, cy, phi, th = sd['cam_x'], sd['cam_y'], sd['cam_phi'], sd['cam_theta']
 tx, ty = sd['tgt_x'], sd['tgt_y']
 cfg = read_config(workload)
-cam = cfg.get('camera', {})
-area = cam.get('min_viewing_angle', 90.0) * cam.get('max_sight_range', 500.0) ** 2
+cam = scenario_tables(cfg)['camera']
+area = cam['min_viewing_angle'] * cam['max_sight_range'] ** 2
 sight = np.sqrt(area / th)
 dx, dy = tx[:, None, :] - cx[:, :, None], ty[:, None, :] - cy[:, :, None]
 dist = np.hypot(dx, dy)
@@ -70,7 +70,7 @@ print('  corr(view, lookups) %.2f  corr(view, pairs in range) %.2f  corr(total, 
 # collision candidates: targets within one step of an obstacle / camera circle
 ox, oy, orad = sd['obs_x'], sd['obs_y'], sd['obs_radius']
 d_to = np.hypot(tx[:, :, None] - ox[:, None, :], ty[:, :, None] - oy[:, None, :]) - orad[:, None, :]
-d_tc = np.hypot(tx[:, :, None] - cx[:, None, :], ty[:, :, None] - cy[:, None, :]) - cam.get('radius', 40.0)
+d_tc = np.hypot(tx[:, :, None] - cx[:, None, :], ty[:, :, None] - cy[:, None, :]) - cam['radius']
 near = (d_to < 20.0).sum(axis=(1, 2)) + (d_tc < 20.0).sum(axis=(1, 2))
 print('  corr(targets phase, near pairs) %.2f   corr(total, near pairs) %.2f' % (np.corrcoef(t[:, 2], near)[0, 1], np.corrcoef(tot, near)[0, 1]))
 for k in range(0, 6):

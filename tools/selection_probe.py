@@ -18,7 +18,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mate_amd.config import read_config  # noqa: E402
+from mate_amd.config import read_config, scenario_tables  # noqa: E402
 from mate_amd.engine import Engine  # noqa: E402
 
 
@@ -26,9 +26,8 @@ def torch_track(eng, state, selection, view, out):
     """HierarchicalCamera.track over the batch in torch: state = export_state rows, selection / view [N, Nc, Nt] bool -> out [N, Nc, 2]."""
     f = eng.export_fields
     col = lambda name: state[:, f[name][0]:f[name][0] + eng.num_cameras if name.startswith('cam') else f[name][0] + eng.num_targets]  # noqa: E731
-    cam = eng.config.get('camera', {})
-    mva, msr = float(cam.get('min_viewing_angle', 90.0)), float(cam.get('max_sight_range', 500.0))
-    rot, zoom = float(cam.get('rotation_step', 5.0)), float(cam.get('zooming_step', 2.5))
+    cam = scenario_tables(eng.config)['camera']
+    mva, msr, rot, zoom = cam['min_viewing_angle'], cam['max_sight_range'], cam['rotation_step'], cam['zooming_step']
     valid = (selection & view).to(torch.float64)
     n = valid.sum(-1)
     nn = n.clamp(min=1.0)
