@@ -17,7 +17,7 @@ import collections
 
 import numpy as np
 
-Case = collections.namedtuple('Case', 'shape n steps seed first why')
+Case = collections.namedtuple('Case', 'shape n steps seed first why target_box', defaults=(None,))
 
 CASES = [
     # NK = 65: the smallest scenario past 64 circles; camera 0 is circle 64, the first one the two LDS near words cannot name
@@ -47,10 +47,50 @@ GREEDY_CASES = [
     Case((9, 2, 0), 24, 40, 4201, 31, 'greedy, two message rounds'),
     Case((16, 16, 9), 8, 30, 4202, 32, 'greedy, four message rounds, Nt = 16'),
 ]
+# The attached launches (selection_kernel, reward_rows_kernel, fragment_rows_kernel, heuristic_drift_kernel, state_rows_kernel) read
+# camera_target_view_mask from bit 0 of the mask words: camera c's row is bits c * Nt .. c * Nt + Nt - 1, so with Nt in {1, 2, 4, 8, 16}
+# -- every shipped scenario -- no row crosses a 32-bit word.  These cases have rows that do (straddling_rows), with every target in a
+# central box `target_box` so that the rows on both sides of the boundary fill (tests/test_shape_edges_cpu.py counts it), and the counts
+# the state rows' loops divide by at zero.  `steps`: the random-policy steps of the CPU count.
+ATTACHED_CASES = [
+    # the smallest straddle: 35 view bits, camera 6's row is bits 30..34; S = 181 is odd and 41 is odd, so the state rows of the partial
+    # last tile end off a 16-byte boundary for f32 and f64 rows alike (40 environments would end on one: 8 * 181 * 4 = 362 * 16)
+    Case((7, 5, 3), 41, 30, 4301, 7, '35 view bits, row 6 straddles', 300.0),
+    # 240 bits in 8 words, seven straddling rows (cameras 2, 4, ..., 14), row 14 ends in the last word (the v.count guard); all sixteen
+    # lanes of a group are cameras (the SharedFieldOfView butterfly over width 16); a full tile and a half one
+    Case((16, 15, 3), 24, 30, 4301, 7, '240 view bits, seven straddling rows', 500.0),
+    # straddle at camera 4 (bits 28..34), no obstacles
+    Case((5, 7, 0), 40, 30, 4301, 7, 'row 4 straddles, no obstacles', 300.0),
+    # the maxima that fit with policies (the shape of GREEDY_CASES): `(1u << Nt) - 1u` at 16, cam_xy[..][32] full, NJ = 41
+    Case((16, 16, 9), 20, 30, 4301, 7, 'sixteen by sixteen with policies', 300.0),
+    # no cameras: the geometry of CASES
+    Case((0, 5, 64), 33, 30, 4301, 7, 'no cameras'),
+    # state rows only: S = 621, a tile of E = 4 environments
+    Case((16, 16, 64), 8, 30, 4301, 7, 'state rows of all maxima, E = 4'),
+]
 
 
 def case_id(case):
     return '%dv%d-%d' % case.shape
+
+
+def attached_case(name):
+    """The case of ATTACHED_CASES with that id ('7v5-3')."""
+    return {case_id(c): c for c in ATTACHED_CASES}[name]
+
+
+def straddling_rows(nc, nt):
+    """{camera: bits of its camera_target_view_mask row in the lower word} for the rows that cross a 32-bit word boundary (the row
+    of camera c is bits c * nt .. c * nt + nt - 1 from bit 0: mate_engine_layout.bit_camera_target = 0)."""
+    return {c: 32 - c * nt % 32 for c in range(nc) if c * nt // 32 != (c * nt + nt - 1) // 32}
+
+
+def straddling_frames(view):
+    """{camera: frames} over a [..., Nc, Nt] boolean camera_target_view_mask: the frames in which a straddling row has a seen target
+    on EACH side of its word boundary at once -- where a row read from one word only differs from the row."""
+    view = np.asarray(view).astype(bool)
+    nc, nt = view.shape[-2:]
+    return {c: int((view[..., c, :low].any(axis=-1) & view[..., c, low:].any(axis=-1)).sum()) for c, low in straddling_rows(nc, nt).items()}
 
 
 CAMERA_SITES = [(float(x), float(y)) for y in (-600, -200, 200, 600) for x in (-600, -200, 200, 600)]
@@ -66,8 +106,9 @@ def _box(site, half):
     return [site[0] - half, site[0] + half, site[1] - half, site[1] + half]
 
 
-def scenario(shape):
-    """The scenario mapping of an (Nc, Nt, No) case (validated by read_config)."""
+def scenario(shape, target_box=None):
+    """The scenario mapping of an (Nc, Nt, No) case (validated by read_config).  `target_box` = h: every target in the central box
+    [-h, h]^2 instead of beside a camera body (most (camera, target) pairs are never seen from there)."""
     from mate_amd.config import read_config
     nc, nt, no = shape
     base = read_config('MATE-8v8-9.yaml')
@@ -81,6 +122,8 @@ def scenario(shape):
         cfg['shuffle_entities'] = False
         order = [no - 1, no // 2, no // 2 - 1, 0, no - 2, 1]      # circle 63 (bit 31 of the second word), 32, 31, 0, ...
         boxes = [_box(OBSTACLE_SITES[order[t % len(order)]], LONE_TARGET_HALF_BOX) for t in range(nt)]
+    if target_box is not None:
+        boxes = [_box((0.0, 0.0), float(target_box)) for _ in range(nt)]
     cfg['target'] = dict(base['target'], location_random_range=boxes)
     if no:
         cfg['obstacle'] = dict(base['obstacle'], location_random_range=[_box(OBSTACLE_SITES[o], OBSTACLE_HALF_BOX) for o in range(no)],
@@ -88,10 +131,14 @@ def scenario(shape):
     return read_config(cfg)
 
 
+def case_scenario(case):
+    return scenario(case.shape, case.target_box)
+
+
 def oracle_batch(O, case, cfg=None):
     """The oracle's batch of a case, reset (its own occlusion tables)."""
     import gpu_util as U
-    cfg = cfg or scenario(case.shape)
+    cfg = cfg or case_scenario(case)
     batch = O.OracleBatch(U.oracle_proto_from_config(cfg, O), case.n, seed=case.seed, first_env_index=case.first)
     batch.reset(threads=8)
     return batch
@@ -103,7 +150,7 @@ def count_events(O, case, batch=None, cfg=None):
     position + the action cut to the target's step size) lies inside a camera's disc; `camera_past_64` -- the same for cameras
     whose index in the walk, No + c, is 64 or more; `obstacle` -- colliding with the destination inside an obstacle's disc."""
     nc, nt, no = case.shape
-    cfg = cfg or scenario(case.shape)
+    cfg = cfg or case_scenario(case)
     batch = batch or oracle_batch(O, case, cfg)
     cam = cfg.get('camera', {})
     rot, zoom = cam.get('rotation_step', 0.0), cam.get('zooming_step', 0.0)
@@ -134,3 +181,14 @@ def count_events(O, case, batch=None, cfg=None):
         counts['camera_past_64'] += int((colliding & in_cam[:, :, past].any(axis=2)).sum())
         counts['obstacle'] += int((colliding & in_obs.any(axis=2)).sum())
     return dict(counts)
+
+
+def count_straddling_frames(O, case):
+    """{camera: frames} of straddling_frames over the (environment, step) frames of the case's random-policy rollout on the oracle alone."""
+    batch = oracle_batch(O, case)
+    nc, nt, _ = case.shape
+    total = collections.Counter({c: 0 for c in straddling_rows(nc, nt)})
+    for _ in range(case.steps):
+        batch.step(auto_reset=False, threads=8)
+        total.update(straddling_frames(batch.gather('camera_target_view_mask').reshape(case.n, nc, nt) != 0))
+    return dict(total)

@@ -184,36 +184,61 @@ def _builtin_engine(config, n, seed):
     return eng
 
 
-@pytest.mark.parametrize('scenario', ['MATE-8v8-9 x 65', '16v16 x 5', 'few cargoes'])
+STRADDLING = ('7v5-3', '16v15-3', '5v7-0')        # tests/shape_edges.py ATTACHED_CASES: camera_target_view_mask rows that cross a 32-bit word
+
+
+@pytest.mark.parametrize('scenario', ['MATE-8v8-9 x 65', '16v16 x 5', 'few cargoes'] + list(STRADDLING) + ['0v5-64'])
 def test_rows_equal_the_torch_shapers_on_the_engines_own_draws(scenario):
     """Both teams, every term and all reductions under step_greedy (auto_reset = 0) against the torch shapers
     (BatchedMultiAgentTracking.auxiliary_camera_rewards' arithmetic, mate_amd.auxiliary_rewards.AuxiliaryTargetRewards) on the same
     records: integer-valued terms exact, everything else 1e-9 (sixteen f64 additions of magnitudes <= 1e3 stay below 1e-10 whatever the
-    order).  65 environments: not a multiple of the sixteen per workgroup; 16 x 16: the mask bits span eight words."""
+    order).  65 environments: not a multiple of the sixteen per workgroup; 16 x 16: the mask bits span eight words, every row on a
+    half-word.  7v5-3, 16v15-3, 5v7-0: rows that cross a word at odd bit positions (this kernel reads them bit by bit through view_bit, not
+    through view_row), the frames with seen targets on both sides counted from the unpacked masks the references read; 0v5-64: no cameras, the target rows alone (the camera team is refused: tests/test_gpu_attached_edges.py)."""
+    import shape_edges
     from mate_amd.auxiliary_rewards import AuxiliaryTargetRewards
     from mate_amd.config import read_config
     from mate_amd import constants as consts
+    target_coefficients = TARGET_COEFFICIENTS
     if scenario == 'MATE-8v8-9 x 65':
         eng = _builtin_engine(read_config('MATE-8v8-9.yaml'), 65, seed=17)
     elif scenario == '16v16 x 5':
         eng = _builtin_engine(_sixteen_by_sixteen(), 5, seed=18)
         assert not eng.specialised and eng.num_cameras * eng.num_targets == 256
-    else:
+    elif scenario == 'few cargoes':
         eng = _few_cargo_engine(6, seed=19)
+    else:
+        from mate_amd.engine import Engine
+        case = shape_edges.attached_case(scenario)
+        eng = Engine(shape_edges.case_scenario(case), case.n, seed=case.seed, first_env_index=case.first)
+        eng.enable_policies()
+        eng.reset()
+        assert not eng.specialised and (eng.num_cameras, eng.num_targets, eng.num_obstacles) == case.shape
+        if not eng.num_cameras:      # (the soft coverage score takes a maximum over the cameras)
+            target_coefficients = {key: c for key, c in TARGET_COEFFICIENTS.items() if key != 'soft_coverage_score'}
     N, Nc, Nt, dev = eng.num_envs, eng.num_cameras, eng.num_targets, eng.device
     branches = {'nearest non-empty': 0, 'all empty': 0}
+    straddling = {c: 0 for c in shape_edges.straddling_rows(Nc, Nt)}
+    assert bool(straddling) == (scenario in STRADDLING)
     for cam_reduction, tgt_reduction in REDUCTION_PAIRS:
-        eng.enable_reward_rows(camera=(CAMERA_COEFFICIENTS, cam_reduction), target=(TARGET_COEFFICIENTS, tgt_reduction), terms=True)
-        shaper = AuxiliaryTargetRewards(eng, TARGET_COEFFICIENTS, tgt_reduction)
+        eng.enable_reward_rows(camera=(CAMERA_COEFFICIENTS, cam_reduction) if Nc else None, target=(target_coefficients, tgt_reduction), terms=True)
+        shaper = AuxiliaryTargetRewards(eng, target_coefficients, tgt_reduction)
         for s in range(4):
             eng.step_greedy(auto_reset=0)
             ref_t = shaper()
+            for c, frames in shape_edges.straddling_frames(eng.unpack_masks()['camera_target_view_mask']).items():
+                straddling[c] += frames
             for k, key in enumerate(TARGET_KEYS):
+                if key not in target_coefficients:
+                    continue
                 got, ref = eng.target_reward_terms[:, :, k], shaper.terms[key]
                 assert float((got - ref).abs().max()) <= 1e-9, (scenario, tgt_reduction, s, key)
                 if key in INTEGER_TERMS:
                     assert torch.equal(got, ref.contiguous()), (scenario, s, key)
             assert float((eng.target_reward_rows - ref_t).abs().max()) <= 1e-9, (scenario, tgt_reduction, s)
+            if not Nc:
+                assert eng.camera_reward_rows is None and float(eng.target_reward_terms[:, :, TARGET_KEYS.index('is_tracked')].abs().sum()) == 0.0
+                continue
             # the camera shaper's arithmetic (environment.py auxiliary_camera_rewards) on the same records
             sc = eng.scalars.double()
             seen = torch.from_numpy(eng.unpack_masks()['camera_target_view_mask']).to(dev)
@@ -240,6 +265,9 @@ def test_rows_equal_the_torch_shapers_on_the_engines_own_draws(scenario):
     assert consts.TERRAIN_WIDTH == 2000.0
     if scenario == 'few cargoes':
         assert branches['nearest non-empty'] > 0 and branches['all empty'] > 0, branches
+    if straddling:      # the rows the references read did have seen targets on both sides of their word boundary
+        print(scenario, 'step_greedy: frames per straddling row', straddling)
+        assert min(straddling.values()) >= 1, straddling
 
 
 # ---------------------------------------------------------------------------------------------- 5: terminal step and restart

@@ -28,13 +28,15 @@ F64_CASES = [c for c in S.CASES if c.shape[0] < 16]
 assert set(INT_KEYS) <= set(U.STATE_KEYS)        # the exact comparison of every state key but F64_STATE covers the integer state
 
 
-def _engine_and_oracle(case, O, dtype, policies=False):
+def _engine_and_oracle(case, O, dtype, policies=False, modes=None):
     """Engine and oracle batch of a case on the same Philox seed and first_env_index, both reset; reset state exact, table knots
-    1e-9 with only tangent-ray flips, then the device's tables on both sides."""
+    1e-9 with only tangent-ray flips, then the device's tables on both sides.  `modes`: (camera, target) of set_obs_mode."""
     from mate_amd.engine import Engine
-    cfg = S.scenario(case.shape)
+    cfg = S.case_scenario(case)
     eng = Engine(cfg, case.n, seed=case.seed, first_env_index=case.first, obs_dtype=dtype)
     assert (eng.num_cameras, eng.num_targets, eng.num_obstacles) == case.shape and not eng.specialised
+    if modes is not None:
+        eng.set_obs_mode(camera=modes[0], target=modes[1])
     if policies:
         eng.enable_policies()
     eng.reset()

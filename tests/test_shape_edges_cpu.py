@@ -7,6 +7,7 @@ import pytest
 import shape_edges as S
 
 MIN_EVENTS = 100
+MIN_STRADDLING_FRAMES = 20
 
 
 @pytest.mark.parametrize('case', S.CASES, ids=S.case_id)
@@ -21,6 +22,39 @@ def test_edge_scenarios_collide_with_the_circles_they_are_about(case, oracle_lib
     if nc + no > 64:
         assert counts['camera_past_64'] >= MIN_EVENTS, (S.case_id(case), counts)
     assert counts['colliding'] >= MIN_EVENTS, (S.case_id(case), counts)
+
+
+@pytest.mark.parametrize('name', ['7v5-3', '16v15-3', '5v7-0'])
+def test_attached_scenarios_fill_their_straddling_rows(name, oracle_lib):
+    """The cases of ATTACHED_CASES whose camera_target_view_mask rows cross a 32-bit word: under the random policy every such row has a
+    seen target on each side of the boundary at once in at least MIN_STRADDLING_FRAMES (environment, step) frames -- a row taken from
+    its first word alone could not agree with the row."""
+    case = S.attached_case(name)
+    nc, nt, _ = case.shape
+    rows = S.straddling_rows(nc, nt)
+    assert rows == {'7v5-3': {6: 2}, '16v15-3': {2: 2, 4: 4, 6: 6, 8: 8, 10: 10, 12: 12, 14: 14}, '5v7-0': {4: 4}}[name]
+    frames = S.count_straddling_frames(oracle_lib, case)
+    print(name, 'frames per straddling row', frames)
+    assert set(frames) == set(rows) and min(frames.values()) >= MIN_STRADDLING_FRAMES, (name, frames)
+
+
+def test_attached_scenarios_have_the_shapes_they_claim():
+    """The arithmetic the attached cases stand on: view bits and words, odd state-row widths, and no straddle where Nt divides 32."""
+    assert [c.shape for c in S.ATTACHED_CASES] == [(7, 5, 3), (16, 15, 3), (5, 7, 0), (16, 16, 9), (0, 5, 64), (16, 16, 64)]
+    assert all(S.straddling_rows(nc, nt) == {} for nc in (1, 4, 16) for nt in (1, 2, 4, 8, 16))
+    assert S.straddling_rows(3, 5) == {} and 16 * 15 == 240 and (14 * 15 + 14) // 32 == 7      # row 14 ends in the eighth word of eight
+    state_dim = lambda nc, nt, no: 13 + 9 * nc + 14 * nt + 3 * no + 2 * nt + 16  # noqa: E731  (csrc/state_rows.hpp state_dim_of)
+    assert state_dim(7, 5, 3) == 181 and state_dim(16, 16, 64) == 621
+    for case in S.ATTACHED_CASES:
+        cfg = S.case_scenario(case)
+        got = tuple(len(cfg.get(k, {}).get('location_random_range', [])) for k in ('camera', 'target', 'obstacle'))
+        assert got == case.shape and 8 <= case.n <= 48
+        if case.target_box is not None:
+            assert all(box == [-case.target_box, case.target_box] * 2 for box in cfg['target']['location_random_range'])
+    view = __import__('numpy').zeros((2, 7, 5), dtype=bool)
+    view[0, 6, [1, 2]] = True      # bits 31 and 32: one on each side
+    view[1, 6, [2, 3]] = True      # bits 32 and 33: both in the upper word
+    assert S.straddling_frames(view) == {6: 1}
 
 
 def test_edge_scenarios_have_the_shapes_and_thresholds_they_claim():
