@@ -14,6 +14,8 @@ Fixture families:
   kat_obstruct.npz                   F3 ray/circle known answers (entities.py:158-184)
   kat_scalar.npz                     F3 normalize_angle / polar clamp (utils.py:155,223-229)
   kat_perceive.npz                   F3 Camera.perceive on crafted geometry (entities.py:491-511)
+  kat_sense.npz                      F3 Sensor.perceive on the range rim, down to the last place (entities.py:229-232; `make_golden.py rims`)
+  kat_perceive_rims.npz              F3 Camera.perceive on its sight, sector-edge, seam and lookup rims (`make_golden.py rims`)
   reset_<cfg>_s<seed>.npz            F1 reset() with EVERY random draw on a tape (environment.py:679-834)
   chain_<cfg>_s<seed>.npz            the example trainers' whole wrapper chain for a camera learner (examples/ippo/camera/config.py:19-51)
   host_reference.npz                 scenario files, read_config() and observation layout (`make_golden.py host`)
@@ -659,6 +661,255 @@ def kat_perceive():
     print(f'kat_perceive: {len(cases)} cases, seen={int(np.array(cases)[:, -1].sum())}')
 
 
+# --------------------------------------------------------------------------- verdicts on their rims
+sys.path.insert(0, os.path.dirname(HERE))
+from rim_scenes import RIM_DELTAS, exact_side, range_ladder, shadow_margin  # noqa: E402  (tests/rim_scenes.py: pure NumPy, shared with the tests)
+
+
+def kat_sense():
+    """Sensor.perceive (entities.py:229-232) of a Target against a Target, a Camera and an Obstacle standing on its range rim."""
+    rng = np.random.RandomState(33)
+    sight = 500.0
+    viewer = Target(location=np.array([0.0, 0.0]), sight_range=sight)
+    rows, kinds, rungs, deltas, block = [], [], [], [], []
+    names = [n for n, _ in range_ladder(sight)]
+
+    def other_of(kind, xy, radius):
+        if kind == 0:
+            other = Target(location=np.array([0.0, 0.0]))
+        elif kind == 1:
+            other = Camera(location=np.array([0.0, 0.0]), radius=40.0)
+        else:
+            other = Obstacle(location=np.array([0.0, 0.0]), radius=float(radius))
+        other.location = np.asarray(xy, dtype=np.float64)      # undo the terrain clip of Entity.reset
+        assert other.radius == radius
+        return other
+
+    def record(kind, t, o, radius, rung, delta, blk):
+        viewer.location = np.asarray(t, dtype=np.float64)
+        seen = bool(viewer.perceive(other_of(kind, o, radius)))
+        if rung != names.index('0') and blk != 1:              # every rung but '0' is decided beyond rounding
+            assert exact_side(t[0], t[1], o[0], o[1], (sight, radius)) == (1 if delta > 0 else -1) and seen == (delta < 0), (kind, t, o, delta)
+        rows.append([t[0], t[1], o[0], o[1], radius, sight, float(seen)])
+        kinds.append(kind); rungs.append(rung); deltas.append(delta); block.append(blk)
+
+    for rep in range(30):
+        for kind in range(3):
+            radius = [0.0, 40.0, float(rng.uniform(25, 100))][kind]
+            lim = sight + radius
+            for rung, (name, delta) in enumerate(range_ladder(lim)):
+                while True:
+                    o = rng.uniform(-1000, 1000, 2)
+                    if rep % 3 == 0:                            # where the f32 shadow of the entity table is coarsest
+                        o[rng.randint(2)] = rng.choice([-1.0, 1.0]) * rng.uniform(900, 1000)
+                    b = rng.uniform(-np.pi, np.pi)
+                    t = o + lim * (1.0 + delta) * np.array([np.cos(b), np.sin(b)])
+                    if np.abs(t).max() <= 1000.0:
+                        break
+                record(kind, t, o, radius, rung, delta, 0)
+    # exactly representable rims (Pythagorean offsets from integer anchors) and their neighbours one and two ulps away
+    for anchor in ([-300.0, 200.0], [512.0, -437.0]):
+        for kind, (a, b), radius in ((0, (300.0, 400.0), 0.0), (1, (324.0, 432.0), 40.0), (2, (330.0, 440.0), 50.0)):
+            for swap in (False, True):
+                for sx in (-1.0, 1.0):
+                    for sy in (-1.0, 1.0):
+                        off = np.array([sx * b, sy * a] if swap else [sx * a, sy * b])
+                        o = np.array(anchor)
+                        t = o + off
+                        assert exact_side(t[0], t[1], o[0], o[1], (sight, radius)) == 0
+                        record(kind, t, o, radius, names.index('0'), 0.0, 1)
+                        for which in range(4):
+                            for ulps in (-2, -1, 1, 2):
+                                p = np.concatenate([t, o])
+                                for _ in range(abs(ulps)):
+                                    p[which] = np.nextafter(p[which], np.inf if ulps > 0 else -np.inf)
+                                record(kind, p[:2], p[2:], radius, names.index('0'), 0.0, 1)
+    # rows the device's f32 shadow of the entity table gets most wrong: all coordinates in the coarsest binade, [512, 1024), an obstacle
+    # radius that rounds badly, 1e-9 either side -- picked, out of 300000 draws a side, where the f32 squared distance is off AGAINST the
+    # verdict by more than 1/64 of the band (rim_scenes.shadow_margin restates the device's f32 test)
+    for sign in (-1.0, 1.0):
+        count = 300000
+        radius = rng.uniform(25, 100, count)
+        o = rng.choice([-1.0, 1.0], (count, 2)) * rng.uniform(900, 1000, (count, 2))
+        b = rng.uniform(-np.pi, np.pi, count)
+        t = o + ((sight + radius) * (1.0 + sign * 1e-9))[:, None] * np.stack([np.cos(b), np.sin(b)], axis=1)
+        against = -sign * shadow_margin(t[:, 0], t[:, 1], o[:, 0], o[:, 1], radius, sight)
+        against[np.abs(t).max(axis=1) > 1000.0] = -np.inf
+        worst = np.argsort(against)[::-1][:16]
+        assert against[worst].min() > 1.0 / 64.0, against[worst]
+        for i in worst:
+            record(2, t[i], o[i], float(radius[i]), names.index('+1e-09' if sign > 0 else '-1e-09'), sign * 1e-9, 2)
+    rows = np.array(rows, dtype=np.float64)
+    np.savez_compressed(os.path.join(HERE, 'kat_sense.npz'), rows=rows, columns=np.str_('tx ty ox oy radius sight_range seen'),
+                        kind=np.array(kinds, dtype=np.int8), kind_names=np.array(['target', 'camera', 'obstacle']),
+                        rung=np.array(rungs, dtype=np.int8), rung_names=np.array(names), delta=np.array(deltas), block=np.array(block, dtype=np.int8))
+    print(f'kat_sense: {len(rows)} rows, seen={int(rows[:, -1].sum())}, {os.path.getsize(os.path.join(HERE, "kat_sense.npz")) / 1024:.0f} KiB')
+
+
+def kat_perceive_rims():
+    """Camera.perceive (entities.py:491-511) with u = 0, tau = 0 on its four rims: the sight range, the sector edge, the sector edge
+    across the +-180 degree seam, and the occlusion lookup.  Same layout as kat_perceive.npz plus `rim` / `delta` per case."""
+    rng = np.random.RandomState(34)
+    RIMS = ['sight', 'sight_exact', 'edge', 'seam', 'lookup_knot', 'lookup_between', 'lookup_crowded']
+    cases, rims, deltas, luts = [], [], [], []
+    tape = TapeRNG()
+
+    def camera(case):
+        cam = Camera(location=np.array([0.0, 0.0]), min_viewing_angle=30.0, max_sight_range=1500.0 if case % 2 == 0 else 700.0,
+                     rotation_step=5.0, zooming_step=2.5, radius=40.0)
+        cam.location = np.array([100.0, -200.0]) if case == 0 else rng.uniform(-600, 600, 2)
+        loc = cam.location.copy()
+        cam.location_random_range = gym.spaces.Box(low=loc, high=loc, dtype=np.float64)
+        cam.reset()
+        nobs = [0, 0, 3, 6, 9, 9, 4, 9][case]
+        obstacles = []
+        for _ in range(nobs):
+            while True:
+                c = cam.location + rng.uniform(-900, 900, 2)
+                r = rng.uniform(25, 100)
+                if np.linalg.norm(c - cam.location) > r + 60:
+                    break
+            ob = Obstacle(location=c, radius=float(r))
+            ob.location = np.asarray(c, dtype=np.float64)
+            ob.radius = float(r)
+            obstacles.append(ob)
+        cam.clear_obstacles()
+        cam.add_obstacles(*obstacles)
+        cam.location_random_range._np_random = tape
+        obs_arr = np.array([np.append(o.location, o.radius) for o in obstacles]).reshape(nobs, 3)
+        luts.append((cam.sight_range_func.x.copy(), cam.sight_range_func.y.copy(), obs_arr, cam.location.copy(), cam.max_sight_range))
+        return cam
+
+    def pose(cam, phi, theta):
+        cam.orientation = float(phi)
+        cam.viewing_angle = float(theta)
+        cam.sight_range = np.sqrt(cam.area_product / cam.viewing_angle)
+
+    def record(case, cam, p, rim, delta):
+        tgt = Target(location=np.array([0.0, 0.0]))
+        tgt.location = np.asarray(p, dtype=np.float64)
+        tape.u = 0.0
+        seen = bool(cam.perceive(tgt, transmittance=0.0))
+        cases.append([case, cam.orientation, cam.viewing_angle, cam.sight_range, p[0], p[1], 0.0, 0.0, float(seen)])
+        rims.append(RIMS.index(rim)); deltas.append(delta)
+        return seen
+
+    def at(cam, dist, angle_deg):
+        a = np.deg2rad(angle_deg)
+        return cam.location + dist * np.array([np.cos(a), np.sin(a)])
+
+    def clear(cam, p, factor=1.01):
+        """The lookup does not decide: the occlusion table at p's bearing is further than p by `factor`."""
+        rel = Vector2D(vector=np.asarray(p) - cam.location)
+        return rel.norm * factor < cam.sight_range_at(rel.angle)
+
+    for case in range(8):
+        cam = camera(case)
+        knots = cam.sight_range_func.x
+        # -- sight range: norm against sqrt(area / theta), well inside the sector, the table far behind
+        for _ in range(8):
+            for delta in RIM_DELTAS + [0.0]:
+                while True:
+                    pose(cam, rng.uniform(-180, 180), rng.uniform(40, 180))
+                    p = at(cam, cam.sight_range * (1.0 + delta), cam.orientation + rng.uniform(-0.4, 0.4) * cam.viewing_angle)
+                    if clear(cam, p):
+                        break
+                seen = record(case, cam, p, 'sight', delta)
+                if delta != 0.0:
+                    assert exact_side(p[0], p[1], cam.location[0], cam.location[1], (cam.sight_range,)) == (1 if delta > 0 else -1)
+                    assert seen == (delta < 0), (case, delta)
+        if case == 0:       # theta 120, R 1500: the sight range is exactly 750 = |(450, 600)|, camera on integers
+            pose(cam, np.rad2deg(np.arctan2(600.0, 450.0)) + 7.0, 120.0)
+            assert cam.sight_range == 750.0
+            for a, b in ((450.0, 600.0), (600.0, 450.0), (-450.0, 600.0), (450.0, -600.0), (-600.0, -450.0)):
+                pose(cam, np.rad2deg(np.arctan2(b, a)) + 7.0, 120.0)
+                base = cam.location + np.array([a, b])
+                record(case, cam, base, 'sight_exact', 0.0)
+                for which in range(2):
+                    for ulps in (-1, 1):
+                        p = base.copy()
+                        p[which] = np.nextafter(p[which], np.inf if ulps > 0 else -np.inf)
+                        record(case, cam, p, 'sight_exact', 0.0)
+        # -- sector edge: bearing = orientation +- theta / 2 +- eps; eps = 0 is a coin flip between two atan2 and is not recorded
+        for _ in range(6):
+            for eps in (1e-10, 1e-8, 1e-6, 1e-4):
+                for edge in (-0.5, 0.5):
+                    for side in (-1.0, 1.0):       # side > 0: outside the sector
+                        while True:
+                            pose(cam, rng.uniform(-180, 180), rng.uniform(30, 180))
+                            p = at(cam, rng.uniform(30, 0.9 * cam.sight_range), cam.orientation + edge * cam.viewing_angle + np.sign(edge) * side * eps)
+                            if clear(cam, p):
+                                break
+                        assert record(case, cam, p, 'edge', side * eps) == (side < 0), (case, eps, edge, side)
+        # -- the same edges across the +-180 degree seam: the camera looks along the seam, the target stands on its other side
+        for phi in (-180.0, 179.999999, 180.0 - 1e-9, -179.5):
+            for _ in range(2):
+                for eps in (1e-10, 1e-8, 1e-6, 1e-4):
+                    for side in (-1.0, 1.0):
+                        edge = -0.5 if phi < 0 else 0.5       # the edge whose bearing wraps to the other sign
+                        while True:
+                            pose(cam, phi, rng.uniform(30, 180))
+                            bearing = cam.orientation + edge * cam.viewing_angle + np.sign(edge) * side * eps
+                            p = at(cam, rng.uniform(30, 0.9 * cam.sight_range), bearing)
+                            if clear(cam, p):
+                                break
+                        rel = Vector2D(vector=p - cam.location)
+                        assert (rel.angle > 0) == (phi < 0), (phi, rel.angle)
+                        assert record(case, cam, p, 'seam', side * eps) == (side < 0), (case, phi, eps, side)
+        # -- the lookup: norm = sight_range_at(angle) (1 + 1e-6) (1 + delta) in an obstructed direction, inside sector and sight range
+        if len(cam.obstacles) == 0:
+            continue
+        pose(cam, 0.0, 30.0 + 1e-3)
+        blocked = np.flatnonzero(cam.sight_range_func.y[:-1] < 0.9 * cam.sight_range)
+        cells = np.floor((knots[:-1] + 180.0) * 2.0).astype(int)        # half-degree cells
+        crowded = [c for c in np.unique(cells) if (cells == c).sum() > 4 and cam.sight_range_func.y[:-1][cells == c].min() < 0.9 * cam.sight_range]
+        assert len(blocked) > 8, (case, len(blocked))
+        for rim in ('lookup_knot', 'lookup_between', 'lookup_crowded'):
+            if rim == 'lookup_crowded' and not crowded:
+                continue
+            for _ in range(6):
+                for delta in [s * d for d in (1e-9, 1e-7, 1e-5) for s in (-1.0, 1.0)]:
+                    for attempt in range(1000):
+                        if rim == 'lookup_knot':
+                            angle = knots[rng.choice(blocked)]
+                        elif rim == 'lookup_between':
+                            k = rng.choice(blocked)
+                            angle = knots[k] + rng.uniform(0.05, 0.95) * (knots[k + 1] - knots[k])
+                        else:
+                            inside = np.flatnonzero(cells == rng.choice(crowded))
+                            angle = rng.uniform(knots[inside[0]], knots[inside[-1]])
+                        angle = normalize_angle(float(angle))
+                        pose(cam, normalize_angle(angle + rng.uniform(-0.3, 0.3) * cam.viewing_angle), 30.0 + 1e-3)
+                        limit = float(cam.sight_range_at(angle)) * (1 + 1e-6)
+                        p = at(cam, limit * (1.0 + delta), angle)
+                        rel = Vector2D(vector=p - cam.location)
+                        if rel.norm > 0.95 * cam.sight_range or limit < 30.0:
+                            continue
+                        realised = rel.norm / (float(cam.sight_range_at(rel.angle)) * (1 + 1e-6)) - 1.0
+                        if 0.5 < realised / delta < 2.0:        # a steep table moves under the rounding of the bearing: redraw
+                            break
+                    else:
+                        raise AssertionError((case, rim, delta))
+                    assert record(case, cam, p, rim, delta) == (delta < 0), (case, rim, delta)
+    width = max(len(l[0]) for l in luts)
+    n = len(luts)
+    phis, rhos = np.full((n, width), np.nan), np.full((n, width), np.nan)
+    counts, nobs = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    obs, cam_xy, rmax = np.full((n, 9, 3), np.nan), np.zeros((n, 2)), np.zeros(n)
+    for i, (x, y, o, loc, rm) in enumerate(luts):
+        counts[i], nobs[i], cam_xy[i], rmax[i] = len(x), len(o), loc, rm
+        phis[i, :len(x)], rhos[i, :len(x)], obs[i, :len(o)] = x, y, o
+    path = os.path.join(HERE, 'kat_perceive_rims.npz')
+    cases = np.array(cases)
+    np.savez_compressed(path, cases=cases, columns=np.str_('case phi theta sight px py u tau seen'),
+                        rim=np.array(rims, dtype=np.int8), rim_names=np.array(RIMS), delta=np.array(deltas),
+                        lut_phis=phis, lut_rhos=rhos, lut_count=counts, obstacles=obs, num_obstacles=nobs,
+                        cam_xy=cam_xy, cam_max_sight_range=rmax)
+    assert min(np.bincount(rims, minlength=len(RIMS))) >= 15
+    print(f'kat_perceive_rims: {len(cases)} cases, seen={int(cases[:, -1].sum())}, per rim {np.bincount(rims).tolist()}, '
+          f'{os.path.getsize(path) / 1024:.0f} KiB')
+
+
 # --------------------------------------------------------------------------- reset() on a tape
 RESET_TAPE = []
 
@@ -1121,10 +1372,16 @@ def main():
         two_episode_fixture('8v8-9', 'MATE-8v8-9.yaml', 21, 500, 96)
         two_episode_fixture('4v2-9', 'MATE-4v2-9.yaml', 22, 500, 64)
         return
+    if sys.argv[1:] == ['rims']:
+        kat_sense()
+        kat_perceive_rims()
+        return
     if not sys.argv[1:]:
         kat_obstruct()
         kat_scalar()
         kat_perceive()
+        kat_sense()
+        kat_perceive_rims()
     plan = [
         # name,                      config,                 seed, policy,  steps, overrides, tweak
         ('trace_4v2-9_random_s0',    'MATE-4v2-9.yaml',        0, 'random',   96, None, None),

@@ -2,7 +2,7 @@
 
 * reset() pinned to the reference: the HIP reset kernel consumes the uniforms the reference's own reset() drew
   (tests/golden/reset_*.npz, recorded by make_golden.py `reset_fixture`) and must produce the reference's state;
-* the F3 known-answer vectors (kat_perceive / kat_obstruct / kat_scalar), which the CPU suite runs on the oracle, driven
+* the F3 known-answer vectors (kat_perceive / kat_perceive_rims / kat_sense / kat_obstruct / kat_scalar), which the CPU suite runs on the oracle, driven
   through the device's own `Camera.perceive`, `Obstacle.obstruct`, `normalize_angle`, step clamp and `Camera.simulate`
   (entities.py:491-511, 158-184, 347-360; utils.py:155-158, 223-229).
 """
@@ -113,6 +113,71 @@ def test_kat_perceive_on_device():
         total += n
         assert not bad.any(), (case, rows[bad][:4])
     assert total == len(cases) and wrong == 0
+
+
+def test_kat_perceive_rims_on_device():
+    """Camera.perceive on its rims (kat_perceive_rims.npz: the sight range down to 1e-12 and to the exact 750 = |(450, 600)| with its
+    ulp neighbours, the sector edge 1e-10 ... 1e-4 degrees either side, the same across the +-180 degree seam, the occlusion lookup
+    1e-9 ... 1e-5 either side on a knot, between knots and in a crowded cell), one environment per case: the recorded bit on every row."""
+    k = G.load('kat_perceive_rims.npz')
+    cases, names = k['cases'], list(k['rim_names'])
+    total = 0
+    for case in range(len(k['lut_count'])):
+        sel = np.flatnonzero(cases[:, 0] == case)
+        rows, n = cases[sel], len(sel)
+        eng = _single_camera_engine(k['cam_max_sight_range'][case], n)
+        cnt = int(k['lut_count'][case])
+        for e in range(n):
+            eng.lut_write(e, 0, k['lut_phis'][case, :cnt], k['lut_rhos'][case, :cnt])
+        eng.load_state_dict({
+            'cam_x': np.full((n, 1), k['cam_xy'][case, 0]), 'cam_y': np.full((n, 1), k['cam_xy'][case, 1]),
+            'cam_phi': rows[:, 1:2], 'cam_theta': rows[:, 2:3], 'tgt_x': rows[:, 4:5], 'tgt_y': rows[:, 5:6]})
+        eng.observe(tape_ct=torch.zeros((n, 1, 1), dtype=torch.float64, device='cuda'))       # u = 0: never through an obstacle
+        got = eng.unpack_masks()['camera_target_view_mask'][:, 0, 0]
+        assert np.allclose(np.sqrt(30.0 * k['cam_max_sight_range'][case] ** 2 / rows[:, 2]), rows[:, 3], rtol=1e-15)
+        bad = np.flatnonzero(got != rows[:, 8].astype(bool))
+        assert not len(bad), [(case, int(sel[i]), names[k['rim'][sel[i]]], float(k['delta'][sel[i]]), rows[i].tolist()) for i in bad[:4]]
+        total += n
+    assert total == len(cases)
+
+
+@pytest.mark.parametrize('dtype', [torch.float64, torch.float32], ids=['f64obs', 'f32obs'])
+def test_kat_sense_on_device(dtype):
+    """Sensor.perceive on its range rim (kat_sense.npz: the edges of the f32 band, 1e-5 ... 1e-12 either side, the nearest f64 point,
+    exactly representable rims and their one- and two-ulp neighbours), one environment per row on a generic 1v2-1 scenario
+    (tests/rim_scenes.py: sense_row_state), through observe() and through step() with zero actions: the recorded bit on every row."""
+    import rim_scenes as RS
+    from mate_amd.config import read_config
+    from mate_amd.engine import Engine
+    k = G.load('kat_sense.npz')
+    rows, kind = k['rows'], k['kind'].astype(int)
+    n = len(rows)
+    assert np.all(rows[:, 5] == RS.SIGHT)
+    cfg = read_config('MATE-1v1-9.yaml', target={'location_random_range': [[-100.0, 100.0, -100.0, 100.0]] * 2},
+                      obstacle={'location_random_range': [[300.0, 400.0, 300.0, 400.0]]})
+    eng = Engine(cfg, n, seed=4, obs_dtype=dtype)
+    assert (eng.num_cameras, eng.num_targets, eng.num_obstacles) == RS.SENSE_SHAPE and cfg['target']['sight_range'] == RS.SIGHT
+    assert cfg['camera']['radius'] == RS.CAMERA_RADIUS
+    eng.reset()
+    eng.load_state_dict(RS.sense_row_state(rows, kind))
+    eng.rebuild_luts()
+    want = rows[:, 6].astype(bool)
+
+    def check(call):
+        got = RS.sense_bits(eng.unpack_masks(), kind)
+        bad = np.flatnonzero(got != want)
+        assert not len(bad), (call, [(int(i), str(k['kind_names'][kind[i]]), str(k['rung_names'][k['rung'][i]]), int(k['block'][i]), rows[i].tolist())
+                                     for i in bad[:4]])
+
+    zeros = torch.zeros((n, 1, 1), dtype=torch.float64, device='cuda')
+    eng.observe(tape_ct=zeros.expand(n, 1, 2).contiguous())
+    check('observe')
+    for act_dtype in (torch.float64, torch.float32):
+        eng.step(torch.zeros((n, 1, 2), dtype=act_dtype, device='cuda'), torch.zeros((n, 2, 2), dtype=act_dtype, device='cuda'),
+                 tape_ct=zeros.expand(n, 1, 2).contiguous(), auto_reset=False)
+        check(('step', act_dtype))
+    sd = eng.state_dict()
+    assert np.array_equal(sd['tgt_x'][:, 0], rows[:, 0]) and np.array_equal(sd['tgt_y'][:, 0], rows[:, 1])       # zero actions moved nothing
 
 
 def test_kat_obstruct_on_device():

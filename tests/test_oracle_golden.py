@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import golden_util as G
+import rim_scenes as RS
 from oracle import oracle as O
 
 F64_TOL = 1e-9
@@ -55,6 +56,49 @@ def test_kat_lut_builder_and_perceive():
         n = int(k['lut_count'][i])
         seen = O.camera_perceive(k['cam_xy'][i], r[1], r[2], r[3], r[4:6], r[6], r[7], k['lut_phis'][i, :n], k['lut_rhos'][i, :n])
         assert seen == bool(r[8])
+
+
+def test_kat_sense():
+    """Sensor.perceive (entities.py:229-232) on its range rim: the oracle's update_view gives the reference's recorded verdict on
+    every row -- the f32 band's edges, 1e-5 ... 1e-12 either side, the nearest f64 point to the rim and the exactly representable
+    rims with their one- and two-ulp neighbours.  Down to 1e-12 the recorded verdict is also that of exact rational arithmetic
+    on the f64 coordinates; on the '0' rung and in the ulp block the reference's bit is the only authority."""
+    k = G.load('kat_sense.npz')
+    rows, kind = k['rows'], k['kind']
+    zero = list(k['rung_names']).index('0')
+    decided = k['rung'] != zero
+    assert decided.sum() > 1000 and (k['block'] == 1).sum() > 500 and not decided[k['block'] == 1].any()
+    # block 2: the f32 shadow of these rows is off against the verdict by more than 1/64 of the band the device hands to f64
+    shadow = k['block'] == 2
+    against = np.where(rows[shadow, 6] != 0, 1.0, -1.0) * RS.shadow_margin(*rows[shadow, :5].T)
+    assert shadow.sum() == 32 and against.min() > 1.0 / 64.0 and against.max() < 1.0 and 0 < rows[shadow, 6].mean() < 1
+    for r in rows[decided]:
+        assert RS.exact_side(r[0], r[1], r[2], r[3], (r[5], r[4])) == (-1 if r[6] else 1), r
+    got = RS.sense_rows_on_oracle(O, rows, kind)
+    bad = np.flatnonzero(got != rows[:, 6].astype(bool))
+    assert not len(bad), [(int(i), str(k['kind_names'][kind[i]]), str(k['rung_names'][k['rung'][i]]), rows[i].tolist()) for i in bad[:5]]
+    for kd in range(3):          # both verdicts on every kind, on the decided rungs and in the ulp block; on '0' over the kinds together
+        for sel in (decided, k['block'] == 1):
+            assert 0 < rows[sel & (kind == kd), 6].mean() < 1, (kd, rows[sel & (kind == kd), 6].mean())
+    assert 0 < rows[~decided & (k['block'] == 0), 6].mean() < 1
+
+
+def test_kat_perceive_rims():
+    """Camera.perceive (entities.py:491-511) on the sight-range, sector-edge, seam and lookup rims: O.camera_perceive gives the
+    recorded verdict on every row; the sight rim down to 1e-12 is also the verdict of exact rational arithmetic."""
+    k = G.load('kat_perceive_rims.npz')
+    names = list(k['rim_names'])
+    for i, r in enumerate(k['cases']):
+        c = int(r[0])
+        n = int(k['lut_count'][c])
+        seen = O.camera_perceive(k['cam_xy'][c], r[1], r[2], r[3], r[4:6], r[6], r[7], k['lut_phis'][c, :n], k['lut_rhos'][c, :n])
+        assert seen == bool(r[8]), (i, names[k['rim'][i]], float(k['delta'][i]), r.tolist())
+        if names[k['rim'][i]] == 'sight' and k['delta'][i] != 0.0:
+            assert RS.exact_side(r[4], r[5], k['cam_xy'][c, 0], k['cam_xy'][c, 1], (r[3],)) == (-1 if r[8] else 1), (i, r.tolist())
+        assert np.isclose(r[3], np.sqrt(30.0 * k['cam_max_sight_range'][c] ** 2 / r[2]), rtol=1e-15, atol=0)    # the sight range the pose implies
+    for rim in range(len(names)):
+        sel = k['rim'] == rim
+        assert sel.sum() >= 15 and 0 < k['cases'][sel, 8].mean() < 1, names[rim]
 
 
 @pytest.mark.parametrize('path', G.trace_files(), ids=lambda p: os.path.basename(p)[6:-4])
