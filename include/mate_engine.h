@@ -85,7 +85,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows, the target opponent) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows, the target and camera opponents) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -345,6 +345,46 @@ int mate_engine_policy_greedy_target_actions(mate_engine *engine, double *target
  * MATE_EINVAL: an unknown opponent. */
 enum { MATE_OPPONENT_GREEDY = 0, MATE_OPPONENT_HEURISTIC = 1 };
 int mate_engine_set_target_opponent(mate_engine *engine, int32_t opponent);
+
+/* Which scripted agent plays the CAMERA team where the engine plays it (the reference's opponent_agent_factory of target configurations under
+ * examples/, mate.evaluate's --camera-agent):
+ *   MATE_OPPONENT_GREEDY     GreedyCameraAgent (mate/agents/greedy.py:13-227), the default; nothing changes while it is selected
+ *   MATE_OPPONENT_HEURISTIC  HeuristicCameraAgent (mate/agents/heuristic.py:17-287): camera 0 collects the team's observations, scores 756 poses
+ *                            per camera against a table over the sensed targets in range, tries 32 orders of greedy assignment and sends
+ *                            every camera with a target in range the winning pose as its goal; a camera without one repeats or, with
+ *                            probability 0.1, re-samples its action.  ONE launch, heuristic_camera_kernel (csrc/opponent_rows.hpp: semantics,
+ *                            draws, mapping), into engine-owned buffers allocated at the first switch: the joint action [N][Nc][2] f64 the
+ *                            stepping launch reads, prev_action, the goals [N][Nc][2] (NaN where none) and their state indices [N][Nc] (-1).
+ * Needs mate_engine_policy_enable (MATE_ESTATE) and, for Heuristic in a scenario with cameras, the tables (MATE_ESTATE):
+ *   mate_engine_heuristic_camera_tables   state_mesh [756][3], coord_grid [2952][2], scores [2952][756] f64 HOST arrays, copied once to the
+ *                                         device (MATE_EINVAL: a null table).  The library has no generator: mate_amd/heuristic_tables.py is
+ *                                         the one the Python host uses; one set per (round(max_sight_range, 8), round(min_viewing_angle, 8)).
+ *   mate_engine_heuristic_camera_tape     permutations_dev [N][32][Nc] int8 recorded permutations of the controller (NULL: Philox draws), and
+ *                                         record_dev [N][32][Nc] int8 that receives the permutations every launch used (NULL: nothing is
+ *                                         stored).  Both hold until replaced.  The Bernoulli and sample uniforms of a parity run come through
+ *                                         mate_policy_tape.camera_resample_u_dev / camera_sample_u_dev, as for the Greedy cameras;
+ *                                         camera_delay_dev is ignored (these agents' messages arrive within the step).
+ *   mate_engine_heuristic_camera_goals    copies the last launch's goals [N][Nc][2] f64 and state indices [N][Nc] i32 out (either may be NULL).
+ * The opponent may change at any call boundary (the setter waits for the handle's launches).  Switching to Heuristic zeroes prev_action and makes
+ * the agents' reset run at their first acting call; switching back marks the Greedy camera agents -- which sat out meanwhile -- for THEIR reset
+ * (prev_action, memory, message delays) at their next acting call, if a Heuristic launch ran in between (else their memory is current and stays).
+ * While Heuristic is selected:
+ *   - mate_engine_step_greedy takes the TWO-launch form: the agents' launch with the camera team not acting, [the drift launch,] the Heuristic
+ *     cameras' launch, the stepping launch reading its buffer.  mate_engine_step_versus_greedy(MATE_TEAM_TARGET) runs no agents' launch (nobody
+ *     of the Greedy pair acts): the Heuristic cameras' launch, then the step.  Identical arguments at every call, no allocation, no
+ *     synchronisation: capturable under mate_engine_device_tick.  An environment idling under a batched restart (done = 2) is skipped: it keeps
+ *     its rows and its prev_action.  mate_engine_policy_actions reports the final camera action.
+ *   - mate_engine_step_versus_greedy(MATE_TEAM_CAMERA), mate_engine_step_selected and mate_engine_rollout_versus_greedy(MATE_TEAM_CAMERA) are
+ *     unaffected: the caller (or the executor) plays the cameras.
+ *   - mate_engine_rollout_greedy and mate_engine_rollout_versus_greedy(MATE_TEAM_TARGET) return MATE_ESTATE: the fused K-frame kernels hold the
+ *     Greedy agents.  (FrameSkip against this opponent is K per-step calls in one graph.)
+ *   - mate_engine_set_obs_mode with a non-plain CAMERA team mode returns MATE_EINVAL, and selecting Heuristic under such a mode does.
+ * A scenario without cameras makes the selection a no-op (bit-identical to Greedy).  Both heuristic opponents may be on together.
+ * MATE_EINVAL: an unknown opponent. */
+int mate_engine_set_camera_opponent(mate_engine *engine, int32_t opponent);
+int mate_engine_heuristic_camera_tables(mate_engine *engine, const double *state_mesh, const double *coord_grid, const double *scores);
+int mate_engine_heuristic_camera_tape(mate_engine *engine, const int8_t *permutations_dev, int8_t *record_dev);
+int mate_engine_heuristic_camera_goals(mate_engine *engine, double *goals_dev, int32_t *indices_dev, void *stream);
 
 /* joint_observation() (environment.py:908-983) without advancing the simulation: recomputes
  * the view masks from the current state (see-through draws from io tape or Philox) and packs. */

@@ -115,6 +115,10 @@ PROTOTYPES = {
     'mate_engine_policy_actions': (INT, [P, P, P, P]),
     'mate_engine_policy_greedy_target_actions': (INT, [P, P, P]),
     'mate_engine_set_target_opponent': (INT, [P, I32]),
+    'mate_engine_set_camera_opponent': (INT, [P, I32]),
+    'mate_engine_heuristic_camera_tables': (INT, [P, P, P, P]),
+    'mate_engine_heuristic_camera_tape': (INT, [P, P, P]),
+    'mate_engine_heuristic_camera_goals': (INT, [P, P, P, P]),
     'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
     'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
     'mate_engine_observe': (INT, [P, IO, P]),

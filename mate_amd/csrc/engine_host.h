@@ -62,6 +62,16 @@ struct Opponent {        // mate_engine_set_target_opponent: which scripted agen
     double *d_final = nullptr;                   // [N][Nt][2] f64, engine-owned, allocated at the first switch to Heuristic: the drift launch's output, the stepping launch's target actions
     bool drifted = false;                        // the last call with the on-device agents ran the drift launch: d_final is what its step consumed (mate_engine_policy_actions)
 };
+struct CameraOpponent {  // mate_engine_set_camera_opponent: which scripted agent plays the camera team where the engine plays it (opponent_rows.hpp: heuristic_camera_kernel)
+    int kind = MATE_OPPONENT_GREEDY;
+    double *d_mesh = nullptr, *d_grid = nullptr, *d_scores = nullptr;      // mate_engine_heuristic_camera_tables: the three tables on the device
+    double *d_action = nullptr, *d_prev = nullptr, *d_goals = nullptr;     // [N][Nc][2] f64 each, engine-owned, allocated at the first switch to Heuristic
+    int32_t *d_index = nullptr, *d_episode = nullptr;                      // [N][Nc] goal state indices; [N] the episode whose first call has reset the agents
+    const int8_t *permutations = nullptr;                                  // mate_engine_heuristic_camera_tape: both hold until replaced
+    int8_t *record = nullptr;
+    bool acted = false;                          // the last call with the on-device agents ran the launch: d_action is what its step consumed (mate_engine_policy_actions)
+    bool ran = false;                            // ... some call has since the switch to Heuristic: the Greedy camera agents' memory is behind (switching back marks them for reset)
+};
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
     FragmentArgs args{};
@@ -119,6 +129,7 @@ struct mate_engine {
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
     Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
+    CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -219,6 +230,8 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   2a drift       heuristic_drift_kernel between the agents' launch and the stepping launch: the Heuristic   step_with_policies
 //                  target opponents' final joint action (opponent_rows.hpp); two-launch form only, where the
 //                  engine plays the targets (heuristic_targets: a property of the call, like `selected`, not of the plan)
+//   2b cameras     heuristic_camera_kernel in front of the stepping launch: the Heuristic camera opponents' joint     step_with_policies
+//                  action (opponent_rows.hpp); two-launch form only, where the engine plays the cameras (heuristic_cameras)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
@@ -250,6 +263,9 @@ static Tiles plan_fragment_rows(const mate_engine *e) { return {blocks_of(e, kAt
 // The engine plays the target team of this call (`team_caller`: -1 both teams are the agents, else the caller's) with the Heuristic agent: the call takes the two-launch
 // form with the drift launch in it (one_launch_step), the fused K-frame launches refuse (rollout_with_policies: their kernels hold the Greedy agents)
 static bool heuristic_targets(const mate_engine *e, int team_caller) { return e->opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_TARGET; }
+// The engine plays the camera team of this call with the Heuristic agent: the two-launch form with heuristic_camera_kernel in front of the stepping launch, no fused K-frame
+// launch.  (A scenario without cameras: the selection is a no-op.)
+static bool heuristic_cameras(const mate_engine *e, int team_caller) { return e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_CAMERA && e->p.Nc > 0; }
 static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;

@@ -541,6 +541,8 @@ extern "C" int mate_engine_set_obs_mode(mate_engine *e, int32_t camera_mode, int
     if (camera_mode < 0 || camera_mode > 2 || target_mode < 0 || target_mode > 2) return fail(MATE_EINVAL, "observation mode must be 0 (plain), 1 (enhanced) or 2 (shared field of view)");
     if (target_mode != 0 && e->opponent.kind == MATE_OPPONENT_HEURISTIC)
         return fail(MATE_EINVAL, "set_obs_mode: the heuristic target opponent (mate_engine_set_target_opponent) senses the cameras of its plain rows: the target team mode must stay 0");
+    if (camera_mode != 0 && e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC)
+        return fail(MATE_EINVAL, "set_obs_mode: the heuristic camera opponent (mate_engine_set_camera_opponent) senses the targets of its plain rows: the camera team mode must stay 0");
     { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
     e->cam_mode = camera_mode; e->tgt_mode = target_mode;
     return apply_obs_tables(e);
@@ -1380,15 +1382,27 @@ static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_st
             e->g.obs_mode == 0 && !e->g.xdesc, team_caller < 0 || (io && (team_caller == 0 ? io->camera_actions_dev : io->target_actions_dev))};
 }
 // step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
-// recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two)
+// recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two),
+// the Heuristic camera opponent (its launch takes the camera agents' place)
 static bool one_launch_step(const mate_engine *e, const FusedCall &c, int team_caller, const mate_step_io *io, const mate_policy_tape *tape) {
-    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller);
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller);
 }
 // 2a: between the agents' launch and the stepping launch -- the Heuristic opponents' final joint action from the Greedy one (`freeze_done`: of the agents' launch)
 static int launch_drift(mate_engine *e, const AttachedPlan &pl, int freeze_done, hipStream_t stream) {
     if (!pl.drift_rows.blocks) return MATE_OK;
     const DriftArgs a{e->q.tgt_act, e->opponent.d_final, e->g.own_masks, e->q.noise_scale, e->p.bit_range, freeze_done};
     HIP_TRY(launch_heuristic_drift(pl.drift_rows.blocks, pl.drift_rows.lds, stream, e->d_params, e->g, a));
+    return MATE_OK;
+}
+
+// 2b: in front of the stepping launch -- the Heuristic camera opponents' joint action, goals and memory (`freeze_done`: of the call).  Identical arguments at
+// every call but for the tapes, no allocation, no synchronisation.
+static int launch_heuristic_cameras(mate_engine *e, const mate_policy_tape *tape, int freeze_done, hipStream_t stream) {
+    CameraOpponent &o = e->camera_opponent;
+    const HeuristicCameraArgs a{o.d_mesh, o.d_grid, o.d_scores, e->g.own_masks, o.d_action, o.d_prev, o.d_goals, o.d_index, o.d_episode,
+                                tape ? tape->camera_resample_u_dev : nullptr, tape ? tape->camera_sample_u_dev : nullptr, o.permutations, o.record, freeze_done};
+    HIP_TRY(launch_heuristic_camera((unsigned)e->N, heuristic_camera_lds_bytes(e->p.Nc), stream, e->d_params, e->g, a));
+    o.ran = true;
     return MATE_OK;
 }
 
@@ -1418,6 +1432,9 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     PolicyPtrs q = e->q;
     std::memset(&q.tape, 0, sizeof(q.tape));
     q.caller_team = team_caller;      // (the agents of the caller's team do not act: greedy_policy_body)
+    const bool hcams = heuristic_cameras(e, team_caller);
+    if (hcams) q.caller_team = MATE_TEAM_CAMERA;      // the Greedy camera agents do not act either: step_greedy runs the Greedy (or Heuristic) targets alone,
+    const bool agents = !(hcams && team_caller == MATE_TEAM_TARGET);      // ... and with the targets the caller's nobody of the Greedy pair acts: no agents' launch
     if (tape) {
         q.tape.cam_binom_u = tape->camera_resample_u_dev; q.tape.cam_sample_u = tape->camera_sample_u_dev;
         q.tape.cam_delay = tape->camera_delay_dev; q.tape.tgt_choice_u = tape->target_choice_u_dev;
@@ -1427,15 +1444,19 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     const unsigned blocks = (unsigned)((e->N + 3) / 4);
     Ptrs gp = e->g;
     gp.freeze_done = auto_reset > 1;
-    launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
-    HIP_TRY(hipGetLastError());
+    if (agents) {
+        launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
+        HIP_TRY(hipGetLastError());
+    }
+    if (hcams) { const int rc_ = launch_heuristic_cameras(e, tape, gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
+    e->camera_opponent.acted = hcams;
     const bool drift = heuristic_targets(e, team_caller);      // (the caller plays the targets: no opponent of that team acts)
     if (drift) { const int rc_ = launch_drift(e, plan_attached(e, selected), gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
     e->opponent.drifted = drift;
     mate_step_io io2;
     if (io) io2 = *io; else std::memset(&io2, 0, sizeof(io2));
     // the caller's team keeps its own pointer and encoding (f32 / f64 / grid indices); the agents' joint action is f64 pairs
-    if (team_caller != 0) { io2.camera_actions_dev = q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
+    if (team_caller != 0) { io2.camera_actions_dev = hcams ? e->camera_opponent.d_action : q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
     if (team_caller != 1) { io2.target_actions_dev = drift ? e->opponent.d_final : q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
     const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
@@ -1545,6 +1566,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (heuristic_targets(e, team_caller))      // (a per-step call never arrives here with it: one_launch_step)
         return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the target opponent is the heuristic one (mate_engine_set_target_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
                     team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
+    if (heuristic_cameras(e, team_caller))
+        return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the camera opponent is the heuristic one (mate_engine_set_camera_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
+                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
     if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }
     if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
@@ -1586,6 +1610,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     { const int rc_ = take_timing_events(e, !e->dev_tick, &t); if (rc_ != MATE_OK) return rc_; }
     e->last_flow = pl.last_flow;
     e->opponent.drifted = false;      // (the target team's joint action of this launch is in q.tgt_act: the Greedy agents', or the caller's)
+    e->camera_opponent.acted = false;
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
@@ -1609,7 +1634,7 @@ extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, (hipStream_t)stream);
     if (camera_actions_dev && e->p.Nc > 0)
-        HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->camera_opponent.acted ? e->camera_opponent.d_action : e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (target_actions_dev)      // what the step consumed: behind a call that ran the drift launch, its output
         HIP_TRY(hipMemcpyAsync(target_actions_dev, e->opponent.drifted ? e->opponent.d_final : e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MATE_OK;
@@ -1620,6 +1645,77 @@ extern "C" int mate_engine_policy_greedy_target_actions(mate_engine *e, double *
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, (hipStream_t)stream);
     HIP_TRY(hipMemcpyAsync(target_actions_dev, e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MATE_OK;
+}
+
+// The Heuristic camera opponent (include/mate_engine.h, csrc/opponent_rows.hpp): tables, tapes, selection, goals.
+extern "C" int mate_engine_heuristic_camera_tables(mate_engine *e, const double *state_mesh, const double *coord_grid, const double *scores) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!state_mesh || !coord_grid || !scores) return fail(MATE_EINVAL, "heuristic_camera_tables: null table");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the tables while they change)
+    CameraOpponent &o = e->camera_opponent;
+    if (!o.d_scores) {
+        int rc;
+        if ((rc = dev_alloc(e, &o.d_mesh, (size_t)kHcStates * 3, false))) return rc;
+        if ((rc = dev_alloc(e, &o.d_grid, (size_t)kHcPoints * 2, false))) return rc;
+        if ((rc = dev_alloc(e, &o.d_scores, (size_t)kHcPoints * kHcStates, false))) { return rc; }
+    }
+    HIP_TRY(hipMemcpy(o.d_mesh, state_mesh, sizeof(double) * kHcStates * 3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(o.d_grid, coord_grid, sizeof(double) * kHcPoints * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(o.d_scores, scores, sizeof(double) * (size_t)kHcPoints * kHcStates, hipMemcpyHostToDevice));
+    return MATE_OK;
+}
+extern "C" int mate_engine_heuristic_camera_tape(mate_engine *e, const int8_t *permutations_dev, int8_t *record_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    e->camera_opponent.permutations = permutations_dev; e->camera_opponent.record = record_dev;
+    return MATE_OK;
+}
+extern "C" int mate_engine_heuristic_camera_goals(mate_engine *e, double *goals_dev, int32_t *indices_dev, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    const CameraOpponent &o = e->camera_opponent;
+    if (!o.d_goals) return fail(MATE_ESTATE, "heuristic_camera_goals: the heuristic camera opponent has not been selected (mate_engine_set_camera_opponent)");
+    HIP_TRY(hipSetDevice(e->device));
+    note_stream(e, (hipStream_t)stream);
+    if (goals_dev) HIP_TRY(hipMemcpyAsync(goals_dev, o.d_goals, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (indices_dev) HIP_TRY(hipMemcpyAsync(indices_dev, o.d_index, sizeof(int32_t) * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MATE_OK;
+}
+extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_camera_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "set_camera_opponent: call mate_engine_policy_enable() first (the Greedy agents of the other team, and the engine's own view masks)");
+    CameraOpponent &o = e->camera_opponent;
+    const int Nc = e->p.Nc;
+    if (opponent == MATE_OPPONENT_HEURISTIC && e->cam_mode != 0)
+        return fail(MATE_EINVAL, "set_camera_opponent: the heuristic camera opponent senses the targets of its plain rows, the camera team's observation mode is %d (mate_engine_set_obs_mode)", e->cam_mode);
+    if (opponent == MATE_OPPONENT_HEURISTIC && Nc > 0 && !o.d_scores)
+        return fail(MATE_ESTATE, "set_camera_opponent: install the heuristic camera tables first (mate_engine_heuristic_camera_tables)");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the buffers the getters switch between)
+    if (opponent == o.kind) return MATE_OK;
+    if (Nc == 0) { o.kind = opponent; return MATE_OK; }      // (nobody to play: a no-op, heuristic_cameras)
+    if (opponent == MATE_OPPONENT_HEURISTIC) {
+        if (!o.d_action) {
+            const size_t pairs = (size_t)e->N * Nc * 2;
+            int rc;
+            if ((rc = dev_alloc(e, &o.d_prev, pairs))) return rc;
+            if ((rc = dev_alloc(e, &o.d_goals, pairs))) return rc;
+            if ((rc = dev_alloc(e, &o.d_index, (size_t)e->N * Nc))) return rc;
+            if ((rc = dev_alloc(e, &o.d_episode, (size_t)e->N))) return rc;
+            const hipError_t err = set_dynamic_lds(heuristic_camera_function(), heuristic_camera_lds_bytes(Nc));
+            if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
+            if ((rc = dev_alloc(e, &o.d_action, pairs))) return rc;      // (last: its presence says all of the above is there)
+        }
+        // the agents start afresh: prev_action (0, 0), and their reset at the first acting call whatever the episode
+        HIP_TRY(hipMemset(o.d_prev, 0, sizeof(double) * 2 * Nc * (size_t)e->N));
+        HIP_TRY(hipMemset(o.d_episode, 0xff, sizeof(int32_t) * (size_t)e->N));
+        o.ran = false;
+    } else if (o.ran) {
+        // the Greedy camera agents sat out while the Heuristic ones played: their reset at their next acting call (PolCtx::cam_episode <- -1)
+        const size_t offset = sizeof(double) * ((size_t)e->q.TW + 2 * (size_t)Nc * e->p.Nt + 2 * (size_t)Nc) + sizeof(int32_t) * ((size_t)Nc * e->p.Nt + 2 * (size_t)Nc * Nc + Nc);
+        HIP_TRY(hipMemset2D(reinterpret_cast<unsigned char *>(e->q.pol) + offset, sizeof(double) * (size_t)e->q.PW, 0xff, sizeof(int32_t), (size_t)e->N));
+    }
+    o.kind = opponent; o.acted = false;
     return MATE_OK;
 }
 

@@ -17,7 +17,7 @@ from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_tab
 from mate_amd.config import scenario_tables
 
 __all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'encode_selection', 'decode_selection',
-           'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS']
+           'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS', 'CAMERA_AGENTS']
 
 SCALAR_NAMES = ('camera_team_reward', 'target_team_reward', 'done', 'coverage_rate', 'real_coverage_rate',
                 'mean_transport_rate', 'num_delivered_cargoes', 'normalized_target_team_reward')
@@ -42,6 +42,7 @@ def export_layout(Nc, Nt, No):
     return layout, off
 
 
+CAMERA_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* for the camera team (HeuristicCameraAgent: heuristic_tables.py, csrc/opponent_rows.hpp)
 TARGET_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* (include/mate_engine.h): the scripted agents that can play the target team
 
 def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
@@ -154,6 +155,9 @@ class Engine:
         check(self.lib.mate_engine_set_episode_stats(self._h, ctypes.c_void_p(self.episode_stats.data_ptr())))
         self.state_dim = layout.state_dim
         self.target_agent = 'greedy'      # the scripted agent of the target team (set_target_opponent)
+        self.camera_agent = 'greedy'      # ... and of the camera team (set_camera_opponent)
+        self._camera_tables_installed = False
+        self._camera_tape = (None, None)      # the tensors mate_engine_heuristic_camera_tape points at
         self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
         self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
         # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
@@ -540,12 +544,55 @@ class Engine:
         With graph_steps > 0 the constructor runs `auto_reset` REAL steps before it captures (Stepper.warmup_steps)."""
         return Stepper(self, cam_act, tgt_act, auto_reset, graph_steps, between, versus, frame_skip)
 
-    def enable_policies(self, target_agent='greedy'):
-        """Allocate the on-device policy state (call before the reset whose observations the agents act on).  `target_agent`:
-        the scripted agent that plays the target team where the engine plays it (set_target_opponent)."""
+    def enable_policies(self, target_agent='greedy', camera_agent='greedy'):
+        """Allocate the on-device policy state (call before the reset whose observations the agents act on).  `target_agent` /
+        `camera_agent`: the scripted agent that plays that team where the engine plays it (set_target_opponent / set_camera_opponent)."""
+        for name, value, known in (('target_agent', target_agent, TARGET_AGENTS), ('camera_agent', camera_agent, CAMERA_AGENTS)):
+            if value not in known:
+                raise ValueError(f"{name} must be one of {known}, got {value!r}")
         check(self.lib.mate_engine_policy_enable(self._h))
         if target_agent != 'greedy' or self.target_agent != 'greedy':
             self.set_target_opponent(target_agent)
+        if camera_agent != 'greedy' or self.camera_agent != 'greedy':
+            self.set_camera_opponent(camera_agent)
+
+    def set_camera_opponent(self, camera_agent):
+        """'greedy' (GreedyCameraAgent, the default) or 'heuristic' (HeuristicCameraAgent, mate/agents/heuristic.py:17-287: a central
+        controller scores 756 poses per camera against the sensed targets in range, tries 32 orders of greedy assignment and hands
+        every camera its goal pose) as the camera team of step_greedy and step_versus_greedy('target')
+        (mate_engine_set_camera_opponent).  Any call boundary; enable_policies first.  The first switch builds the three tables
+        (heuristic_tables.py) and installs them.  While 'heuristic' those calls run the heuristic cameras' launch in front of the
+        step, the fused rollouts against the engine's cameras and a non-plain camera observation mode are refused; a scenario
+        without cameras is unaffected."""
+        if camera_agent not in CAMERA_AGENTS:
+            raise ValueError(f"camera_agent must be one of {CAMERA_AGENTS}, got {camera_agent!r}")
+        if camera_agent == 'heuristic' and self.num_cameras > 0 and not self._camera_tables_installed:
+            from mate_amd.heuristic_tables import heuristic_camera_tables
+            camera = scenario_tables(self.config)['camera']
+            mesh, grid, scores = heuristic_camera_tables(camera['max_sight_range'], camera['min_viewing_angle'])
+            check(self.lib.mate_engine_heuristic_camera_tables(self._h, *(table.ctypes.data_as(ctypes.c_void_p) for table in (mesh, grid, scores))))
+            self._camera_tables_installed = True
+        check(self.lib.mate_engine_set_camera_opponent(self._h, CAMERA_AGENTS.index(camera_agent)))
+        self.camera_agent = camera_agent
+
+    def heuristic_camera_tape(self, permutations=None, record=None):
+        """Recorded permutations for the heuristic cameras' controller ([N, 32, Nc] int8 on the device; None: Philox draws) and a
+        tensor of that shape that receives the permutations every launch used (None: nothing is stored).  Both hold until replaced."""
+        shape = (self.num_envs, 32, self.num_cameras)
+        for name, value in (('permutations', permutations), ('record', record)):
+            if value is not None and (value.dtype != torch.int8 or tuple(value.shape) != shape or not value.is_contiguous() or value.device != self.device):
+                raise ValueError(f'{name} must be a contiguous int8 tensor of shape {shape} on {self.device}')
+        check(self.lib.mate_engine_heuristic_camera_tape(self._h, None if permutations is None else ctypes.c_void_p(permutations.data_ptr()),
+                                                         None if record is None else ctypes.c_void_p(record.data_ptr())))
+        self._camera_tape = (permutations, record)
+
+    def heuristic_camera_goals(self):
+        """(goals [N, Nc, 2] f64 -- (orientation, viewing angle), NaN where a camera has none --, state indices [N, Nc] i32, -1 where
+        none) of the heuristic cameras' last launch."""
+        goals = torch.zeros((self.num_envs, self.num_cameras, 2), dtype=torch.float64, device=self.device)
+        index = torch.zeros((self.num_envs, self.num_cameras), dtype=torch.int32, device=self.device)
+        check(self.lib.mate_engine_heuristic_camera_goals(self._h, ctypes.c_void_p(goals.data_ptr()), ctypes.c_void_p(index.data_ptr()), self._stream()))
+        return goals, index
 
     def set_target_opponent(self, target_agent):
         """'greedy' (GreedyTargetAgent, the default) or 'heuristic' (HeuristicTargetAgent, mate/agents/heuristic.py:290-337: the
@@ -1106,6 +1153,9 @@ class Stepper:
         if self.frame_skip > 1 and versus in ('camera', 0) and eng.target_agent != 'greedy':
             raise ValueError(f"make_stepper(versus='camera', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the target opponent is "
                              f"{eng.target_agent!r} (Engine.set_target_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
+        if self.frame_skip > 1 and versus in ('target', 1) and eng.camera_agent != 'greedy' and eng.num_cameras > 0:
+            raise ValueError(f"make_stepper(versus='target', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the camera opponent is "
+                             f"{eng.camera_agent!r} (Engine.set_camera_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
         # versus = 'camera' / 'target': the caller's team (MultiCamera / MultiTarget); the other team is played by the on-device
         # greedy agents (Engine.step_versus_greedy) and its tensor argument is ignored

@@ -13,7 +13,7 @@ from mate_amd import constants as consts
 from mate_amd import spaces
 from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
-from mate_amd.engine import SCALAR_NAMES, TARGET_AGENTS, Engine, fragment_coefficient_table
+from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, TARGET_AGENTS, Engine, fragment_coefficient_table
 from mate_amd.utils import Message, Team, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
@@ -442,11 +442,11 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         goal = None if goal is None else torch.from_numpy(np.nan_to_num(np.asarray(goal, dtype=np.float64), nan=0.0)[None].copy()).to(dev)
         return ct, goal
 
-    def enable_greedy_policies(self, target_agent='greedy'):
+    def enable_greedy_policies(self, target_agent='greedy', camera_agent='greedy'):
         """Let the engine play GreedyCameraAgent vs GreedyTargetAgent itself (`step_greedy`); call before the reset()
         whose observations the agents first act on.  target_agent='heuristic': HeuristicTargetAgent plays the targets
-        (Engine.set_target_opponent)."""
-        self.engine.enable_policies(target_agent=target_agent)
+        (Engine.set_target_opponent); camera_agent='heuristic': HeuristicCameraAgent the cameras (Engine.set_camera_opponent)."""
+        self.engine.enable_policies(target_agent=target_agent, camera_agent=camera_agent)
         self._policies_on = True
 
     def step_greedy(self):
@@ -626,10 +626,11 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
 
 
 def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, target_reward_shaping=None, enhanced_observation=None,
-                       shared_field_of_view=None, camera_selection=None, target_agent='greedy'):
+                       shared_field_of_view=None, camera_selection=None, target_agent='greedy', camera_agent='greedy'):
     """The argument rules of BatchedMultiAgentTracking(frame_skip=K, learner=...), checked ahead of everything that needs a GPU.
     Returns None without `frame_skip`, else {'frame_skip', 'learner', 'shaping'}: the learner's (coefficients, reduction) or None."""
     assert target_agent in TARGET_AGENTS, f'target_agent = {target_agent!r}: one of {TARGET_AGENTS}'
+    assert camera_agent in CAMERA_AGENTS, f'camera_agent = {camera_agent!r}: one of {CAMERA_AGENTS}'
     if frame_skip is None:
         assert learner is None, "learner = ... belongs to frame_skip = K (the fused learner-versus-greedy fragments)"
         return None
@@ -644,6 +645,8 @@ def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, 
     assert not camera_selection, 'camera_selection steps one frame per call: it does not combine with frame_skip'
     assert learner != 'camera' or target_agent == 'greedy', \
         f"target_agent = {target_agent!r} is not available with frame_skip, learner = 'camera': the fused K-frame launch holds the Greedy agents (step per frame instead)"
+    assert learner != 'target' or camera_agent == 'greedy', \
+        f"camera_agent = {camera_agent!r} is not available with frame_skip, learner = 'target': the fused K-frame launch holds the Greedy agents (step per frame instead)"
     other = target_reward_shaping if learner == 'camera' else camera_reward_shaping
     assert other is None, f"frame_skip with learner = {learner!r} shapes the learner's rewards only (the other team is the greedy agents)"
     shaping = camera_reward_shaping if learner == 'camera' else target_reward_shaping
@@ -686,17 +689,20 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
-                 learner=None, first_rows=False, target_agent='greedy', **kwargs):
+                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
         self._target_shapers = {}                         # (auxiliary_target_rewards: one shaper per (coefficients, reduction))
         self._fragment_live = None                        # (_fragment_reset: the scalar record that says which environments were reset)
         self._fragment = fragment_arguments(self.config, frame_skip, learner, camera_reward_shaping, target_reward_shaping, enhanced_observation,
-                                            shared_field_of_view, camera_selection, target_agent)
+                                            shared_field_of_view, camera_selection, target_agent, camera_agent)
         assert target_agent == 'greedy' or not any(team in ('both', 'target') for team in (enhanced_observation, shared_field_of_view)), \
             f"target_agent = {target_agent!r} senses the cameras of its plain rows: no enhanced_observation / shared_field_of_view for the target team"
-        self.target_agent = target_agent
+        assert camera_agent == 'greedy' or not any(team in ('both', 'camera') for team in (enhanced_observation, shared_field_of_view)), \
+            f"camera_agent = {camera_agent!r} senses the targets of its plain rows: no enhanced_observation / shared_field_of_view for the camera team"
+        assert camera_agent == 'greedy' or not camera_selection, f"camera_agent = {camera_agent!r}: camera_selection plays the camera team itself"
+        self.target_agent, self.camera_agent = target_agent, camera_agent
         assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
             self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype,
@@ -743,7 +749,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
-        if self._fragment or (target_agent != 'greedy' and not camera_selection):
+        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection):
             self.enable_greedy_policies()
 
     def seed(self, seed):
@@ -861,7 +867,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
 
     def enable_greedy_policies(self):
-        self.engine.enable_policies(target_agent=self.target_agent)
+        self.engine.enable_policies(target_agent=self.target_agent, camera_agent=self.camera_agent)
         self._policies_on = True
 
     def step_versus_greedy(self, team, joint_action):

@@ -98,6 +98,8 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--episodes', type=int, default=1)
     ap.add_argument('--policy', choices=['greedy', 'random'], default='greedy')
+    ap.add_argument('--camera-agent', choices=['greedy', 'heuristic'], default='greedy',
+                    help="the scripted agent of the camera team under --policy greedy (mate.evaluate's --camera-agent)")
     ap.add_argument('--target-agent', choices=['greedy', 'heuristic'], default='greedy',
                     help="the scripted agent of the target team under --policy greedy (mate.evaluate's --target-agent)")
     ap.add_argument('--max-episode-steps', type=int, default=None)
@@ -107,7 +109,10 @@ def main():
     overrides = {} if args.max_episode_steps is None else {'max_episode_steps': args.max_episode_steps}
     env = mate_amd.MultiAgentTracking(args.config, **overrides)
     if args.policy == 'greedy':
-        env.enable_greedy_policies(target_agent=args.target_agent)
+        agents = {'target_agent': args.target_agent}
+        if args.camera_agent != 'greedy':
+            agents['camera_agent'] = args.camera_agent
+        env.enable_greedy_policies(**agents)
     env.seed(args.seed)
     rows = []
     for episode in range(args.episodes):
