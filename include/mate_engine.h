@@ -36,6 +36,9 @@
  *                            tables with more rays are built by the full-size launch behind it
  *   MATE_NO_IMAGE=1          the fused rollouts pack observations through the descriptor table even for a shape with a
  *                            row-image compilation (same rows; tests compare the two)
+ *   MATE_HEADLINE_UNIT=0     the fused random-policy rollout of MATE-4v8-9 (f32 rows, row image, one environment per wave) stays on
+ *                            rollout_kernel instead of the kernel compiled for that one form (headline_rollout_kernel; same bytes:
+ *                            tests compare the two, benchmarks use it as the A/B lever)
  *   MATE_POLICY_SPLIT=1      mate_engine_step_greedy / _step_versus_greedy as two launches (the agents' kernel, then the step
  *                            kernel) even where the fused one-launch form applies (same results; tests compare the two)
  *   MATE_STEP_GREEDY_ROLLOUT=1  the one-launch form of mate_engine_step_greedy / _step_versus_greedy on the fused rollout kernel with a

@@ -17,6 +17,7 @@
 #include "opponent_rows.hpp"
 #include "state_rows.hpp"
 #include "shape_groups.hpp"
+#include "headline_kernels.hpp"
 
 using namespace mate;
 
@@ -39,6 +40,7 @@ struct Switches {
     bool step_greedy_rollout = false;   // MATE_STEP_GREEDY_ROLLOUT=1: the one-launch form of step_greedy / step_versus_greedy on rollout_greedy_kernel with one step (round 3) instead of step_greedy_kernel
     bool pipelined_low_priority = true; // MATE_PIPELINED_PRIORITY=0: the side stream of the pipelined restarts at the default priority instead of the device's lowest
     bool pipelined_serial = false;      // MATE_PIPELINED_SERIAL=1: the pipelined-restart protocol with the resets on the CALLER's stream (the tests' reference)
+    bool headline_unit = true;          // MATE_HEADLINE_UNIT=0: the row-image random-policy rollout of MATE-4v8-9 stays on rollout_kernel instead of headline_rollout_kernel (same bytes; the tests' reference, the A/B lever)
 };
 // ---- attached state, one struct per feature: the launch's arguments, the engine-owned buffers (kept across re-attachments), whether it is on
 struct StateRows {       // mate_engine_enable_state_rows: the caller's [N][S] buffer, its type, its (scale, bias) table on the device (null: raw rows)
@@ -187,6 +189,11 @@ static LaunchPlan plan_step(const mate_engine *e, int mode, const Ptrs &g) {
     else { pl.step = e->k.step[flow]; pl.blocks = blocks_of(e, 4); pl.lds = e->step_lds; }
     return pl;
 }
+// The engine's row-image random-policy rollout is the headline's form -- the compiled MATE-4v8-9 set with its row image, f32 rows -- and the library has
+// headline_rollout_kernel (headline_kernels.hpp; a profiling build has none): which launches run it is plan_rollout_random's choice.
+static bool headline_form(const mate_engine *e) {
+    return e->k.specialised && e->k.image && !e->p.obs_f64 && e->p.Nc == 4 && e->p.Nt == 8 && e->p.No == 9 && headline_rollout_function(0) != nullptr;
+}
 // rollout_random(); `g`: the call's record pointers, tapes cleared
 static LaunchPlan plan_rollout_random(const mate_engine *e, const Ptrs &g) {
     LaunchPlan pl;
@@ -195,6 +202,12 @@ static LaunchPlan plan_rollout_random(const mate_engine *e, const Ptrs &g) {
     pl.blocks = blocks_of(e, 4 * pl.E);
     if (pl.E > 1) { pl.step = e->k.rollout_sub[flow]; pl.lds = pl.E * e->step_lds; }
     else { pl.step = e->k.rollout[flow]; pl.lds = (flow == FLOW_RANDOM && e->k.image) ? 4 * e->image_wave_bytes : e->step_lds; }
+    // the headline's own kernel in place of rollout[FLOW_RANDOM], the instantiation of the launch's store form: same rows, same flow reported
+    // (MATE_HEADLINE_UNIT=0: never; a launch with a debug hook set -- phase clocks, a skip mask -- keeps the kernel that honours it)
+    if (pl.E == 1 && flow == FLOW_RANDOM && e->sw.headline_unit && headline_form(e) && !g.phase_clocks && !g.debug_skip) {
+        pl.step = headline_rollout_function(g.store_shifted);
+        pl.lds = headline_lds_bytes(e->image_wave_bytes);
+    }
     return pl;
 }
 // The three kernels a launch with the on-device agents can be, each with its workgroup's LDS: the environments' slices and the agents' (+ 1024 bytes: the

@@ -64,6 +64,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "shape_group.inc"
 #undef MATE_SHAPE_GROUP
 #include "opponent_kernels.inc"
+#include "headline_kernels.hip"
 #endif
 
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
@@ -103,6 +104,7 @@ static Switches read_switches() {
     if (const char *v = getenv("MATE_STEP_SPLIT")) w.step_split = atoi(v) != 0;
     if (const char *v = getenv("MATE_PIPELINED_PRIORITY")) w.pipelined_low_priority = atoi(v) != 0;
     w.pipelined_serial = flag("MATE_PIPELINED_SERIAL");
+    if (const char *v = getenv("MATE_HEADLINE_UNIT")) w.headline_unit = atoi(v) != 0;
     return w;
 }
 
@@ -430,6 +432,7 @@ extern "C" int mate_engine_create(const mate_config *cfg, int64_t num_envs, int3
         for (int f = 0; f < 3; ++f) opt_in(k.step[f], e->step_lds);
         for (int f = 0; f < 2; ++f) opt_in(k.rollout[f], f == 1 && k.image ? 4 * e->image_wave_bytes : e->step_lds);
         for (int f = 0; f < 3; ++f) opt_in(k.rollout_sub[f], k.sub_wave * e->step_lds);
+        if (headline_form(e)) for (int f = 0; f < 2; ++f) opt_in(headline_rollout_function(f), headline_lds_bytes(e->image_wave_bytes));
         with_obs_type(p.obs_f64 != 0, [&](auto tag) { opt_in(&reset_kernel<decltype(tag)>, e->reset_lds); });
         if (err != hipSuccess) rc = fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
     }
