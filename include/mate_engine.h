@@ -631,6 +631,38 @@ typedef struct mate_first_rows {
 } mate_first_rows;
 int mate_engine_enable_first_rows(mate_engine *engine, const mate_first_rows *config);   /* NULL detaches */
 
+/* Per-episode metric records (csrc/episode_rows.hpp): what the reference's example trainers report at every episode's end (examples/utils/callbacks.py:
+ * MetricCollector's mean over the agents of each learner step's infos, CustomMetricCallback.on_episode_end's mean / last / episode_<key> sums over the
+ * episode's steps), kept on the device for ONE team's perspective.  While attached every stepping call -- step, step_random, step_greedy,
+ * step_versus_greedy, step_selected, rollout_random, rollout_greedy, rollout_versus_greedy -- enqueues one more launch, episode_rows_kernel, behind the
+ * reward and the fragment launch and ahead of the restart; no stepping kernel is involved.  A learner step is one frame of the call whose scalar record does
+ * not say done = 2 -- also in a mate_engine_rollout_versus_greedy call with fragment rows attached: a fragment counts as its frames, not as one step.  The
+ * running sums live in an engine-owned table across launches; a learner step that says done = 1 appends ONE record of MATE_EPISODE_COLUMNS doubles and
+ * clears them:
+ *    0 env (first_env_index + i)   1 episode (the engine's episode number, the one in the Philox key)   2 steps (learner steps)   3 frames (live frames)
+ *    4 length (the engine's episode step count at the end: frames == length says the record covers the whole episode)
+ *    5 episode_raw_reward (the team's reward)   6 episode_normalized_raw_reward   7 episode_reward (the agent-order sum of the learner's reward row: the
+ *      attached reward rows of the team in a one-frame call in overwrite mode, else the team reward once per agent; NaN where shaped rows exist but do
+ *      not describe every step: accumulate mode, a multi-frame call, a fragment's shaped rows)
+ *    8 raw_reward = [5] / steps   9 normalized_raw_reward = [6] / steps   10 coverage_rate   11 real_coverage_rate (step-order sums / steps)
+ *   12 mean_transport_rate   13 num_delivered_cargoes (of the last step)
+ *   14 num_tracked: cameras, and only where every call brought io->masks_dev (NaN otherwise): popcount of the camera -> target bits / cameras per frame,
+ *      step-order sum / steps
+ *   15 team
+ * Every sum is f64 in step order, product then add.  Record number n (counted from 0 in *count_dev, which the caller zeroes and the engine only adds to)
+ * lives in slot n % capacity of records_dev [capacity][MATE_EPISODE_COLUMNS]; older records are overwritten; the order among the environments that
+ * finish in one launch is unspecified.  capacity >= num_envs keeps the launch parallel (one atomic add per wave); a smaller ring is served by one
+ * serial workgroup.  A reset of an environment (reset, masked reset, reset_tape, a restart, import_state) discards its sums without a record, and
+ * so does seed(); after import_state the episodes in progress give records with frames < length.  The calls then need io->scalars_dev, 16-byte
+ * aligned (MATE_EINVAL); pipelined restarts return MATE_ESTATE.  No allocation, no synchronisation, identical arguments at every call: capturable.
+ * records_dev == NULL detaches.
+ * MATE_EINVAL: an unknown team, a camera team in a scenario without cameras, capacity < 1, a null counter, buffers not 8-byte aligned.
+ * MATE_ESTATE: before the first reset / import_state.
+ * mate_engine_clear_episode_records forgets the episodes in progress (an async memset on `stream`); the ring and the counter are the caller's. */
+#define MATE_EPISODE_COLUMNS 16
+int mate_engine_enable_episode_records(mate_engine *engine, int32_t team, double *records_dev, int64_t capacity, int64_t *count_dev);
+int mate_engine_clear_episode_records(mate_engine *engine, void *stream);
+
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,
                          double *rhos_host, int32_t capacity, int32_t *count);

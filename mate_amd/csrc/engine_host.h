@@ -18,6 +18,7 @@
 #include "state_rows.hpp"
 #include "shape_groups.hpp"
 #include "headline_kernels.hpp"
+#include "episode_rows.hpp"
 
 using namespace mate;
 
@@ -86,6 +87,11 @@ struct FirstRows {       // mate_engine_enable_first_rows: the caller's buffers;
     float *scalars = nullptr;                    // [N][8]: 2.0f everywhere behind the fragment launch, then the restart's own record (column 2 = 0) where it restarted
     void *final_obs = nullptr;                   // [N][A][D] obs_dtype or null: what the fragment's obs held before the first row replaced it
 };
+struct EpisodeRecords {  // mate_engine_enable_episode_records: scalars, masks, rows and K of `args` are the launch's own
+    bool on = false;
+    EpisodeArgs args{};                          // team, A, the caller's ring and counter, the engine-owned sums
+    double *d_sums = nullptr;                    // [N][kEpisodeWords], allocated at the first enable: the learner steps of the episodes in progress
+};
 struct mate_engine {
     Switches sw{};
     hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
@@ -132,7 +138,7 @@ struct mate_engine {
     void *d_xab = nullptr;
     Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
     CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
-    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first;      // what is attached around the stepping launches (plan_attached)
+    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -249,6 +255,8 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
 //   5b first_rows  a memset node: every record of the first-row scalars reads 2.0f, "not restarted"          attached_behind_step
+//   5c episodes    episode_rows_kernel over the call's frames: the learner steps into the episodes' running    attached_behind_step
+//                  sums, one record per episode that ends (it reads 3's rows)
 //   6              the restart epilogue, a reset or an import (first_rows: the fused call's own restart      restart_finished
 //                  stores the learner team's plain first rows and its record into the first-row buffers)
 //   6b first_rows  behind THAT restart only: fragment_rows_kernel, K = 1, twice over the restart's records   attached_behind_restart
@@ -258,8 +266,8 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   8 state        state_rows_kernel, last                                                                  attached_last
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
-    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
+    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, action_mask = false, state = false;
+    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, episode_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
 };
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
 // Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
@@ -271,6 +279,8 @@ static Tiles plan_state_rows(const mate_engine *e, bool f64) {
     return {blocks_of(e, E), 256, (size_t)state_rows_lds_bytes(p.SW, p.DW, S, E, sz), E};
 }
 static Tiles plan_fragment_rows(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
+// A workgroup per tile, or ONE for all of them where the ring is smaller than the batch (episode_rows.hpp: the serial form)
+static Tiles plan_episode_rows(const mate_engine *e) { return {e->episodes.args.capacity < e->N ? 1u : blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
 // `selected`: the call is mate_engine_step_selected; `fused_team`: the call is mate_engine_rollout_versus_greedy for that team (-1: any other).  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
 // The engine plays the target team of this call (`team_caller`: -1 both teams are the agents, else the caller's) with the Heuristic agent: the call takes the two-launch
@@ -286,11 +296,13 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.reward = e->reward.on;
     pl.fragment = e->fragment.on && fused_team == e->fragment.args.team;
     pl.first_rows = pl.fragment && e->first.on;
+    pl.episodes = e->episodes.on;
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
     pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
     if (e->opponent.kind == MATE_OPPONENT_HEURISTIC) pl.drift_rows = pl.reward_rows;      // (launched by the two-launch form where the engine plays the targets: heuristic_targets)
     pl.fragment_rows = plan_fragment_rows(e);
+    if (pl.episodes) pl.episode_rows = plan_episode_rows(e);
     pl.state_rows = plan_state_rows(e, e->state.f64);
     return pl;
 }

@@ -65,6 +65,7 @@ static int fail(int code, const char *fmt, ...) {
 #undef MATE_SHAPE_GROUP
 #include "opponent_kernels.inc"
 #include "headline_kernels.hip"
+#include "episode_kernels.hip"
 #endif
 
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
@@ -583,6 +584,14 @@ extern "C" int mate_engine_get_layout(const mate_engine *e, mate_layout *out) {
     return MATE_OK;
 }
 
+// The episode records' running sums (csrc/episode_rows.hpp) forget the episodes in progress: behind seed() and import_state, whose episode numbers may repeat the tags'.
+// Every tag of the table reads NaN: no episode number equals it, the next launch starts every environment's sums from zero
+static int clear_episode_sums(mate_engine *e, hipStream_t stream) {
+    if (!e->episodes.d_sums) return MATE_OK;
+    HIP_TRY(hipMemsetAsync(e->episodes.d_sums, 0xff, (size_t)e->N * kEpisodeWords * sizeof(double), stream));
+    return MATE_OK;
+}
+
 extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (e->dev_tick) return fail(MATE_ESTATE, "seed() while the step counter is device-resident (mate_engine_device_tick)");
@@ -593,6 +602,7 @@ extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     // whatever ran before.  Here: the key, and every counter that enters a Philox counter word (episode, tick) rewound.
     hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, e->last_stream, (const Params *)e->d_params, (const Ptrs)e->g);
     HIP_TRY(hipGetLastError());
+    { const int rc_ = clear_episode_sums(e, e->last_stream); if (rc_ != MATE_OK) return rc_; }
     HIP_TRY(wait_for_launches(e));
     e->tick = 0;
     return MATE_OK;
@@ -707,6 +717,21 @@ static int launch_fragment_rows(mate_engine *e, const Tiles &t, const FragmentAr
         return with_obs_type(shaped_f64, [&](auto out) { return launch_tiles(fragment_rows_kernel<decltype(obs), decltype(out)>, t, stream, e->d_params, a); });
     });
 }
+// 5c: the call's learner steps, its `frames` frames, with the learner's reward row where one describes the step
+static int launch_episode_records(mate_engine *e, const AttachedPlan &pl, const mate_step_io *io, int frames, hipStream_t stream) {
+    EpisodeArgs a = e->episodes.args;
+    const bool camera = a.team == MATE_TEAM_CAMERA;
+    a.scalars = io->scalars_dev; a.masks = io->masks_dev; a.K = frames;
+    a.dyn = e->g.dyn; a.serial = a.capacity < e->N;
+    if (pl.fragment && e->fragment.args.shaped && e->fragment.args.team == a.team) {      // (the fragment's shaped row is the sum over its frames: no row per step)
+        a.reward_nan = 1;
+    } else if (pl.reward && (camera ? e->reward.args.cam_rows : e->reward.args.tgt_rows)) {      // (the rows of the call's LAST frame, and sums of them in accumulate mode)
+        a.rows = camera ? e->reward.args.cam_rows : e->reward.args.tgt_rows; a.rows_f64 = e->reward.f64;
+        a.reward_nan = e->reward.accumulate || frames > 1;
+    }
+    HIP_TRY(launch_episode_rows(pl.episode_rows.blocks, stream, e->d_params, a));
+    return MATE_OK;
+}
 // What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
 // `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own);
 // `fused_team`: it is mate_engine_rollout_versus_greedy for that team (-1: any other call).
@@ -729,6 +754,11 @@ static int check_attached_call(const mate_engine *e, const mate_step_io *io, boo
             return fail(MATE_EINVAL, "fragment rows are attached (mate_engine_enable_fragment_rows): the call needs io->scalars_dev, 16-byte aligned, and the learner team's observation rows");
         if (e->fragment.need_masks && !io->masks_dev)
             return fail(MATE_EINVAL, "fragment rows are attached with a mask term (num_tracked / is_tracked): the call needs io->masks_dev");
+    }
+    if (pipelined && e->episodes.on) return fail(MATE_ESTATE, no_pipeline, "episode records are", "episode_records", "them");
+    if (e->episodes.on) {      // (the episode launch walks the call's scalar records, 16 bytes at a time; the masks are optional: without them num_tracked reads NaN)
+        if (!io || !io->scalars_dev || (reinterpret_cast<uintptr_t>(io->scalars_dev) & 15u))
+            return fail(MATE_EINVAL, "episode records are attached (mate_engine_enable_episode_records): the call needs io->scalars_dev, 16-byte aligned");
     }
     return MATE_OK;
 }
@@ -756,6 +786,7 @@ static int attached_behind_step(mate_engine *e, bool selected, const mate_step_i
         if (rc != MATE_OK) return rc;
     }
     if (pl.first_rows) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->first.scalars), 0x40000000 /* 2.0f */, 8 * (size_t)e->N, stream));
+    if (pl.episodes) { const int rc = launch_episode_records(e, pl, io, frames, stream); if (rc != MATE_OK) return rc; }
     return MATE_OK;
 }
 // One K = 1 launch of the fragment kernel over the first-row records: the rows of `src` through `columns` into `dst`, for exactly the environments whose record the restart
@@ -988,6 +1019,38 @@ extern "C" int mate_engine_enable_first_rows(mate_engine *e, const mate_first_ro
     e->first.rows = cfg->rows_dev; e->first.scalars = cfg->scalars_dev; e->first.final_obs = cfg->final_obs_dev;
     e->first.on = true;
     return MATE_OK;
+}
+
+// ---- per-episode metric records: attaching, and forgetting the episodes in progress (include/mate_engine.h, csrc/episode_rows.hpp)
+extern "C" int mate_engine_enable_episode_records(mate_engine *e, int32_t team, double *records_dev, int64_t capacity, int64_t *count_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!records_dev) { e->episodes.on = false; return MATE_OK; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_episode_records called before reset() (or import_state)");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "episode records: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (team == MATE_TEAM_CAMERA && e->p.Nc == 0) return fail(MATE_EINVAL, "episode records: the scenario has no cameras to keep records for");
+    if (capacity < 1) return fail(MATE_EINVAL, "episode records: capacity must be at least 1");
+    if (!count_dev) return fail(MATE_EINVAL, "episode records: null counter");
+    if ((reinterpret_cast<uintptr_t>(records_dev) | reinterpret_cast<uintptr_t>(count_dev)) & 7u) return fail(MATE_EINVAL, "episode records: the ring and the counter must be 8-byte aligned");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the arguments while they change)
+    EpisodeRecords &r = e->episodes;
+    { int rc = MATE_OK; if (!r.d_sums && (rc = dev_alloc(e, &r.d_sums, (size_t)e->N * kEpisodeWords, false))) return rc; }
+    mate_layout layout;
+    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    EpisodeArgs a{};
+    a.sums = r.d_sums; a.records = records_dev; a.count = reinterpret_cast<unsigned long long *>(count_dev);
+    a.capacity = capacity; a.N = e->N; a.team = team; a.A = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
+    a.bit_ct = layout.bit_camera_target;
+    r.args = a;
+    r.on = true;
+    note_stream(e, e->last_stream);
+    return clear_episode_sums(e, e->last_stream);
+}
+extern "C" int mate_engine_clear_episode_records(mate_engine *e, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    { const int rc_ = enter(e, (hipStream_t)stream, "clear_episode_records"); if (rc_ != MATE_OK) return rc_; }
+    note_stream(e, (hipStream_t)stream);
+    return clear_episode_sums(e, (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_fragment_coefficients(mate_engine *e, double **coefficients_dev, int32_t *count) {
@@ -1759,6 +1822,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(import_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, src_dev);
     HIP_TRY(hipGetLastError());
+    { const int rc_ = clear_episode_sums(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
     // all environments step together, so they share one tick: adopt the imported one
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     int32_t tick = 0;

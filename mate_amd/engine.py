@@ -169,6 +169,7 @@ class Engine:
         self._clear_reward_rows()
         self._clear_selection()
         self._clear_fragment_rows()
+        self._clear_episode_records()
 
     # The detached value of every attached feature, written once: __init__ and the feature's disable_* both come here.
     def _clear_state_rows(self):
@@ -196,10 +197,17 @@ class Engine:
     def _clear_first_rows(self):
         self.fragment_first_rows = self.fragment_first_scalars = self.fragment_final_obs = None      # (enable_fragment_rows(first_rows=True))
 
+    def _clear_episode_records(self):
+        # while episode records are attached (enable_episode_records): the ring [capacity, 16] f64, the count of records ever appended
+        # [1] int64, the team's code, and how many of them episode_records() has handed out
+        self.episode_ring = self.episode_count = self.episode_team = None
+        self._episode_read = 0
+
     def close(self):
         if getattr(self, '_h', None):
             self.lib.mate_engine_destroy(self._h)
             self._h = None
+            self._clear_episode_records()
 
     __del__ = close
 
@@ -860,6 +868,49 @@ class Engine:
         """Detach the fragment launch (and the first rows with it): rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
         check(self.lib.mate_engine_enable_fragment_rows(self._h, None))
         self._clear_fragment_rows()
+
+    # ------------------------------------------------------------------ per-episode metric records
+    EPISODE_COLUMNS = ('env', 'episode', 'steps', 'frames', 'length', 'episode_raw_reward', 'episode_normalized_raw_reward', 'episode_reward',
+                       'raw_reward', 'normalized_raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'num_delivered_cargoes',
+                       'num_tracked', 'team')
+
+    def enable_episode_records(self, team, capacity=None):
+        """Attach the episode launch (mate_engine_enable_episode_records): behind every stepping call the engine adds the call's learner
+        steps -- its frames; a fragment counts as its frames -- to per-environment
+        running sums and appends one record of EPISODE_COLUMNS (the reference's CustomMetricCallback keys, for `team`'s perspective) to
+        episode_ring [capacity, 16] f64 whenever an episode ends; episode_count [1] int64 counts the records ever appended, record n lives
+        in row n % capacity.  capacity defaults to max(4 num_envs, 1024); below num_envs the launch serialises.  num_tracked is kept for
+        the camera team where the calls bring masks (want_masks), NaN otherwise.  Call after the first reset().  Returns episode_ring."""
+        code = _team_code(team)
+        capacity = max(4 * self.num_envs, 1024) if capacity is None else int(capacity)
+        with torch.cuda.device(self.device):
+            ring = torch.zeros((max(capacity, 1), len(self.EPISODE_COLUMNS)), dtype=torch.float64, device=self.device)
+            count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.mate_engine_enable_episode_records(self._h, code, ctypes.c_void_p(ring.data_ptr()), capacity, ctypes.c_void_p(count.data_ptr())))
+        self.episode_ring, self.episode_count, self.episode_team, self._episode_read = ring, count, code, 0
+        return self.episode_ring
+
+    def disable_episode_records(self):
+        """Detach the episode launch: every flow goes back to its launch sequence without it; the tensors become None."""
+        check(self.lib.mate_engine_enable_episode_records(self._h, 0, None, 0, None))
+        self._clear_episode_records()
+
+    def clear_episode_records(self):
+        """Forget the episodes in progress (their next records start from this call); the ring and the count stay."""
+        check(self.lib.mate_engine_clear_episode_records(self._h, self._stream()))
+
+    def episode_records(self):
+        """(records, dropped): the records appended since the last call, oldest first, [M, 16] f64 on the device (a copy), and how many
+        more were overwritten in the ring before they were read.  Waits for the stream's launches."""
+        assert self.episode_ring is not None, 'call enable_episode_records() first'
+        torch.cuda.current_stream(self.device).synchronize()
+        total, capacity = int(self.episode_count.item()), self.episode_ring.shape[0]
+        fresh = total - self._episode_read
+        kept = min(fresh, capacity)
+        rows = torch.arange(total - kept, total, dtype=torch.int64, device=self.device) % capacity
+        self._episode_read = total
+        return self.episode_ring[rows], fresh - kept
 
     @property
     def fragment_restarted(self):

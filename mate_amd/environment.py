@@ -683,13 +683,18 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     restarted is instead the new episode's FIRST row, through the same transform -- the row env.reset() hands the reference's trainers --
     and `info` additionally holds 'restarted' [num_envs] bool and 'final_observation' [num_envs, agents, D], whose rows hold, for the
     restarted environments only, what the returned row would have been without it (the terminal row); rewards, done and the other
-    info keys do not change.  Without `frame_skip` nothing about the class changes."""
+    info keys do not change.  Without `frame_skip` nothing about the class changes.
+
+    `episode_records` = 'camera' | 'target' | True (the `learner` of a fragment environment, else 'target'): per-episode metric records
+    for that team -- the reference's CustomMetricCallback keys -- kept on the device behind every stepping call (DESIGN.md section 3.12,
+    Engine.enable_episode_records; attached behind the first reset()); `episodes()` returns the ones that arrived since its last call.  A learner step
+    of a record is a frame, also under `frame_skip`."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
-                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', **kwargs):
+                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -703,6 +708,10 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             f"camera_agent = {camera_agent!r} senses the targets of its plain rows: no enhanced_observation / shared_field_of_view for the camera team"
         assert camera_agent == 'greedy' or not camera_selection, f"camera_agent = {camera_agent!r}: camera_selection plays the camera team itself"
         self.target_agent, self.camera_agent = target_agent, camera_agent
+        assert episode_records in (None, True, 'camera', 'target'), f"episode_records = {episode_records!r}: None, True, 'camera' or 'target'"
+        if episode_records is True:
+            episode_records = self._fragment['learner'] if self._fragment else 'target'
+        self._episode_team = episode_records              # (attached behind the first reset(): Engine.enable_episode_records)
         assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
             self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype,
@@ -712,6 +721,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
         self.engine = Engine(self.config, self.num_envs, device=device, seed=seed, first_env_index=first_env_index, obs_dtype=obs_dtype)
         self.num_cameras, self.num_targets, self.num_obstacles = self.engine.num_cameras, self.engine.num_targets, self.engine.num_obstacles
+        assert self._episode_team != 'camera' or self.num_cameras > 0, "episode_records = 'camera' needs cameras"
         self._setup_spaces()
         self.device = self.engine.device
         if relative_coordinates or rescaled_observation:   # the reference's RelativeCoordinates / RescaledObservation wrappers, fused
@@ -781,7 +791,23 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         for shaper in self._target_shapers.values():
             shaper.observe_reset()
         if self._fragment:
-            return self._fragment_reset(env_mask)
+            out = self._fragment_reset(env_mask)
+        if self._episode_team and self.engine.episode_team is None:      # (behind the reward rows, which its launch reads)
+            self.engine.enable_episode_records(self._episode_team)
+        return out
+
+    def _want_masks(self):
+        """The calls that may go without the view masks bring them for the reward launch, and for the camera team's num_tracked record."""
+        return bool(self._reward_shaping) or self._episode_team == 'camera'
+
+    def episodes(self):
+        """The episode records that arrived since the last call (`episode_records`): {column: [M] f64 tensor} for Engine.EPISODE_COLUMNS,
+        oldest first, and 'dropped': how many more the ring lost before they were read.  Waits for the stream's launches."""
+        assert self._episode_team, "built without episode_records = 'camera' | 'target' | True"
+        assert self.engine.episode_team is not None, 'reset() first'
+        records, dropped = self.engine.episode_records()
+        out = {name: records[:, k] for k, name in enumerate(self.engine.EPISODE_COLUMNS)}
+        out['dropped'] = dropped
         return out
 
     def _fragment_reset(self, env_mask=None):
@@ -846,7 +872,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def step_random(self):
         """One step under the on-device uniform random policy (no action tensors)."""
-        self.engine.step_random(auto_reset=self.auto_reset, want_masks=bool(self._reward_shaping))
+        self.engine.step_random(auto_reset=self.auto_reset, want_masks=self._want_masks())
         return self._result()
 
     def _rollout_result(self, out):
@@ -858,13 +884,13 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     def rollout_random(self, steps):
         """`steps` env.step(random action) iterations in ONE launch (the fastest flow, profiles/HISTORY.md 3.1b): every tensor of
         step()'s result with a leading [steps] axis.  Finished episodes restart after the launch."""
-        return self._rollout_result(self.engine.rollout_random(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
+        return self._rollout_result(self.engine.rollout_random(steps, auto_reset=int(self.auto_reset), want_masks=self._want_masks()))
 
     def rollout_greedy(self, steps):
         """`steps` iterations of mate.group_step with the reference's Greedy camera / target agents + env.step in ONE
         launch (agents on the device, profiles/HISTORY.md 3.1c)."""
         self._need_policies()
-        return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
+        return self._rollout_result(self.engine.rollout_greedy(steps, auto_reset=int(self.auto_reset), want_masks=self._want_masks()))
 
     def enable_greedy_policies(self):
         self.engine.enable_policies(target_agent=self.target_agent, camera_agent=self.camera_agent)
@@ -883,7 +909,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         """FrameSkip(MultiCamera | MultiTarget, frame_skip) in one launch (examples/utils/wrappers.py:301-323): rollout-shaped
         result; `rewards.sum(0)` is the wrapper's reward, `done.any(0)` its done."""
         self._need_policies()
-        return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset), want_masks=bool(self._reward_shaping)))
+        return self._rollout_result(self.engine.rollout_versus_greedy(team, joint_action, frame_skip, auto_reset=int(self.auto_reset), want_masks=self._want_masks()))
 
     def step_selected(self, selection, **replay):
         """One frame of HierarchicalCamera.step (examples/hrl/wrappers.py:93-152) for every environment: `selection` is [num_envs,

@@ -9,6 +9,12 @@ status keys and the same update rule (the row is kept from the first delivery on
 (`Engine.step_greedy`), so the whole loop is one policy launch + one step launch per step.
 
     python -m mate_amd.evaluate [--config MATE-4v2-9.yaml] [--seed 0] [--episodes 1] [--policy greedy|random]
+
+With `--num-envs N` the episodes run on the batched environment instead, N at a time under the on-device agents, and the report is
+the mean and standard deviation over the first `--episodes` episode records (Engine.enable_episode_records: the per-episode metrics
+of the reference's example trainers) of the columns EPISODE_REPORT.
+
+    python -m mate_amd.evaluate --num-envs 4096 --episodes 4096 [--policy greedy|random] [--team target|camera]
 """
 import argparse
 import time
@@ -16,7 +22,10 @@ from collections import OrderedDict
 
 import numpy as np
 
-__all__ = ['COLUMNS', 'evaluate', 'random_policy', 'format_row']
+__all__ = ['COLUMNS', 'EPISODE_REPORT', 'evaluate', 'evaluate_batched', 'random_policy', 'format_row', 'build_parser']
+
+# the columns of an episode record (Engine.EPISODE_COLUMNS) the batched form reports: the three episode_ sums, the five means, the two last values
+EPISODE_REPORT = slice(5, 15)
 
 # name -> format of the reference's table (mate/evaluate.py:52-71)
 COLUMNS = OrderedDict([
@@ -92,7 +101,32 @@ def evaluate(env, joint_policy=None, verbose=False, history=None):
     return status
 
 
-def main():
+def evaluate_batched(env, episodes, policy='greedy', chunk=16):
+    """Runs `env` (a BatchedMultiAgentTracking built with episode_records) under the on-device agents -- 'greedy': both teams' scripted
+    agents, fused `chunk` frames per launch where both are the Greedy ones; 'random': the uniform policy -- until `episodes` episode
+    records have arrived.  Returns them, oldest first, [episodes, 16] f64 on the host."""
+    import torch
+    env.reset()
+    fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy')
+    rows, have = [], 0
+    limit = (env.max_episode_steps + chunk) * (2 + episodes // env.num_envs)      # (every environment ends an episode within max_episode_steps frames)
+    for _ in range(0, limit, chunk):
+        if policy == 'random':
+            env.rollout_random(chunk)
+        elif fused:
+            env.rollout_greedy(chunk)
+        else:
+            for _ in range(chunk):
+                env.engine.step_greedy(auto_reset=env.auto_reset)
+        records = env.episodes()
+        rows.append(torch.stack([records[name] for name in env.engine.EPISODE_COLUMNS], dim=1).cpu())
+        have += rows[-1].shape[0]
+        if have >= episodes:
+            return torch.cat(rows)[:episodes].numpy()
+    raise RuntimeError(f'{have} of {episodes} episode records after {limit} frames')
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog='python -m mate_amd.evaluate', description=__doc__.split('\n')[0])
     ap.add_argument('--config', '--cfg', default='MATE-4v2-9.yaml')
     ap.add_argument('--seed', type=int, default=0)
@@ -104,9 +138,30 @@ def main():
                     help="the scripted agent of the target team under --policy greedy (mate.evaluate's --target-agent)")
     ap.add_argument('--max-episode-steps', type=int, default=None)
     ap.add_argument('--verbose', action='store_true')
-    args = ap.parse_args()
+    ap.add_argument('--num-envs', type=int, default=None,
+                    help='run the batched environment, this many episodes at a time, and report episode records (without: the N = 1 loop)')
+    ap.add_argument('--team', choices=['camera', 'target'], default='target',
+                    help='with --num-envs: the team whose rewards the records hold (num_tracked is kept for the camera team)')
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     import mate_amd
     overrides = {} if args.max_episode_steps is None else {'max_episode_steps': args.max_episode_steps}
+    if args.num_envs is not None:
+        from .engine import Engine
+        env = mate_amd.BatchedMultiAgentTracking(args.config, num_envs=args.num_envs, seed=args.seed, episode_records=args.team,
+                                                 target_agent=args.target_agent, camera_agent=args.camera_agent, **overrides)
+        if args.policy == 'greedy':
+            env.enable_greedy_policies()
+        records = evaluate_batched(env, args.episodes, args.policy)
+        names = Engine.EPISODE_COLUMNS[EPISODE_REPORT]
+        print(f'{len(records)} episodes of {args.config}, {args.num_envs} at a time, team {args.team}:')
+        for name, column in zip(names, records[:, EPISODE_REPORT].T):
+            print(f'  {name}: {column.mean():.6g} +- {column.std():.6g}')
+        env.close()
+        return records
     env = mate_amd.MultiAgentTracking(args.config, **overrides)
     if args.policy == 'greedy':
         agents = {'target_agent': args.target_agent}
