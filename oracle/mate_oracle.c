@@ -680,6 +680,8 @@ static void assign_goals(mo_env *e, const double *goal_u, uniform_fn uf, double 
     *reward = rw; *delayed = dl;
 }
 
+void mo_assign_goals(mo_env *e, const double *goal_u, double *out) { assign_goals(e, goal_u, goal_uniform_step, &out[0], &out[1]); }
+
 /* coverage metrics computed inside joint_observation (environment.py:966-979) */
 static void update_metrics(mo_env *e) {
     int nb = 0, tb = 0, tr = 0;

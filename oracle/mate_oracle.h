@@ -57,6 +57,9 @@ void mo_build_luts(mo_env *env);                      /* Camera.add_obstacles fo
 int mo_get_lut(const mo_env *env, int camera, int outer, double *phis, double *rhos, int cap);
 int mo_set_lut(mo_env *env, int camera, int outer, const double *phis, const double *rhos, int n);
 void mo_update_view(mo_env *env, const double *tape_ct); /* environment.py:1356-1388 (a6); tape [Nc*Nt] or NULL */
+/* _assign_goals alone (environment.py:1271-1324) on the state and tracked_bits as they stand; goal_u [Nt] as in mo_step;
+ * out = {target_team_reward, delayed_target_team_reward} */
+void mo_assign_goals(mo_env *env, const double *goal_u, double *out);
 /* One env.step() (environment.py:590-676).  tape_ct [Nc*Nt] uniforms for the
  * see-through draw and goal_u [Nt] uniforms for the goal choice; NULL = use the
  * counter-based Philox streams shared with the HIP engine. */

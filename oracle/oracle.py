@@ -65,6 +65,7 @@ def _load():
     lib.mo_set_lut.argtypes = [P, I, I, c_double_p, c_double_p, I]
     lib.mo_update_view.argtypes = [P, c_double_p]
     lib.mo_step.argtypes = [P, c_double_p, c_double_p, c_double_p, c_double_p]
+    lib.mo_assign_goals.argtypes = [P, c_double_p, c_double_p]
     lib.mo_observe.argtypes = [P, c_double_p, c_double_p]
     lib.mo_policy_create.restype = P
     lib.mo_policy_create.argtypes = []
@@ -294,6 +295,14 @@ class OracleEnv:
             goal_u = np.ascontiguousarray(np.nan_to_num(goal_u, nan=0.0), dtype=np.float64)
             gp = _dp(goal_u)
         lib.mo_step(self._h, _dp(cam_act), _dp(tgt_act), tp, gp)
+
+    def assign_goals(self, goal_u=None):
+        """_assign_goals alone on the state and tracked_bits as they stand: (target_team_reward, delayed_target_team_reward)."""
+        out = np.zeros(2)
+        if goal_u is not None:
+            goal_u = np.ascontiguousarray(goal_u, dtype=np.float64)
+        lib.mo_assign_goals(self._h, _dp(goal_u) if goal_u is not None else None, _dp(out))
+        return float(out[0]), float(out[1])
 
     def observe(self):
         cam = np.zeros((max(self.Nc, 1), self.Dc))
