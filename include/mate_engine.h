@@ -663,6 +663,35 @@ int mate_engine_enable_first_rows(mate_engine *engine, const mate_first_rows *co
 int mate_engine_enable_episode_records(mate_engine *engine, int32_t team, double *records_dev, int64_t capacity, int64_t *count_dev);
 int mate_engine_clear_episode_records(mate_engine *engine, void *stream);
 
+/* MoreTrainingInformation rows (csrc/info_rows.hpp): what the reference's mate.MoreTrainingInformation wrapper
+ * (wrappers/more_training_information.py:42-98) adds to every agent's info at a step, as three f64 outputs per environment (integers and booleans stored
+ * exactly as doubles; the column order is the ABI):
+ *   camera_rows_dev [N][Nc][MATE_INFO_CAMERA_COLUMNS]   0 num_tracked = camera_target_view_mask[c, :].sum()   1 is_sensed = target_camera_view_mask[:, c].any()
+ *   target_rows_dev [N][Nt][MATE_INFO_TARGET_COLUMNS]   0 goal (-1: none)   1 goal_distance (warehouse_distances[goal]; 1000 without a goal)
+ *       2 .. 5 warehouse_distances = max(|location - WAREHOUSES[w]| - 75, 0)   6 individual_done (target_dones[t]: the goal differs from the goal before this
+ *       step and that goal was >= 0)   7 is_tracked = camera_target_view_mask[:, t].any()   8 is_colliding
+ *   cargo_rows_dev  [N][MATE_INFO_CARGO_COLUMNS]        0 .. 3 remaining_cargo_counts   4 .. 7 awaiting_cargo_counts   8 .. 23 remaining_cargoes [warehouse][destination]
+ * The wrapper's other keys exist already: `state` is the state rows; the five masks are the call's mask words; camera_states / target_states are the private
+ * slices of the plain observation rows; obstacle_states is part of the state row.
+ * mate_engine_enable_info_rows attaches one launch, info_rows_kernel, behind every stepping call -- step, step_random, step_greedy, step_versus_greedy,
+ * step_selected, rollout_random, rollout_greedy, rollout_versus_greedy -- behind the reward launch and ahead of the restart: the rows describe the step the
+ * call's scalar record describes, the terminal one included.  A multi-frame call leaves the rows of its LAST frame, with individual_done = NaN (a delivery
+ * between the frames cannot be seen from the end state); the goals of that frame are what the next call compares with.  individual_done is measured against an
+ * engine-owned snapshot of the previous step's goals and episode number, independent of the reward rows': a step of another episode than the snapshot's
+ * reports 0; every reset, masked reset, reset_tape, restart and import_state is followed by a snapshot-only launch.  An environment whose record says done = 2
+ * keeps its rows and its snapshot untouched; a reset does not rewrite the rows (the reference has no info at reset()); observe() does not run the launch.
+ * The buffers are the caller's, 16-byte aligned; a null pointer means that output is not written; all three null detaches.  While attached the calls need
+ * io->scalars_dev and io->masks_dev (MATE_EINVAL); pipelined restarts return MATE_ESTATE.  No allocation, no synchronisation, identical arguments at every
+ * call: capturable.
+ * MATE_EINVAL: a misaligned buffer, camera rows in a scenario without cameras.  MATE_ESTATE: before the first reset / import_state.
+ * mate_engine_info_rows is the same launch on demand, from the current records, nothing attached: individual_done reads NaN and no snapshot is touched;
+ * masks_dev ([N][mask_words], e.g. the last call's) may be null: num_tracked, is_sensed and is_tracked then read NaN. */
+#define MATE_INFO_CAMERA_COLUMNS 2
+#define MATE_INFO_TARGET_COLUMNS 9
+#define MATE_INFO_CARGO_COLUMNS 24
+int mate_engine_enable_info_rows(mate_engine *engine, double *camera_rows_dev, double *target_rows_dev, double *cargo_rows_dev);
+int mate_engine_info_rows(mate_engine *engine, const uint32_t *masks_dev, double *camera_rows_dev, double *target_rows_dev, double *cargo_rows_dev, void *stream);
+
 /* Occlusion table of one camera (Camera.sight_range_func, entities.py:457-479): host buffers. */
 int mate_engine_lut_read(mate_engine *engine, int64_t env, int32_t camera, double *phis_host,
                          double *rhos_host, int32_t capacity, int32_t *count);

@@ -19,6 +19,7 @@
 #include "shape_groups.hpp"
 #include "headline_kernels.hpp"
 #include "episode_rows.hpp"
+#include "info_rows.hpp"
 
 using namespace mate;
 
@@ -92,6 +93,11 @@ struct EpisodeRecords {  // mate_engine_enable_episode_records: scalars, masks, 
     EpisodeArgs args{};                          // team, A, the caller's ring and counter, the engine-owned sums
     double *d_sums = nullptr;                    // [N][kEpisodeWords], allocated at the first enable: the learner steps of the episodes in progress
 };
+struct InfoRows {        // mate_engine_enable_info_rows: scalars, masks, mode and done_nan of `args` are the launch's own
+    bool on = false;
+    InfoArgs args{};                             // the caller's three row buffers (any may be null), the engine-owned snapshot
+    int32_t *d_snapshot = nullptr;               // [N][Nt + 1], allocated at the first enable: the goals and the episode the next step's individual_done compares with
+};
 struct mate_engine {
     Switches sw{};
     hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
@@ -138,7 +144,7 @@ struct mate_engine {
     void *d_xab = nullptr;
     Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
     CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
-    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes;      // what is attached around the stepping launches (plan_attached)
+    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -252,6 +258,7 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   2b cameras     heuristic_camera_kernel in front of the stepping launch: the Heuristic camera opponents' joint     step_with_policies
 //                  action (opponent_rows.hpp); two-launch form only, where the engine plays the cameras (heuristic_cameras)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
+//   3b info        info_rows_kernel: MoreTrainingInformation's per-agent rows of the launch's last frame       attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
 //   5b first_rows  a memset node: every record of the first-row scalars reads 2.0f, "not restarted"          attached_behind_step
@@ -261,13 +268,13 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //                  stores the learner team's plain first rows and its record into the first-row buffers)
 //   6b first_rows  behind THAT restart only: fragment_rows_kernel, K = 1, twice over the restart's records   attached_behind_restart
 //                  -- obs -> final_obs (plain copy; where asked for), then first rows -> obs (column table)
-//   6c             with reward rows the snapshot-only launch                                                attached_behind_restart
+//   6c             with reward rows the snapshot-only launch; with info rows theirs                        attached_behind_restart
 //   7 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
 //   8 state        state_rows_kernel, last                                                                  attached_last
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
-    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, episode_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
+    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, info = false, action_mask = false, state = false;
+    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, episode_rows, info_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
 };
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
 // Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
@@ -281,6 +288,9 @@ static Tiles plan_state_rows(const mate_engine *e, bool f64) {
 static Tiles plan_fragment_rows(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
 // A workgroup per tile, or ONE for all of them where the ring is smaller than the batch (episode_rows.hpp: the serial form)
 static Tiles plan_episode_rows(const mate_engine *e) { return {e->episodes.args.capacity < e->N ? 1u : blocks_of(e, kAttachedEnvsPerBlock), 256, 0, kAttachedEnvsPerBlock}; }
+static Tiles plan_info_rows(const mate_engine *e) {
+    return {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)info_rows_lds_bytes(e->p.DW, e->p.Nc, e->p.Nt), kAttachedEnvsPerBlock};
+}
 // `selected`: the call is mate_engine_step_selected; `fused_team`: the call is mate_engine_rollout_versus_greedy for that team (-1: any other).  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
 // The engine plays the target team of this call (`team_caller`: -1 both teams are the agents, else the caller's) with the Heuristic agent: the call takes the two-launch
@@ -297,12 +307,14 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.fragment = e->fragment.on && fused_team == e->fragment.args.team;
     pl.first_rows = pl.fragment && e->first.on;
     pl.episodes = e->episodes.on;
+    pl.info = e->info.on;
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
     pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
     if (e->opponent.kind == MATE_OPPONENT_HEURISTIC) pl.drift_rows = pl.reward_rows;      // (launched by the two-launch form where the engine plays the targets: heuristic_targets)
     pl.fragment_rows = plan_fragment_rows(e);
     if (pl.episodes) pl.episode_rows = plan_episode_rows(e);
+    if (pl.info) pl.info_rows = plan_info_rows(e);
     pl.state_rows = plan_state_rows(e, e->state.f64);
     return pl;
 }

@@ -66,6 +66,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "opponent_kernels.inc"
 #include "headline_kernels.hip"
 #include "episode_kernels.hip"
+#include "info_kernels.hip"
 #endif
 
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
@@ -732,6 +733,15 @@ static int launch_episode_records(mate_engine *e, const AttachedPlan &pl, const 
     HIP_TRY(launch_episode_rows(pl.episode_rows.blocks, stream, e->d_params, a));
     return MATE_OK;
 }
+// 3b, 6c: the training-information rows of the step `scalars` / `masks` describe (INFO_STEP; `frames` of the call: more than one and individual_done reads NaN),
+// or the snapshot-only form behind new records
+static int launch_info(mate_engine *e, const AttachedPlan &pl, int mode, const float *scalars, const uint32_t *masks, int frames, hipStream_t stream) {
+    InfoArgs a = e->info.args;
+    a.mode = mode; a.scalars = scalars; a.masks = masks; a.done_nan = frames > 1;
+    a.dyn = e->g.dyn;
+    HIP_TRY(launch_info_rows(pl.info_rows.blocks, pl.info_rows.lds, stream, e->d_params, a));
+    return MATE_OK;
+}
 // What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
 // `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own);
 // `fused_team`: it is mate_engine_rollout_versus_greedy for that team (-1: any other call).
@@ -760,6 +770,9 @@ static int check_attached_call(const mate_engine *e, const mate_step_io *io, boo
         if (!io || !io->scalars_dev || (reinterpret_cast<uintptr_t>(io->scalars_dev) & 15u))
             return fail(MATE_EINVAL, "episode records are attached (mate_engine_enable_episode_records): the call needs io->scalars_dev, 16-byte aligned");
     }
+    if (pipelined && e->info.on) return fail(MATE_ESTATE, no_pipeline, "training-information rows are", "info_rows", "them");
+    if (e->info.on && (!io || !io->scalars_dev || !io->masks_dev))      // (the info launch reads the step's scalar record and masks)
+        return fail(MATE_EINVAL, "training-information rows are attached (mate_engine_enable_info_rows): the call needs io->scalars_dev and io->masks_dev");
     return MATE_OK;
 }
 // 1: ahead of the stepping launch (and of the opponents' agents) -- the executor's joint action of this frame
@@ -767,7 +780,7 @@ static int attached_ahead_of_step(mate_engine *e, bool selected, hipStream_t str
     const AttachedPlan pl = plan_attached(e, selected);
     return pl.execute ? launch_selection(e, pl, SELECTION_EXECUTE, nullptr, stream) : MATE_OK;
 }
-// 3, 4, 5, 5b: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers), the fragment of all
+// 3, 3b, 4, 5, 5b, 5c: behind the stepping launch, ahead of the restart of what it finished -- the rows of the launch's last frame (`frames` > 1: rollout-shaped buffers), the fragment of all
 // of them, and, with first rows, their scalar records back to "not restarted" (2.0f in every word: only column 2 is read, so no template buffer) -- on EVERY such call, so that no
 // environment claims a restart this call did not make
 static int attached_behind_step(mate_engine *e, bool selected, const mate_step_io *io, int frames, hipStream_t stream, int fused_team = -1) {
@@ -777,6 +790,7 @@ static int attached_behind_step(mate_engine *e, bool selected, const mate_step_i
         const int rc = launch_reward_rows(e, pl, e->reward.accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
         if (rc != MATE_OK) return rc;
     }
+    if (pl.info) { const int rc = launch_info(e, pl, INFO_STEP, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, frames, stream); if (rc != MATE_OK) return rc; }
     if (pl.observe) { const int rc = launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream); if (rc != MATE_OK) return rc; }
     if (pl.fragment) {
         FragmentArgs a = e->fragment.args;
@@ -799,7 +813,7 @@ static int launch_first_rows(mate_engine *e, const Tiles &t, const void *src, vo
 }
 // 6b, 6c: behind a restart launch, a reset or an import.  6b (`fused_team`: the restart is the one mate_engine_rollout_versus_greedy for that team has just enqueued, -1: any
 // other) -- the restarted environments' fragment row moves to final_obs where asked for, then their first row goes through the fragment's transform into its place.
-// 6c -- the goals and episodes the next step's sparse_delivery is measured against
+// 6c -- the goals and episodes the next step's sparse_delivery (reward rows) and individual_done (info rows) are measured against
 static int attached_behind_restart(mate_engine *e, hipStream_t stream, int fused_team = -1) {
     const AttachedPlan pl = plan_attached(e, false, fused_team);
     if (pl.first_rows) {
@@ -808,7 +822,8 @@ static int attached_behind_restart(mate_engine *e, hipStream_t stream, int fused
         const int rc = launch_first_rows(e, pl.fragment_rows, e->first.rows, obs, e->fragment.args.columns, stream);
         if (rc != MATE_OK) return rc;
     }
-    return pl.reward ? launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream) : MATE_OK;
+    if (pl.reward) { const int rc = launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream); if (rc != MATE_OK) return rc; }
+    return pl.info ? launch_info(e, pl, INFO_SNAPSHOT, nullptr, nullptr, 1, stream) : MATE_OK;
 }
 // 7, 8: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
 static int attached_last(mate_engine *e, int rc, hipStream_t stream) {
@@ -1051,6 +1066,50 @@ extern "C" int mate_engine_clear_episode_records(mate_engine *e, void *stream) {
     { const int rc_ = enter(e, (hipStream_t)stream, "clear_episode_records"); if (rc_ != MATE_OK) return rc_; }
     note_stream(e, (hipStream_t)stream);
     return clear_episode_sums(e, (hipStream_t)stream);
+}
+
+// ---- MoreTrainingInformation rows: attaching, and the on-demand launch (include/mate_engine.h, csrc/info_rows.hpp)
+static int check_info_buffers(const mate_engine *e, const double *camera_rows, const double *target_rows, const double *cargo_rows) {
+    if ((reinterpret_cast<uintptr_t>(camera_rows) | reinterpret_cast<uintptr_t>(target_rows) | reinterpret_cast<uintptr_t>(cargo_rows)) & 15u)
+        return fail(MATE_EINVAL, "info rows: the row buffers must be 16-byte aligned");
+    if (camera_rows && e->p.Nc == 0) return fail(MATE_EINVAL, "info rows: the scenario has no cameras to write camera rows for");
+    return MATE_OK;
+}
+extern "C" int mate_engine_enable_info_rows(mate_engine *e, double *camera_rows_dev, double *target_rows_dev, double *cargo_rows_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!camera_rows_dev && !target_rows_dev && !cargo_rows_dev) { e->info.on = false; return MATE_OK; }
+    if (!e->was_reset) return fail(MATE_ESTATE, "enable_info_rows called before reset() (or import_state)");
+    { const int rc = check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev); if (rc != MATE_OK) return rc; }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the arguments while they change)
+    InfoRows &r = e->info;
+    { int rc = MATE_OK; if (!r.d_snapshot && (rc = dev_alloc(e, &r.d_snapshot, (size_t)e->N * (e->p.Nt + 1)))) return rc; }
+    mate_layout layout;
+    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    InfoArgs a{};
+    a.snapshot = r.d_snapshot; a.cam_rows = camera_rows_dev; a.tgt_rows = target_rows_dev; a.cargo_rows = cargo_rows_dev;
+    a.N = e->N; a.bit_ct = layout.bit_camera_target; a.bit_tr = layout.bit_target_row;
+    r.args = a;
+    r.on = true;
+    // the goals and episodes of the records as they are: the first step's individual_done is measured against them
+    note_stream(e, e->last_stream);
+    return launch_info(e, plan_attached(e, false), INFO_SNAPSHOT, nullptr, nullptr, 1, e->last_stream);
+}
+extern "C" int mate_engine_info_rows(mate_engine *e, const uint32_t *masks_dev, double *camera_rows_dev, double *target_rows_dev, double *cargo_rows_dev, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!camera_rows_dev && !target_rows_dev && !cargo_rows_dev) return fail(MATE_EINVAL, "info_rows: no output buffer");
+    { const int rc = check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev); if (rc != MATE_OK) return rc; }
+    { const int rc_ = enter(e, (hipStream_t)stream, "info_rows"); if (rc_ != MATE_OK) return rc_; }
+    mate_layout layout;
+    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    InfoArgs a{};
+    a.mode = INFO_ON_DEMAND; a.masks = masks_dev; a.dyn = e->g.dyn;
+    a.cam_rows = camera_rows_dev; a.tgt_rows = target_rows_dev; a.cargo_rows = cargo_rows_dev;
+    a.N = e->N; a.bit_ct = layout.bit_camera_target; a.bit_tr = layout.bit_target_row;
+    note_stream(e, (hipStream_t)stream);
+    const Tiles t = plan_info_rows(e);
+    HIP_TRY(launch_info_rows(t.blocks, t.lds, (hipStream_t)stream, e->d_params, a));
+    return MATE_OK;
 }
 
 extern "C" int mate_engine_fragment_coefficients(mate_engine *e, double **coefficients_dev, int32_t *count) {

@@ -170,6 +170,7 @@ class Engine:
         self._clear_selection()
         self._clear_fragment_rows()
         self._clear_episode_records()
+        self._clear_info_rows()
 
     # The detached value of every attached feature, written once: __init__ and the feature's disable_* both come here.
     def _clear_state_rows(self):
@@ -202,6 +203,10 @@ class Engine:
         # [1] int64, the team's code, and how many of them episode_records() has handed out
         self.episode_ring = self.episode_count = self.episode_team = None
         self._episode_read = 0
+
+    def _clear_info_rows(self):
+        # while the training-information rows are attached (enable_info_rows): [N, Nc, 2] / [N, Nt, 9] / [N, 24] f64, None for an output that is off
+        self.info_camera_rows = self.info_target_rows = self.info_cargo_rows = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -912,6 +917,84 @@ class Engine:
         self._episode_read = total
         return self.episode_ring[rows], fresh - kept
 
+    # ------------------------------------------------------------------ MoreTrainingInformation rows
+    INFO_CAMERA_COLUMNS = ('num_tracked', 'is_sensed')
+    INFO_TARGET_COLUMNS = ('goal', 'goal_distance') + tuple(f'warehouse_distances_{w}' for w in range(4)) + ('individual_done', 'is_tracked', 'is_colliding')
+    INFO_CARGO_COLUMNS = (tuple(f'remaining_cargo_counts_{w}' for w in range(4)) + tuple(f'awaiting_cargo_counts_{w}' for w in range(4)) +
+                          tuple(f'remaining_cargoes_{w}_{d}' for w in range(4) for d in range(4)))
+
+    def _info_tensors(self, camera, target, cargo):
+        """Fresh (camera, target, cargo) row tensors, None for an output that is off (`camera` is off without cameras)."""
+        N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
+        with torch.cuda.device(self.device):
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)  # noqa: E731
+            return (new(N, Nc, len(self.INFO_CAMERA_COLUMNS)) if camera and Nc else None,
+                    new(N, Nt, len(self.INFO_TARGET_COLUMNS)) if target else None,
+                    new(N, len(self.INFO_CARGO_COLUMNS)) if cargo else None)
+
+    @staticmethod
+    def _row_pointers(rows):
+        return [ctypes.c_void_p(r.data_ptr()) if r is not None else None for r in rows]
+
+    def enable_info_rows(self, camera=True, target=True, cargo=True):
+        """Keep what the reference's mate.MoreTrainingInformation wrapper adds to the agents' infos current on the device
+        (mate_engine_enable_info_rows): from now on every stepping call enqueues one more launch behind the stepping launch and AHEAD
+        of the restart of finished episodes, which writes `info_camera_rows` [N, Nc, 2] (INFO_CAMERA_COLUMNS), `info_target_rows`
+        [N, Nt, 9] (INFO_TARGET_COLUMNS) and `info_cargo_rows` [N, 24] (INFO_CARGO_COLUMNS), all f64 -- the rows describe the step
+        `scalars` describes, the terminal one included; info() names the columns.  The tensors are allocated once and are the same at
+        every call; `camera` is silently off without cameras.  A fused K-frame rollout leaves the rows of its LAST frame with
+        individual_done = NaN.  Call after the first reset(); a Stepper built afterwards captures the launch.  The stepping calls then
+        need their masks output (step_random(want_masks=True), rollouts with want_masks=True).  Returns the three tensors."""
+        wanted = (bool(camera) and self.num_cameras > 0, bool(target), bool(cargo))
+        assert any(wanted), 'enable_info_rows needs at least one output'
+        have = (self.info_camera_rows, self.info_target_rows, self.info_cargo_rows)
+        fresh = self._info_tensors(*[w and h is None for w, h in zip(wanted, have)])
+        rows = tuple((h if h is not None else f) if w else None for w, h, f in zip(wanted, have, fresh))
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.mate_engine_enable_info_rows(self._h, *self._row_pointers(rows)))
+        self.info_camera_rows, self.info_target_rows, self.info_cargo_rows = rows
+        self._forget_calls()
+        return rows
+
+    def _info_attached(self):
+        return self.info_camera_rows is not None or self.info_target_rows is not None or self.info_cargo_rows is not None
+
+    def disable_info_rows(self):
+        """Detach the training-information rows: the calls go back to their launch sequence without them; the tensors become None."""
+        check(self.lib.mate_engine_enable_info_rows(self._h, None, None, None))
+        self._clear_info_rows()
+
+    def info_rows(self, masks=None):
+        """(camera [N, Nc, 2] or None without cameras, target [N, Nt, 9], cargo [N, 24]): the rows of the CURRENT records by one launch on
+        the current stream, in fresh tensors; nothing is attached.  individual_done reads NaN (no previous step to compare with);
+        `masks` = the packed mask words [N, mask_words] of those records (Engine.masks behind a step that brought them), None: num_tracked,
+        is_sensed and is_tracked read NaN."""
+        if masks is not None:
+            assert masks.dtype == torch.int32 and masks.is_contiguous() and masks.device == self.device and masks.shape == (self.num_envs, self.layout.mask_words)
+        rows = self._info_tensors(True, True, True)
+        check(self.lib.mate_engine_info_rows(self._h, ctypes.c_void_p(masks.data_ptr()) if masks is not None else None, *self._row_pointers(rows), self._stream()))
+        return rows
+
+    @staticmethod
+    def info_views(camera_rows, target_rows, cargo_rows):
+        """{name: view} over the three row tensors (None: that output's names are absent): [N, Nc] / [N, Nt] columns,
+        warehouse_distances [N, Nt, 4], remaining_cargo_counts / awaiting_cargo_counts [N, 4], remaining_cargoes [N, 4, 4]."""
+        out = {}
+        if camera_rows is not None:
+            out.update(num_tracked=camera_rows[:, :, 0], is_sensed=camera_rows[:, :, 1])
+        if target_rows is not None:
+            out.update(goal=target_rows[:, :, 0], goal_distance=target_rows[:, :, 1], warehouse_distances=target_rows[:, :, 2:6],
+                       individual_done=target_rows[:, :, 6], is_tracked=target_rows[:, :, 7], is_colliding=target_rows[:, :, 8])
+        if cargo_rows is not None:
+            out.update(remaining_cargo_counts=cargo_rows[:, 0:4], awaiting_cargo_counts=cargo_rows[:, 4:8],
+                       remaining_cargoes=cargo_rows[:, 8:24].view(-1, 4, 4))
+        return out
+
+    def info(self):
+        """{name: view} over the attached rows (enable_info_rows), see info_views; the same storage at every call."""
+        assert self._info_attached(), 'call enable_info_rows() first'
+        return self.info_views(self.info_camera_rows, self.info_target_rows, self.info_cargo_rows)
+
     @property
     def fragment_restarted(self):
         """[N] bool: the environments the last rollout_versus_greedy of the attached team restarted -- whose fragment_obs row is the new
@@ -1237,7 +1320,7 @@ class Stepper:
         self.outputs = None
         if self.frame_skip > 1 and not self.selection:
             # (the reward launch reads the last frame's masks; the fragment launch every frame's, for a mask term)
-            shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus)
+            shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus) or eng._info_attached()
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
             eng._bind_outputs(self.io, buf['camera_obs'], buf['target_obs'], buf['scalars'], buf['masks'] if shaped else None)
             self.outputs = (buf['camera_obs'][:self.frame_skip], buf['target_obs'][:self.frame_skip], buf['scalars'][:self.frame_skip])
@@ -1379,6 +1462,10 @@ class EngineGroups:
         """Engine.enable_state_rows on every group, each on its own stream; returns the groups' state tensors (group g holds the rows
         of the global environments [g N / G, (g + 1) N / G))."""
         return self.each(lambda g, eng: eng.enable_state_rows(normalize=normalize, dtype=dtype))
+
+    def enable_info_rows(self, camera=True, target=True, cargo=True):
+        """Engine.enable_info_rows on every group, each on its own stream; returns the groups' (camera, target, cargo) row tensors."""
+        return self.each(lambda g, eng: eng.enable_info_rows(camera=camera, target=target, cargo=cargo))
 
     def synchronize(self):
         for s in self.streams:

@@ -688,13 +688,17 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     `episode_records` = 'camera' | 'target' | True (the `learner` of a fragment environment, else 'target'): per-episode metric records
     for that team -- the reference's CustomMetricCallback keys -- kept on the device behind every stepping call (DESIGN.md section 3.12,
     Engine.enable_episode_records; attached behind the first reset()); `episodes()` returns the ones that arrived since its last call.  A learner step
-    of a record is a frame, also under `frame_skip`."""
+    of a record is a frame, also under `frame_skip`.
+
+    `training_information` = True: what the reference's mate.MoreTrainingInformation wrapper adds to the agents' infos, kept on the device
+    behind every stepping call (Engine.enable_info_rows; attached behind the first reset()): `infos()` names the
+    columns, `target_dones()` is the per-target done of RepeatedRewardIndividualDone(target_done_at_destination=True)."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
-                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, **kwargs):
+                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -712,6 +716,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if episode_records is True:
             episode_records = self._fragment['learner'] if self._fragment else 'target'
         self._episode_team = episode_records              # (attached behind the first reset(): Engine.enable_episode_records)
+        self._training_information = bool(training_information)      # (attached behind the first reset(): Engine.enable_info_rows)
+        self._info_frames = 0                             # frames of the last stepping call (target_dones: individual_done is NaN behind a multi-frame one)
         assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
             self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype,
@@ -788,6 +794,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self.engine.enable_reward_rows(camera=self._reward_shaping.get('camera'), target=self._reward_shaping.get('target'), dtype=self._reward_dtype)
         if self.camera_selection and self.engine.selection is None:
             self.engine.enable_selection(self.camera_selection == 'multi')
+        if self._training_information and not self.engine._info_attached():      # (behind the reward rows)
+            self.engine.enable_info_rows()
         for shaper in self._target_shapers.values():
             shaper.observe_reset()
         if self._fragment:
@@ -797,8 +805,39 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         return out
 
     def _want_masks(self):
-        """The calls that may go without the view masks bring them for the reward launch, and for the camera team's num_tracked record."""
-        return bool(self._reward_shaping) or self._episode_team == 'camera'
+        """The calls that may go without the view masks bring them for the reward launch, for the camera team's num_tracked record and for the
+        training-information rows."""
+        return bool(self._reward_shaping) or self._episode_team == 'camera' or self._training_information
+
+    def infos(self):
+        """The training information of the step that last ran (`training_information`): {name: view} of Engine.info() -- num_tracked,
+        is_sensed [num_envs, num_cameras]; goal, goal_distance, individual_done, is_tracked, is_colliding [num_envs, num_targets];
+        warehouse_distances [num_envs, num_targets, 4]; remaining_cargo_counts, awaiting_cargo_counts [num_envs, 4]; remaining_cargoes
+        [num_envs, 4, 4], all f64 -- plus the common scalar columns of that step by name (coverage_rate, real_coverage_rate,
+        mean_transport_rate, num_delivered_cargoes, normalized_raw_reward).  Written ahead of the auto-reset: the terminal step's values too.
+        Behind a multi-frame call (rollout_*, step_fragment) the rows describe its last frame and individual_done is NaN."""
+        assert self._training_information, 'built without training_information=True'
+        assert self.engine._info_attached(), 'reset() first'
+        out = self.engine.info()
+        out.update(self._columns(self._info_scalars())[2])
+        return out
+
+    def _info_scalars(self):
+        """The scalar records [num_envs, 8] of the frame the training-information rows describe: the last frame of the last stepping call."""
+        rollout = self.engine._rollout
+        if self._info_frames > 1 and rollout is not None:
+            return rollout['scalars'][self._info_frames - 1]
+        return self.engine.scalars
+
+    def target_dones(self):
+        """[num_envs, num_targets] bool: the targets that delivered their cargo at the step that last ran -- the `done` of the reference's
+        RepeatedRewardIndividualDone(target_done_at_destination=True).  Raises behind a multi-frame call, where the column is NaN."""
+        assert self._training_information, 'built without training_information=True'
+        assert self.engine._info_attached(), 'reset() first'
+        if self._info_frames > 1:
+            raise RuntimeError(f'target_dones() behind a call of {self._info_frames} frames: a delivery between the frames cannot be seen from its end state '
+                               '(individual_done is NaN); step frame by frame for per-target dones')
+        return self.engine.info_target_rows[:, :, 6] > 0
 
     def episodes(self):
         """The episode records that arrived since the last call (`episode_records`): {column: [M] f64 tensor} for Engine.EPISODE_COLUMNS,
@@ -839,7 +878,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         assert self._fragment, 'built without frame_skip = K, learner = ...'
         spec, eng = self._fragment, self.engine
         assert eng.fragment_team is not None, 'reset() first'
-        eng.rollout_versus_greedy(spec['learner'], joint_action, spec['frame_skip'], auto_reset=int(self.auto_reset))
+        self._info_frames = spec['frame_skip']
+        eng.rollout_versus_greedy(spec['learner'], joint_action, spec['frame_skip'], auto_reset=int(self.auto_reset), want_masks=self._training_information)
         camera = spec['learner'] == 'camera'
         sums, means = eng.fragment_rewards, eng.fragment_info
         if eng.fragment_shaped is not None:
@@ -862,6 +902,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         return (col['camera_team_reward'], col['target_team_reward']), col['done'], info
 
     def _result(self):
+        self._info_frames = 1
         rewards, done, info = self._columns(self.engine.scalars)
         return (self.engine.camera_obs, self.engine.target_obs), rewards, done > 0, info
 
@@ -877,6 +918,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def _rollout_result(self, out):
         cam, tgt, s = out
+        self._info_frames = int(s.shape[0])
         rewards, done, info = self._columns(s)
         info['skipped'] = done == 2          # slots after the end of an episode inside the launch (no step, stale rows)
         return (cam, tgt), rewards, done == 1, info

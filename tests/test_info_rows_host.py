@@ -1,0 +1,136 @@
+"""CPU: the NumPy restatement of MoreTrainingInformation (tests/info_ref.py) against every recorded reference trace, the census of the
+seven traces tests/test_gpu_info_rows.py replays, and the host side of the training-information rows (csrc/info_rows.hpp): prototypes,
+header, resource record, source digest, column names, the environment's argument.
+
+The traces hold, for every step of the reference, its own target_dones, target_warehouse_distances (the norms, ahead of the wrapper's
+`- 75, max 0`), the colliding flags, the masks and the cargo arrays: from the fixture's positions, goals and masks the restatement must
+give exactly those -- np.linalg.norm of a 2-vector and `dx dx + dy dy, the root` are the same three operations."""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import golden_util as G
+import info_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, 'mate_amd', 'lib')
+GPU_TRACES = ['trace_1v1-9_greedy_s7', 'trace_2v3-64_random_s8', 'trace_2v4-0_greedy_s5', 'trace_4v2-9_greedy_ep1_s22', 'trace_4v8-9_greedy_done',
+              'trace_8v8-9_greedy_ep1_s21', 'trace_nav_greedy_s1']
+
+
+def rows_of_trace(fx):
+    """The restatement over every step of a trace: (camera [T, Nc, 2] or None without cameras' masks, target [T, Nt, 9], cargo [T, 24])."""
+    goals = np.asarray(fx['step/tgt_goals'])
+    previous = np.concatenate([np.asarray(fx['reset/tgt_goals'])[None], goals[:-1]])
+    return R.rows(fx['step/tgt_xy'], goals, fx['step/tgt_colliding'], fx['step/remaining_cargoes'], fx['step/awaiting_cargo_counts'],
+                  fx['step/camera_target_view_mask'], fx['step/target_camera_view_mask'], previous)
+
+
+@pytest.mark.parametrize('path', G.trace_files(), ids=lambda p: os.path.basename(p)[6:-4])
+def test_restatement_equals_the_reference_on_every_step(path):
+    fx = G.load(path)
+    camera, target, cargo = rows_of_trace(fx)
+    goals = np.asarray(fx['step/tgt_goals'])
+    assert np.array_equal(target[..., 0], goals)
+    assert np.array_equal(target[..., 6], np.asarray(fx['step/target_dones']).astype(np.float64))
+    assert np.array_equal(target[..., 8], np.asarray(fx['step/tgt_colliding']).astype(np.float64))
+    wd = np.maximum(np.asarray(fx['step/target_warehouse_distances']) - 75.0, 0.0)
+    assert np.array_equal(target[..., 2:6], wd)
+    want = np.where(goals >= 0, np.take_along_axis(wd, np.maximum(goals, 0)[..., None], axis=-1)[..., 0], 1000.0)
+    assert np.array_equal(target[..., 1], want)
+    ct, tc = np.asarray(fx['step/camera_target_view_mask']), np.asarray(fx['step/target_camera_view_mask'])
+    assert np.array_equal(target[..., 7], ct.any(axis=1)) and np.array_equal(camera[..., 0], ct.sum(axis=2)) and np.array_equal(camera[..., 1], tc.any(axis=1))
+    remaining = np.asarray(fx['step/remaining_cargoes'])
+    assert np.array_equal(cargo[:, 0:4], remaining.sum(axis=-1)) and np.array_equal(cargo[:, 4:8], fx['step/awaiting_cargo_counts'])
+    assert np.array_equal(cargo[:, 8:24], remaining.reshape(len(remaining), 16))
+    # the first recorded step's previous goals are the reset's: the reference has no delivery at reset()
+    assert not np.asarray(fx['reset/target_dones']).any()
+
+
+def test_census_of_the_traces_the_gpu_test_replays():
+    """Every branch of the rows occurs in the seven replayed traces; the counts are the reference's own data."""
+    count = dict(delivery=0, no_goal=0, colliding=0, tracked=0, sensed=0, clamped=0, episode_end=0)
+    for name in GPU_TRACES:
+        fx = G.load(name + '.npz')
+        camera, target, _ = rows_of_trace(fx)
+        count['delivery'] += int(np.asarray(fx['step/target_dones']).sum())
+        count['no_goal'] += int((target[..., 0] == -1).sum())
+        count['colliding'] += int(target[..., 8].sum())
+        count['tracked'] += int(target[..., 7].sum())
+        count['sensed'] += int(camera[..., 1].sum())
+        count['clamped'] += int((np.asarray(fx['step/target_warehouse_distances']) <= 75.0).sum())
+        count['episode_end'] += int(np.asarray(fx['step/done']).sum())
+    print(count)
+    assert all(v >= 1 for v in count.values()), count
+    # counted on the fixtures in the tree: (environment-step, agent) occurrences over the 1126 recorded steps
+    assert list(count.values()) == [27, 2281, 662, 2922, 2087, 22, 6], count
+
+
+def test_model_keeps_idle_environments_and_other_episodes_report_nothing():
+    sd = {'tgt_x': np.array([[900.0, 0.0]] * 2), 'tgt_y': np.array([[900.0, 0.0]] * 2), 'tgt_goals': np.array([[1.0, 2.0]] * 2), 'tgt_colliding': np.zeros((2, 2)),
+          'remaining_cargoes': np.arange(32.0).reshape(2, 4, 4), 'awaiting_cargo_counts': np.ones((2, 4)), 'episode': np.array([1.0, 1.0])}
+    model = R.Model(sd, 0)
+    after = dict(sd, tgt_goals=np.array([[0.0, 2.0]] * 2), episode=np.array([1.0, 2.0]))
+    ran = model.step(after, None, np.array([0.0, 0.0]))
+    assert ran.all() and model.target[0, :, 6].tolist() == [1.0, 0.0] and model.target[1, :, 6].tolist() == [0.0, 0.0]
+    assert model.target[0, 0, 1] == 0.0 == model.target[0, 0, 2] and model.target[0, 1, 1] == np.sqrt(2.0 * 925.0 ** 2) - 75.0      # 35 from warehouse 0's centre: clamped
+    assert np.isnan(model.target[..., 7]).all() and model.cargo[0, 0] == 6.0 and model.cargo[1, 8] == 16.0
+    before = model.target.copy()
+    model.step(dict(after, tgt_goals=np.array([[3.0, 3.0]] * 2)), None, np.array([2.0, 0.0]), frames=3)
+    assert np.array_equal(model.target[0], before[0], equal_nan=True) and np.isnan(model.target[1, :, 6]).all() and model.goals.tolist() == [[0, 2], [3, 3]]
+
+
+@pytest.fixture(scope='module')
+def header():
+    with open(os.path.join(ROOT, 'include', 'mate_engine.h')) as fh:
+        return re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
+
+
+def test_header_and_prototypes_declare_the_two_functions(header):
+    for name, value in (('CAMERA', 2), ('TARGET', 9), ('CARGO', 24)):
+        assert re.search(r'#define\s+MATE_INFO_%s_COLUMNS\s+%d\b' % (name, value), header)
+    assert re.search(r'#define\s+MATE_ABI_VERSION\s+1\b', header)
+    assert re.search(r'int\s+mate_engine_enable_info_rows\s*\(\s*mate_engine\s*\*\s*\w+(\s*,\s*double\s*\*\s*\w+){3}\s*\)\s*;', header)
+    assert re.search(r'int\s+mate_engine_info_rows\s*\(\s*mate_engine\s*\*\s*\w+\s*,\s*const\s+uint32_t\s*\*\s*\w+(\s*,\s*double\s*\*\s*\w+){3}\s*,\s*void\s*\*\s*\w+\s*\)\s*;', header)
+    from mate_amd import _native
+    assert len(_native.PROTOTYPES['mate_engine_enable_info_rows'][1]) == 4 and len(_native.PROTOTYPES['mate_engine_info_rows'][1]) == 6
+
+
+def test_column_tuples():
+    from mate_amd.engine import Engine
+    for names, width in ((Engine.INFO_CAMERA_COLUMNS, R.CAMERA_COLUMNS), (Engine.INFO_TARGET_COLUMNS, R.TARGET_COLUMNS), (Engine.INFO_CARGO_COLUMNS, R.CARGO_COLUMNS)):
+        assert isinstance(names, tuple) and len(names) == width == len(set(names))
+    assert (len(Engine.INFO_CAMERA_COLUMNS), len(Engine.INFO_TARGET_COLUMNS), len(Engine.INFO_CARGO_COLUMNS)) == (2, 9, 24)
+    assert Engine.INFO_TARGET_COLUMNS[0] == 'goal' and Engine.INFO_TARGET_COLUMNS[6:] == ('individual_done', 'is_tracked', 'is_colliding')
+
+
+def _load(name):
+    path = os.path.join(LIB, name)
+    assert os.path.exists(path), 'run __graft_entry__.build() first'
+    with open(path) as fh:
+        return json.load(fh)
+
+
+def test_the_info_kernel_reports_apart_and_without_scratch():
+    kernels = _load('kernel_resources_info.json')
+    assert kernels and all('info_rows_kernel' in name for name in kernels), sorted(kernels)
+    for name, r in kernels.items():
+        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['VGPRs Spill'] == 0 and r['SGPRs Spill'] == 0, (name, r)
+    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json'):
+        assert not set(kernels) & set(_load(other)), other
+        assert not any('info_rows_kernel' in name for name in _load(other)), other
+
+
+def test_the_source_digest_covers_the_info_sources():
+    from mate_amd import build
+    names = {os.path.basename(d) for d in build.DEPS}
+    assert {'info_rows.hpp', 'info_kernels.hip', 'attached_tile.hpp'} <= names
+
+
+def test_training_information_argument_of_the_batched_environment():
+    import inspect
+    from mate_amd.environment import BatchedMultiAgentTracking
+    assert inspect.signature(BatchedMultiAgentTracking.__init__).parameters['training_information'].default is False
