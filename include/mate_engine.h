@@ -389,6 +389,58 @@ int mate_engine_heuristic_camera_tables(mate_engine *engine, const double *state
 int mate_engine_heuristic_camera_tape(mate_engine *engine, const int8_t *permutations_dev, int8_t *record_dev);
 int mate_engine_heuristic_camera_goals(mate_engine *engine, double *goals_dev, int32_t *indices_dev, void *stream);
 
+/* Opponent MIXTURES: per environment and EPISODE, which scripted agent plays a team the engine plays (the reference's MixtureCameraAgent /
+ * MixtureTargetAgent, mate/agents/mixture.py -- the opponents PSRO trains against; spawn() seeds a team's agents alike, so the whole team plays
+ * one candidate per episode), over five kinds:
+ *   MATE_SCRIPTED_GREEDY / _HEURISTIC   the two pairs above
+ *   MATE_SCRIPTED_NAIVE                 NaiveCameraAgent / NaiveTargetAgent (mate/agents/naive.py)
+ *   MATE_SCRIPTED_RANDOM                RandomCameraAgent / RandomTargetAgent (mate/agents/random.py): a uniform action held for random_frame_skip
+ *                                       acting calls -- NOT mate_engine_step_random, which draws anew on every frame
+ *   MATE_SCRIPTED_EXTERNAL              rows the caller writes, before each stepping call and for every environment, into the engine-owned
+ *                                       [N][n][2] f64 buffer mate_engine_scripted_external returns (a learned population member the host
+ *                                       evaluates on the batch; the device picks the rows of the environments that drew it)
+ * ONE more launch, scripted_opponent_kernel (csrc/scripted_rows.hpp: semantics, draws, mapping), behind the agents' launch, the Heuristic cameras'
+ * launch and the drift launch and ahead of the stepping launch of mate_engine_step_greedy, mate_engine_step_versus_greedy and
+ * mate_engine_step_selected (the two-launch form): at a team's first acting call of an episode it draws the team's kind,
+ *   k = searchsorted(cumsum(w / sum w), u, side='right') over the candidates with positive weight in the order given,
+ * computes the Naive or Random agents where the kind asks for them, and writes the team's FINAL joint action -- the Greedy row, the Heuristic
+ * row, the external row or its own -- into an engine-owned buffer the stepping launch reads.  mate_engine_policy_actions reports those rows.
+ * Identical arguments at every call, no allocation, no synchronisation: capturable under mate_engine_device_tick.  The Greedy agents' launch
+ * (Greedy or Heuristic targets; Greedy cameras) and the Heuristic cameras' launch run only where some candidate with positive weight needs
+ * them, and then for EVERY environment, whatever its choice.  An environment idling under a batched restart keeps memory, choice and final row.
+ *   mate_engine_set_opponent_mixture   kinds[count], weights[count] (NULL: all 1).  count = 0 clears the team's mixture (the plain selection it
+ *       replaced returns; the Greedy agents of the team reset at their next acting call).  ONE candidate of kind Greedy or Heuristic is exactly
+ *       that plain selection: no launch, the same bytes.  Installing or changing a mixture makes the team's reset -- and draw -- run at its next
+ *       acting call; Greedy agents that sat out under the old mixture and act under the new one reset at that call too.  While a mixture is installed for a team, that team's mate_engine_set_target_opponent / mate_engine_set_camera_opponent
+ *       returns MATE_ESTATE, and while it is anything but {Greedy} the fused K-frame launches that would play the team (mate_engine_rollout_greedy,
+ *       mate_engine_rollout_versus_greedy of the other team) return MATE_ESTATE: FrameSkip is K per-step calls in one graph.
+ *       MATE_EINVAL: a team that is neither, an unknown or repeated kind, more than five candidates, a negative or non-finite weight, all weights
+ *       zero, random_frame_skip < 1, a Heuristic candidate under a non-plain observation mode of the team.  MATE_ESTATE: before
+ *       mate_engine_policy_enable; a Heuristic camera candidate without mate_engine_heuristic_camera_tables.  A refused call changes nothing.
+ *   mate_engine_scripted_tape          recorded draws (the four tape members; any of them NULL: Philox for that member) and a record of the draws
+ *       used (the four record_ members, the same shapes; any of them NULL: not stored), installed with ONE call.  camera_u_dev [N][Nc][2] (Naive: [0]; Random: both), target_u_dev [N][Nt][3] (the binomial u, the two sample uniforms;
+ *       Random: the latter two), target_reset_dev [N][Nt][4] (the two sample uniforms of prev_noise, goal, inc, as doubles), choice_dev [2][N]
+ *       int32 kinds by team (-1, or a kind outside the mixture: draw).  The record's doubles read NaN where nothing was drawn; its choice rows
+ *       receive the kind each team under a mixture holds.  Both hold until replaced.  MATE_EINVAL: record_camera_u_dev or record_target_reset_dev not aligned to 16 bytes (the
+ *       launch stores pairs of doubles there), any other buffer not aligned to its element size.
+ *   mate_engine_scripted_memory        copies a team's memory out (device buffers, any may be NULL): choice [N] (the kind; -1 before the first
+ *       draw), goal [N][Nt], inc [N][Nt], prev_noise [N][Nt][2] (the Naive targets'; ignored for the cameras), prev_action [N][n][2] and counter
+ *       [N] (the Random agents').  MATE_ESTATE: no mixture with a launch has been installed for the team.
+ *   mate_engine_scripted_external      the team's [N][n][2] f64 external buffer (MATE_ESTATE as above).
+ *   mate_engine_scripted_rows          copies one SOURCE of the team's final rows out, [N][n][2] f64 as the last launch read it: kind Greedy (the
+ *       Greedy agents' joint action), Heuristic (MATE_ESTATE while the team has no Heuristic candidate) or External; MATE_EINVAL for Naive and
+ *       Random, whose rows exist only as final rows (mate_engine_policy_actions). */
+enum { MATE_SCRIPTED_GREEDY = 0, MATE_SCRIPTED_HEURISTIC = 1, MATE_SCRIPTED_NAIVE = 2, MATE_SCRIPTED_RANDOM = 3, MATE_SCRIPTED_EXTERNAL = 4 };
+int mate_engine_set_opponent_mixture(mate_engine *engine, int32_t team, const int32_t *kinds, const double *weights, int32_t count,
+                                     int32_t random_frame_skip);
+int mate_engine_scripted_tape(mate_engine *engine, const double *camera_u_dev, const double *target_u_dev, const double *target_reset_dev,
+                              const int32_t *choice_dev, double *record_camera_u_dev, double *record_target_u_dev,
+                              double *record_target_reset_dev, int32_t *record_choice_dev);
+int mate_engine_scripted_memory(mate_engine *engine, int32_t team, int32_t *choice_dev, int32_t *goal_dev, int32_t *inc_dev,
+                                double *prev_noise_dev, double *prev_action_dev, int32_t *counter_dev, void *stream);
+int mate_engine_scripted_external(mate_engine *engine, int32_t team, double **rows_dev);
+int mate_engine_scripted_rows(mate_engine *engine, int32_t team, int32_t kind, double *rows_dev, void *stream);
+
 /* joint_observation() (environment.py:908-983) without advancing the simulation: recomputes
  * the view masks from the current state (see-through draws from io tape or Philox) and packs. */
 int mate_engine_observe(mate_engine *engine, const mate_step_io *io, void *stream);

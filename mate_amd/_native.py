@@ -119,6 +119,11 @@ PROTOTYPES = {
     'mate_engine_heuristic_camera_tables': (INT, [P, P, P, P]),
     'mate_engine_heuristic_camera_tape': (INT, [P, P, P]),
     'mate_engine_heuristic_camera_goals': (INT, [P, P, P, P]),
+    'mate_engine_set_opponent_mixture': (INT, [P, I32, ctypes.POINTER(I32), F64P, I32, I32]),
+    'mate_engine_scripted_tape': (INT, [P, P, P, P, P, P, P, P, P]),
+    'mate_engine_scripted_memory': (INT, [P, I32, P, P, P, P, P, P, P]),
+    'mate_engine_scripted_external': (INT, [P, I32, ctypes.POINTER(P)]),
+    'mate_engine_scripted_rows': (INT, [P, I32, I32, P, P]),
     'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
     'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
     'mate_engine_observe': (INT, [P, IO, P]),

@@ -20,6 +20,7 @@
 #include "headline_kernels.hpp"
 #include "episode_rows.hpp"
 #include "info_rows.hpp"
+#include "scripted_rows.hpp"
 
 using namespace mate;
 
@@ -75,6 +76,21 @@ struct CameraOpponent {  // mate_engine_set_camera_opponent: which scripted agen
     int8_t *record = nullptr;
     bool acted = false;                          // the last call with the on-device agents ran the launch: d_action is what its step consumed (mate_engine_policy_actions)
     bool ran = false;                            // ... some call has since the switch to Heuristic: the Greedy camera agents' memory is behind (switching back marks them for reset)
+};
+struct ScriptedMixture { // mate_engine_set_opponent_mixture, one per team: the candidates with positive weight, the engine-owned memory of scripted_opponent_kernel (scripted_rows.hpp)
+    bool installed = false;                      // the team's setter is refused meanwhile (a single Greedy or Heuristic candidate is that plain selection and nothing else)
+    bool launch = false;                         // the team's rows come from the scripted launch: every mixture but {Greedy} and {Heuristic}
+    int count = 0, kinds[kScriptedKinds] = {}, frame_skip = 20, restore = MATE_OPPONENT_GREEDY;      // (restore: the plain selection the mixture replaced, back at the clear)
+    double cum[kScriptedKinds] = {};
+    bool has[kScriptedKinds] = {};
+    double *d_final = nullptr, *d_external = nullptr, *d_prev_action = nullptr, *d_prev_location = nullptr, *d_prev_noise = nullptr;      // [N][n][2] each, allocated at the first install that launches
+    int32_t *d_episode = nullptr, *d_choice = nullptr, *d_counter = nullptr, *d_goal = nullptr, *d_inc = nullptr;                       // [N], [N], [N], [N][Nt], [N][Nt]
+    bool acted = false;                          // the last call with the on-device agents ran the scripted launch for the team: d_final is what its step consumed (mate_engine_policy_actions)
+    bool only_greedy() const { return !installed || (count == 1 && kinds[0] == MATE_SCRIPTED_GREEDY); }
+};
+struct Scripted {        // both teams' mixtures and the draws of their one launch (mate_engine_scripted_tape: both hold until replaced)
+    ScriptedMixture team[2];
+    ScriptedDraws tape{}, record{};
 };
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
@@ -144,6 +160,7 @@ struct mate_engine {
     void *d_xab = nullptr;
     Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
     CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
+    Scripted scripted;                   // the opponent mixtures (scripted_plays: whether a call runs scripted_opponent_kernel)
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -257,6 +274,9 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //                  engine plays the targets (heuristic_targets: a property of the call, like `selected`, not of the plan)
 //   2b cameras     heuristic_camera_kernel in front of the stepping launch: the Heuristic camera opponents' joint     step_with_policies
 //                  action (opponent_rows.hpp); two-launch form only, where the engine plays the cameras (heuristic_cameras)
+//   2c scripted    scripted_opponent_kernel behind 2a / 2b and the agents' launch, ahead of the stepping launch: the Naive and     step_with_policies
+//                  Random agents and, per environment, the row of the episode's mixture choice as the team's FINAL joint action
+//                  (scripted_rows.hpp); two-launch form only, for the teams the engine plays under a mixture (scripted_plays)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   3b info        info_rows_kernel: MoreTrainingInformation's per-agent rows of the launch's last frame       attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
@@ -299,6 +319,11 @@ static bool heuristic_targets(const mate_engine *e, int team_caller) { return e-
 // The engine plays the camera team of this call with the Heuristic agent: the two-launch form with heuristic_camera_kernel in front of the stepping launch, no fused K-frame
 // launch.  (A scenario without cameras: the selection is a no-op.)
 static bool heuristic_cameras(const mate_engine *e, int team_caller) { return e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_CAMERA && e->p.Nc > 0; }
+// The engine plays `team` of this call under a mixture whose rows come from the scripted launch (a scenario without cameras has no camera team to play)
+static bool scripted_plays_team(const mate_engine *e, int team, int team_caller) {
+    return e->scripted.team[team].launch && team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0);
+}
+static bool scripted_plays(const mate_engine *e, int team_caller) { return scripted_plays_team(e, MATE_TEAM_CAMERA, team_caller) || scripted_plays_team(e, MATE_TEAM_TARGET, team_caller); }
 static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;

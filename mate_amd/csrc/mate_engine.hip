@@ -67,6 +67,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "headline_kernels.hip"
 #include "episode_kernels.hip"
 #include "info_kernels.hip"
+#include "scripted_kernels.hip"
 #endif
 
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
@@ -1508,9 +1509,9 @@ static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_st
 }
 // step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
 // recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two),
-// the Heuristic camera opponent (its launch takes the camera agents' place)
+// the Heuristic camera opponent (its launch takes the camera agents' place), an opponent mixture whose rows come from the scripted launch
 static bool one_launch_step(const mate_engine *e, const FusedCall &c, int team_caller, const mate_step_io *io, const mate_policy_tape *tape) {
-    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller);
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller) && !scripted_plays(e, team_caller);
 }
 // 2a: between the agents' launch and the stepping launch -- the Heuristic opponents' final joint action from the Greedy one (`freeze_done`: of the agents' launch)
 static int launch_drift(mate_engine *e, const AttachedPlan &pl, int freeze_done, hipStream_t stream) {
@@ -1528,6 +1529,29 @@ static int launch_heuristic_cameras(mate_engine *e, const mate_policy_tape *tape
                                 tape ? tape->camera_resample_u_dev : nullptr, tape ? tape->camera_sample_u_dev : nullptr, o.permutations, o.record, freeze_done};
     HIP_TRY(launch_heuristic_camera((unsigned)e->N, heuristic_camera_lds_bytes(e->p.Nc), stream, e->d_params, e->g, a));
     o.ran = true;
+    return MATE_OK;
+}
+
+// 2c: behind the agents' launch, 2a and 2b, ahead of the stepping launch -- the Naive and Random agents and the mixtures' choice of the final rows, for the teams the
+// engine plays under a mixture (`freeze_done`: of the agents' launch).  Identical arguments at every call but for the team the caller plays, no allocation, no synchronisation.
+static ScriptedTeam scripted_team_args(const mate_engine *e, int team, bool plays) {
+    const ScriptedMixture &m = e->scripted.team[team];
+    ScriptedTeam t{};
+    if (!plays) return t;
+    t.on = 1; t.count = m.count; t.frame_skip = m.frame_skip; t.n = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
+    for (int i = 0; i < kScriptedKinds; ++i) { t.kinds[i] = m.kinds[i]; t.cum[i] = m.cum[i]; }
+    t.rows[SCRIPTED_GREEDY] = team == MATE_TEAM_CAMERA ? e->q.cam_act : e->q.tgt_act;
+    t.rows[SCRIPTED_HEURISTIC] = team == MATE_TEAM_CAMERA ? e->camera_opponent.d_action : e->opponent.d_final;
+    t.rows[SCRIPTED_EXTERNAL] = m.d_external;
+    t.final_act = m.d_final; t.episode = m.d_episode; t.choice = m.d_choice; t.counter = m.d_counter; t.prev_action = m.d_prev_action;
+    t.goal = m.d_goal; t.inc = m.d_inc; t.prev_location = m.d_prev_location; t.prev_noise = m.d_prev_noise;
+    return t;
+}
+static int launch_scripted(mate_engine *e, int team_caller, int freeze_done, hipStream_t stream) {
+    ScriptedArgs a{};
+    for (int team = 0; team < 2; ++team) a.team[team] = scripted_team_args(e, team, scripted_plays_team(e, team, team_caller));
+    a.tape = e->scripted.tape; a.record = e->scripted.record; a.freeze_done = freeze_done;
+    HIP_TRY(launch_scripted_opponents(blocks_of(e, kAttachedEnvsPerBlock), (size_t)attached_tile_lds_bytes(e->p.DW), stream, e->d_params, e->g, a));
     return MATE_OK;
 }
 
@@ -1559,7 +1583,15 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     q.caller_team = team_caller;      // (the agents of the caller's team do not act: greedy_policy_body)
     const bool hcams = heuristic_cameras(e, team_caller);
     if (hcams) q.caller_team = MATE_TEAM_CAMERA;      // the Greedy camera agents do not act either: step_greedy runs the Greedy (or Heuristic) targets alone,
-    const bool agents = !(hcams && team_caller == MATE_TEAM_TARGET);      // ... and with the targets the caller's nobody of the Greedy pair acts: no agents' launch
+    bool agents = !(hcams && team_caller == MATE_TEAM_TARGET);      // ... and with the targets the caller's nobody of the Greedy pair acts: no agents' launch
+    const bool mix_c = scripted_plays_team(e, MATE_TEAM_CAMERA, team_caller), mix_t = scripted_plays_team(e, MATE_TEAM_TARGET, team_caller);
+    if (mix_c || mix_t) {      // under a mixture a team's Greedy agents act where a candidate with positive weight needs their row (the Heuristic targets build on it)
+        const ScriptedMixture &mc = e->scripted.team[MATE_TEAM_CAMERA], &mt = e->scripted.team[MATE_TEAM_TARGET];
+        const bool need_c = team_caller != MATE_TEAM_CAMERA && (mix_c ? mc.has[MATE_SCRIPTED_GREEDY] : !hcams);
+        const bool need_t = team_caller != MATE_TEAM_TARGET && (mix_t ? (mt.has[MATE_SCRIPTED_GREEDY] || mt.has[MATE_SCRIPTED_HEURISTIC]) : true);
+        agents = need_c || need_t;
+        q.caller_team = need_c && need_t ? -1 : (need_c ? MATE_TEAM_TARGET : MATE_TEAM_CAMERA);
+    }
     if (tape) {
         q.tape.cam_binom_u = tape->camera_resample_u_dev; q.tape.cam_sample_u = tape->camera_sample_u_dev;
         q.tape.cam_delay = tape->camera_delay_dev; q.tape.tgt_choice_u = tape->target_choice_u_dev;
@@ -1578,11 +1610,13 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     const bool drift = heuristic_targets(e, team_caller);      // (the caller plays the targets: no opponent of that team acts)
     if (drift) { const int rc_ = launch_drift(e, plan_attached(e, selected), gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
     e->opponent.drifted = drift;
+    if (mix_c || mix_t) { const int rc_ = launch_scripted(e, team_caller, gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
+    e->scripted.team[MATE_TEAM_CAMERA].acted = mix_c; e->scripted.team[MATE_TEAM_TARGET].acted = mix_t;
     mate_step_io io2;
     if (io) io2 = *io; else std::memset(&io2, 0, sizeof(io2));
     // the caller's team keeps its own pointer and encoding (f32 / f64 / grid indices); the agents' joint action is f64 pairs
-    if (team_caller != 0) { io2.camera_actions_dev = hcams ? e->camera_opponent.d_action : q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
-    if (team_caller != 1) { io2.target_actions_dev = drift ? e->opponent.d_final : q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
+    if (team_caller != 0) { io2.camera_actions_dev = mix_c ? e->scripted.team[MATE_TEAM_CAMERA].d_final : hcams ? e->camera_opponent.d_action : q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
+    if (team_caller != 1) { io2.target_actions_dev = mix_t ? e->scripted.team[MATE_TEAM_TARGET].d_final : drift ? e->opponent.d_final : q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
     const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
     e->greedy_team_bits = 0;
@@ -1688,7 +1722,11 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
                                      : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow, team_caller}, auto_reset == 1 || pipelined, true, team_caller >= 0};
     if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
-    if (heuristic_targets(e, team_caller))      // (a per-step call never arrives here with it: one_launch_step)
+    for (int team = 0; team < 2; ++team)        // (a per-step call never arrives here with it: one_launch_step)
+        if (team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0) && !e->scripted.team[team].only_greedy())
+            return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the %s team plays an opponent mixture (mate_engine_set_opponent_mixture): step per frame, or clear the mixture",
+                        team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy", team == MATE_TEAM_CAMERA ? "camera" : "target");
+    if (heuristic_targets(e, team_caller))
         return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the target opponent is the heuristic one (mate_engine_set_target_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
                     team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
     if (heuristic_cameras(e, team_caller))
@@ -1736,6 +1774,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     e->last_flow = pl.last_flow;
     e->opponent.drifted = false;      // (the target team's joint action of this launch is in q.tgt_act: the Greedy agents', or the caller's)
     e->camera_opponent.acted = false;
+    e->scripted.team[MATE_TEAM_CAMERA].acted = e->scripted.team[MATE_TEAM_TARGET].acted = false;
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
@@ -1759,9 +1798,9 @@ extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, (hipStream_t)stream);
     if (camera_actions_dev && e->p.Nc > 0)
-        HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->camera_opponent.acted ? e->camera_opponent.d_action : e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->scripted.team[MATE_TEAM_CAMERA].acted ? e->scripted.team[MATE_TEAM_CAMERA].d_final : e->camera_opponent.acted ? e->camera_opponent.d_action : e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (target_actions_dev)      // what the step consumed: behind a call that ran the drift launch, its output
-        HIP_TRY(hipMemcpyAsync(target_actions_dev, e->opponent.drifted ? e->opponent.d_final : e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(target_actions_dev, e->scripted.team[MATE_TEAM_TARGET].acted ? e->scripted.team[MATE_TEAM_TARGET].d_final : e->opponent.drifted ? e->opponent.d_final : e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MATE_OK;
 }
 extern "C" int mate_engine_policy_greedy_target_actions(mate_engine *e, double *target_actions_dev, void *stream) {
@@ -1806,8 +1845,14 @@ extern "C" int mate_engine_heuristic_camera_goals(mate_engine *e, double *goals_
     if (indices_dev) HIP_TRY(hipMemcpyAsync(indices_dev, o.d_index, sizeof(int32_t) * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MATE_OK;
 }
+static int set_camera_opponent(mate_engine *e, int32_t opponent);
 extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent) {
     if (!e) return fail(MATE_EINVAL, "null engine");
+    if (e->scripted.team[MATE_TEAM_CAMERA].installed)
+        return fail(MATE_ESTATE, "set_camera_opponent: an opponent mixture is installed for the camera team (mate_engine_set_opponent_mixture): clear it first (count = 0)");
+    return set_camera_opponent(e, opponent);
+}
+static int set_camera_opponent(mate_engine *e, int32_t opponent) {
     if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_camera_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
     if (!e->policy_ready) return fail(MATE_ESTATE, "set_camera_opponent: call mate_engine_policy_enable() first (the Greedy agents of the other team, and the engine's own view masks)");
     CameraOpponent &o = e->camera_opponent;
@@ -1846,8 +1891,14 @@ extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent)
 
 // Which scripted agent plays the target team where the engine plays it (include/mate_engine.h).  No agent memory differs between the two, so the
 // switch is a flag and, once, the final-action buffer.
+static int set_target_opponent(mate_engine *e, int32_t opponent);
 extern "C" int mate_engine_set_target_opponent(mate_engine *e, int32_t opponent) {
     if (!e) return fail(MATE_EINVAL, "null engine");
+    if (e->scripted.team[MATE_TEAM_TARGET].installed)
+        return fail(MATE_ESTATE, "set_target_opponent: an opponent mixture is installed for the target team (mate_engine_set_opponent_mixture): clear it first (count = 0)");
+    return set_target_opponent(e, opponent);
+}
+static int set_target_opponent(mate_engine *e, int32_t opponent) {
     if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_target_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
     if (!e->policy_ready) return fail(MATE_ESTATE, "set_target_opponent: call mate_engine_policy_enable() first (the Greedy agents the heuristic opponent builds on, and the engine's own view masks)");
     if (opponent == MATE_OPPONENT_HEURISTIC && e->tgt_mode != 0)
@@ -1858,6 +1909,149 @@ extern "C" int mate_engine_set_target_opponent(mate_engine *e, int32_t opponent)
         if (rc != MATE_OK) return rc;
     }
     e->opponent.kind = opponent;
+    return MATE_OK;
+}
+
+// The opponent mixtures (include/mate_engine.h, csrc/scripted_rows.hpp): install / clear, draws, memory, the external rows.
+// The Greedy agents of `team` run their agent.reset at their next acting call (PolCtx::cam_episode / tgt_episode <- -1): they may have sat out under a mixture.
+static int mark_greedy_reset(mate_engine *e, int team) {
+    const size_t Nc = (size_t)e->p.Nc, Nt = (size_t)e->p.Nt;
+    const size_t offset = team == MATE_TEAM_CAMERA ? sizeof(double) * ((size_t)e->q.TW + 2 * Nc * Nt + 2 * Nc) + sizeof(int32_t) * (Nc * Nt + 2 * Nc * Nc + Nc)
+                                                   : sizeof(double) * 4 * Nt + sizeof(int32_t) * 3 * Nt;
+    HIP_TRY(hipMemset2D(reinterpret_cast<unsigned char *>(e->q.pol) + offset, sizeof(double) * (size_t)e->q.PW, 0xff, sizeof(int32_t), (size_t)e->N));
+    return MATE_OK;
+}
+extern "C" int mate_engine_set_opponent_mixture(mate_engine *e, int32_t team, const int32_t *kinds, const double *weights, int32_t count, int32_t random_frame_skip) {
+    static const char *const names[2] = {"camera", "target"};
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "set_opponent_mixture: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (count < 0 || count > kScriptedKinds || (count > 0 && !kinds)) return fail(MATE_EINVAL, "set_opponent_mixture: the %s mixture takes 0 .. %d candidates (got %d) and their kinds", names[team], kScriptedKinds, count);
+    // every check ahead of every change: a refused call leaves the engine as it was
+    ScriptedMixture next;
+    double total = 0.0;
+    for (int i = 0; i < count; ++i) {
+        const int kind = kinds[i];
+        const double w = weights ? weights[i] : 1.0;
+        if (kind < 0 || kind >= kScriptedKinds) return fail(MATE_EINVAL, "set_opponent_mixture: candidate %d of the %s mixture has the unknown kind %d (MATE_SCRIPTED_*)", i, names[team], kind);
+        for (int k = 0; k < i; ++k) if (kinds[k] == kind) return fail(MATE_EINVAL, "set_opponent_mixture: kind %d appears twice in the %s mixture", kind, names[team]);
+        if (!std::isfinite(w) || w < 0.0) return fail(MATE_EINVAL, "set_opponent_mixture: weight %d of the %s mixture is negative or not finite", i, names[team]);
+        total += w;
+    }
+    if (count > 0 && !(total > 0.0)) return fail(MATE_EINVAL, "set_opponent_mixture: every weight of the %s mixture is zero", names[team]);
+    if (random_frame_skip < 1) return fail(MATE_EINVAL, "set_opponent_mixture: random_frame_skip of the %s mixture must be at least 1 (got %d)", names[team], random_frame_skip);
+    double running = 0.0;
+    for (int i = 0; i < count; ++i) {      // the candidates with positive weight in the order given (mixture.py:41-43): p = w / sum, cum = cumsum(p)
+        const double w = weights ? weights[i] : 1.0;
+        if (!(w > 0.0)) continue;
+        running += w / total;
+        next.kinds[next.count] = kinds[i]; next.cum[next.count] = running; next.has[kinds[i]] = true; ++next.count;
+    }
+    if (!e->policy_ready) return fail(MATE_ESTATE, "set_opponent_mixture (%s team): call mate_engine_policy_enable() first (the Greedy agents, and the engine's own view masks)", names[team]);
+    const int mode = team == MATE_TEAM_CAMERA ? e->cam_mode : e->tgt_mode;
+    if (next.has[MATE_SCRIPTED_HEURISTIC] && mode != 0)
+        return fail(MATE_EINVAL, "set_opponent_mixture: the Heuristic candidate of the %s mixture senses the opponents of its plain rows, the team's observation mode is %d (mate_engine_set_obs_mode)", names[team], mode);
+    if (next.has[MATE_SCRIPTED_HEURISTIC] && team == MATE_TEAM_CAMERA && e->p.Nc > 0 && !e->camera_opponent.d_scores)
+        return fail(MATE_ESTATE, "set_opponent_mixture: the camera mixture has a Heuristic candidate: install the heuristic camera tables first (mate_engine_heuristic_camera_tables)");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads what changes below)
+    ScriptedMixture &m = e->scripted.team[team];
+    const int n = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
+    const int plain_now = team == MATE_TEAM_CAMERA ? e->camera_opponent.kind : e->opponent.kind;
+    const int restore = m.installed ? m.restore : plain_now;
+    auto set_plain = [&](int kind) { return team == MATE_TEAM_CAMERA ? set_camera_opponent(e, kind) : set_target_opponent(e, kind); };
+    if (count == 0) {                      // clear: the plain selection the mixture replaced; Greedy agents that sat out start afresh
+        if (!m.installed) return MATE_OK;
+        const bool launched = m.launch;
+        { const int rc_ = set_plain(restore); if (rc_ != MATE_OK) return rc_; }
+        m.installed = m.launch = m.acted = false; m.count = 0;
+        for (bool &h : m.has) h = false;
+        return launched ? mark_greedy_reset(e, team) : MATE_OK;
+    }
+    next.launch = n > 0 && !(next.count == 1 && (next.kinds[0] == MATE_SCRIPTED_GREEDY || next.kinds[0] == MATE_SCRIPTED_HEURISTIC));
+    if (next.launch && !m.d_final) {       // the memory of scripted_opponent_kernel, once
+        const size_t pairs = (size_t)e->N * n * 2;
+        int rc;
+        if ((rc = dev_alloc(e, &m.d_external, pairs))) return rc;
+        if ((rc = dev_alloc(e, &m.d_prev_action, pairs))) return rc;
+        if ((rc = dev_alloc(e, &m.d_episode, (size_t)e->N))) return rc;
+        if ((rc = dev_alloc(e, &m.d_choice, (size_t)e->N))) return rc;
+        if ((rc = dev_alloc(e, &m.d_counter, (size_t)e->N))) return rc;
+        if (team == MATE_TEAM_TARGET) {
+            if ((rc = dev_alloc(e, &m.d_prev_location, pairs))) return rc;
+            if ((rc = dev_alloc(e, &m.d_prev_noise, pairs))) return rc;
+            if ((rc = dev_alloc(e, &m.d_goal, (size_t)e->N * n))) return rc;
+            if ((rc = dev_alloc(e, &m.d_inc, (size_t)e->N * n))) return rc;
+        }
+        if ((rc = dev_alloc(e, &m.d_final, pairs))) return rc;      // (last: its presence says all of the above is there)
+    }
+    // the Heuristic machinery of the team is on exactly where a candidate needs it (heuristic_targets / heuristic_cameras read the plain selection)
+    { const int rc_ = set_plain(next.has[MATE_SCRIPTED_HEURISTIC] ? MATE_OPPONENT_HEURISTIC : MATE_OPPONENT_GREEDY); if (rc_ != MATE_OK) return rc_; }
+    // Greedy agents that sat out under the old mixture and act under the new one (as a candidate, or as the plain selection) start afresh, as the
+    // reference's new mixture agent resets the candidate it draws
+    auto runs_greedy = [&](const ScriptedMixture &x) { return !x.launch || x.has[MATE_SCRIPTED_GREEDY] || (team == MATE_TEAM_TARGET && x.has[MATE_SCRIPTED_HEURISTIC]); };
+    if (m.launch && !runs_greedy(m) && runs_greedy(next)) { const int rc_ = mark_greedy_reset(e, team); if (rc_ != MATE_OK) return rc_; }
+    if (next.launch) {                     // the team's reset, the draw included, at its next acting call whatever the episode
+        HIP_TRY(hipMemset(m.d_episode, 0xff, sizeof(int32_t) * (size_t)e->N));
+        HIP_TRY(hipMemset(m.d_choice, 0xff, sizeof(int32_t) * (size_t)e->N));
+    }
+    m.installed = true; m.launch = next.launch; m.acted = false; m.restore = restore; m.frame_skip = random_frame_skip;
+    m.count = next.count;
+    for (int i = 0; i < kScriptedKinds; ++i) { m.kinds[i] = next.kinds[i]; m.cum[i] = next.cum[i]; m.has[i] = next.has[i]; }
+    return MATE_OK;
+}
+extern "C" int mate_engine_scripted_tape(mate_engine *e, const double *camera_u_dev, const double *target_u_dev, const double *target_reset_dev, const int32_t *choice_dev,
+                                         double *record_camera_u_dev, double *record_target_u_dev, double *record_target_reset_dev, int32_t *record_choice_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if ((reinterpret_cast<uintptr_t>(record_camera_u_dev) & 15u) || (reinterpret_cast<uintptr_t>(record_target_reset_dev) & 15u))
+        return fail(MATE_EINVAL, "scripted_tape: record_camera_u_dev and record_target_reset_dev must be aligned to 16 bytes (the launch stores pairs of doubles)");
+    if ((reinterpret_cast<uintptr_t>(camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_reset_dev) & 7u) ||
+        (reinterpret_cast<uintptr_t>(record_target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(choice_dev) & 3u) || (reinterpret_cast<uintptr_t>(record_choice_dev) & 3u))
+        return fail(MATE_EINVAL, "scripted_tape: a buffer is not aligned to its element size");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    // (ScriptedDraws is one type for both: the launch only ever reads through `tape`)
+    e->scripted.tape = ScriptedDraws{const_cast<double *>(camera_u_dev), const_cast<double *>(target_u_dev), const_cast<double *>(target_reset_dev), const_cast<int32_t *>(choice_dev)};
+    e->scripted.record = ScriptedDraws{record_camera_u_dev, record_target_u_dev, record_target_reset_dev, record_choice_dev};
+    return MATE_OK;
+}
+extern "C" int mate_engine_scripted_memory(mate_engine *e, int32_t team, int32_t *choice_dev, int32_t *goal_dev, int32_t *inc_dev, double *prev_noise_dev, double *prev_action_dev,
+                                           int32_t *counter_dev, void *stream_) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_memory: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    const ScriptedMixture &m = e->scripted.team[team];
+    if (!m.d_final) return fail(MATE_ESTATE, "scripted_memory: no opponent mixture with a launch of its own has been installed for the team (mate_engine_set_opponent_mixture)");
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(e->device));
+    note_stream(e, stream);
+    const size_t N = (size_t)e->N, n = (size_t)(team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt);
+    if (choice_dev) HIP_TRY(hipMemcpyAsync(choice_dev, m.d_choice, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, stream));
+    if (counter_dev) HIP_TRY(hipMemcpyAsync(counter_dev, m.d_counter, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, stream));
+    if (prev_action_dev) HIP_TRY(hipMemcpyAsync(prev_action_dev, m.d_prev_action, sizeof(double) * 2 * n * N, hipMemcpyDeviceToDevice, stream));
+    if (team == MATE_TEAM_TARGET) {
+        if (goal_dev) HIP_TRY(hipMemcpyAsync(goal_dev, m.d_goal, sizeof(int32_t) * n * N, hipMemcpyDeviceToDevice, stream));
+        if (inc_dev) HIP_TRY(hipMemcpyAsync(inc_dev, m.d_inc, sizeof(int32_t) * n * N, hipMemcpyDeviceToDevice, stream));
+        if (prev_noise_dev) HIP_TRY(hipMemcpyAsync(prev_noise_dev, m.d_prev_noise, sizeof(double) * 2 * n * N, hipMemcpyDeviceToDevice, stream));
+    }
+    return MATE_OK;
+}
+extern "C" int mate_engine_scripted_external(mate_engine *e, int32_t team, double **rows_dev) {
+    if (!e || !rows_dev) return fail(MATE_EINVAL, "null argument");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_external: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (!e->scripted.team[team].d_final) return fail(MATE_ESTATE, "scripted_external: no opponent mixture with a launch of its own has been installed for the team (mate_engine_set_opponent_mixture)");
+    *rows_dev = e->scripted.team[team].d_external;
+    return MATE_OK;
+}
+extern "C" int mate_engine_scripted_rows(mate_engine *e, int32_t team, int32_t kind, double *rows_dev, void *stream) {
+    if (!e || !rows_dev) return fail(MATE_EINVAL, "null argument");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_rows: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (kind != MATE_SCRIPTED_GREEDY && kind != MATE_SCRIPTED_HEURISTIC && kind != MATE_SCRIPTED_EXTERNAL)
+        return fail(MATE_EINVAL, "scripted_rows: the sources are MATE_SCRIPTED_GREEDY, _HEURISTIC and _EXTERNAL (the Naive and Random rows exist as final rows only)");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "scripted_rows: policies are not enabled");
+    const ScriptedTeam t = scripted_team_args(e, team, true);
+    const double *src = t.rows[kind];
+    if (!src || (kind == MATE_SCRIPTED_HEURISTIC && !e->scripted.team[team].has[MATE_SCRIPTED_HEURISTIC]))
+        return fail(MATE_ESTATE, "scripted_rows: the team's mixture (mate_engine_set_opponent_mixture) has no such source");
+    HIP_TRY(hipSetDevice(e->device));
+    note_stream(e, (hipStream_t)stream);
+    HIP_TRY(hipMemcpyAsync(rows_dev, src, sizeof(double) * 2 * (size_t)t.n * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MATE_OK;
 }
 

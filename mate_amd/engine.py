@@ -17,7 +17,7 @@ from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_tab
 from mate_amd.config import scenario_tables
 
 __all__ = ['Engine', 'EngineGroups', 'Stepper', 'export_layout', 'reward_coefficient_table', 'encode_selection', 'decode_selection',
-           'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS', 'CAMERA_AGENTS']
+           'SCALAR_NAMES', 'REWARD_REDUCTIONS', 'TARGET_AGENTS', 'CAMERA_AGENTS', 'SCRIPTED_AGENTS', 'mixture_table']
 
 SCALAR_NAMES = ('camera_team_reward', 'target_team_reward', 'done', 'coverage_rate', 'real_coverage_rate',
                 'mean_transport_rate', 'num_delivered_cargoes', 'normalized_target_team_reward')
@@ -44,6 +44,38 @@ def export_layout(Nc, Nt, No):
 
 CAMERA_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* for the camera team (HeuristicCameraAgent: heuristic_tables.py, csrc/opponent_rows.hpp)
 TARGET_AGENTS = ('greedy', 'heuristic')      # MATE_OPPONENT_* (include/mate_engine.h): the scripted agents that can play the target team
+
+SCRIPTED_AGENTS = ('greedy', 'heuristic', 'naive', 'random', 'external')      # MATE_SCRIPTED_*: the candidates of an opponent mixture (csrc/scripted_rows.hpp)
+
+
+def mixture_table(candidates, weights=None, random_frame_skip=20):
+    """(kinds, weights) of an opponent mixture as mate_engine_set_opponent_mixture takes them, checked without a device: `candidates` a name
+    of SCRIPTED_AGENTS, a sequence of names, or a dict name -> weight; `weights` (None: all 1) one non-negative finite number per candidate,
+    not all zero (MixtureCameraAgent / MixtureTargetAgent, mate/agents/mixture.py:28-39).  ValueError otherwise."""
+    import math
+    if isinstance(candidates, str):
+        candidates = [candidates]
+    if isinstance(candidates, dict):
+        if weights is not None:
+            raise ValueError('a mixture given as a dict carries its weights: pass no `weights`')
+        candidates, weights = list(candidates.keys()), list(candidates.values())
+    candidates = list(candidates)
+    if not candidates:
+        raise ValueError('a mixture needs at least one candidate (clear_opponent_mixture removes one)')
+    weights = [1.0] * len(candidates) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(candidates):
+        raise ValueError(f'{len(candidates)} candidates but {len(weights)} weights')
+    for name in candidates:
+        if name not in SCRIPTED_AGENTS:
+            raise ValueError(f'mixture candidates must be of {SCRIPTED_AGENTS}, got {name!r}')
+    if len(set(candidates)) != len(candidates):
+        raise ValueError(f'a mixture names every candidate once, got {candidates}')
+    if any(not math.isfinite(w) or w < 0.0 for w in weights) or not any(w > 0.0 for w in weights):
+        raise ValueError(f'mixture weights must be non-negative and finite with at least one positive value, got {weights}')
+    if int(random_frame_skip) != random_frame_skip or random_frame_skip < 1:
+        raise ValueError(f'random_frame_skip must be an integer >= 1, got {random_frame_skip!r}')
+    return [SCRIPTED_AGENTS.index(name) for name in candidates], weights
+
 
 def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
     """The reference's HierarchicalCamera action (examples/hrl/wrappers.py) -> the int32 words [N, Nc] mate_engine_enable_selection reads:
@@ -158,6 +190,9 @@ class Engine:
         self.camera_agent = 'greedy'      # ... and of the camera team (set_camera_opponent)
         self._camera_tables_installed = False
         self._camera_tape = (None, None)      # the tensors mate_engine_heuristic_camera_tape points at
+        self.mixtures = [None, None]          # per team: None or {name: weight} of the installed opponent mixture (set_opponent_mixture)
+        self._plain_agents = [None, None]     # ... and the plain selection it replaced
+        self._scripted_tape = (None, None)    # the tensors mate_engine_scripted_tape points at
         self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
         self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
         # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
@@ -617,6 +652,103 @@ class Engine:
             raise ValueError(f"target_agent must be one of {TARGET_AGENTS}, got {target_agent!r}")
         check(self.lib.mate_engine_set_target_opponent(self._h, TARGET_AGENTS.index(target_agent)))
         self.target_agent = target_agent
+
+    def set_opponent_mixture(self, team, candidates, weights=None, random_frame_skip=20):
+        """A per-episode MIXTURE of scripted agents as `team` ('camera' / 'target') where the engine plays it (MixtureCameraAgent /
+        MixtureTargetAgent, mate/agents/mixture.py): at the team's first acting call of every episode each environment draws ONE candidate
+        for the whole team.  `candidates`: names of SCRIPTED_AGENTS (or a dict name -> weight) -- 'greedy', 'heuristic', 'naive'
+        (mate/agents/naive.py), 'random' (mate/agents/random.py: an action held for `random_frame_skip` calls), 'external' (the rows the
+        caller writes into external_actions(team) before every stepping call).  One more launch in front of the step of step_greedy,
+        step_versus_greedy and step_selected (mate_engine_set_opponent_mixture); a single 'greedy' or 'heuristic' candidate is that plain
+        selection.  enable_policies first.  While installed, set_*_opponent of the team is refused, and unless the mixture is
+        {'greedy'} so are the fused rollouts that would play the team."""
+        team = _team_code(team)
+        kinds, weights = mixture_table(candidates, weights, random_frame_skip)
+        names = [SCRIPTED_AGENTS[k] for k, w in zip(kinds, weights) if w > 0.0]
+        if 'heuristic' in names and team == 0 and self.num_cameras > 0 and not self._camera_tables_installed:
+            from mate_amd.heuristic_tables import heuristic_camera_tables
+            camera = scenario_tables(self.config)['camera']
+            mesh, grid, scores = heuristic_camera_tables(camera['max_sight_range'], camera['min_viewing_angle'])
+            check(self.lib.mate_engine_heuristic_camera_tables(self._h, *(table.ctypes.data_as(ctypes.c_void_p) for table in (mesh, grid, scores))))
+            self._camera_tables_installed = True
+        check(self.lib.mate_engine_set_opponent_mixture(self._h, team, (ctypes.c_int32 * len(kinds))(*kinds), (ctypes.c_double * len(kinds))(*weights),
+                                                        len(kinds), int(random_frame_skip)))
+        if self.mixtures[team] is None:
+            self._plain_agents[team] = self.camera_agent if team == 0 else self.target_agent
+        self.mixtures[team] = {SCRIPTED_AGENTS[k]: w for k, w in zip(kinds, weights) if w > 0.0}
+        plain = 'heuristic' if 'heuristic' in names else 'greedy'      # (the Heuristic machinery of the team is on where a candidate needs it)
+        if team == 0:
+            self.camera_agent = plain
+        else:
+            self.target_agent = plain
+
+    def clear_opponent_mixture(self, team):
+        """Remove the team's mixture: the plain selection it replaced plays again (its Greedy agents reset at their next acting call)."""
+        team = _team_code(team)
+        check(self.lib.mate_engine_set_opponent_mixture(self._h, team, None, None, 0, 20))
+        if self.mixtures[team] is not None:
+            if team == 0:
+                self.camera_agent = self._plain_agents[team]
+            else:
+                self.target_agent = self._plain_agents[team]
+        self.mixtures[team] = None
+
+    def _scripted_shapes(self):
+        N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
+        return (('camera_u', (N, Nc, 2), torch.float64), ('target_u', (N, Nt, 3), torch.float64), ('target_reset', (N, Nt, 4), torch.float64),
+                ('choice', (2, N), torch.int32))
+
+    def scripted_record(self):
+        """A fresh record for scripted_tape(record=...): dict of device tensors of the tape's shapes."""
+        return {name: torch.zeros(shape, dtype=dtype, device=self.device) for name, shape, dtype in self._scripted_shapes()}
+
+    def scripted_tape(self, tape=None, record=None):
+        """Recorded draws for the mixtures' launch and a record of the draws it used (mate_engine_scripted_tape): dicts of contiguous device
+        tensors camera_u [N, Nc, 2], target_u [N, Nt, 3], target_reset [N, Nt, 4] f64 and choice [2, N] int32 (names of SCRIPTED_AGENTS by
+        index, -1: draw).  A member the tape lacks is drawn (Philox); the record reads NaN where nothing was drawn.  Both hold until replaced."""
+        pointers = []
+        for which, given in (('tape', tape), ('record', record)):
+            for name, shape, dtype in self._scripted_shapes():
+                value = None if given is None else given.get(name)
+                if value is not None and (value.dtype != dtype or tuple(value.shape) != shape or not value.is_contiguous() or value.device != self.device):
+                    raise ValueError(f'{which}[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
+                pointers.append(None if value is None else ctypes.c_void_p(value.data_ptr()))
+        check(self.lib.mate_engine_scripted_tape(self._h, *pointers))
+        self._scripted_tape = (tape, record)
+
+    def scripted_memory(self, team):
+        """The team's memory of the mixtures' launch as a dict of device tensors: choice [N] (index into SCRIPTED_AGENTS, -1 before the first
+        draw), prev_action [N, n, 2] and counter [N] (the Random agents'), and for the targets goal, inc [N, Nt] and prev_noise [N, Nt, 2]
+        (the Naive agents')."""
+        team = _team_code(team)
+        N, n = self.num_envs, (self.num_cameras, self.num_targets)[team]
+        out = {'choice': torch.zeros(N, dtype=torch.int32, device=self.device), 'counter': torch.zeros(N, dtype=torch.int32, device=self.device),
+               'prev_action': torch.zeros((N, n, 2), dtype=torch.float64, device=self.device)}
+        if team == 1:
+            out.update(goal=torch.zeros((N, n), dtype=torch.int32, device=self.device), inc=torch.zeros((N, n), dtype=torch.int32, device=self.device),
+                       prev_noise=torch.zeros((N, n, 2), dtype=torch.float64, device=self.device))
+        ptr = lambda name: ctypes.c_void_p(out[name].data_ptr()) if name in out else None
+        check(self.lib.mate_engine_scripted_memory(self._h, team, ptr('choice'), ptr('goal'), ptr('inc'), ptr('prev_noise'), ptr('prev_action'), ptr('counter'),
+                                                   self._stream()))
+        return out
+
+    def external_actions(self, team):
+        """The engine-owned [N, n, 2] f64 tensor of the 'external' candidate of the team's mixture: fill it, for every environment, before each
+        stepping call; the environments that drew 'external' play its rows."""
+        team = _team_code(team)
+        n = (self.num_cameras, self.num_targets)[team]
+        ptr = ctypes.c_void_p()
+        check(self.lib.mate_engine_scripted_external(self._h, team, ctypes.byref(ptr)))
+        count = self.num_envs * n * 2
+        return torch.as_tensor(_EngineOwned(self, ptr.value, count, '<f8'), device=self.device).view(self.num_envs, n, 2)
+
+    def scripted_rows(self, team, kind):
+        """One source of the team's final rows as the mixtures' last launch read it ([N, n, 2] f64): kind 'greedy', 'heuristic' or 'external'."""
+        team = _team_code(team)
+        n = (self.num_cameras, self.num_targets)[team]
+        rows = torch.zeros((self.num_envs, n, 2), dtype=torch.float64, device=self.device)
+        check(self.lib.mate_engine_scripted_rows(self._h, team, SCRIPTED_AGENTS.index(kind), ctypes.c_void_p(rows.data_ptr()), self._stream()))
+        return rows
 
     def _policy_tape(self, policy_tape, keep):
         if policy_tape is None:
@@ -1290,6 +1422,10 @@ class Stepper:
         if self.frame_skip > 1 and versus in ('target', 1) and eng.camera_agent != 'greedy' and eng.num_cameras > 0:
             raise ValueError(f"make_stepper(versus='target', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the camera opponent is "
                              f"{eng.camera_agent!r} (Engine.set_camera_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
+        for team, name in ((1, 'camera'), (0, 'target')):      # (the team the ENGINE plays against the learner `name`)
+            if self.frame_skip > 1 and versus in (name, 1 - team) and eng.mixtures[team] is not None and set(eng.mixtures[team]) != {'greedy'} and (team == 1 or eng.num_cameras > 0):
+                raise ValueError(f"make_stepper(versus={name!r}, frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the opponents play the mixture "
+                                 f"{eng.mixtures[team]} (Engine.set_opponent_mixture) -- step per frame (frame_skip=1) or clear the mixture")
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
         # versus = 'camera' / 'target': the caller's team (MultiCamera / MultiTarget); the other team is played by the on-device
         # greedy agents (Engine.step_versus_greedy) and its tensor argument is ignored

@@ -13,7 +13,7 @@ from mate_amd import constants as consts
 from mate_amd import spaces
 from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
-from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, TARGET_AGENTS, Engine, fragment_coefficient_table
+from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, fragment_coefficient_table, mixture_table
 from mate_amd.utils import Message, Team, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
@@ -442,11 +442,16 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         goal = None if goal is None else torch.from_numpy(np.nan_to_num(np.asarray(goal, dtype=np.float64), nan=0.0)[None].copy()).to(dev)
         return ct, goal
 
-    def enable_greedy_policies(self, target_agent='greedy', camera_agent='greedy'):
+    def enable_greedy_policies(self, target_agent='greedy', camera_agent='greedy', target_mixture=None, camera_mixture=None):
         """Let the engine play GreedyCameraAgent vs GreedyTargetAgent itself (`step_greedy`); call before the reset()
         whose observations the agents first act on.  target_agent='heuristic': HeuristicTargetAgent plays the targets
-        (Engine.set_target_opponent); camera_agent='heuristic': HeuristicCameraAgent the cameras (Engine.set_camera_opponent)."""
+        (Engine.set_target_opponent); camera_agent='heuristic': HeuristicCameraAgent the cameras (Engine.set_camera_opponent).
+        target_mixture / camera_mixture: a name of SCRIPTED_AGENTS or a dict name -> weight, the per-episode opponent mixture of that
+        team (Engine.set_opponent_mixture) in place of the plain agent."""
+        mixtures = {team: mixture_table(spec) and spec for team, spec in (('target', target_mixture), ('camera', camera_mixture)) if spec is not None}
         self.engine.enable_policies(target_agent=target_agent, camera_agent=camera_agent)
+        for team, spec in mixtures.items():
+            self.engine.set_opponent_mixture(team, spec)
         self._policies_on = True
 
     def step_greedy(self):
@@ -698,7 +703,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
-                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False, **kwargs):
+                 learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
+                 target_mixture=None, camera_mixture=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -712,6 +718,16 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             f"camera_agent = {camera_agent!r} senses the targets of its plain rows: no enhanced_observation / shared_field_of_view for the camera team"
         assert camera_agent == 'greedy' or not camera_selection, f"camera_agent = {camera_agent!r}: camera_selection plays the camera team itself"
         self.target_agent, self.camera_agent = target_agent, camera_agent
+        # target_mixture / camera_mixture: a name of SCRIPTED_AGENTS or a dict name -> weight -- the per-episode opponent mixture of that team
+        # (Engine.set_opponent_mixture), checked now, installed by enable_greedy_policies
+        self._mixtures = {team: spec for team, spec in (('target', target_mixture), ('camera', camera_mixture)) if spec is not None}
+        for team, spec in self._mixtures.items():
+            kinds, weights = mixture_table(spec)
+            only_greedy = [SCRIPTED_AGENTS[k] for k, w in zip(kinds, weights) if w > 0.0] == ['greedy']
+            assert not self._fragment or self._fragment['learner'] == team or only_greedy, \
+                f"{team}_mixture = {spec!r} is not available with frame_skip against that team: the fused K-frame launch holds the Greedy agents (step per frame instead)"
+            assert team != 'camera' or not camera_selection, 'camera_mixture: camera_selection plays the camera team itself'
+            assert (target_agent if team == 'target' else camera_agent) == 'greedy', f'{team}_mixture replaces {team}_agent: name the agent as a candidate'
         assert episode_records in (None, True, 'camera', 'target'), f"episode_records = {episode_records!r}: None, True, 'camera' or 'target'"
         if episode_records is True:
             episode_records = self._fragment['learner'] if self._fragment else 'target'
@@ -765,7 +781,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
-        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection):
+        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or (self._mixtures and not self._policies_on):
             self.enable_greedy_policies()
 
     def seed(self, seed):
@@ -936,6 +952,9 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     def enable_greedy_policies(self):
         self.engine.enable_policies(target_agent=self.target_agent, camera_agent=self.camera_agent)
+        for team, spec in self._mixtures.items():
+            if self.engine.mixtures[0 if team == 'camera' else 1] is None:
+                self.engine.set_opponent_mixture(team, spec)
         self._policies_on = True
 
     def step_versus_greedy(self, team, joint_action):

@@ -107,7 +107,7 @@ def evaluate_batched(env, episodes, policy='greedy', chunk=16):
     records have arrived.  Returns them, oldest first, [episodes, 16] f64 on the host."""
     import torch
     env.reset()
-    fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy')
+    fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy' and not any(env.engine.mixtures))
     rows, have = [], 0
     limit = (env.max_episode_steps + chunk) * (2 + episodes // env.num_envs)      # (every environment ends an episode within max_episode_steps frames)
     for _ in range(0, limit, chunk):
@@ -126,6 +126,19 @@ def evaluate_batched(env, episodes, policy='greedy', chunk=16):
     raise RuntimeError(f'{have} of {episodes} episode records after {limit} frames')
 
 
+def parse_mixture(text):
+    """'naive' or 'greedy:1,random:1' -> {name: weight} as Engine.set_opponent_mixture takes it (argparse reports a ValueError as a usage error)."""
+    from .engine import SCRIPTED_AGENTS, mixture_table
+    mixture = {}
+    for part in text.split(','):
+        name, _, weight = part.strip().partition(':')
+        if name in mixture or name == 'external' or name not in SCRIPTED_AGENTS:
+            raise ValueError(f'{name!r}: the candidates are {SCRIPTED_AGENTS[:4]}, each at most once')
+        mixture[name] = float(weight) if weight else 1.0
+    mixture_table(mixture)
+    return mixture
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog='python -m mate_amd.evaluate', description=__doc__.split('\n')[0])
     ap.add_argument('--config', '--cfg', default='MATE-4v2-9.yaml')
@@ -136,6 +149,11 @@ def build_parser():
                     help="the scripted agent of the camera team under --policy greedy (mate.evaluate's --camera-agent)")
     ap.add_argument('--target-agent', choices=['greedy', 'heuristic'], default='greedy',
                     help="the scripted agent of the target team under --policy greedy (mate.evaluate's --target-agent)")
+    ap.add_argument('--camera-mixture', type=parse_mixture, default=None, metavar='NAME[:W][,NAME[:W]...]',
+                    help="a per-episode opponent mixture as the camera team under --policy greedy, e.g. greedy:1,random:1 "
+                         "(MixtureCameraAgent over greedy, heuristic, naive, random; in place of --camera-agent)")
+    ap.add_argument('--target-mixture', type=parse_mixture, default=None, metavar='NAME[:W][,NAME[:W]...]',
+                    help="... as the target team, e.g. naive (MixtureTargetAgent; in place of --target-agent)")
     ap.add_argument('--max-episode-steps', type=int, default=None)
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--num-envs', type=int, default=None,
@@ -152,7 +170,8 @@ def main(argv=None):
     if args.num_envs is not None:
         from .engine import Engine
         env = mate_amd.BatchedMultiAgentTracking(args.config, num_envs=args.num_envs, seed=args.seed, episode_records=args.team,
-                                                 target_agent=args.target_agent, camera_agent=args.camera_agent, **overrides)
+                                                 target_agent=args.target_agent, camera_agent=args.camera_agent,
+                                                 target_mixture=args.target_mixture, camera_mixture=args.camera_mixture, **overrides)
         if args.policy == 'greedy':
             env.enable_greedy_policies()
         records = evaluate_batched(env, args.episodes, args.policy)
@@ -167,6 +186,10 @@ def main(argv=None):
         agents = {'target_agent': args.target_agent}
         if args.camera_agent != 'greedy':
             agents['camera_agent'] = args.camera_agent
+        if args.target_mixture is not None:
+            agents['target_mixture'] = args.target_mixture
+        if args.camera_mixture is not None:
+            agents['camera_mixture'] = args.camera_mixture
         env.enable_greedy_policies(**agents)
     env.seed(args.seed)
     rows = []
