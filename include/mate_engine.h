@@ -839,6 +839,35 @@ int mate_engine_hbm_probe(int32_t device, const void *src, void *dst, int64_t by
 int mate_engine_memory_hold(int32_t device, int64_t bytes, void **token_out);
 int mate_engine_memory_release(void *token);
 
+/* Communication channels for the scripted agents' messages: the reference's NoCommunication, RandomMessageDropout, RestrictedCommunicationRange
+ * and MessageFilter wrappers (mate/wrappers/) on the device.  A channel belongs to a TEAM (MATE_TEAM_CAMERA / MATE_TEAM_TARGET) and decides, per step
+ * and per routed message sender -> recipient of that team's Greedy agents (and of the Heuristic targets, which inherit the Greedy targets' exchange),
+ * whether the message arrives: only where the team is not `disabled`, norm2(recipient - sender) <= `range_limit` (< 0 or +inf: no limit), the
+ * pair's binomial(1, dropout_rate) draws 0 (u > 1 - p for p <= 0.5, else u <= p, draws 1), and the pair's byte of `mask_dev` ([N][n][n] uint8,
+ * [sender][recipient], read at every launch; NULL: all ones) is non-zero.  The sender never knows: a Greedy camera redraws its delay and clears its
+ * message, a broadcasting target clears its flag; only delivered messages change the recipients' memory.  Naive and Random agents send nothing.
+ *
+ * mate_engine_set_channel needs mate_engine_policy_enable (MATE_ESTATE otherwise), waits for the handle's launches, and may change at any call
+ * boundary; NULL clears the team's channel.  MATE_EINVAL: a team that is neither, a rate outside [0, 1] or not finite, a NaN range_limit.  MATE_ESTATE:
+ * a camera channel while the Heuristic camera agent is selected or is a mixture candidate with positive weight (its fallback when a response is lost is an
+ * assignment solve the device does not have) -- and selecting or installing that opponent while a camera channel is set.  A refused call changes nothing.
+ * While a channel is set for a team whose communicating agents act in a call, mate_engine_step_greedy / _step_versus_greedy / _step_selected take the
+ * two-launch form with greedy_channel_kernel as the agents' launch (capturable under mate_engine_device_tick: identical arguments, no allocation, no
+ * synchronisation), and mate_engine_rollout_greedy / _rollout_versus_greedy return MATE_ESTATE: step per frame.  A channel of the caller's own team, or of
+ * a team nobody of the Greedy / Heuristic-target agents plays in the call, is inert: same flow, same bytes.
+ * Not provided: ExtraCommunicationDelays (a queue of stale message contents per pair; not used by the reference's evaluation script).
+ *
+ * mate_engine_channel_tape: the dropout uniforms of the two teams, [N][n][n] f64 [sender][recipient] (NULL: Philox, stream 26, keyed by seed, global
+ * environment index, tick and team << 8 | sender << 4 | recipient), and buffers that receive the uniform every verdict used (NaN where none was drawn;
+ * NULL: not stored).  All four hold until replaced.
+ * mate_engine_channel_edges: the team's two engine-owned int8 matrices [N][n][n], as the last agents' launch with a channel left them: `sent` (what the agents
+ * handed to the channel) and `delivered` (what arrived: the reference's camera_ / target_communication_edges).  An environment that launch skipped keeps its rows. */
+typedef struct { int32_t disabled; double range_limit; /* < 0 or +inf: none */ double dropout_rate; const uint8_t *mask_dev; } mate_channel;
+int mate_engine_set_channel(mate_engine *engine, int32_t team, const mate_channel *cfg);      /* NULL clears */
+int mate_engine_channel_tape(mate_engine *engine, const double *camera_u_dev, const double *target_u_dev,
+                             double *record_camera_u_dev, double *record_target_u_dev); /* [N][n][n]; NULL: Philox / not stored */
+int mate_engine_channel_edges(mate_engine *engine, int32_t team, int8_t **sent_dev, int8_t **delivered_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,11 @@ class MateFirstRows(ctypes.Structure):
     _fields_ = [('rows_dev', ctypes.c_void_p), ('scalars_dev', ctypes.c_void_p), ('final_obs_dev', ctypes.c_void_p)]
 
 
+class MateChannel(ctypes.Structure):
+    """mate_channel: one team's communication channel (mate_engine_set_channel)."""
+    _fields_ = [('disabled', ctypes.c_int32), ('range_limit', ctypes.c_double), ('dropout_rate', ctypes.c_double), ('mask_dev', ctypes.c_void_p)]
+
+
 P, I32, I64, U64, INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
 F64P, IO, TAPE = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape)
 
@@ -124,6 +129,9 @@ PROTOTYPES = {
     'mate_engine_scripted_memory': (INT, [P, I32, P, P, P, P, P, P, P]),
     'mate_engine_scripted_external': (INT, [P, I32, ctypes.POINTER(P)]),
     'mate_engine_scripted_rows': (INT, [P, I32, I32, P, P]),
+    'mate_engine_set_channel': (INT, [P, I32, ctypes.POINTER(MateChannel)]),
+    'mate_engine_channel_tape': (INT, [P, P, P, P, P]),
+    'mate_engine_channel_edges': (INT, [P, I32, ctypes.POINTER(P), ctypes.POINTER(P)]),
     'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
     'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
     'mate_engine_observe': (INT, [P, IO, P]),

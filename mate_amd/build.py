@@ -17,7 +17,8 @@ DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('engine_kernels.hpp', 'r
                                                           'headline_kernels.hpp', 'headline_kernels.hip',
                                                           'episode_rows.hpp', 'episode_kernels.hip',
                                                           'info_rows.hpp', 'info_kernels.hip',
-                                                          'scripted_rows.hpp', 'scripted_kernels.hip')] + [
+                                                          'scripted_rows.hpp', 'scripted_kernels.hip',
+                                                          'channel_rows.hpp', 'channel_kernels.hip')] + [
     os.path.join(os.path.dirname(HERE), 'include', 'mate_engine.h')]
 OUT = os.path.join(HERE, 'lib', 'libmate_engine.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
@@ -69,6 +70,9 @@ INFO_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_info.json')
 # ... and the scripted opponents' and mixtures' (csrc/scripted_kernels.hip: scripted_opponent_kernel, tests/test_scripted_host.py)
 SCRIPTED_SRC = os.path.join(HERE, 'csrc', 'scripted_kernels.hip')
 SCRIPTED_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_scripted.json')
+# ... and the communication channels' (csrc/channel_kernels.hip: greedy_channel_kernel, tests/test_channel_host.py)
+CHANNEL_SRC = os.path.join(HERE, 'csrc', 'channel_kernels.hip')
+CHANNEL_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_channel.json')
 _REMARK = re.compile(r'remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Dynamic Stack|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\S+)')
 
 
@@ -87,11 +91,11 @@ N_SHAPE_GROUPS = 6      # csrc/shape_groups.hpp: the compiled scenario shapes in
 
 
 def _compile_and_link(out, extra=(), verbose=False, remarks=False):
-    """The engine as twelve translation units compiled in parallel -- mate_engine.hip (host side, generic kernels, reset), one
+    """The engine as thirteen translation units compiled in parallel -- mate_engine.hip (host side, generic kernels, reset), one
     shape_group.hip per group of compiled scenario shapes, opponent_kernels.hip, headline_kernels.hip, episode_kernels.hip,
-    info_kernels.hip and scripted_kernels.hip -- and linked into `out`.  Returns the compilers' stderr (remarks) as a sextuple: of the
-    engine's units, of the opponents' unit, of the headline's unit, of the episode records' unit, of the training-information rows'
-    unit, of the scripted opponents' unit."""
+    info_kernels.hip, scripted_kernels.hip and channel_kernels.hip -- and linked into `out`.  Returns the compilers' stderr (remarks) as
+    a septuple: of the engine's units, of the opponents' unit, of the headline's unit, of the episode records' unit, of the
+    training-information rows' unit, of the scripted opponents' unit, of the communication channels' unit."""
     import concurrent.futures
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objdir = os.path.join(os.path.dirname(OUT), 'obj', os.path.splitext(os.path.basename(out))[0])
@@ -104,6 +108,7 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     units += [(EPISODE_SRC, [], os.path.join(objdir, 'episode_kernels.o'))]
     units += [(INFO_SRC, [], os.path.join(objdir, 'info_kernels.o'))]
     units += [(SCRIPTED_SRC, [], os.path.join(objdir, 'scripted_kernels.o'))]
+    units += [(CHANNEL_SRC, [], os.path.join(objdir, 'channel_kernels.o'))]
 
     def compile_unit(unit):
         src, defs, obj = unit
@@ -116,7 +121,7 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     workers = max(1, min(len(units), int(os.environ.get('MATE_BUILD_JOBS', '0')) or (os.cpu_count() or 2)))
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
         results = list(pool.map(compile_unit, units))
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text = '', '', '', '', '', ''
+    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text = '', '', '', '', '', '', ''
     for (src, _, _), (cmd, done) in zip(units, results):
         if done.returncode != 0:
             sys.stderr.write(done.stderr)
@@ -131,6 +136,8 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
             info_text += done.stderr
         elif src == SCRIPTED_SRC:
             scripted_text += done.stderr
+        elif src == CHANNEL_SRC:
+            channel_text += done.stderr
         else:
             text += done.stderr
     link = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + [u[2] for u in units]
@@ -140,22 +147,22 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     if done.returncode != 0:
         sys.stderr.write(done.stderr)
         raise subprocess.CalledProcessError(done.returncode, link)
-    return text, opponent_text, headline_text, episode_text, info_text, scripted_text
+    return text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text
 
 
 def build_engine(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text = _compile_and_link(OUT, verbose=verbose, remarks=True)
+    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text = _compile_and_link(OUT, verbose=verbose, remarks=True)
     kernels, opponents, headline, episodes = parse_resources(text), parse_resources(opponent_text), parse_resources(headline_text), parse_resources(episode_text)
-    info, scripted = parse_resources(info_text), parse_resources(scripted_text)
-    for path, table in ((RESOURCES, kernels), (OPPONENT_RESOURCES, opponents), (HEADLINE_RESOURCES, headline), (EPISODE_RESOURCES, episodes), (INFO_RESOURCES, info), (SCRIPTED_RESOURCES, scripted)):
+    info, scripted, channel = parse_resources(info_text), parse_resources(scripted_text), parse_resources(channel_text)
+    for path, table in ((RESOURCES, kernels), (OPPONENT_RESOURCES, opponents), (HEADLINE_RESOURCES, headline), (EPISODE_RESOURCES, episodes), (INFO_RESOURCES, info), (SCRIPTED_RESOURCES, scripted), (CHANNEL_RESOURCES, channel)):
         with open(path, 'w') as f:
             json.dump(table, f, indent=1, sort_keys=True)
     # A kernel that needs private scratch memory (a spilled register, an outlined helper that takes the environment
     # context by reference) costs ~5 us more per LAUNCH than one that does not -- a third of the headline step.
-    bad = [k for k, r in list(kernels.items()) + list(opponents.items()) + list(headline.items()) + list(episodes.items()) + list(info.items()) + list(scripted.items()) if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
+    bad = [k for k, r in list(kernels.items()) + list(opponents.items()) + list(headline.items()) + list(episodes.items()) + list(info.items()) + list(scripted.items()) + list(channel.items()) if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
     if bad:
         os.remove(OUT)
         raise RuntimeError('kernels with private scratch memory: ' + ', '.join(bad))

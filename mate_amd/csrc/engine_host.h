@@ -21,6 +21,7 @@
 #include "episode_rows.hpp"
 #include "info_rows.hpp"
 #include "scripted_rows.hpp"
+#include "channel_rows.hpp"
 
 using namespace mate;
 
@@ -92,6 +93,16 @@ struct Scripted {        // both teams' mixtures and the draws of their one laun
     ScriptedMixture team[2];
     ScriptedDraws tape{}, record{};
 };
+struct Channels {        // mate_engine_set_channel, one per team: the settings, the draws of greedy_channel_kernel (mate_engine_channel_tape: hold until replaced), the engine-owned edge matrices
+    struct Team {
+        bool set = false, disabled = false;
+        double limit = -1.0, rate = 0.0;             // limit < 0: none
+        const uint8_t *mask = nullptr;
+        const double *tape_u = nullptr; double *record_u = nullptr;
+        int8_t *d_sent = nullptr, *d_delivered = nullptr;      // [N][n][n] each, allocated at the first set_channel / channel_edges
+    } team[2];
+    int lds_bytes = 0;                               // per wave of greedy_channel_kernel (ChannelArgs::lds_bytes), its dynamic LDS opted in: set with the edge matrices
+};
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
     FragmentArgs args{};
@@ -161,6 +172,7 @@ struct mate_engine {
     Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
     CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
     Scripted scripted;                   // the opponent mixtures (scripted_plays: whether a call runs scripted_opponent_kernel)
+    Channels channel;                    // the communication channels (channel_plays: whether a call's agents' launch is greedy_channel_kernel)
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -324,6 +336,17 @@ static bool scripted_plays_team(const mate_engine *e, int team, int team_caller)
     return e->scripted.team[team].launch && team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0);
 }
 static bool scripted_plays(const mate_engine *e, int team_caller) { return scripted_plays_team(e, MATE_TEAM_CAMERA, team_caller) || scripted_plays_team(e, MATE_TEAM_TARGET, team_caller); }
+// A channel is set for `team` and the team's COMMUNICATING agents act in this call -- the Greedy agents, or the Heuristic targets that build on the Greedy
+// targets' exchange; not the caller's own team, not a mixture without such a candidate: the agents' launch of the two-launch form is greedy_channel_kernel
+// (one_launch_step), the fused K-frame launches refuse (rollout_with_policies).  Everywhere else the channel is inert.
+static bool channel_plays_team(const mate_engine *e, int team, int team_caller) {
+    if (!e->channel.team[team].set || team == team_caller) return false;
+    const ScriptedMixture &m = e->scripted.team[team];
+    const bool mix = scripted_plays_team(e, team, team_caller);
+    if (team == MATE_TEAM_CAMERA) return e->p.Nc > 0 && !heuristic_cameras(e, team_caller) && (!mix || m.has[MATE_SCRIPTED_GREEDY]);
+    return !mix || m.has[MATE_SCRIPTED_GREEDY] || m.has[MATE_SCRIPTED_HEURISTIC];
+}
+static bool channel_plays(const mate_engine *e, int team_caller) { return channel_plays_team(e, MATE_TEAM_CAMERA, team_caller) || channel_plays_team(e, MATE_TEAM_TARGET, team_caller); }
 static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;

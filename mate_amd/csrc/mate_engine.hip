@@ -1509,9 +1509,10 @@ static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_st
 }
 // step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
 // recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two),
-// the Heuristic camera opponent (its launch takes the camera agents' place), an opponent mixture whose rows come from the scripted launch
+// the Heuristic camera opponent (its launch takes the camera agents' place), an opponent mixture whose rows come from the scripted launch,
+// a communication channel of a team whose talking agents act (greedy_channel_kernel is the agents' launch then)
 static bool one_launch_step(const mate_engine *e, const FusedCall &c, int team_caller, const mate_step_io *io, const mate_policy_tape *tape) {
-    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller) && !scripted_plays(e, team_caller);
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller) && !scripted_plays(e, team_caller) && !channel_plays(e, team_caller);
 }
 // 2a: between the agents' launch and the stepping launch -- the Heuristic opponents' final joint action from the Greedy one (`freeze_done`: of the agents' launch)
 static int launch_drift(mate_engine *e, const AttachedPlan &pl, int freeze_done, hipStream_t stream) {
@@ -1553,6 +1554,27 @@ static int launch_scripted(mate_engine *e, int team_caller, int freeze_done, hip
     a.tape = e->scripted.tape; a.record = e->scripted.record; a.freeze_done = freeze_done;
     HIP_TRY(launch_scripted_opponents(blocks_of(e, kAttachedEnvsPerBlock), (size_t)attached_tile_lds_bytes(e->p.DW), stream, e->d_params, e->g, a));
     return MATE_OK;
+}
+
+// The agents' launch of the two-launch form with a channel in it: greedy_channel_kernel for the teams `q.caller_team` lets act.  Identical arguments at every
+// call but for the team the caller plays, no allocation, no synchronisation.
+static ChannelArgs channel_args(const mate_engine *e, int team_caller) {
+    ChannelArgs a{};
+    for (int team = 0; team < 2; ++team) {
+        const Channels::Team &c = e->channel.team[team];
+        ChannelTeam &t = a.team[team];
+        t.set = c.set; t.disabled = c.disabled; t.limit = c.limit; t.rate = c.rate; t.mask = c.mask;
+        t.tape_u = c.tape_u; t.record_u = c.record_u; t.sent = c.d_sent; t.delivered = c.d_delivered;
+        if (scripted_plays_team(e, team, team_caller)) {
+            const ScriptedMixture &m = e->scripted.team[team];
+            t.mix.on = 1; t.mix.count = m.count;
+            for (int i = 0; i < kScriptedKinds; ++i) { t.mix.kinds[i] = m.kinds[i]; t.mix.cum[i] = m.cum[i]; }
+            t.mix.episode = m.d_episode; t.mix.choice = m.d_choice;
+            t.mix.tape_choice = e->scripted.tape.choice ? e->scripted.tape.choice + (int64_t)team * e->N : nullptr;
+        }
+    }
+    a.lds_bytes = e->channel.lds_bytes;
+    return a;
 }
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
@@ -1601,7 +1623,9 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     const unsigned blocks = (unsigned)((e->N + 3) / 4);
     Ptrs gp = e->g;
     gp.freeze_done = auto_reset > 1;
-    if (agents) {
+    if (agents && channel_plays(e, team_caller)) {      // the channel inside the agents' `communicate` phase (channel_rows.hpp)
+        HIP_TRY(launch_greedy_channel(e->p.obs_f64 != 0, blocks, 4 * (size_t)e->channel.lds_bytes, stream, e->d_params, gp, q, channel_args(e, team_caller)));
+    } else if (agents) {
         launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
         HIP_TRY(hipGetLastError());
     }
@@ -1726,6 +1750,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
         if (team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0) && !e->scripted.team[team].only_greedy())
             return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the %s team plays an opponent mixture (mate_engine_set_opponent_mixture): step per frame, or clear the mixture",
                         team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy", team == MATE_TEAM_CAMERA ? "camera" : "target");
+    if (channel_plays(e, team_caller))
+        return fail(MATE_ESTATE, "%s: the fused launches deliver every message, a communication channel is set for the %s team (mate_engine_set_channel): step per frame, or clear the channel",
+                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy", channel_plays_team(e, MATE_TEAM_CAMERA, team_caller) ? "camera" : "target");
     if (heuristic_targets(e, team_caller))
         return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the target opponent is the heuristic one (mate_engine_set_target_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
                     team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
@@ -1850,6 +1877,8 @@ extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent)
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (e->scripted.team[MATE_TEAM_CAMERA].installed)
         return fail(MATE_ESTATE, "set_camera_opponent: an opponent mixture is installed for the camera team (mate_engine_set_opponent_mixture): clear it first (count = 0)");
+    if (opponent == MATE_OPPONENT_HEURISTIC && e->channel.team[MATE_TEAM_CAMERA].set)
+        return fail(MATE_ESTATE, "set_camera_opponent: a communication channel is set for the camera team (mate_engine_set_channel), and the heuristic camera agent's fallback for a lost response is not on the device: clear the channel first");
     return set_camera_opponent(e, opponent);
 }
 static int set_camera_opponent(mate_engine *e, int32_t opponent) {
@@ -1952,6 +1981,8 @@ extern "C" int mate_engine_set_opponent_mixture(mate_engine *e, int32_t team, co
         return fail(MATE_EINVAL, "set_opponent_mixture: the Heuristic candidate of the %s mixture senses the opponents of its plain rows, the team's observation mode is %d (mate_engine_set_obs_mode)", names[team], mode);
     if (next.has[MATE_SCRIPTED_HEURISTIC] && team == MATE_TEAM_CAMERA && e->p.Nc > 0 && !e->camera_opponent.d_scores)
         return fail(MATE_ESTATE, "set_opponent_mixture: the camera mixture has a Heuristic candidate: install the heuristic camera tables first (mate_engine_heuristic_camera_tables)");
+    if (next.has[MATE_SCRIPTED_HEURISTIC] && team == MATE_TEAM_CAMERA && e->channel.team[MATE_TEAM_CAMERA].set)
+        return fail(MATE_ESTATE, "set_opponent_mixture: the camera mixture has a Heuristic candidate and a communication channel is set for the camera team (mate_engine_set_channel): clear the channel first");
     { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads what changes below)
     ScriptedMixture &m = e->scripted.team[team];
     const int n = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
@@ -1996,6 +2027,67 @@ extern "C" int mate_engine_set_opponent_mixture(mate_engine *e, int32_t team, co
     m.installed = true; m.launch = next.launch; m.acted = false; m.restore = restore; m.frame_skip = random_frame_skip;
     m.count = next.count;
     for (int i = 0; i < kScriptedKinds; ++i) { m.kinds[i] = next.kinds[i]; m.cum[i] = next.cum[i]; m.has[i] = next.has[i]; }
+    return MATE_OK;
+}
+// The communication channels (include/mate_engine.h, csrc/channel_rows.hpp): settings, draws, edge matrices.
+static int channel_buffers(mate_engine *e) {      // the edge matrices of both teams and the kernel's LDS, once
+    Channels &c = e->channel;
+    if (c.lds_bytes) return MATE_OK;
+    const int lds = round_up(e->q.lds_bytes + channel_staging_bytes(e->p.Nc, e->p.Nt), 16);
+    if (4 * (size_t)lds > kLdsCeiling) return fail(MATE_EINVAL, "set_channel: %zu bytes of LDS per workgroup do not fit", 4 * (size_t)lds);
+    int rc;
+    for (int team = 0; team < 2; ++team) {
+        const size_t n = (size_t)(team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt);
+        if (!c.team[team].d_sent && (rc = dev_alloc(e, &c.team[team].d_sent, (size_t)e->N * n * n))) return rc;
+        if (!c.team[team].d_delivered && (rc = dev_alloc(e, &c.team[team].d_delivered, (size_t)e->N * n * n))) return rc;
+    }
+    for (int f64 = 0; f64 < 2; ++f64) {
+        const hipError_t err = set_dynamic_lds(greedy_channel_function(f64 != 0), 4 * (size_t)lds);
+        if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
+    }
+    c.lds_bytes = lds;
+    return MATE_OK;
+}
+extern "C" int mate_engine_set_channel(mate_engine *e, int32_t team, const mate_channel *cfg) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "set_channel: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (cfg && (!std::isfinite(cfg->dropout_rate) || cfg->dropout_rate < 0.0 || cfg->dropout_rate > 1.0))
+        return fail(MATE_EINVAL, "set_channel: the dropout rate must lie in [0, 1] (got %g)", cfg->dropout_rate);
+    if (cfg && std::isnan(cfg->range_limit)) return fail(MATE_EINVAL, "set_channel: the range limit is NaN (negative or +inf: no limit)");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "set_channel: call mate_engine_policy_enable() first (the agents whose messages the channel carries)");
+    if (cfg && team == MATE_TEAM_CAMERA) {
+        const ScriptedMixture &m = e->scripted.team[MATE_TEAM_CAMERA];
+        if (e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC || m.has[MATE_SCRIPTED_HEURISTIC] || (m.installed && m.restore == MATE_OPPONENT_HEURISTIC))
+            return fail(MATE_ESTATE, "set_channel: the heuristic camera agent plays (or is a candidate of) the camera team, and its fallback for a lost response is not on the device: select MATE_OPPONENT_GREEDY first");
+    }
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the settings)
+    { const int rc_ = channel_buffers(e); if (rc_ != MATE_OK) return rc_; }
+    Channels::Team &c = e->channel.team[team];
+    if (!cfg) { c.set = false; c.disabled = false; c.limit = -1.0; c.rate = 0.0; c.mask = nullptr; return MATE_OK; }
+    c.set = true; c.disabled = cfg->disabled != 0;
+    c.limit = (cfg->range_limit < 0.0 || std::isinf(cfg->range_limit)) ? -1.0 : cfg->range_limit;
+    c.rate = cfg->dropout_rate; c.mask = cfg->mask_dev;
+    return MATE_OK;
+}
+extern "C" int mate_engine_channel_tape(mate_engine *e, const double *camera_u_dev, const double *target_u_dev, double *record_camera_u_dev, double *record_target_u_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if ((reinterpret_cast<uintptr_t>(camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(record_camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(record_target_u_dev) & 7u))
+        return fail(MATE_EINVAL, "channel_tape: a buffer is not aligned to its element size");
+    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    e->channel.team[MATE_TEAM_CAMERA].tape_u = camera_u_dev; e->channel.team[MATE_TEAM_TARGET].tape_u = target_u_dev;
+    e->channel.team[MATE_TEAM_CAMERA].record_u = record_camera_u_dev; e->channel.team[MATE_TEAM_TARGET].record_u = record_target_u_dev;
+    return MATE_OK;
+}
+extern "C" int mate_engine_channel_edges(mate_engine *e, int32_t team, int8_t **sent_dev, int8_t **delivered_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "channel_edges: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "channel_edges: call mate_engine_policy_enable() first");
+    if (!e->channel.lds_bytes) {
+        { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+        { const int rc_ = channel_buffers(e); if (rc_ != MATE_OK) return rc_; }
+    }
+    if (sent_dev) *sent_dev = e->channel.team[team].d_sent;
+    if (delivered_dev) *delivered_dev = e->channel.team[team].d_delivered;
     return MATE_OK;
 }
 extern "C" int mate_engine_scripted_tape(mate_engine *e, const double *camera_u_dev, const double *target_u_dev, const double *target_reset_dev, const int32_t *choice_dev,

@@ -161,11 +161,22 @@ __device__ __forceinline__ double zoom_lookup(const PolicyPtrs &q, double K) {
 // `L` lanes per environment (Ctx): camera c is lane c of the environment's group, target t lane L / 2 + t (32 + t in a whole wave).
 // The draws are keyed by the lane a role has in a WHOLE wave (camera c: c, target t: 32 + t,
 // pair k: k), so every L draws the same numbers.
-template <typename ObsT, int L = 64>
+// `Channel`: what stands between a sent message and its recipient (channel_rows.hpp: greedy_channel_kernel's verdicts and edge rows).  The default
+// delivers everything: its hooks are constexpr no-ops, and every kernel of this header compiles to what it was without them.
+struct NoChannel {
+    // camera pair lane (sender s, recipient c), k = s Nc + c: the bits that arrive of the `bits` sent
+    __device__ __forceinline__ constexpr int camera(int /*k*/, int /*s*/, int /*c*/, int bits) const { return bits; }
+    // recipient lane t, broadcasting sender s: whether the s -> t copy arrives
+    __device__ __forceinline__ constexpr bool target(int /*s*/, int /*t*/) const { return true; }
+    // every target lane t behind the exchange (`needers`: the senders of this step)
+    __device__ __forceinline__ constexpr void targets_done(uint32_t /*needers*/, int /*t*/) const {}
+};
+
+template <typename ObsT, int L = 64, typename Channel = NoChannel>
 __device__ __forceinline__ void greedy_policy_body(const Params &p, const PolicyPtrs &q, PolCtx<ObsT> &a, const double *st, const double *dy,
                                                    const int32_t *di, const uint32_t *mk,
                                                    int wave, int lane, int64_t env, bool active, double *lds_cam_act, double *lds_tgt_act,
-                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true) {
+                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true, const Channel ch = Channel()) {
     constexpr int TB = L / 2;                       // the target agents' first lane
     const int shift = (int)(threadIdx.x & 63) & ~(L - 1);      // the group's first hardware lane (0 when L == 64)
     auto group_ballot = [&](bool x) -> unsigned long long {
@@ -288,6 +299,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
             }
         }
         a.delay(s, c) = d;
+        bits = ch.camera(k, s, c, bits);                     // the sender does not know: its delay is redrawn either way, the rest sees what arrived
         a.send_bits(s, c) = bits;
         // receive_responses: the recipient learns its neighbour (greedy.py:192-226).  One round of pairs: every lane has read
         // neighbor(s, c) above before any lane writes here (one wave, one instruction stream, LDS operations in order)
@@ -342,10 +354,11 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     const uint32_t needers = (uint32_t)(group_ballot(broadcasts) >> TB);      // (target t on lane L / 2 + t; nobody: the sets stay as they are)
     if (needers != 0u && tgts && tl >= 0 && tl < Nt) {
         int set = a.tgt_nonempty(tl);
-        for (uint32_t m = needers; m != 0u; m &= m - 1u) set &= a.tgt_nonempty(__ffs((int)m) - 1);
+        for (uint32_t m = needers; m != 0u; m &= m - 1u) { const int s = __ffs((int)m) - 1; if (ch.target(s, tl)) set &= a.tgt_nonempty(s); }
         a.tgt_nonempty(tl) = set;
         a.tgt_need(tl) = 0;
     }
+    if (tgts && tl >= 0 && tl < Nt) ch.targets_done(needers, tl);
     wave_sync();
 
     POL_STAMP(11);

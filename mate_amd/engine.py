@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from mate_amd import _native, constants as consts, spaces
-from mate_amd._native import MateConfig, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
+from mate_amd._native import MateChannel, MateConfig, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_table, reward_term_keys      # noqa: F401 (this module's names too)
 from mate_amd.config import scenario_tables
 
@@ -75,6 +75,42 @@ def mixture_table(candidates, weights=None, random_frame_skip=20):
     if int(random_frame_skip) != random_frame_skip or random_frame_skip < 1:
         raise ValueError(f'random_frame_skip must be an integer >= 1, got {random_frame_skip!r}')
     return [SCRIPTED_AGENTS.index(name) for name in candidates], weights
+
+
+NO_COMMUNICATION = ('both', 'camera', 'target', 'none')      # mate.NoCommunication's `team`, the reference's --no-communication
+
+
+def channel_settings(range_limit=None, dropout_rate=0.0):
+    """(limit, rate) of a communication channel as mate_engine_set_channel takes them, checked without a device: `range_limit` None, inf or
+    negative for no limit (-1.0), never NaN; `dropout_rate` a finite number in [0, 1] (RandomMessageDropout's assertion).  ValueError otherwise."""
+    import math
+    limit = -1.0 if range_limit is None else float(range_limit)
+    if math.isnan(limit):
+        raise ValueError('the range limit of a channel is NaN (None, inf or a negative number: no limit)')
+    if limit < 0.0 or math.isinf(limit):
+        limit = -1.0
+    rate = float(dropout_rate)
+    if not math.isfinite(rate) or rate < 0.0 or rate > 1.0:
+        raise ValueError(f'the dropout rate of a channel must be a float number between 0 and 1, got {dropout_rate!r}')
+    return limit, rate
+
+
+def channel_table(no_communication='none', message_dropout=0.0, communication_range=None):
+    """Per team (camera, target): None, or the keywords of Engine.set_channel, from the three keywords the environments and the evaluation script
+    take -- `no_communication` one of NO_COMMUNICATION, `message_dropout` a rate or (camera_rate, target_rate), `communication_range` a limit or
+    (camera_limit, target_limit) (None: no limit).  Checked without a device; ValueError otherwise."""
+    if no_communication not in NO_COMMUNICATION:
+        raise ValueError(f'no_communication must be one of {NO_COMMUNICATION}, got {no_communication!r}')
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    rates, limits = pair(message_dropout), pair(communication_range)
+    if len(rates) != 2 or len(limits) != 2:
+        raise ValueError('message_dropout and communication_range take one value or a (camera, target) pair')
+    table = []
+    for team, name in enumerate(('camera', 'target')):
+        limit, rate = channel_settings(limits[team], 0.0 if rates[team] is None else rates[team])
+        disabled = no_communication in ('both', name)
+        table.append(dict(disabled=disabled, range_limit=None if limit < 0 else limit, dropout_rate=rate) if disabled or limit >= 0 or rate > 0 else None)
+    return table
 
 
 def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
@@ -193,6 +229,8 @@ class Engine:
         self.mixtures = [None, None]          # per team: None or {name: weight} of the installed opponent mixture (set_opponent_mixture)
         self._plain_agents = [None, None]     # ... and the plain selection it replaced
         self._scripted_tape = (None, None)    # the tensors mate_engine_scripted_tape points at
+        self.channels = [None, None]          # per team: None or the settings of its communication channel (set_channel)
+        self._channel_tape = (None, None, None)      # the tensors mate_engine_channel_tape points at
         self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
         self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
         # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
@@ -749,6 +787,65 @@ class Engine:
         rows = torch.zeros((self.num_envs, n, 2), dtype=torch.float64, device=self.device)
         check(self.lib.mate_engine_scripted_rows(self._h, team, SCRIPTED_AGENTS.index(kind), ctypes.c_void_p(rows.data_ptr()), self._stream()))
         return rows
+
+    # ------------------------------------------------------------------ communication channels (mate/wrappers/: NoCommunication, RandomMessageDropout, RestrictedCommunicationRange, MessageFilter)
+    def set_channel(self, team, *, disabled=False, range_limit=None, dropout_rate=0.0, mask=None):
+        """A communication channel for `team` ('camera' / 'target'): per step and per message sender -> recipient of the team's Greedy agents
+        (and of the Heuristic targets, which inherit the Greedy targets' exchange) the message arrives only where the team is not `disabled`
+        (NoCommunication), the two are at most `range_limit` apart (RestrictedCommunicationRange; None / inf / negative: no limit), the
+        pair's binomial(1, dropout_rate) draws 0 (RandomMessageDropout) and `mask` ([N, n, n] uint8 on the device, [sender][recipient],
+        read at every launch; None: all ones -- a MessageFilter with any function) is non-zero.  enable_policies first; any call boundary.
+        While set for a team whose talking agents act, step_greedy / step_versus_greedy / step_selected take the two-launch form and the
+        fused rollouts that would play the team are refused; a channel of the caller's own team or of Naive / Random agents is inert.
+        Refused for a camera team the Heuristic agent plays (mate_engine_set_channel)."""
+        team = _team_code(team)
+        limit, rate = channel_settings(range_limit, dropout_rate)
+        n = (self.num_cameras, self.num_targets)[team]
+        if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (self.num_envs, n, n) or not mask.is_contiguous() or mask.device != self.device):
+            raise ValueError(f'mask must be a contiguous uint8 tensor of shape {(self.num_envs, n, n)} on {self.device}')
+        cfg = MateChannel(int(bool(disabled)), limit, rate, None if mask is None else mask.data_ptr())
+        check(self.lib.mate_engine_set_channel(self._h, team, ctypes.byref(cfg)))
+        self.channels[team] = {'disabled': bool(disabled), 'range_limit': None if limit < 0 else limit, 'dropout_rate': rate, 'mask': mask}
+
+    def clear_channel(self, team):
+        """Remove the team's channel: every message arrives again."""
+        team = _team_code(team)
+        check(self.lib.mate_engine_set_channel(self._h, team, None))
+        self.channels[team] = None
+
+    def channel_tape(self, camera_u=None, target_u=None, record=False):
+        """Recorded dropout uniforms for the channels ([N, n, n] f64 device tensors, [sender][recipient]; None: Philox) and -- `record` -- two
+        tensors of those shapes that receive the uniform every verdict used, NaN where none was drawn (mate_engine_channel_tape).  All hold
+        until replaced.  Returns (record_camera_u, record_target_u), or None."""
+        N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
+        for name, value, n in (('camera_u', camera_u, Nc), ('target_u', target_u, Nt)):
+            if value is not None and (value.dtype != torch.float64 or tuple(value.shape) != (N, n, n) or not value.is_contiguous() or value.device != self.device):
+                raise ValueError(f'{name} must be a contiguous float64 tensor of shape {(N, n, n)} on {self.device}')
+        records = None
+        if record:
+            records = tuple(torch.full((N, n, n), float('nan'), dtype=torch.float64, device=self.device) for n in (Nc, Nt))
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        check(self.lib.mate_engine_channel_tape(self._h, ptr(camera_u), ptr(target_u), *(ptr(r) for r in (records or (None, None)))))
+        self._channel_tape = (camera_u, target_u, records)
+        return records
+
+    def channel_edges(self, team):
+        """(sent, delivered): zero-copy [N, n, n] int8 views, [sender][recipient], of the team's engine-owned edge matrices as the last
+        agents' launch with a channel left them -- what the agents handed to the channel, and what arrived (the reference's
+        camera_communication_edges / target_communication_edges)."""
+        team = _team_code(team)
+        n = (self.num_cameras, self.num_targets)[team]
+        sent, delivered = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self.lib.mate_engine_channel_edges(self._h, team, ctypes.byref(sent), ctypes.byref(delivered)))
+        count = self.num_envs * n * n
+        if count == 0:
+            return tuple(torch.zeros((self.num_envs, n, n), dtype=torch.int8, device=self.device) for _ in range(2))
+        return tuple(torch.as_tensor(_EngineOwned(self, p.value, count, '|i1'), device=self.device).view(self.num_envs, n, n) for p in (sent, delivered))
+
+    def channel_active(self, team_caller=None):
+        """Whether a channel is set for a team the engine plays in a call where `team_caller` (None: neither) is the caller's."""
+        caller = None if team_caller is None else _team_code(team_caller)
+        return any(self.channels[t] is not None and t != caller for t in (0, 1))
 
     def _policy_tape(self, policy_tape, keep):
         if policy_tape is None:
@@ -1426,6 +1523,10 @@ class Stepper:
             if self.frame_skip > 1 and versus in (name, 1 - team) and eng.mixtures[team] is not None and set(eng.mixtures[team]) != {'greedy'} and (team == 1 or eng.num_cameras > 0):
                 raise ValueError(f"make_stepper(versus={name!r}, frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the opponents play the mixture "
                                  f"{eng.mixtures[team]} (Engine.set_opponent_mixture) -- step per frame (frame_skip=1) or clear the mixture")
+        for team, name in ((1, 'camera'), (0, 'target')):
+            if self.frame_skip > 1 and versus in (name, 1 - team) and eng.channels[team] is not None and (team == 1 or eng.num_cameras > 0):
+                raise ValueError(f"make_stepper(versus={name!r}, frame_skip={self.frame_skip}) is one fused K-frame launch, which delivers every message: the opponents' team has the "
+                                 f"communication channel {eng.channels[team]} (Engine.set_channel) -- step per frame (frame_skip=1) or clear the channel")
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
         # versus = 'camera' / 'target': the caller's team (MultiCamera / MultiTarget); the other team is played by the on-device
         # greedy agents (Engine.step_versus_greedy) and its tensor argument is ignored

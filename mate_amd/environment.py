@@ -13,7 +13,7 @@ from mate_amd import constants as consts
 from mate_amd import spaces
 from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
-from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, fragment_coefficient_table, mixture_table
+from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, channel_table, fragment_coefficient_table, mixture_table
 from mate_amd.utils import Message, Team, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
@@ -49,6 +49,17 @@ class EnvMeta(type(_EnvBase)):
 
 
 # --------------------------------------------------------------------------------------------- entity views
+def _names_of(mixture):
+    """The candidates with positive weight of a mixture given as a name, a sequence of names or a dict name -> weight (None: none)."""
+    if mixture is None:
+        return ()
+    if isinstance(mixture, str):
+        return (mixture,)
+    if isinstance(mixture, dict):
+        return tuple(name for name, w in mixture.items() if w > 0.0)
+    return tuple(mixture)
+
+
 class _EntityView:
     """Read-only window onto one entity of one environment (the reference exposes live objects)."""
 
@@ -285,7 +296,10 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
     metadata = {'render.modes': ['human', 'rgb_array'], 'video.frames_per_second': 60, 'video.output_frames_per_second': 60}
     DEFAULT_CONFIG_FILE = DEFAULT_CONFIG_FILE
 
-    def __init__(self, config=None, device=0, obs_dtype=torch.float64, **kwargs):
+    def __init__(self, config=None, device=0, obs_dtype=torch.float64, no_communication='none', message_dropout=0.0, communication_range=None, **kwargs):
+        # the reference's NoCommunication / RandomMessageDropout / RestrictedCommunicationRange wrappers for the step_greedy() path (Engine.set_channel;
+        # DESIGN.md section 3.15): checked now, set by enable_greedy_policies
+        self._channels = channel_table(no_communication, message_dropout, communication_range)
         self._setup_scenario(config, kwargs)
         self._device_index, self._obs_dtype = device, obs_dtype
         self._seed_value = 0
@@ -452,7 +466,16 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self.engine.enable_policies(target_agent=target_agent, camera_agent=camera_agent)
         for team, spec in mixtures.items():
             self.engine.set_opponent_mixture(team, spec)
+        for team, spec in enumerate(self._channels):
+            if spec is not None:
+                self.engine.set_channel(team, **spec)
         self._policies_on = True
+
+    def communication_edges(self):
+        """((camera sent, camera delivered), (target sent, target delivered)) of the last step_greedy() / step_versus_greedy(): [n, n] int8 arrays,
+        [sender][recipient] -- what the on-device agents handed to their channel and what arrived (Engine.channel_edges)."""
+        self._need_policies()
+        return tuple(tuple(x[0].cpu().numpy() for x in self.engine.channel_edges(team)) for team in (0, 1))
 
     def step_greedy(self):
         """`env.step(mate.group_step(...))` of both teams with the reference's Greedy agents computed on the device
@@ -704,7 +727,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
                  learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
-                 target_mixture=None, camera_mixture=None, **kwargs):
+                 target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -728,6 +751,14 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                 f"{team}_mixture = {spec!r} is not available with frame_skip against that team: the fused K-frame launch holds the Greedy agents (step per frame instead)"
             assert team != 'camera' or not camera_selection, 'camera_mixture: camera_selection plays the camera team itself'
             assert (target_agent if team == 'target' else camera_agent) == 'greedy', f'{team}_mixture replaces {team}_agent: name the agent as a candidate'
+        # no_communication / message_dropout / communication_range: the reference's NoCommunication, RandomMessageDropout and RestrictedCommunicationRange
+        # wrappers as the channel of the teams the engine plays (Engine.set_channel), checked now, set by enable_greedy_policies
+        self._channels = channel_table(no_communication, message_dropout, communication_range)
+        for team, spec in zip(('camera', 'target'), self._channels):
+            assert spec is None or not self._fragment or self._fragment['learner'] == team, \
+                f"a communication channel of the {team} team is not available with frame_skip against that team: the fused K-frame launch delivers every message (step per frame instead)"
+            assert spec is None or team != 'camera' or (camera_agent == 'greedy' and 'heuristic' not in _names_of(camera_mixture)), \
+                "a communication channel of the camera team needs Greedy cameras: HeuristicCameraAgent's fallback for a lost response is not on the device"
         assert episode_records in (None, True, 'camera', 'target'), f"episode_records = {episode_records!r}: None, True, 'camera' or 'target'"
         if episode_records is True:
             episode_records = self._fragment['learner'] if self._fragment else 'target'
@@ -781,7 +812,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
-        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or (self._mixtures and not self._policies_on):
+        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or ((self._mixtures or any(self._channels)) and not self._policies_on):
             self.enable_greedy_policies()
 
     def seed(self, seed):
@@ -955,7 +986,17 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         for team, spec in self._mixtures.items():
             if self.engine.mixtures[0 if team == 'camera' else 1] is None:
                 self.engine.set_opponent_mixture(team, spec)
+        for team, spec in enumerate(self._channels):
+            if spec is not None and self.engine.channels[team] is None:
+                self.engine.set_channel(team, **spec)
         self._policies_on = True
+
+    def communication_edges(self):
+        """((camera sent, camera delivered), (target sent, target delivered)): [num_envs, n, n] int8 tensors on the GPU, [sender][recipient], as the
+        last agents' launch with a channel left them -- what the on-device agents handed to their channel and what arrived (the reference's
+        camera_communication_edges / target_communication_edges, per environment).  Views of engine-owned memory: copy what must outlive the next step."""
+        self._need_policies()
+        return tuple(self.engine.channel_edges(team) for team in (0, 1))
 
     def step_versus_greedy(self, team, joint_action):
         """MultiCamera(env, target_agent=GreedyTargetAgent()) for team = 'camera', MultiTarget(env,

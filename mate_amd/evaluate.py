@@ -107,7 +107,8 @@ def evaluate_batched(env, episodes, policy='greedy', chunk=16):
     records have arrived.  Returns them, oldest first, [episodes, 16] f64 on the host."""
     import torch
     env.reset()
-    fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy' and not any(env.engine.mixtures))
+    # (an active communication channel is like a non-Greedy opponent: the fused launch delivers every message, so per-step calls)
+    fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy' and not any(env.engine.mixtures) and not env.engine.channel_active())
     rows, have = [], 0
     limit = (env.max_episode_steps + chunk) * (2 + episodes // env.num_envs)      # (every environment ends an episode within max_episode_steps frames)
     for _ in range(0, limit, chunk):
@@ -139,6 +140,22 @@ def parse_mixture(text):
     return mixture
 
 
+def parse_rate(text):
+    """A dropout rate in [0, 1] (argparse reports a ValueError as a usage error)."""
+    from .engine import channel_settings
+    return channel_settings(None, float(text))[1]
+
+
+def parse_limit(text):
+    """A range limit: a non-negative number (argparse reports a ValueError as a usage error)."""
+    from .engine import channel_settings
+    limit = float(text)
+    if limit < 0.0:
+        raise ValueError('a communication range is not negative')
+    channel_settings(limit, 0.0)
+    return limit
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog='python -m mate_amd.evaluate', description=__doc__.split('\n')[0])
     ap.add_argument('--config', '--cfg', default='MATE-4v2-9.yaml')
@@ -154,6 +171,12 @@ def build_parser():
                          "(MixtureCameraAgent over greedy, heuristic, naive, random; in place of --camera-agent)")
     ap.add_argument('--target-mixture', type=parse_mixture, default=None, metavar='NAME[:W][,NAME[:W]...]',
                     help="... as the target team, e.g. naive (MixtureTargetAgent; in place of --target-agent)")
+    ap.add_argument('--no-communication', choices=['both', 'camera', 'target', 'none'], default='none',
+                    help="disable intra-team communication of the scripted agents under --policy greedy (mate.evaluate's --no-communication: mate.NoCommunication)")
+    ap.add_argument('--message-dropout', type=parse_rate, default=0.0, metavar='RATE',
+                    help='drop every message of the scripted agents with this probability (mate.RandomMessageDropout)')
+    ap.add_argument('--communication-range', type=parse_limit, default=None, metavar='LIMIT',
+                    help='deliver a message only between agents at most this far apart (mate.RestrictedCommunicationRange)')
     ap.add_argument('--max-episode-steps', type=int, default=None)
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--num-envs', type=int, default=None,
@@ -171,7 +194,9 @@ def main(argv=None):
         from .engine import Engine
         env = mate_amd.BatchedMultiAgentTracking(args.config, num_envs=args.num_envs, seed=args.seed, episode_records=args.team,
                                                  target_agent=args.target_agent, camera_agent=args.camera_agent,
-                                                 target_mixture=args.target_mixture, camera_mixture=args.camera_mixture, **overrides)
+                                                 target_mixture=args.target_mixture, camera_mixture=args.camera_mixture,
+                                                 no_communication=args.no_communication, message_dropout=args.message_dropout,
+                                                 communication_range=args.communication_range, **overrides)
         if args.policy == 'greedy':
             env.enable_greedy_policies()
         records = evaluate_batched(env, args.episodes, args.policy)
@@ -181,7 +206,8 @@ def main(argv=None):
             print(f'  {name}: {column.mean():.6g} +- {column.std():.6g}')
         env.close()
         return records
-    env = mate_amd.MultiAgentTracking(args.config, **overrides)
+    env = mate_amd.MultiAgentTracking(args.config, no_communication=args.no_communication, message_dropout=args.message_dropout,
+                                      communication_range=args.communication_range, **overrides)
     if args.policy == 'greedy':
         agents = {'target_agent': args.target_agent}
         if args.camera_agent != 'greedy':

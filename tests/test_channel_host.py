@@ -1,0 +1,151 @@
+"""Host-side tests of the communication channels (csrc/channel_rows.hpp), no GPU: the NumPy verdict of tests/channel_ref.py against the sent -> delivered
+matrices the reference's own wrappers recorded (tests/golden/channel_*.npz, tests/golden/make_channel_golden.py); the binomial rule; the Python-level
+validation and the evaluation script's flags; the resource record of the new translation unit; the build's sources; the C ABI's prototypes."""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import channel_ref as C
+import golden_util as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, 'mate_amd', 'lib')
+FIXTURES = {      # name -> (no_communication, range_limit (-1: none), dropout_rate)
+    'channel_4v8-9_none': ('both', -1.0, 0.0), 'channel_4v8-9_camera_only': ('target', -1.0, 0.0), 'channel_4v8-9_drop30': ('none', -1.0, 0.3),
+    'channel_4v8-9_drop70': ('none', -1.0, 0.7), 'channel_4v8-9_range1400': ('none', 1400.0, 0.0), 'channel_8v8-9_range1000': ('none', 1000.0, 0.0),
+    'channel_8v8-9_range1000_drop30': ('none', 1000.0, 0.3),
+}
+
+
+@pytest.mark.parametrize('name', sorted(FIXTURES))
+def test_verdict_equals_the_recorded_reference(name):
+    """Every recorded step, both teams: delivered == sent & verdict(settings, recorded uniforms, recorded locations); a uniform was drawn exactly for
+    the messages that reached the dropout wrapper; every dropout and range fixture shows, per team, at least 3 delivered and 3 dropped messages between
+    different agents."""
+    fx = G.load(name + '.npz')
+    no_comm, limit, rate = str(fx['channel/no_communication']), float(fx['channel/range_limit']), float(fx['channel/dropout_rate'])
+    assert (no_comm, limit, rate) == FIXTURES[name]
+    for tag, team in (('cam', 'camera'), ('tgt', 'target')):
+        sent, delivered, u, xy = (fx[f'step/chan_{tag}_{k}'] for k in ('sent', 'delivered', 'u', 'xy'))
+        n = sent.shape[-1]
+        assert sent.dtype == delivered.dtype == np.int8 and sent.shape == delivered.shape == u.shape == (len(fx['step/done']), n, n) and sent.max() == 1
+        disabled = no_comm in ('both', team)
+        verdict = C.channel_verdict(disabled, limit, rate, None, u, xy)
+        assert np.array_equal(delivered != 0, (sent != 0) & verdict), tag
+        in_range = C.pair_distances(xy) <= limit if limit >= 0 else np.ones(sent.shape, dtype=bool)
+        assert np.array_equal(np.isfinite(u), (sent != 0) & in_range & (not disabled) if rate > 0 else np.zeros(sent.shape, dtype=bool)), tag
+        off = ~np.eye(n, dtype=bool)[None]
+        kept, dropped = int(((delivered != 0) & off).sum()), int(((sent != 0) & (delivered == 0) & off).sum())
+        if limit >= 0 or rate > 0:
+            assert kept >= 3 and dropped >= 3, (tag, kept, dropped)
+        if disabled:
+            assert kept == 0 and dropped >= 3 and not delivered.any(), tag
+        if tag == 'cam':
+            assert not sent[:, np.arange(n), np.arange(n)].any()      # a camera never writes to itself
+        else:
+            rows = sent.any(axis=2)                                   # a broadcast goes to every target, its sender included
+            assert np.array_equal(sent != 0, np.broadcast_to(rows[:, :, None], sent.shape))
+    if name == 'channel_4v8-9_camera_only':
+        assert np.array_equal(fx['step/chan_cam_sent'], fx['step/chan_cam_delivered']) and fx['step/chan_cam_sent'].sum() >= 3
+
+
+def test_binomial_rule_at_the_rates_of_the_issue():
+    """binomial(1, p) of a uniform u: 1 iff u > 1 - p where p <= 0.5, else iff u <= p -- numpy's legacy sampler on the same stream, and the ends."""
+    u = np.array([0.0, 0.25, 0.3, 0.5, 0.6999999, 0.7, 0.7000001, 0.9999999])
+    assert not C.binomial_one(0.0, u).any()                       # rate 0 keeps everything
+    assert C.binomial_one(1.0, u).all()                           # rate 1 drops everything
+    assert C.binomial_one(0.3, u).tolist() == [False, False, False, False, False, False, True, True]      # u > 0.7
+    assert C.binomial_one(0.5, u).tolist() == [False, False, False, False, True, True, True, True]        # u > 0.5
+    assert C.binomial_one(0.7, u).tolist() == [True, True, True, True, True, True, False, False]          # u <= 0.7
+    for rate in (0.3, 0.5, 0.7):
+        a, b = np.random.RandomState(99), np.random.RandomState(99)
+        draws = np.array([a.binomial(1, rate) for _ in range(2000)])
+        assert np.array_equal(draws != 0, C.binomial_one(rate, b.random_sample(2000)))
+    keep = C.channel_verdict(False, None, 0.3, None, np.array([[np.nan, 0.9], [0.1, np.nan]]), np.zeros((2, 2)))
+    assert keep.tolist() == [[True, False], [True, True]]         # no draw drops nothing
+    xy = np.array([[100.0, 100.0], [400.0, 500.0]])
+    assert C.pair_distances(xy)[0, 1] == 500.0
+    nan = np.full((2, 2), np.nan)
+    assert C.channel_verdict(False, 500.0, 0.0, None, nan, xy).all()
+    assert C.channel_verdict(False, np.nextafter(500.0, 0.0), 0.0, None, nan, xy).tolist() == [[True, False], [False, True]]
+    assert C.channel_verdict(False, 0.0, 0.0, None, nan, xy).tolist() == [[True, False], [False, True]]      # the broadcast's copy to its own sender: 0 <= 0
+    assert not C.channel_verdict(True, None, 0.0, None, nan, xy).any()
+    assert C.channel_verdict(False, None, 0.0, np.array([[1, 0], [2, 1]]), nan, xy).tolist() == [[True, False], [True, True]]
+
+
+def test_python_level_validation_needs_no_device():
+    from mate_amd.engine import NO_COMMUNICATION, channel_settings, channel_table
+    from mate_amd.evaluate import build_parser
+    assert NO_COMMUNICATION == ('both', 'camera', 'target', 'none')
+    assert channel_settings() == (-1.0, 0.0) and channel_settings(float('inf'), 1.0) == (-1.0, 1.0) and channel_settings(-3.0, 0.5) == (-1.0, 0.5)
+    assert channel_settings(0.0, 0) == (0.0, 0.0) and channel_settings(1400, 0.3) == (1400.0, 0.3)
+    for bad in (lambda: channel_settings(float('nan')), lambda: channel_settings(None, -0.1), lambda: channel_settings(None, 1.0001),
+                lambda: channel_settings(None, float('nan')), lambda: channel_settings(None, float('inf')), lambda: channel_table('cameras'),
+                lambda: channel_table('none', (0.1, 0.2, 0.3)), lambda: channel_table('none', 0.0, (float('nan'), None))):
+        with pytest.raises(ValueError):
+            bad()
+    assert channel_table() == [None, None]
+    assert channel_table('both') == [dict(disabled=True, range_limit=None, dropout_rate=0.0)] * 2
+    assert channel_table('target', 0.3) == [dict(disabled=False, range_limit=None, dropout_rate=0.3), dict(disabled=True, range_limit=None, dropout_rate=0.3)]
+    assert channel_table('none', (0.0, 0.7), (1400.0, None)) == [dict(disabled=False, range_limit=1400.0, dropout_rate=0.0), dict(disabled=False, range_limit=None, dropout_rate=0.7)]
+    args = build_parser().parse_args([])
+    assert args.no_communication == 'none' and args.message_dropout == 0.0 and args.communication_range is None      # the reference's default
+    args = build_parser().parse_args(['--num-envs', '8', '--no-communication', 'camera', '--message-dropout', '0.3', '--communication-range', '1400'])
+    assert args.no_communication == 'camera' and args.message_dropout == 0.3 and args.communication_range == 1400.0
+    for bad in (['--no-communication', 'all'], ['--message-dropout', '1.5'], ['--message-dropout', 'nan'], ['--communication-range', '-1'], ['--communication-range', 'nan']):
+        with pytest.raises(SystemExit):
+            build_parser().parse_args(bad)
+
+
+def test_environment_arguments_are_checked_ahead_of_the_device():
+    from mate_amd.environment import BatchedMultiAgentTracking, MultiAgentTracking
+    for kw in (dict(no_communication='all'), dict(message_dropout=2.0), dict(communication_range=float('nan')), dict(no_communication='camera', camera_agent='heuristic'),
+               dict(message_dropout=0.3, camera_mixture={'greedy': 1.0, 'heuristic': 1.0}), dict(no_communication='target', frame_skip=4, learner='camera')):
+        with pytest.raises((ValueError, AssertionError)):
+            BatchedMultiAgentTracking('MATE-4v8-9.yaml', num_envs=2, **kw)
+    for kw in (dict(no_communication='all'), dict(message_dropout=-1.0)):
+        with pytest.raises(ValueError):
+            MultiAgentTracking('MATE-4v8-9.yaml', **kw)
+
+
+def test_resource_record_of_the_channel_unit():
+    """csrc/channel_kernels.hip reports apart (mate_amd/build.py): only greedy_channel_kernel instances, no scratch, no dynamic stack, no spills, no kernel
+    name of another record -- and kernel_resources.json is still the parent's, byte for byte: no existing kernel changed."""
+    with open(os.path.join(LIB, 'kernel_resources_channel.json')) as fh:
+        mine = json.load(fh)
+    assert len(mine) == 2 and all('greedy_channel_kernel' in name for name in mine)      # f32 and f64 observations, the generic shape
+    for name, r in mine.items():
+        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0, (name, r)
+    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json',
+                  'kernel_resources_info.json', 'kernel_resources_scripted.json'):
+        with open(os.path.join(LIB, other)) as fh:
+            assert not set(json.load(fh)) & set(mine), other
+    with open(os.path.join(LIB, 'kernel_resources.json'), 'rb') as a, open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json'), 'rb') as b:
+        assert a.read() == b.read()
+
+
+def test_sources_are_in_the_digest_and_the_header_declares_the_calls():
+    import ctypes
+    from mate_amd import _native, build
+    names = {os.path.basename(d) for d in build.DEPS}
+    assert {'channel_rows.hpp', 'channel_kernels.hip'} <= names
+    with open(os.path.join(ROOT, 'include', 'mate_engine.h')) as fh:
+        header = fh.read()
+    assert re.search(r'#define\s+MATE_ABI_VERSION\s+1\b', header)
+    for call in ('set_channel', 'channel_tape', 'channel_edges'):
+        assert 'mate_engine_' + call in _native.PROTOTYPES and re.search(r'\bint mate_engine_%s\(' % call, header)
+    assert len(_native.PROTOTYPES['mate_engine_set_channel'][1]) == 3 and len(_native.PROTOTYPES['mate_engine_channel_tape'][1]) == 5
+    assert len(_native.PROTOTYPES['mate_engine_channel_edges'][1]) == 4
+    declared = re.search(r'typedef struct \{([^}]*)\} mate_channel;', header).group(1)
+    members = re.findall(r'(\w+)\s*;', re.sub(r'/\*.*?\*/', '', declared))
+    assert members == [name for name, _ in _native.MateChannel._fields_] == ['disabled', 'range_limit', 'dropout_rate', 'mask_dev']
+    assert ctypes.sizeof(_native.MateChannel) == 32
+    with open(os.path.join(ROOT, 'mate_amd', 'csrc', 'channel_rows.hpp')) as fh:
+        text = fh.read()
+    streams = [int(v) for v in re.findall(r'S_CHAN_\w+ = (\d+)', text)]
+    with open(os.path.join(ROOT, 'mate_amd', 'csrc', 'scripted_rows.hpp')) as fh:
+        before = [int(v) for v in re.findall(r'S_SCR_\w+ = (\d+)', fh.read())]
+    assert max(before) == 25 and streams and min(streams) == 26 and sorted(streams) == list(range(26, 26 + len(streams)))      # the new stream numbers follow 25
