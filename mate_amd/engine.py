@@ -258,13 +258,15 @@ class Engine:
     def _clear_selection(self):
         # while target selection is attached (enable_selection): the learner's selection [N, Nc] int32, the executor's joint action
         # [N, Nc, 2] (engine-owned), the metrics [N, Nc, 4] f64, the contributing frames [N] int32 and action_mask() [N, Nc, 2 Nt | Nt + 1] u8
-        self.selection = self.selection_actions = self.selection_metrics = self.selection_frames = self.action_mask = None
+        self.selection = self.selection_metrics = self.selection_frames = self.action_mask = None
+        self._selection_actions_view = None      # (selection_actions: built at every read, never kept)
         self.multi_selection, self.selection_accumulate = None, False
 
     def _clear_fragment_rows(self):
         # while fragment rows are attached (enable_fragment_rows): what FrameSkip hands the learner per K-frame launch
         self.fragment_obs = self.fragment_rewards = self.fragment_done = self.fragment_frames = self.fragment_info = None
-        self.fragment_shaped = self.fragment_coefficients = self.fragment_team = None
+        self.fragment_shaped = self.fragment_team = None
+        self._fragment_coefficients_view = None      # (fragment_coefficients: built at every read, never kept)
         self.fragment_frame_skip, self._fragment_masks = 0, False
         self._clear_first_rows()
 
@@ -286,8 +288,21 @@ class Engine:
             self.lib.mate_engine_destroy(self._h)
             self._h = None
             self._clear_episode_records()
+            self._selection_actions_view = self._fragment_coefficients_view = None      # (views of memory that is gone)
 
     __del__ = close
+
+    # Zero-copy tensors over engine-owned memory keep the Engine alive (_EngineOwned).  The Engine must not keep THEM: that cycle would leave
+    # its destruction -- mate_engine_destroy waits for the device and frees -- to the cyclic collector, which may run inside another
+    # engine's stream capture.  So these two are (pointer, count, typestr, shape) records and the tensor is built at every read.
+    def _owned_view(self, view):
+        if view is None:
+            return None
+        ptr, count, typestr, shape = view
+        return torch.as_tensor(_EngineOwned(self, ptr, count, typestr), device=self.device).view(shape)
+
+    selection_actions = property(lambda self: self._owned_view(self._selection_actions_view))
+    fragment_coefficients = property(lambda self: self._owned_view(self._fragment_coefficients_view))
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
@@ -1081,7 +1096,7 @@ class Engine:
         check(self.lib.mate_engine_enable_fragment_rows(self._h, ctypes.byref(cfg)))
         ptr, count = ctypes.c_void_p(), ctypes.c_int32()
         check(self.lib.mate_engine_fragment_coefficients(self._h, ctypes.byref(ptr), ctypes.byref(count)))
-        self.fragment_coefficients = torch.as_tensor(_EngineOwned(self, ptr.value, count.value, '<f8'), device=self.device) if shaping is not None else None
+        self._fragment_coefficients_view = (ptr.value, count.value, '<f8', (count.value,)) if shaping is not None else None
         self.fragment_obs, self.fragment_rewards, self.fragment_done = out['obs'], out['rewards'], out['done']
         self.fragment_frames, self.fragment_info, self.fragment_shaped = out['frames'], out['info'], out['shaped']
         self.fragment_team, self.fragment_frame_skip, self._fragment_masks = cfg.team, frame_skip, masks
@@ -1299,8 +1314,8 @@ class Engine:
                                                     ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(action_mask.data_ptr()), flags))
         ptr, code = ctypes.c_void_p(), ctypes.c_int32()
         check(self.lib.mate_engine_selection_actions(self._h, ctypes.byref(ptr), ctypes.byref(code)))
-        # the engine-owned joint action as a zero-copy tensor (the engine outlives it: the tensor keeps `self`)
-        self.selection_actions = torch.as_tensor(_EngineOwned(self, ptr.value, N * Nc * 2, '<f8' if code.value == 1 else '<f4'), device=self.device).view(N, Nc, 2)
+        # the engine-owned joint action as a zero-copy tensor (the engine outlives it: the tensor keeps `self`; built at every read)
+        self._selection_actions_view = (ptr.value, N * Nc * 2, '<f8' if code.value == 1 else '<f4', (N, Nc, 2))
         self.selection, self.selection_metrics, self.selection_frames, self.action_mask = selection, metrics, frames, action_mask
         self.multi_selection, self.selection_accumulate = bool(multi_selection), bool(accumulate)
         return selection

@@ -184,6 +184,27 @@ def _builtin_engine(config, n, seed):
     return eng
 
 
+def camera_shaper(eng, coefficients, reduction, view):
+    """(terms {key: [N, Nc]}, rows [N, Nc]) f64: the camera shaper's arithmetic (BatchedMultiAgentTracking.auxiliary_camera_rewards) on the step
+    Engine.scalars describes, `view` its unpacked camera_target_view_mask; the soft coverage score only where a coefficient names it."""
+    N, Nc, dev = eng.num_envs, eng.num_cameras, eng.device
+    sc = eng.scalars.double()
+    seen = torch.from_numpy(np.asarray(view)).to(dev)
+    terms = {'raw_reward': sc[:, 0:1].expand(N, Nc), 'coverage_rate': sc[:, 3:4].expand(N, Nc), 'real_coverage_rate': sc[:, 4:5].expand(N, Nc),
+             'mean_transport_rate': sc[:, 5:6].expand(N, Nc),
+             'num_tracked': seen.sum(dim=2).double(), 'baseline': torch.ones((N, Nc), dtype=torch.float64, device=dev)}
+    if 'soft_coverage_score' in coefficients:
+        terms['soft_coverage_score'] = eng.soft_coverage()[1]
+    rows = torch.zeros((N, Nc), dtype=torch.float64, device=dev)
+    for key, c in coefficients.items():
+        rows = rows + c * terms[key]
+    if reduction != 'none':
+        one = {'mean': rows.mean(dim=1), 'sum': rows.sum(dim=1), 'max': rows.max(dim=1).values, 'min': rows.min(dim=1).values}[reduction]
+        rows = one[:, None].expand(N, Nc)
+    return terms, rows
+
+
+SHAPER_BAR = 1e-9                                # rows and terms against the torch shapers on the same records (tests/stack_cases.py imports it)
 STRADDLING = ('7v5-3', '16v15-3', '5v7-0')        # tests/shape_edges.py ATTACHED_CASES: camera_target_view_mask rows that cross a 32-bit word
 
 
@@ -232,29 +253,19 @@ def test_rows_equal_the_torch_shapers_on_the_engines_own_draws(scenario):
                 if key not in target_coefficients:
                     continue
                 got, ref = eng.target_reward_terms[:, :, k], shaper.terms[key]
-                assert float((got - ref).abs().max()) <= 1e-9, (scenario, tgt_reduction, s, key)
+                assert float((got - ref).abs().max()) <= SHAPER_BAR, (scenario, tgt_reduction, s, key)
                 if key in INTEGER_TERMS:
                     assert torch.equal(got, ref.contiguous()), (scenario, s, key)
-            assert float((eng.target_reward_rows - ref_t).abs().max()) <= 1e-9, (scenario, tgt_reduction, s)
+            assert float((eng.target_reward_rows - ref_t).abs().max()) <= SHAPER_BAR, (scenario, tgt_reduction, s)
             if not Nc:
                 assert eng.camera_reward_rows is None and float(eng.target_reward_terms[:, :, TARGET_KEYS.index('is_tracked')].abs().sum()) == 0.0
                 continue
             # the camera shaper's arithmetic (environment.py auxiliary_camera_rewards) on the same records
-            sc = eng.scalars.double()
-            seen = torch.from_numpy(eng.unpack_masks()['camera_target_view_mask']).to(dev)
-            terms = {'raw_reward': sc[:, 0:1].expand(N, Nc), 'coverage_rate': sc[:, 3:4].expand(N, Nc), 'real_coverage_rate': sc[:, 4:5].expand(N, Nc),
-                     'mean_transport_rate': sc[:, 5:6].expand(N, Nc), 'soft_coverage_score': eng.soft_coverage()[1],
-                     'num_tracked': seen.sum(dim=2).double(), 'baseline': torch.ones((N, Nc), dtype=torch.float64, device=dev)}
-            ref_c = torch.zeros((N, Nc), dtype=torch.float64, device=dev)
-            for key, c in CAMERA_COEFFICIENTS.items():
-                ref_c = ref_c + c * terms[key]
-            if cam_reduction != 'none':
-                one = {'mean': ref_c.mean(dim=1), 'sum': ref_c.sum(dim=1), 'max': ref_c.max(dim=1).values, 'min': ref_c.min(dim=1).values}[cam_reduction]
-                ref_c = one[:, None].expand(N, Nc)
+            terms, ref_c = camera_shaper(eng, CAMERA_COEFFICIENTS, cam_reduction, eng.unpack_masks()['camera_target_view_mask'])
             for k, key in enumerate(CAMERA_KEYS):
-                assert float((eng.camera_reward_terms[:, :, k] - terms[key]).abs().max()) <= 1e-9, (scenario, s, key)
+                assert float((eng.camera_reward_terms[:, :, k] - terms[key]).abs().max()) <= SHAPER_BAR, (scenario, s, key)
             assert torch.equal(eng.camera_reward_terms[:, :, 5], terms['num_tracked'].contiguous())
-            assert float((eng.camera_reward_rows - ref_c).abs().max()) <= 1e-9, (scenario, cam_reduction, s)
+            assert float((eng.camera_reward_rows - ref_c).abs().max()) <= SHAPER_BAR, (scenario, cam_reduction, s)
             # which goal-distance branches the inputs reached (the torch shaper's own inputs: the exported state)
             sd = eng.state_dict()
             no_goal, known_empty = sd['tgt_goals'] < 0, sd['tgt_empty_bits'].astype(bool).all(axis=2)
