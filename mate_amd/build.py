@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'csrc', 'mate_engine.hip')
 DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('engine_kernels.hpp', 'reset_kernels.hpp', 'policy_kernels.hpp', 'aux_kernels.hpp', 'attached_tile.hpp', 'state_rows.hpp', 'reward_rows.hpp', 'fragment_rows.hpp', 'selection_rows.hpp', 'device_math.hpp', 'instrument.hpp',
-                                                          'shape_groups.hpp', 'shape_group.inc', 'shape_group.hip', 'engine_host.h',
+                                                          'shape_groups.hpp', 'shape_group.inc', 'shape_group.hip', 'engine_host.h', 'opponent_host.inc',
                                                           'opponent_rows.hpp', 'opponent_kernels.inc', 'opponent_kernels.hip',
                                                           'headline_kernels.hpp', 'headline_kernels.hip',
                                                           'episode_rows.hpp', 'episode_kernels.hip',

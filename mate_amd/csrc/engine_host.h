@@ -1,6 +1,7 @@
 // engine_host.h -- the host's state of one engine (struct mate_engine, the environment switches, one struct per attached feature) and the launch plans: the pure
-// decisions over that state of which kernel a stepping entry point runs, on how many workgroups, with how much LDS (LaunchPlan), and of what is enqueued around it
-// in which order (AttachedPlan: the ONE place that order is written).  Host only: included by mate_engine.hip, never by the shape-group units; nothing here calls HIP.
+// decisions over that state of which kernel a stepping entry point runs, on how many workgroups, with how much LDS (LaunchPlan), of who plays each team of a call with
+// the on-device agents, which launches that takes and whose rows the step consumes (OpponentPlan), and of what is enqueued around the stepping launch in which order
+// (AttachedPlan: the ONE place that order is written).  Host only: included by mate_engine.hip, never by the shape-group units; nothing here calls HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,20 +64,19 @@ struct Selection {       // mate_engine_enable_selection: phase, masks and scala
     double *d_actions = nullptr;
     bool masks_stale = false;                    // a state-only restart (rollout_random's) or import_state ran since the view masks were last written
 };
-struct Opponent {        // mate_engine_set_target_opponent: which scripted agent plays the target team where the engine plays it
-    int kind = MATE_OPPONENT_GREEDY;
-    double *d_final = nullptr;                   // [N][Nt][2] f64, engine-owned, allocated at the first switch to Heuristic: the drift launch's output, the stepping launch's target actions
-    bool drifted = false;                        // the last call with the on-device agents ran the drift launch: d_final is what its step consumed (mate_engine_policy_actions)
+enum RowSource { ROWS_CALLER, ROWS_GREEDY, ROWS_HEURISTIC, ROWS_FINAL };      // whose rows a stepping launch consumes for a team (rows_of): the caller's own, the Greedy agents', the Heuristic launch's, the mixture's final ones
+struct Opponents {       // mate_engine_set_camera_opponent / _set_target_opponent, one record per team: the plain selection, what the last call consumed
+    int kind[2] = {MATE_OPPONENT_GREEDY, MATE_OPPONENT_GREEDY};      // which scripted agent plays the team where the engine plays it (under a mixture: Heuristic exactly where a candidate needs its machinery)
+    int consumed[2] = {ROWS_GREEDY, ROWS_GREEDY};      // the source the last call's stepping launch read for the team (step_with_policies sets it from the plan, the fused launches clear it; mate_engine_policy_actions)
+    double *d_drift = nullptr;                   // [N][Nt][2] f64, engine-owned, allocated at the first switch to Heuristic targets: the drift launch's output, the stepping launch's target actions
 };
-struct CameraOpponent {  // mate_engine_set_camera_opponent: which scripted agent plays the camera team where the engine plays it (opponent_rows.hpp: heuristic_camera_kernel)
-    int kind = MATE_OPPONENT_GREEDY;
+struct CameraOpponent {  // the Heuristic camera agents' tables and memory (opponent_rows.hpp: heuristic_camera_kernel)
     double *d_mesh = nullptr, *d_grid = nullptr, *d_scores = nullptr;      // mate_engine_heuristic_camera_tables: the three tables on the device
     double *d_action = nullptr, *d_prev = nullptr, *d_goals = nullptr;     // [N][Nc][2] f64 each, engine-owned, allocated at the first switch to Heuristic
     int32_t *d_index = nullptr, *d_episode = nullptr;                      // [N][Nc] goal state indices; [N] the episode whose first call has reset the agents
     const int8_t *permutations = nullptr;                                  // mate_engine_heuristic_camera_tape: both hold until replaced
     int8_t *record = nullptr;
-    bool acted = false;                          // the last call with the on-device agents ran the launch: d_action is what its step consumed (mate_engine_policy_actions)
-    bool ran = false;                            // ... some call has since the switch to Heuristic: the Greedy camera agents' memory is behind (switching back marks them for reset)
+    bool ran = false;                            // some call has run the launch since the switch to Heuristic: the Greedy camera agents' memory is behind (switching back marks them for reset)
 };
 struct ScriptedMixture { // mate_engine_set_opponent_mixture, one per team: the candidates with positive weight, the engine-owned memory of scripted_opponent_kernel (scripted_rows.hpp)
     bool installed = false;                      // the team's setter is refused meanwhile (a single Greedy or Heuristic candidate is that plain selection and nothing else)
@@ -86,7 +86,6 @@ struct ScriptedMixture { // mate_engine_set_opponent_mixture, one per team: the 
     bool has[kScriptedKinds] = {};
     double *d_final = nullptr, *d_external = nullptr, *d_prev_action = nullptr, *d_prev_location = nullptr, *d_prev_noise = nullptr;      // [N][n][2] each, allocated at the first install that launches
     int32_t *d_episode = nullptr, *d_choice = nullptr, *d_counter = nullptr, *d_goal = nullptr, *d_inc = nullptr;                       // [N], [N], [N], [N][Nt], [N][Nt]
-    bool acted = false;                          // the last call with the on-device agents ran the scripted launch for the team: d_final is what its step consumed (mate_engine_policy_actions)
     bool only_greedy() const { return !installed || (count == 1 && kinds[0] == MATE_SCRIPTED_GREEDY); }
 };
 struct Scripted {        // both teams' mixtures and the draws of their one launch (mate_engine_scripted_tape: both hold until replaced)
@@ -164,15 +163,15 @@ struct mate_engine {
     PolicyPtrs q{};
     int greedy_team_bits = 0;  // during mate_engine_step_greedy / _step_versus_greedy: teams whose joint action the policy kernel wrote
     // observation post-processing fused into the packer (set_obs_mode / set_obs_transform)
-    int cam_mode = 0, tgt_mode = 0;
+    int team_mode[2] = {0, 0};      // per team (set_obs_mode)
     bool xf_relative = false, xf_cam = false, xf_tgt = false;
     std::vector<double> xf_cam_scale, xf_cam_bias, xf_tgt_scale, xf_tgt_bias;
     uint2 *d_xdesc = nullptr;
     void *d_xab = nullptr;
-    Opponent opponent;         // the target team's scripted agent (heuristic_targets: whether a call runs the drift launch)
-    CameraOpponent camera_opponent;      // the camera team's (heuristic_cameras: whether a call runs heuristic_camera_kernel)
-    Scripted scripted;                   // the opponent mixtures (scripted_plays: whether a call runs scripted_opponent_kernel)
-    Channels channel;                    // the communication channels (channel_plays: whether a call's agents' launch is greedy_channel_kernel)
+    Opponents opponents;       // who plays each team where the engine plays it, whose rows the last call consumed -- what a CALL makes of these four: plan_opponents
+    CameraOpponent camera_opponent;      // the Heuristic camera agents' tables and memory
+    Scripted scripted;                   // the opponent mixtures
+    Channels channel;                    // the communication channels
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -281,14 +280,9 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 // launches" section of mate_engine.hip has one function per position; each reads this plan and launches what it names, with the geometry it carries.
 //   1 execute      selection_kernel, SELECTION_EXECUTE: the camera team's joint action of this frame       attached_ahead_of_step (step_selected)
 //   2              the stepping launch (and, two-launch form, the opponents' agents in front of it)
-//   2a drift       heuristic_drift_kernel between the agents' launch and the stepping launch: the Heuristic   step_with_policies
-//                  target opponents' final joint action (opponent_rows.hpp); two-launch form only, where the
-//                  engine plays the targets (heuristic_targets: a property of the call, like `selected`, not of the plan)
-//   2b cameras     heuristic_camera_kernel in front of the stepping launch: the Heuristic camera opponents' joint     step_with_policies
-//                  action (opponent_rows.hpp); two-launch form only, where the engine plays the cameras (heuristic_cameras)
-//   2c scripted    scripted_opponent_kernel behind 2a / 2b and the agents' launch, ahead of the stepping launch: the Naive and     step_with_policies
-//                  Random agents and, per environment, the row of the episode's mixture choice as the team's FINAL joint action
-//                  (scripted_rows.hpp); two-launch form only, for the teams the engine plays under a mixture (scripted_plays)
+//   2a..2c         the two-launch form's launches between the two, in this order: the agents' launch (policy_kernel or greedy_channel_kernel),     step_with_policies
+//                  heuristic_camera_kernel, heuristic_drift_kernel, scripted_opponent_kernel -- WHICH of them a call runs, for which teams, and whose
+//                  rows the stepping launch then consumes is the call's OpponentPlan (plan_opponents, below)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   3b info        info_rows_kernel: MoreTrainingInformation's per-agent rows of the launch's last frame       attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
@@ -306,8 +300,9 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
     bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, info = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, drift_rows, fragment_rows, episode_rows, info_rows, state_rows;      // (selection: the three phases are one kernel on one grid; drift_rows: blocks 0 unless the opponent is Heuristic)
+    Tiles soft_coverage, reward_rows, selection, fragment_rows, episode_rows, info_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
 };
+static Tiles plan_attached_tile(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock}; }      // the shared tile of attached_tile.hpp
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
 // Environments per workgroup: 16, or fewer where the tile (records + rows of the type) would take more than 40 KB of LDS
 static Tiles plan_state_rows(const mate_engine *e, bool f64) {
@@ -325,28 +320,6 @@ static Tiles plan_info_rows(const mate_engine *e) {
 }
 // `selected`: the call is mate_engine_step_selected; `fused_team`: the call is mate_engine_rollout_versus_greedy for that team (-1: any other).  The action mask is the view the executor would act on next, so while selection is
 // attached it follows every call that leaves new records (a reset and observe() too), as long as the engine's mask words are current.
-// The engine plays the target team of this call (`team_caller`: -1 both teams are the agents, else the caller's) with the Heuristic agent: the call takes the two-launch
-// form with the drift launch in it (one_launch_step), the fused K-frame launches refuse (rollout_with_policies: their kernels hold the Greedy agents)
-static bool heuristic_targets(const mate_engine *e, int team_caller) { return e->opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_TARGET; }
-// The engine plays the camera team of this call with the Heuristic agent: the two-launch form with heuristic_camera_kernel in front of the stepping launch, no fused K-frame
-// launch.  (A scenario without cameras: the selection is a no-op.)
-static bool heuristic_cameras(const mate_engine *e, int team_caller) { return e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC && team_caller != MATE_TEAM_CAMERA && e->p.Nc > 0; }
-// The engine plays `team` of this call under a mixture whose rows come from the scripted launch (a scenario without cameras has no camera team to play)
-static bool scripted_plays_team(const mate_engine *e, int team, int team_caller) {
-    return e->scripted.team[team].launch && team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0);
-}
-static bool scripted_plays(const mate_engine *e, int team_caller) { return scripted_plays_team(e, MATE_TEAM_CAMERA, team_caller) || scripted_plays_team(e, MATE_TEAM_TARGET, team_caller); }
-// A channel is set for `team` and the team's COMMUNICATING agents act in this call -- the Greedy agents, or the Heuristic targets that build on the Greedy
-// targets' exchange; not the caller's own team, not a mixture without such a candidate: the agents' launch of the two-launch form is greedy_channel_kernel
-// (one_launch_step), the fused K-frame launches refuse (rollout_with_policies).  Everywhere else the channel is inert.
-static bool channel_plays_team(const mate_engine *e, int team, int team_caller) {
-    if (!e->channel.team[team].set || team == team_caller) return false;
-    const ScriptedMixture &m = e->scripted.team[team];
-    const bool mix = scripted_plays_team(e, team, team_caller);
-    if (team == MATE_TEAM_CAMERA) return e->p.Nc > 0 && !heuristic_cameras(e, team_caller) && (!mix || m.has[MATE_SCRIPTED_GREEDY]);
-    return !mix || m.has[MATE_SCRIPTED_GREEDY] || m.has[MATE_SCRIPTED_HEURISTIC];
-}
-static bool channel_plays(const mate_engine *e, int team_caller) { return channel_plays_team(e, MATE_TEAM_CAMERA, team_caller) || channel_plays_team(e, MATE_TEAM_TARGET, team_caller); }
 static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused_team = -1) {
     AttachedPlan pl;
     pl.execute = pl.observe = selected;
@@ -358,11 +331,67 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.info = e->info.on;
     pl.state = e->state.on();
     if (e->reward.soft) pl.soft_coverage = plan_soft_coverage(e);
-    pl.reward_rows = pl.selection = {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock};
-    if (e->opponent.kind == MATE_OPPONENT_HEURISTIC) pl.drift_rows = pl.reward_rows;      // (launched by the two-launch form where the engine plays the targets: heuristic_targets)
+    pl.reward_rows = pl.selection = plan_attached_tile(e);
     pl.fragment_rows = plan_fragment_rows(e);
     if (pl.episodes) pl.episode_rows = plan_episode_rows(e);
     if (pl.info) pl.info_rows = plan_info_rows(e);
     pl.state_rows = plan_state_rows(e, e->state.f64);
+    return pl;
+}
+
+// ---- the opponents
+// Who plays each team of ONE call with the on-device agents (`team_caller`: -1 both teams are the engine's, else the caller's team), which launches that takes
+// and whose rows the stepping launch consumes.  Everything else reads this: one_launch_step and step_with_policies (the launches, in the order of the fields),
+// rollout_with_policies (the refusal), scripted_team_args, channel_args.
+enum FusedRefusal { FUSED_OK, FUSED_MIXTURE, FUSED_CHANNEL, FUSED_HEURISTIC };
+struct OpponentPlan {
+    struct Team {
+        bool engine = false;       // the engine plays the team in this call: not the caller's, and it has agents (a scenario without cameras: every camera selection is a no-op)
+        int source = ROWS_CALLER;  // whose rows the stepping launch consumes (rows_of)
+        bool greedy = false;       // its Greedy agents act in the agents' launch: they play, or a candidate of the mixture needs their row (the Heuristic targets build on it)
+        bool heuristic = false;    // its Heuristic launch runs: heuristic_camera_kernel in the Greedy cameras' place / heuristic_drift_kernel behind the Greedy targets
+        bool scripted = false;     // it is in the scripted launch: a mixture whose rows come from scripted_opponent_kernel
+        bool channel = false;      // its channel is live: set, and its communicating agents act -- the Greedy ones, or the Heuristic targets that inherit the Greedy targets' exchange
+    } team[2];
+    bool agents = false;           // there is an agents' launch ...
+    int caller_team = -1;          // ... with this q.caller_team (the team whose Greedy agents sit out; -1: neither) ...
+    bool channel_kernel = false;   // ... and it is greedy_channel_kernel (channel_rows.hpp)
+    Tiles drift_rows;              // the drift launch's geometry (blocks 0: none)
+    bool one_launch = true;        // the opponents allow the one-launch step: plain Greedy agents, no live channel
+    int refusal = FUSED_OK, refusal_team = -1;      // why a fused K-frame launch is refused (their kernels hold the Greedy agents and deliver every message), and for which team
+};
+static int agents_of(const mate_engine *e, int team) { return team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt; }
+// THE one mapping of a source to the buffer a stepping launch reads for `team` (null: the caller's own pointer)
+static const double *rows_of(const mate_engine *e, int team, int source) {
+    switch (source) {
+    case ROWS_GREEDY: return team == MATE_TEAM_CAMERA ? e->q.cam_act : e->q.tgt_act;
+    case ROWS_HEURISTIC: return team == MATE_TEAM_CAMERA ? e->camera_opponent.d_action : e->opponents.d_drift;
+    case ROWS_FINAL: return e->scripted.team[team].d_final;
+    default: return nullptr;
+    }
+}
+static OpponentPlan plan_opponents(const mate_engine *e, int team_caller) {
+    OpponentPlan pl;
+    for (int team = 0; team < 2; ++team) {
+        OpponentPlan::Team &t = pl.team[team];
+        const ScriptedMixture &m = e->scripted.team[team];
+        const bool camera = team == MATE_TEAM_CAMERA;
+        t.engine = team != team_caller && agents_of(e, team) > 0;
+        t.heuristic = t.engine && e->opponents.kind[team] == MATE_OPPONENT_HEURISTIC;
+        t.scripted = t.engine && m.launch;
+        t.source = team == team_caller ? ROWS_CALLER : t.scripted ? ROWS_FINAL : t.heuristic ? ROWS_HEURISTIC : ROWS_GREEDY;      // (nobody to play: the Greedy buffer, empty)
+        t.greedy = team != team_caller && (t.scripted ? m.has[MATE_SCRIPTED_GREEDY] || (!camera && m.has[MATE_SCRIPTED_HEURISTIC]) : camera ? !t.heuristic : true);
+        t.channel = e->channel.team[team].set && t.engine && t.greedy && !(camera && t.heuristic);
+        // the refusals in the order rollout_with_policies has always checked them: a mixture of either team (camera first), a channel (camera first), the Heuristic targets, the Heuristic cameras
+        if (t.engine && !m.only_greedy() && pl.refusal != FUSED_MIXTURE) { pl.refusal = FUSED_MIXTURE; pl.refusal_team = team; }
+    }
+    const OpponentPlan::Team &c = pl.team[MATE_TEAM_CAMERA], &t = pl.team[MATE_TEAM_TARGET];
+    if (pl.refusal == FUSED_OK && (c.channel || t.channel)) { pl.refusal = FUSED_CHANNEL; pl.refusal_team = c.channel ? MATE_TEAM_CAMERA : MATE_TEAM_TARGET; }
+    if (pl.refusal == FUSED_OK && (c.heuristic || t.heuristic)) { pl.refusal = FUSED_HEURISTIC; pl.refusal_team = t.heuristic ? MATE_TEAM_TARGET : MATE_TEAM_CAMERA; }
+    pl.agents = c.greedy || t.greedy;
+    pl.caller_team = c.greedy && t.greedy ? -1 : c.greedy ? MATE_TEAM_TARGET : MATE_TEAM_CAMERA;
+    pl.channel_kernel = c.channel || t.channel;
+    if (t.heuristic) pl.drift_rows = plan_attached_tile(e);
+    pl.one_launch = !c.heuristic && !t.heuristic && !c.scripted && !t.scripted && !pl.channel_kernel;
     return pl;
 }

@@ -24,6 +24,7 @@
 
 using namespace mate;
 
+static const char *const kTeamNames[2] = {"camera", "target"};      // by MATE_TEAM_*: the error texts' words
 static thread_local std::string g_error;
 static int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -41,6 +42,7 @@ static int fail(int code, const char *fmt, ...) {
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) { (void)hipGetLastError(); return fail(MATE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); }    \
     } while (0)
+#define MATE_TRY(expr) do { const int rc_ = (expr); if (rc_ != MATE_OK) return rc_; } while (0)      // (an engine function's own status: the error text is set)
 
 // Without -DMATE_SPLIT_BUILD (a plain `hipcc mate_engine.hip`, as the experiment scripts under tools/ do) the shape groups are
 // compiled right here, one after the other; mate_amd/build.py compiles them as translation units of their own, in parallel.
@@ -131,7 +133,7 @@ static hipError_t wait_for_launches(mate_engine *e) {
 // The opening of an entry point that launches on `stream`: the pipelined-restart mode is left and, for the calls that need an
 // episode in progress (`who`: their name in the message), a reset must have run.  Of a host-side accessor: the launches drain.
 static int enter(mate_engine *e, hipStream_t stream, const char *who = nullptr) {
-    { const int rc = leave_pipelined(e, stream); if (rc != MATE_OK) return rc; }
+    MATE_TRY(leave_pipelined(e, stream));
     if (who && !e->was_reset) return fail(MATE_ESTATE, "%s called before reset() (or import_state)", who);
     HIP_TRY(hipSetDevice(e->device));
     return MATE_OK;
@@ -473,9 +475,9 @@ static int upload_interleaved(void *dst, const double *a, const double *b, size_
 static int apply_obs_tables(mate_engine *e) {
     const Params &p = e->p;
     std::vector<uint32_t> desc;
-    build_descriptors(p, desc, e->cam_mode, e->tgt_mode);
+    build_descriptors(p, desc, e->team_mode[MATE_TEAM_CAMERA], e->team_mode[MATE_TEAM_TARGET]);
     HIP_TRY(hipMemcpy(const_cast<uint32_t *>(e->g.desc), desc.data(), desc.size() * 4, hipMemcpyHostToDevice));
-    e->g.obs_mode = e->cam_mode | (e->tgt_mode << 2);
+    e->g.obs_mode = e->team_mode[MATE_TEAM_CAMERA] | (e->team_mode[MATE_TEAM_TARGET] << 2);
     const bool relative = e->xf_relative;
     const double *cam_scale = e->xf_cam ? e->xf_cam_scale.data() : nullptr, *cam_bias = e->xf_cam ? e->xf_cam_bias.data() : nullptr;
     const double *tgt_scale = e->xf_tgt ? e->xf_tgt_scale.data() : nullptr, *tgt_bias = e->xf_tgt ? e->xf_tgt_bias.data() : nullptr;
@@ -531,7 +533,7 @@ extern "C" int mate_engine_set_obs_transform(mate_engine *e, int32_t relative, c
                                              const double *tgt_scale, const double *tgt_bias) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if ((cam_scale && !cam_bias) || (tgt_scale && !tgt_bias)) return fail(MATE_EINVAL, "scale without bias");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     const Params &p = e->p;
     e->xf_relative = relative != 0;
     e->xf_cam = cam_scale != nullptr; e->xf_tgt = tgt_scale != nullptr;
@@ -545,25 +547,24 @@ extern "C" int mate_engine_set_obs_transform(mate_engine *e, int32_t relative, c
 extern "C" int mate_engine_set_obs_mode(mate_engine *e, int32_t camera_mode, int32_t target_mode) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (camera_mode < 0 || camera_mode > 2 || target_mode < 0 || target_mode > 2) return fail(MATE_EINVAL, "observation mode must be 0 (plain), 1 (enhanced) or 2 (shared field of view)");
-    if (target_mode != 0 && e->opponent.kind == MATE_OPPONENT_HEURISTIC)
-        return fail(MATE_EINVAL, "set_obs_mode: the heuristic target opponent (mate_engine_set_target_opponent) senses the cameras of its plain rows: the target team mode must stay 0");
-    if (camera_mode != 0 && e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC)
-        return fail(MATE_EINVAL, "set_obs_mode: the heuristic camera opponent (mate_engine_set_camera_opponent) senses the targets of its plain rows: the camera team mode must stay 0");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
-    e->cam_mode = camera_mode; e->tgt_mode = target_mode;
+    const int mode[2] = {camera_mode, target_mode};
+    for (int team = MATE_TEAM_TARGET; team >= MATE_TEAM_CAMERA; --team)
+        if (mode[team] != 0 && e->opponents.kind[team] == MATE_OPPONENT_HEURISTIC)
+            return fail(MATE_EINVAL, "set_obs_mode: the heuristic %s opponent (mate_engine_set_%s_opponent) senses the %ss of its plain rows: the %s team mode must stay 0", kTeamNames[team], kTeamNames[team], kTeamNames[1 - team], kTeamNames[team]);
+    MATE_TRY(enter_host(e));
+    e->team_mode[MATE_TEAM_CAMERA] = camera_mode; e->team_mode[MATE_TEAM_TARGET] = target_mode;
     return apply_obs_tables(e);
 }
 
 extern "C" int mate_engine_set_action_grids(mate_engine *e, const double *camera_grid, int32_t n_cam, const double *target_grid, int32_t n_tgt) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (n_cam < 0 || n_tgt < 0 || (n_cam > 0 && !camera_grid) || (n_tgt > 0 && !target_grid)) return fail(MATE_EINVAL, "invalid action grid");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     auto upload = [&](const double *src, int n, const double2 **dst, int32_t *count) -> int {
         *dst = nullptr; *count = 0;
         if (n == 0) return MATE_OK;
         double2 *buf = nullptr;
-        int rc = dev_alloc(e, &buf, (size_t)n);
-        if (rc) return rc;
+        MATE_TRY(dev_alloc(e, &buf, (size_t)n));
         HIP_TRY(hipMemcpy(buf, src, (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
         *dst = buf; *count = n;
         return MATE_OK;
@@ -598,13 +599,13 @@ extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (e->dev_tick) return fail(MATE_ESTATE, "seed() while the step counter is device-resident (mate_engine_device_tick)");
     e->p.seed_lo = (uint32_t)seed; e->p.seed_hi = (uint32_t)(seed >> 32);
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     HIP_TRY(hipMemcpy(e->d_params, &e->p, sizeof(Params), hipMemcpyHostToDevice));
     // the reference re-creates its generators (environment.py:1219-1225): the same seed gives the same episodes again,
     // whatever ran before.  Here: the key, and every counter that enters a Philox counter word (episode, tick) rewound.
     hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, e->last_stream, (const Params *)e->d_params, (const Ptrs)e->g);
     HIP_TRY(hipGetLastError());
-    { const int rc_ = clear_episode_sums(e, e->last_stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(clear_episode_sums(e, e->last_stream));
     HIP_TRY(wait_for_launches(e));
     e->tick = 0;
     return MATE_OK;
@@ -710,7 +711,7 @@ static int launch_reward_rows(mate_engine *e, const AttachedPlan &pl, int mode, 
 // (the masks are the engine's own copy, Ptrs::own_masks: every step, reset and restart launch that writes a view writes it there)
 static int launch_selection(mate_engine *e, const AttachedPlan &pl, int phase, const float *scalars, hipStream_t stream) {
     SelectionArgs a = e->selection.args;
-    a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->cam_mode;
+    a.phase = phase; a.scalars = scalars; a.masks = e->g.own_masks; a.cam_mode = e->team_mode[MATE_TEAM_CAMERA];
     return with_obs_type(e->selection.act_f64, [&](auto tag) { return launch_tiles(selection_kernel<decltype(tag)>, pl.selection, stream, e->d_params, e->g, a); });
 }
 // `a`: complete arguments (the attached ones with the call's buffers and frames, or the on-demand form's)
@@ -788,20 +789,18 @@ static int attached_behind_step(mate_engine *e, bool selected, const mate_step_i
     const AttachedPlan pl = plan_attached(e, selected, fused_team);
     const size_t last = (size_t)(frames - 1) * (size_t)e->N;
     if (pl.reward) {
-        const int rc = launch_reward_rows(e, pl, e->reward.accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream);
-        if (rc != MATE_OK) return rc;
+        MATE_TRY(launch_reward_rows(e, pl, e->reward.accumulate ? REWARD_ACCUMULATE : REWARD_OVERWRITE, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, stream));
     }
-    if (pl.info) { const int rc = launch_info(e, pl, INFO_STEP, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, frames, stream); if (rc != MATE_OK) return rc; }
-    if (pl.observe) { const int rc = launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream); if (rc != MATE_OK) return rc; }
+    if (pl.info) MATE_TRY(launch_info(e, pl, INFO_STEP, io->scalars_dev + last * 8, io->masks_dev + last * e->p.MW, frames, stream));
+    if (pl.observe) MATE_TRY(launch_selection(e, pl, SELECTION_OBSERVE, io->scalars_dev + last * 8, stream));
     if (pl.fragment) {
         FragmentArgs a = e->fragment.args;
         a.scalars = io->scalars_dev; a.masks = io->masks_dev; a.K = frames;
         a.rows = a.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev;
-        const int rc = launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream);
-        if (rc != MATE_OK) return rc;
+        MATE_TRY(launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream));
     }
     if (pl.first_rows) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->first.scalars), 0x40000000 /* 2.0f */, 8 * (size_t)e->N, stream));
-    if (pl.episodes) { const int rc = launch_episode_records(e, pl, io, frames, stream); if (rc != MATE_OK) return rc; }
+    if (pl.episodes) MATE_TRY(launch_episode_records(e, pl, io, frames, stream));
     return MATE_OK;
 }
 // One K = 1 launch of the fragment kernel over the first-row records: the rows of `src` through `columns` into `dst`, for exactly the environments whose record the restart
@@ -819,18 +818,17 @@ static int attached_behind_restart(mate_engine *e, hipStream_t stream, int fused
     const AttachedPlan pl = plan_attached(e, false, fused_team);
     if (pl.first_rows) {
         void *const obs = e->fragment.args.obs;
-        if (e->first.final_obs) { const int rc = launch_first_rows(e, pl.fragment_rows, obs, e->first.final_obs, nullptr, stream); if (rc != MATE_OK) return rc; }
-        const int rc = launch_first_rows(e, pl.fragment_rows, e->first.rows, obs, e->fragment.args.columns, stream);
-        if (rc != MATE_OK) return rc;
+        if (e->first.final_obs) MATE_TRY(launch_first_rows(e, pl.fragment_rows, obs, e->first.final_obs, nullptr, stream));
+        MATE_TRY(launch_first_rows(e, pl.fragment_rows, e->first.rows, obs, e->fragment.args.columns, stream));
     }
-    if (pl.reward) { const int rc = launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream); if (rc != MATE_OK) return rc; }
+    if (pl.reward) MATE_TRY(launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream));
     return pl.info ? launch_info(e, pl, INFO_SNAPSHOT, nullptr, nullptr, 1, stream) : MATE_OK;
 }
 // 7, 8: the LAST launches of every call that leaves new records (`rc`: what it returned so far), behind its auto-reset launch: a restarted environment's rows show the new episode
 static int attached_last(mate_engine *e, int rc, hipStream_t stream) {
     if (rc != MATE_OK) return rc;
     const AttachedPlan pl = plan_attached(e, false);
-    if (pl.action_mask) { const int rc_ = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, stream); if (rc_ != MATE_OK) return rc_; }
+    if (pl.action_mask) MATE_TRY(launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, stream));
     return pl.state ? launch_state_rows(e, pl.state_rows, e->state.dst, e->state.f64, e->state.ab, stream) : MATE_OK;
 }
 // 6 .. 8 behind reset, reset_tape and import_state: new records without a step
@@ -842,8 +840,7 @@ static int upload_state_table(mate_engine *e, void **table, const double *scale,
     const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
     if (!*table) {
         unsigned char *buf = nullptr;
-        const int rc = dev_alloc(e, &buf, (size_t)2 * S * 8);
-        if (rc != MATE_OK) return rc;
+        MATE_TRY(dev_alloc(e, &buf, (size_t)2 * S * 8));
         *table = buf;
     }
     return upload_interleaved(*table, scale, bias, (size_t)S, f64);
@@ -858,21 +855,21 @@ static int check_state_rows_args(const mate_engine *e, const void *dst, int32_t 
 }
 
 extern "C" int mate_engine_enable_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias) {
-    { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
+    MATE_TRY(check_state_rows_args(e, dst_dev, out_dtype, scale, bias));
     if (!dst_dev) { e->state.dst = nullptr; e->state.ab = nullptr; return MATE_OK; }
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_state_rows called before reset() (or import_state)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the table while it is rewritten)
     const bool f64 = out_dtype == MATE_OBS_F64;
-    if (scale) { const int rc = upload_state_table(e, &e->state.d_ab, scale, bias, f64); if (rc != MATE_OK) return rc; }
+    if (scale) MATE_TRY(upload_state_table(e, &e->state.d_ab, scale, bias, f64));
     e->state.dst = dst_dev; e->state.f64 = f64; e->state.ab = scale ? e->state.d_ab : nullptr;
     return MATE_OK;
 }
 
 extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out_dtype, const double *scale, const double *bias, void *stream) {
-    { const int rc = check_state_rows_args(e, dst_dev, out_dtype, scale, bias); if (rc != MATE_OK) return rc; }
+    MATE_TRY(check_state_rows_args(e, dst_dev, out_dtype, scale, bias));
     if (!dst_dev) return fail(MATE_EINVAL, "state_rows: null output buffer");
-    { const int rc_ = enter(e, (hipStream_t)stream, "state_rows"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream, "state_rows"));
     const bool f64 = out_dtype == MATE_OBS_F64;
     if (scale) {      // the table of the previous call is kept: the same map again costs no upload and no wait
         const int S = state_dim_of(e->p.Nc, e->p.Nt, e->p.No);
@@ -881,8 +878,7 @@ extern "C" int mate_engine_state_rows(mate_engine *e, void *dst_dev, int32_t out
         if (table.size() != e->state.demand_table.size() || std::memcmp(table.data(), e->state.demand_table.data(), table.size() * 8) != 0) {
             HIP_TRY(wait_for_launches(e));      // (an earlier on-demand launch may still read the old table)
             e->state.demand_table.clear();
-            const int rc = upload_state_table(e, &e->state.d_ab_demand, scale, bias, f64);
-            if (rc != MATE_OK) return rc;
+            MATE_TRY(upload_state_table(e, &e->state.d_ab_demand, scale, bias, f64));
             e->state.demand_table = table;
         }
     }
@@ -1013,7 +1009,7 @@ extern "C" int mate_engine_enable_fragment_rows(mate_engine *e, const mate_fragm
     FragmentRows &f = e->fragment;
     FragmentArgs a{};
     bool f64 = false, masks = false;
-    { const int rc = fragment_args_of(e, cfg, &f.d_coef, &f.d_columns, &a, &f64, &masks); if (rc != MATE_OK) return rc; }
+    MATE_TRY(fragment_args_of(e, cfg, &f.d_coef, &f.d_columns, &a, &f64, &masks));
     if (!f.on || a.team != f.args.team || !a.obs) e->first = FirstRows{};      // (first rows complete the rows of ONE team's fragment: another team, or no rows, detaches them)
     f.args = a; f.f64 = f64; f.need_masks = masks;
     f.on = true;
@@ -1052,7 +1048,7 @@ extern "C" int mate_engine_enable_episode_records(mate_engine *e, int32_t team, 
     EpisodeRecords &r = e->episodes;
     { int rc = MATE_OK; if (!r.d_sums && (rc = dev_alloc(e, &r.d_sums, (size_t)e->N * kEpisodeWords, false))) return rc; }
     mate_layout layout;
-    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    MATE_TRY(mate_engine_get_layout(e, &layout));
     EpisodeArgs a{};
     a.sums = r.d_sums; a.records = records_dev; a.count = reinterpret_cast<unsigned long long *>(count_dev);
     a.capacity = capacity; a.N = e->N; a.team = team; a.A = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
@@ -1064,7 +1060,7 @@ extern "C" int mate_engine_enable_episode_records(mate_engine *e, int32_t team, 
 }
 extern "C" int mate_engine_clear_episode_records(mate_engine *e, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, (hipStream_t)stream, "clear_episode_records"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream, "clear_episode_records"));
     note_stream(e, (hipStream_t)stream);
     return clear_episode_sums(e, (hipStream_t)stream);
 }
@@ -1080,13 +1076,13 @@ extern "C" int mate_engine_enable_info_rows(mate_engine *e, double *camera_rows_
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (!camera_rows_dev && !target_rows_dev && !cargo_rows_dev) { e->info.on = false; return MATE_OK; }
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_info_rows called before reset() (or import_state)");
-    { const int rc = check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev); if (rc != MATE_OK) return rc; }
+    MATE_TRY(check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev));
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (leaves the pipelined-restart mode; no launch reads the arguments while they change)
     InfoRows &r = e->info;
     { int rc = MATE_OK; if (!r.d_snapshot && (rc = dev_alloc(e, &r.d_snapshot, (size_t)e->N * (e->p.Nt + 1)))) return rc; }
     mate_layout layout;
-    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    MATE_TRY(mate_engine_get_layout(e, &layout));
     InfoArgs a{};
     a.snapshot = r.d_snapshot; a.cam_rows = camera_rows_dev; a.tgt_rows = target_rows_dev; a.cargo_rows = cargo_rows_dev;
     a.N = e->N; a.bit_ct = layout.bit_camera_target; a.bit_tr = layout.bit_target_row;
@@ -1099,10 +1095,10 @@ extern "C" int mate_engine_enable_info_rows(mate_engine *e, double *camera_rows_
 extern "C" int mate_engine_info_rows(mate_engine *e, const uint32_t *masks_dev, double *camera_rows_dev, double *target_rows_dev, double *cargo_rows_dev, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (!camera_rows_dev && !target_rows_dev && !cargo_rows_dev) return fail(MATE_EINVAL, "info_rows: no output buffer");
-    { const int rc = check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev); if (rc != MATE_OK) return rc; }
-    { const int rc_ = enter(e, (hipStream_t)stream, "info_rows"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(check_info_buffers(e, camera_rows_dev, target_rows_dev, cargo_rows_dev));
+    MATE_TRY(enter(e, (hipStream_t)stream, "info_rows"));
     mate_layout layout;
-    { const int rc = mate_engine_get_layout(e, &layout); if (rc != MATE_OK) return rc; }
+    MATE_TRY(mate_engine_get_layout(e, &layout));
     InfoArgs a{};
     a.mode = INFO_ON_DEMAND; a.masks = masks_dev; a.dyn = e->g.dyn;
     a.cam_rows = camera_rows_dev; a.tgt_rows = target_rows_dev; a.cargo_rows = cargo_rows_dev;
@@ -1125,11 +1121,11 @@ extern "C" int mate_engine_fragment_rows(mate_engine *e, const mate_fragment_row
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (!cfg || !rows) return fail(MATE_EINVAL, "fragment_rows: null config or buffers");
     if (frames < 1) return fail(MATE_EINVAL, "fragment_rows: frames must be at least 1");
-    { const int rc_ = enter(e, (hipStream_t)stream, "fragment_rows"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream, "fragment_rows"));
     FragmentRows &f = e->fragment;
     FragmentArgs a{};
     bool f64 = false, masks = false;
-    { const int rc = fragment_args_of(e, cfg, &f.d_coef_demand, &f.d_columns_demand, &a, &f64, &masks); if (rc != MATE_OK) return rc; }
+    MATE_TRY(fragment_args_of(e, cfg, &f.d_coef_demand, &f.d_columns_demand, &a, &f64, &masks));
     a.rows = cfg->team == MATE_TEAM_CAMERA ? rows->camera_obs_dev : rows->target_obs_dev;
     a.scalars = rows->scalars_dev; a.masks = rows->masks_dev; a.K = frames;
     if (!a.scalars || (reinterpret_cast<uintptr_t>(a.scalars) & 15u)) return fail(MATE_EINVAL, "fragment_rows: scalars_dev must be there and 16-byte aligned");
@@ -1141,12 +1137,12 @@ extern "C" int mate_engine_fragment_rows(mate_engine *e, const mate_fragment_row
 
 extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream));
     Ptrs g = e->g;
     apply_io(g, io);
     g.tape_ct = nullptr; g.tape_goal = nullptr;
     g.reset_mask = env_mask_dev;
-    { const int rc_ = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream));
     if (!env_mask_dev) {
         e->was_reset = true; e->selection.masks_stale = false;
         if (!e->dev_tick) {      // nothing is finished any more: the lists of a batched-reset interval in progress are void
@@ -1161,21 +1157,21 @@ extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, co
 extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_dev, const mate_step_io *io, const double *tape_dev,
                                       int32_t tape_len, int32_t *draws_used_dev, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream));
     if (!tape_dev || tape_len < 1) return fail(MATE_EINVAL, "reset_tape needs a tape");
     Ptrs g = e->g;
     apply_io(g, io);
     g.tape_goal = nullptr;                  // io->tape_camera_target_dev: see-through uniforms of the first view
     g.reset_mask = env_mask_dev;
     g.reset_tape = tape_dev; g.reset_tape_len = tape_len; g.reset_draws = draws_used_dev;
-    { const int rc_ = launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream));
     if (!env_mask_dev) { e->was_reset = true; e->selection.masks_stale = false; }
     return attached_behind_new_records(e, (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_rebuild_luts(mate_engine *e, void *stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream));
     return launch_reset(e, restart_ptrs(e), RESET_ALL, PH_LUT, (hipStream_t)stream);
 }
 
@@ -1208,8 +1204,7 @@ constexpr int kStepFlow = 0x10000, kRolloutFlow = 0x20000;
 static int flush_pending(mate_engine *e, int auto_reset, int flow_tag, hipStream_t stream) {
     if (e->steps_since_reset == 0 || (auto_reset > 1 ? (auto_reset | flow_tag) : auto_reset) == e->pending_interval) return MATE_OK;
     if (e->dev_tick) return fail(MATE_ESTATE, "auto_reset changed inside a reset interval while the step counter is device-resident");
-    int rc = launch_reset(e, restart_ptrs(e), RESET_FLAGGED, PH_PLACE | PH_LUT | PH_VIEW, stream);
-    if (rc != MATE_OK) return rc;
+    MATE_TRY(launch_reset(e, restart_ptrs(e), RESET_FLAGGED, PH_PLACE | PH_LUT | PH_VIEW, stream));
     HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), stream));
     e->steps_since_reset = 0; e->pending_interval = 0;
     return attached_behind_restart(e, stream);
@@ -1227,8 +1222,7 @@ static int leave_pipelined(mate_engine *e, hipStream_t stream) {
     if (e->pipe_count > 0) {         // an interval left open (restarts behind every pipe_every-th launch): what it has listed restarts now
         Ptrs r = restart_ptrs(e);
         r.pipelined = 1;
-        int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, true);
-        if (rc != MATE_OK) return rc;
+        MATE_TRY(launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, stream, true));
         HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), stream));
         e->parity ^= 1;
         e->pipe_count = 0;
@@ -1272,8 +1266,7 @@ static int pipelined_restart(mate_engine *e, hipStream_t stream) {
     Ptrs r = restart_ptrs(e);
     r.pipelined = 1;
     const bool multi_before = e->multi_stream;
-    int rc = launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, rs, true);
-    if (rc != MATE_OK) return rc;
+    MATE_TRY(launch_reset(e, r, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, rs, true));
     HIP_TRY(hipMemsetAsync(e->g.done_count + e->parity, 0, sizeof(int32_t), rs));      // (the list is consumed: the launch after next appends to it afresh)
     if (!serial) { HIP_TRY(hipEventRecord(e->ev_reset[e->parity], rs)); e->reset_in_flight[e->parity] = true; }
     // (launch_reset noted the side stream: the accessors order it through leave_pipelined's event waits, so it neither becomes
@@ -1286,11 +1279,11 @@ static int pipelined_restart(mate_engine *e, hipStream_t stream) {
 extern "C" int mate_engine_device_tick(mate_engine *e, int32_t enable, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
-    { const int rc_ = enter(e, stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, stream));
     note_stream(e, stream);
     if ((enable != 0) == e->dev_tick && (!enable || enable == e->dev_interval)) return MATE_OK;
     if (enable && e->dev_tick) return fail(MATE_ESTATE, "device_tick: already enabled with interval %d", e->dev_interval);
-    if (enable) { int rc = flush_pending(e, 0, 0, stream); if (rc != MATE_OK) return rc; }
+    if (enable) MATE_TRY(flush_pending(e, 0, 0, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (enable) {
         e->p.dev_tick = e->tick; e->p.dev_group = (uint32_t)e->parity; e->p.dev_tick_on = 1;
@@ -1354,8 +1347,7 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
     }
     r.tick_advance = how.frames * (uint32_t)auto_reset;
     const int kind = batched ? how.kind_batched : RESET_DONE;
-    const int rc = launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate);
-    if (rc != MATE_OK) return rc;
+    MATE_TRY(launch_reset(e, r, kind, how.phases, stream, batched ? how.split_batched : how.split_immediate));
     if (kind == RESET_DONE && !e->dev_tick) e->parity ^= 1;      // (the list is consumed: the next launches append to the other one)
     return attached_behind_restart(e, stream, how.fused_team);      // (new episodes: their first rows; their goals are what the next step's sparse_delivery compares with)
 }
@@ -1363,7 +1355,7 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
 // The per-step launch and what follows it, behind the state checks of the call: launch_step's, or those step_with_policies makes ahead of its agents' launch
 static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream, bool selected) {
     note_stream(e, stream);
-    if (mode != MODE_OBSERVE) { int rc = flush_pending(e, auto_reset, kStepFlow, stream); if (rc != MATE_OK) return rc; }
+    if (mode != MODE_OBSERVE) MATE_TRY(flush_pending(e, auto_reset, kStepFlow, stream));
     Ptrs g = e->g;
     apply_io(g, io);
     if (e->greedy_team_bits) g.act_f64 |= e->greedy_team_bits;          // the on-device agents' team(s): f64 joint actions
@@ -1376,7 +1368,7 @@ static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int a
     g.freeze_done = auto_reset > 1;
     if (mode == MODE_OBSERVE || auto_reset == 0) g.done_count = nullptr;
     Timed t;
-    { const int rc_ = take_timing_events(e, !e->dev_tick && mode != MODE_OBSERVE, &t); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(take_timing_events(e, !e->dev_tick && mode != MODE_OBSERVE, &t));
     const LaunchPlan pl = plan_step(e, mode, g);
     e->last_flow = pl.last_flow;
     if (pl.E > 1) { g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0; }      // (the sub-wave rollout kernel with ONE step)
@@ -1385,7 +1377,7 @@ static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int a
     e->selection.masks_stale = false;
     if (mode == MODE_OBSERVE) return MATE_OK;
     if (!e->dev_tick) e->tick += 1;
-    { const int rc_ = attached_behind_step(e, selected, io, 1, stream); if (rc_ != MATE_OK) return rc_; }      // (the finished step's rows, the terminal one included: ahead of the restart)
+    MATE_TRY(attached_behind_step(e, selected, io, 1, stream));      // (the finished step's rows, the terminal one included: ahead of the restart)
     // (the restart writes the caller's observation buffers and masks; the immediate one, idle almost always, stays ONE launch, and so
     // does the interval's unless the on-device agents play: their ~1.2 k-step episodes finish somewhere in the batch all the time)
     return restart_finished(e, auto_reset, Restart{io, true, RESET_DONE, PH_PLACE | PH_LUT | PH_VIEW, false, e->greedy_team_bits != 0, 1u, kStepFlow}, stream);
@@ -1393,9 +1385,9 @@ static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int a
 
 static int launch_step(mate_engine *e, const mate_step_io *io, int mode, int auto_reset, hipStream_t stream) {
     if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter(e, stream, "step()/observe()"); if (rc_ != MATE_OK) return rc_; }
-    if (mode != MODE_OBSERVE) { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
-    if (mode != MODE_OBSERVE) { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, stream, "step()/observe()"));
+    if (mode != MODE_OBSERVE) MATE_TRY(check_device_tick(e, auto_reset, 1, true));
+    if (mode != MODE_OBSERVE) MATE_TRY(check_attached_call(e, io, false, false));
     return step_launches(e, io, mode, auto_reset, stream, false);
 }
 
@@ -1408,12 +1400,12 @@ extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, i
 static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
-    { const int rc_ = enter(e, stream, "rollout"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, stream, "rollout"));
     if (e->dev_tick) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
-    { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(check_attached_call(e, io, false, false));
     note_stream(e, stream);
-    { int rc = flush_pending(e, auto_reset, kRolloutFlow, stream); if (rc != MATE_OK) return rc; }
+    MATE_TRY(flush_pending(e, auto_reset, kRolloutFlow, stream));
     Ptrs g = e->g;
     apply_io(g, io);
     g.mode = MODE_STEP_RANDOM; g.parity = e->parity; g.reset_kind = -1; g.tick = e->tick; g.rollout_steps = steps;
@@ -1421,14 +1413,14 @@ static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t s
     g.rotate_prio = e->sw.rollout_rotate;
     if (auto_reset != 1) g.done_count = nullptr;     // no list: nothing restarts (0), or a batched reset finds the finished ones by their flag (k > 1)
     Timed t;
-    { const int rc_ = take_timing_events(e, true, &t); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(take_timing_events(e, true, &t));
     const LaunchPlan pl = plan_rollout_random(e, g);
     e->last_flow = pl.last_flow;
     // (this flow has always gone through the extended launch, timed or not -- null events: not through launch())
     hipExtLaunchKernelGGL(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t.a, t.b, 0, (const Params *)e->d_params, (const Ptrs)g);
     HIP_TRY(hipGetLastError());
     e->tick += (uint32_t)steps;
-    { const int rc_ = attached_behind_step(e, false, io, steps, stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(attached_behind_step(e, false, io, steps, stream));
     // (state only, placement and tables: the next rollout observes the fresh episode on its first step)
     if (auto_reset >= 1) e->selection.masks_stale = true;      // (... and until then the view masks of a restarted environment are its finished episode's)
     return restart_finished(e, auto_reset, Restart{nullptr, false, RESET_FLAGGED, PH_PLACE | PH_LUT, false, false, 0u, kRolloutFlow}, stream);
@@ -1448,11 +1440,10 @@ static int policy_enable(mate_engine *e) {
     q.memory_period = 25;      // greedy.py:21
     q.noise_scale = 0.5;       // greedy.py:236
     q.lds_bytes = round_up((q.PW + policy_staging_words(p.Nc, p.Nt) + p.SW + p.DW) * 8 + p.MW * 4 + 4, 16);   // (+ one mask word of slack: seen_mask reads two)
-    int rc;
-    if ((rc = dev_alloc(e, &q.pol, (size_t)e->N * q.PW))) return rc;
-    if ((rc = dev_alloc(e, &q.cam_act, (size_t)e->N * std::max(p.Nc, 1) * 2))) return rc;
-    if ((rc = dev_alloc(e, &q.tgt_act, (size_t)e->N * p.Nt * 2))) return rc;
-    if (!e->g.own_masks && (rc = dev_alloc(e, &e->g.own_masks, (size_t)e->N * p.MW))) return rc;
+    MATE_TRY(dev_alloc(e, &q.pol, (size_t)e->N * q.PW));
+    MATE_TRY(dev_alloc(e, &q.cam_act, (size_t)e->N * std::max(p.Nc, 1) * 2));
+    MATE_TRY(dev_alloc(e, &q.tgt_act, (size_t)e->N * p.Nt * 2));
+    if (!e->g.own_masks) MATE_TRY(dev_alloc(e, &e->g.own_masks, (size_t)e->N * p.MW));
     q.masks = e->g.own_masks;
     {   // GreedyCameraAgent's zoom solve (greedy.py:139-145) as a function of K = area_product / distance^2 alone, tabulated with the
         // reference's own iteration (policy_kernels.hpp: zoom_lookup interpolates it to 1.5e-13)
@@ -1473,7 +1464,7 @@ static int policy_enable(mate_engine *e) {
             tab[(size_t)i] = b;
         }
         double *d_tab = nullptr;
-        if ((rc = dev_alloc(e, &d_tab, (size_t)n, false))) return rc;
+        MATE_TRY(dev_alloc(e, &d_tab, (size_t)n, false));
         HIP_TRY(hipMemcpy(d_tab, tab.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         q.zoom_tab = d_tab; q.zoom_inv_h = kInvH; q.zoom_n = e->sw.zoom_iterate ? 0 : n;      // 0 entries: zoom_lookup iterates
     }
@@ -1510,72 +1501,11 @@ static FusedCall fused_call(const mate_engine *e, int team_caller, const mate_st
 // step_greedy / step_versus_greedy as one launch: a complete call, and nothing that only the two-launch form serves -- MATE_POLICY_SPLIT=1,
 // recorded agent draws, tapes of the step itself, f64 observations, the Heuristic target opponent (its drift launch sits between the two),
 // the Heuristic camera opponent (its launch takes the camera agents' place), an opponent mixture whose rows come from the scripted launch,
-// a communication channel of a team whose talking agents act (greedy_channel_kernel is the agents' launch then)
-static bool one_launch_step(const mate_engine *e, const FusedCall &c, int team_caller, const mate_step_io *io, const mate_policy_tape *tape) {
-    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && !heuristic_targets(e, team_caller) && !heuristic_cameras(e, team_caller) && !scripted_plays(e, team_caller) && !channel_plays(e, team_caller);
+// a communication channel of a team whose talking agents act (greedy_channel_kernel is the agents' launch then): OpponentPlan::one_launch
+static bool one_launch_step(const mate_engine *e, const FusedCall &c, const OpponentPlan &op, const mate_step_io *io, const mate_policy_tape *tape) {
+    return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && op.one_launch;
 }
-// 2a: between the agents' launch and the stepping launch -- the Heuristic opponents' final joint action from the Greedy one (`freeze_done`: of the agents' launch)
-static int launch_drift(mate_engine *e, const AttachedPlan &pl, int freeze_done, hipStream_t stream) {
-    if (!pl.drift_rows.blocks) return MATE_OK;
-    const DriftArgs a{e->q.tgt_act, e->opponent.d_final, e->g.own_masks, e->q.noise_scale, e->p.bit_range, freeze_done};
-    HIP_TRY(launch_heuristic_drift(pl.drift_rows.blocks, pl.drift_rows.lds, stream, e->d_params, e->g, a));
-    return MATE_OK;
-}
-
-// 2b: in front of the stepping launch -- the Heuristic camera opponents' joint action, goals and memory (`freeze_done`: of the call).  Identical arguments at
-// every call but for the tapes, no allocation, no synchronisation.
-static int launch_heuristic_cameras(mate_engine *e, const mate_policy_tape *tape, int freeze_done, hipStream_t stream) {
-    CameraOpponent &o = e->camera_opponent;
-    const HeuristicCameraArgs a{o.d_mesh, o.d_grid, o.d_scores, e->g.own_masks, o.d_action, o.d_prev, o.d_goals, o.d_index, o.d_episode,
-                                tape ? tape->camera_resample_u_dev : nullptr, tape ? tape->camera_sample_u_dev : nullptr, o.permutations, o.record, freeze_done};
-    HIP_TRY(launch_heuristic_camera((unsigned)e->N, heuristic_camera_lds_bytes(e->p.Nc), stream, e->d_params, e->g, a));
-    o.ran = true;
-    return MATE_OK;
-}
-
-// 2c: behind the agents' launch, 2a and 2b, ahead of the stepping launch -- the Naive and Random agents and the mixtures' choice of the final rows, for the teams the
-// engine plays under a mixture (`freeze_done`: of the agents' launch).  Identical arguments at every call but for the team the caller plays, no allocation, no synchronisation.
-static ScriptedTeam scripted_team_args(const mate_engine *e, int team, bool plays) {
-    const ScriptedMixture &m = e->scripted.team[team];
-    ScriptedTeam t{};
-    if (!plays) return t;
-    t.on = 1; t.count = m.count; t.frame_skip = m.frame_skip; t.n = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
-    for (int i = 0; i < kScriptedKinds; ++i) { t.kinds[i] = m.kinds[i]; t.cum[i] = m.cum[i]; }
-    t.rows[SCRIPTED_GREEDY] = team == MATE_TEAM_CAMERA ? e->q.cam_act : e->q.tgt_act;
-    t.rows[SCRIPTED_HEURISTIC] = team == MATE_TEAM_CAMERA ? e->camera_opponent.d_action : e->opponent.d_final;
-    t.rows[SCRIPTED_EXTERNAL] = m.d_external;
-    t.final_act = m.d_final; t.episode = m.d_episode; t.choice = m.d_choice; t.counter = m.d_counter; t.prev_action = m.d_prev_action;
-    t.goal = m.d_goal; t.inc = m.d_inc; t.prev_location = m.d_prev_location; t.prev_noise = m.d_prev_noise;
-    return t;
-}
-static int launch_scripted(mate_engine *e, int team_caller, int freeze_done, hipStream_t stream) {
-    ScriptedArgs a{};
-    for (int team = 0; team < 2; ++team) a.team[team] = scripted_team_args(e, team, scripted_plays_team(e, team, team_caller));
-    a.tape = e->scripted.tape; a.record = e->scripted.record; a.freeze_done = freeze_done;
-    HIP_TRY(launch_scripted_opponents(blocks_of(e, kAttachedEnvsPerBlock), (size_t)attached_tile_lds_bytes(e->p.DW), stream, e->d_params, e->g, a));
-    return MATE_OK;
-}
-
-// The agents' launch of the two-launch form with a channel in it: greedy_channel_kernel for the teams `q.caller_team` lets act.  Identical arguments at every
-// call but for the team the caller plays, no allocation, no synchronisation.
-static ChannelArgs channel_args(const mate_engine *e, int team_caller) {
-    ChannelArgs a{};
-    for (int team = 0; team < 2; ++team) {
-        const Channels::Team &c = e->channel.team[team];
-        ChannelTeam &t = a.team[team];
-        t.set = c.set; t.disabled = c.disabled; t.limit = c.limit; t.rate = c.rate; t.mask = c.mask;
-        t.tape_u = c.tape_u; t.record_u = c.record_u; t.sent = c.d_sent; t.delivered = c.d_delivered;
-        if (scripted_plays_team(e, team, team_caller)) {
-            const ScriptedMixture &m = e->scripted.team[team];
-            t.mix.on = 1; t.mix.count = m.count;
-            for (int i = 0; i < kScriptedKinds; ++i) { t.mix.kinds[i] = m.kinds[i]; t.mix.cum[i] = m.cum[i]; }
-            t.mix.episode = m.d_episode; t.mix.choice = m.d_choice;
-            t.mix.tape_choice = e->scripted.tape.choice ? e->scripted.tape.choice + (int64_t)team * e->N : nullptr;
-        }
-    }
-    a.lds_bytes = e->channel.lds_bytes;
-    return a;
-}
+#include "opponent_host.inc"      // the opponents' launches, setters and accessors
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 
@@ -1585,10 +1515,11 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (!e) return fail(MATE_EINVAL, "null engine");
     // (pipelined restarts still in flight rewrite records, masks and `done` tags on the side stream: the agents' kernel of the
     // two-launch form reads all three, so the mode is left HERE, not only in launch_step behind it)
-    { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
-    if (!selected) { const int rc_ = check_attached_call(e, io, false, false); if (rc_ != MATE_OK) return rc_; }      // (ahead of the agents' launch: a rejected call leaves their memory alone; step_selected has made it)
+    MATE_TRY(leave_pipelined(e, stream));
+    if (!selected) MATE_TRY(check_attached_call(e, io, false, false));      // (ahead of the agents' launch: a rejected call leaves their memory alone; step_selected has made it)
     const FusedCall c = fused_call(e, team_caller, io);
-    if (one_launch_step(e, c, team_caller, io, tape) && plan_with_policies(e, true, team_caller).fits())
+    const OpponentPlan op = plan_opponents(e, team_caller);
+    if (one_launch_step(e, c, op, io, tape) && plan_with_policies(e, true, team_caller).fits())
         return rollout_with_policies(e, team_caller, io, 1, auto_reset, (void *)stream, true, selected);
     if (!c.reset) return fail(MATE_ESTATE, "step_greedy called before reset() (or import_state)");
     // (works with a device-resident step counter too -- the agents take their tick from the environment record -- so the
@@ -1597,23 +1528,12 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (team_caller == 0 && e->p.Nc == 0) return fail(MATE_EINVAL, "the scenario has no cameras to act for");
     if (!c.action) return fail(MATE_EINVAL, "step_versus_greedy needs the %s team's joint action", team_caller == 0 ? "camera" : "target");
     // (with the checks above, everything launch_step checks: made here, ahead of the policy launch that advances the agents' memory -- a rejected call must leave it alone)
-    { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(check_device_tick(e, auto_reset, 1, true));
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, stream);
     PolicyPtrs q = e->q;
     std::memset(&q.tape, 0, sizeof(q.tape));
-    q.caller_team = team_caller;      // (the agents of the caller's team do not act: greedy_policy_body)
-    const bool hcams = heuristic_cameras(e, team_caller);
-    if (hcams) q.caller_team = MATE_TEAM_CAMERA;      // the Greedy camera agents do not act either: step_greedy runs the Greedy (or Heuristic) targets alone,
-    bool agents = !(hcams && team_caller == MATE_TEAM_TARGET);      // ... and with the targets the caller's nobody of the Greedy pair acts: no agents' launch
-    const bool mix_c = scripted_plays_team(e, MATE_TEAM_CAMERA, team_caller), mix_t = scripted_plays_team(e, MATE_TEAM_TARGET, team_caller);
-    if (mix_c || mix_t) {      // under a mixture a team's Greedy agents act where a candidate with positive weight needs their row (the Heuristic targets build on it)
-        const ScriptedMixture &mc = e->scripted.team[MATE_TEAM_CAMERA], &mt = e->scripted.team[MATE_TEAM_TARGET];
-        const bool need_c = team_caller != MATE_TEAM_CAMERA && (mix_c ? mc.has[MATE_SCRIPTED_GREEDY] : !hcams);
-        const bool need_t = team_caller != MATE_TEAM_TARGET && (mix_t ? (mt.has[MATE_SCRIPTED_GREEDY] || mt.has[MATE_SCRIPTED_HEURISTIC]) : true);
-        agents = need_c || need_t;
-        q.caller_team = need_c && need_t ? -1 : (need_c ? MATE_TEAM_TARGET : MATE_TEAM_CAMERA);
-    }
+    q.caller_team = op.caller_team;      // (the agents of that team do not act: greedy_policy_body)
     if (tape) {
         q.tape.cam_binom_u = tape->camera_resample_u_dev; q.tape.cam_sample_u = tape->camera_sample_u_dev;
         q.tape.cam_delay = tape->camera_delay_dev; q.tape.tgt_choice_u = tape->target_choice_u_dev;
@@ -1623,24 +1543,22 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     const unsigned blocks = (unsigned)((e->N + 3) / 4);
     Ptrs gp = e->g;
     gp.freeze_done = auto_reset > 1;
-    if (agents && channel_plays(e, team_caller)) {      // the channel inside the agents' `communicate` phase (channel_rows.hpp)
-        HIP_TRY(launch_greedy_channel(e->p.obs_f64 != 0, blocks, 4 * (size_t)e->channel.lds_bytes, stream, e->d_params, gp, q, channel_args(e, team_caller)));
-    } else if (agents) {
+    // the launches in the order of the plan's fields: the agents', the Heuristic cameras', the drift, the scripted one; then whose rows the step consumes
+    if (op.channel_kernel) {      // the channel inside the agents' `communicate` phase (channel_rows.hpp)
+        HIP_TRY(launch_greedy_channel(e->p.obs_f64 != 0, blocks, 4 * (size_t)e->channel.lds_bytes, stream, e->d_params, gp, q, channel_args(e, op)));
+    } else if (op.agents) {
         launch(e->k.policy, dim3(blocks), dim3(256), 4 * q.lds_bytes + 1024, stream, Timed{}, e->d_params, gp, q);   // + the shared zoom-solve exchange
         HIP_TRY(hipGetLastError());
     }
-    if (hcams) { const int rc_ = launch_heuristic_cameras(e, tape, gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
-    e->camera_opponent.acted = hcams;
-    const bool drift = heuristic_targets(e, team_caller);      // (the caller plays the targets: no opponent of that team acts)
-    if (drift) { const int rc_ = launch_drift(e, plan_attached(e, selected), gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
-    e->opponent.drifted = drift;
-    if (mix_c || mix_t) { const int rc_ = launch_scripted(e, team_caller, gp.freeze_done, stream); if (rc_ != MATE_OK) return rc_; }
-    e->scripted.team[MATE_TEAM_CAMERA].acted = mix_c; e->scripted.team[MATE_TEAM_TARGET].acted = mix_t;
+    if (op.team[MATE_TEAM_CAMERA].heuristic) MATE_TRY(launch_heuristic_cameras(e, tape, gp.freeze_done, stream));
+    if (op.team[MATE_TEAM_TARGET].heuristic) MATE_TRY(launch_drift(e, op, gp.freeze_done, stream));
+    if (op.team[MATE_TEAM_CAMERA].scripted || op.team[MATE_TEAM_TARGET].scripted) MATE_TRY(launch_scripted(e, op, gp.freeze_done, stream));
     mate_step_io io2;
     if (io) io2 = *io; else std::memset(&io2, 0, sizeof(io2));
     // the caller's team keeps its own pointer and encoding (f32 / f64 / grid indices); the agents' joint action is f64 pairs
-    if (team_caller != 0) { io2.camera_actions_dev = mix_c ? e->scripted.team[MATE_TEAM_CAMERA].d_final : hcams ? e->camera_opponent.d_action : q.cam_act; io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
-    if (team_caller != 1) { io2.target_actions_dev = mix_t ? e->scripted.team[MATE_TEAM_TARGET].d_final : drift ? e->opponent.d_final : q.tgt_act; io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
+    if (team_caller != MATE_TEAM_CAMERA) { io2.camera_actions_dev = rows_of(e, MATE_TEAM_CAMERA, op.team[MATE_TEAM_CAMERA].source); io2.act_dtype &= ~MATE_ACT_CAMERA_DISCRETE; }
+    if (team_caller != MATE_TEAM_TARGET) { io2.target_actions_dev = rows_of(e, MATE_TEAM_TARGET, op.team[MATE_TEAM_TARGET].source); io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
+    for (int team = 0; team < 2; ++team) e->opponents.consumed[team] = op.team[team].source;
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
     const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
     e->greedy_team_bits = 0;
@@ -1671,10 +1589,9 @@ extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const 
     if (!e->was_reset) return fail(MATE_ESTATE, "enable_selection called before reset() (or import_state)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(wait_for_launches(e));      // (no launch reads the arguments while they change)
-    int rc = MATE_OK;
-    if (!e->selection.d_actions && (rc = dev_alloc(e, &e->selection.d_actions, (size_t)e->N * e->p.Nc * 2))) return rc;
+    if (!e->selection.d_actions) MATE_TRY(dev_alloc(e, &e->selection.d_actions, (size_t)e->N * e->p.Nc * 2));
     mate_layout layout;
-    if ((rc = mate_engine_get_layout(e, &layout))) return rc;
+    MATE_TRY(mate_engine_get_layout(e, &layout));
     SelectionArgs a{};
     a.selection = selection_dev; a.actions = e->selection.d_actions;
     a.metrics = metrics_dev; a.frames = frames_dev; a.action_mask = action_mask_dev;
@@ -1685,7 +1602,7 @@ extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const 
     const AttachedPlan pl = plan_attached(e, false);
     if (!pl.action_mask) return MATE_OK;
     // action_mask() of the observation rows as they are, complete when the call returns (the caller need not know the stream)
-    if ((rc = launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, e->last_stream))) return rc;
+    MATE_TRY(launch_selection(e, pl, SELECTION_ACTION_MASK, nullptr, e->last_stream));
     HIP_TRY(hipStreamSynchronize(e->last_stream));
     return MATE_OK;
 }
@@ -1706,15 +1623,15 @@ extern "C" int mate_engine_selection_actions(mate_engine *e, void **actions_dev,
 extern "C" int mate_engine_step_selected(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
-    { const int rc_ = check_attached_call(e, io, false, true, auto_reset); if (rc_ != MATE_OK) return rc_; }
-    { const int rc_ = check_device_tick(e, auto_reset, 1, true); if (rc_ != MATE_OK) return rc_; }      // (a rejected call launches nothing)
+    MATE_TRY(check_attached_call(e, io, false, true, auto_reset));
+    MATE_TRY(check_device_tick(e, auto_reset, 1, true));      // (a rejected call launches nothing)
     // the state checks of the stepping flows and what they enqueue ahead of their launch, all AHEAD of the executor: a rejected call
     // leaves the action buffer alone; pipelined restarts in flight are joined before the executor reads the mask words; an open
     // reset interval of another flow restarts what it finished before the executor looks at it
-    { const int rc_ = enter(e, stream, "step_selected"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, stream, "step_selected"));
     if (!e->policy_ready) return fail(MATE_ESTATE, "step_selected: call mate_engine_policy_enable() before the reset whose observations the policies act on");
     note_stream(e, stream);
-    { const int rc_ = flush_pending(e, auto_reset, kStepFlow, stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(flush_pending(e, auto_reset, kStepFlow, stream));
     mate_step_io io2 = *io;
     io2.camera_actions_dev = e->selection.d_actions;
     io2.act_dtype = (io->act_dtype & ~(0xff | MATE_ACT_CAMERA_DISCRETE)) | (e->selection.act_f64 ? MATE_ACT_F64 : MATE_ACT_F32);
@@ -1738,6 +1655,16 @@ struct PolicyFlow {
                                  // FrameSkip in a HIP graph; the auto-reset launch behind every auto_reset-th launch advances the counter by auto_reset * K
 };
 
+// The fused K-frame launches hold the Greedy agents and deliver every message: the one refusal the opponents of the call give (OpponentPlan::refusal), `who` refusing
+static int refuse_fused(const OpponentPlan &op, const char *who) {
+    const char *team = op.refusal == FUSED_OK ? "" : kTeamNames[op.refusal_team];
+    switch (op.refusal) {
+    case FUSED_MIXTURE: return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the %s team plays an opponent mixture (mate_engine_set_opponent_mixture): step per frame, or clear the mixture", who, team);
+    case FUSED_CHANNEL: return fail(MATE_ESTATE, "%s: the fused launches deliver every message, a communication channel is set for the %s team (mate_engine_set_channel): step per frame, or clear the channel", who, team);
+    case FUSED_HEURISTIC: return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the %s opponent is the heuristic one (mate_engine_set_%s_opponent): step per frame, or select MATE_OPPONENT_GREEDY", who, team, team);
+    default: return MATE_OK;
+    }
+}
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step, bool selected) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     const FusedCall c = fused_call(e, team_caller, io);
@@ -1746,21 +1673,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
                                      : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow, team_caller}, auto_reset == 1 || pipelined, true, team_caller >= 0};
     if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
-    for (int team = 0; team < 2; ++team)        // (a per-step call never arrives here with it: one_launch_step)
-        if (team_caller != team && (team == MATE_TEAM_TARGET || e->p.Nc > 0) && !e->scripted.team[team].only_greedy())
-            return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the %s team plays an opponent mixture (mate_engine_set_opponent_mixture): step per frame, or clear the mixture",
-                        team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy", team == MATE_TEAM_CAMERA ? "camera" : "target");
-    if (channel_plays(e, team_caller))
-        return fail(MATE_ESTATE, "%s: the fused launches deliver every message, a communication channel is set for the %s team (mate_engine_set_channel): step per frame, or clear the channel",
-                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy", channel_plays_team(e, MATE_TEAM_CAMERA, team_caller) ? "camera" : "target");
-    if (heuristic_targets(e, team_caller))
-        return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the target opponent is the heuristic one (mate_engine_set_target_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
-                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
-    if (heuristic_cameras(e, team_caller))
-        return fail(MATE_ESTATE, "%s: the fused launches hold the Greedy agents, the camera opponent is the heuristic one (mate_engine_set_camera_opponent): step per frame, or select MATE_OPPONENT_GREEDY",
-                    team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy");
+    MATE_TRY(refuse_fused(plan_opponents(e, team_caller), team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy"));      // (a per-step call never arrives here with one: one_launch_step)
     if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
-    { const int rc_ = check_device_tick(e, auto_reset, steps, false); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(check_device_tick(e, auto_reset, steps, false));
     if (!c.ready) return fail(MATE_ESTATE, "call mate_engine_policy_enable() before the reset whose observations the policies act on");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
     hipStream_t stream = (hipStream_t)stream_;
@@ -1768,11 +1683,11 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     if (auto_reset < -(1 << 16)) return fail(MATE_EINVAL, "auto_reset = %d: pipelined restarts every -auto_reset launches take 1 .. 65536", auto_reset);
     const int pipe_every = pipelined ? -auto_reset : 1;
     if (pipelined && (!flow.may_pipeline || e->dev_tick)) return fail(MATE_EINVAL, "pipelined restarts (auto_reset = MATE_RESET_PIPELINED) belong to the fused rollouts");
-    if (!per_step) { const int rc_ = check_attached_call(e, io, pipelined, false, 0, team_caller); if (rc_ != MATE_OK) return rc_; }      // (per_step: step_with_policies has made it)
-    if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) { const int rc_ = leave_pipelined(e, stream); if (rc_ != MATE_OK) return rc_; }
+    if (!per_step) MATE_TRY(check_attached_call(e, io, pipelined, false, 0, team_caller));      // (per_step: step_with_policies has made it)
+    if (!pipelined || (e->pipelined && e->pipe_every != pipe_every)) MATE_TRY(leave_pipelined(e, stream));
     note_stream(e, stream);
-    { int rc = flush_pending(e, auto_reset, flow.restart.flow_tag, stream); if (rc != MATE_OK) return rc; }
-    if (pipelined) { const int rc_ = enter_pipelined(e, pipe_every, stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(flush_pending(e, auto_reset, flow.restart.flow_tag, stream));
+    if (pipelined) MATE_TRY(enter_pipelined(e, pipe_every, stream));
     Ptrs g = e->g;
     apply_io(g, io);
     g.pipelined = pipelined ? 1 : 0;
@@ -1797,16 +1712,14 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     std::memset(&q.tape, 0, sizeof(q.tape));
     q.caller_team = team_caller;
     Timed t;
-    { const int rc_ = take_timing_events(e, !e->dev_tick, &t); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(take_timing_events(e, !e->dev_tick, &t));
     e->last_flow = pl.last_flow;
-    e->opponent.drifted = false;      // (the target team's joint action of this launch is in q.tgt_act: the Greedy agents', or the caller's)
-    e->camera_opponent.acted = false;
-    e->scripted.team[MATE_TEAM_CAMERA].acted = e->scripted.team[MATE_TEAM_TARGET].acted = false;
+    e->opponents.consumed[MATE_TEAM_CAMERA] = e->opponents.consumed[MATE_TEAM_TARGET] = ROWS_GREEDY;      // (the joint actions of this launch are in q.cam_act / q.tgt_act: the Greedy agents', or the caller's)
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
     if (!e->dev_tick) e->tick += (uint32_t)steps;
-    { const int rc_ = attached_behind_step(e, selected, io, steps, stream, per_step ? -1 : team_caller); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(attached_behind_step(e, selected, io, steps, stream, per_step ? -1 : team_caller));
     return pipelined ? pipelined_restart(e, stream) : restart_finished(e, auto_reset, flow.restart, stream);
 }
 
@@ -1819,15 +1732,17 @@ extern "C" int mate_engine_rollout_versus_greedy(mate_engine *e, int32_t team, c
     return attached_last(e, rollout_with_policies(e, team, io, steps, auto_reset, stream), (hipStream_t)stream);
 }
 
-// Copy the joint actions the last mate_engine_step_greedy produced into caller buffers ([N][Nc][2], [N][Nt][2] f64).
+// Copy the joint actions the last mate_engine_step_greedy produced into caller buffers ([N][Nc][2], [N][Nt][2] f64): what that call's stepping launch
+// read, and so until the NEXT stepping call -- a setter in between (opponent, mixture, channel) does not change what is reported.
 extern "C" int mate_engine_policy_actions(mate_engine *e, double *camera_actions_dev, double *target_actions_dev, void *stream) {
     if (!e || !e->policy_ready) return fail(MATE_ESTATE, "policies are not enabled");
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, (hipStream_t)stream);
-    if (camera_actions_dev && e->p.Nc > 0)
-        HIP_TRY(hipMemcpyAsync(camera_actions_dev, e->scripted.team[MATE_TEAM_CAMERA].acted ? e->scripted.team[MATE_TEAM_CAMERA].d_final : e->camera_opponent.acted ? e->camera_opponent.d_action : e->q.cam_act, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (target_actions_dev)      // what the step consumed: behind a call that ran the drift launch, its output
-        HIP_TRY(hipMemcpyAsync(target_actions_dev, e->scripted.team[MATE_TEAM_TARGET].acted ? e->scripted.team[MATE_TEAM_TARGET].d_final : e->opponent.drifted ? e->opponent.d_final : e->q.tgt_act, sizeof(double) * 2 * e->p.Nt * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    double *const dst[2] = {e->p.Nc > 0 ? camera_actions_dev : nullptr, target_actions_dev};
+    for (int team = 0; team < 2; ++team) {      // what the last call's step consumed (the caller's own rows are not the engine's to report: the Greedy buffer then, as ever)
+        const double *src = rows_of(e, team, e->opponents.consumed[team]);
+        if (dst[team]) HIP_TRY(hipMemcpyAsync(dst[team], src ? src : rows_of(e, team, ROWS_GREEDY), sizeof(double) * 2 * agents_of(e, team) * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
     return MATE_OK;
 }
 extern "C" int mate_engine_policy_greedy_target_actions(mate_engine *e, double *target_actions_dev, void *stream) {
@@ -1839,321 +1754,13 @@ extern "C" int mate_engine_policy_greedy_target_actions(mate_engine *e, double *
     return MATE_OK;
 }
 
-// The Heuristic camera opponent (include/mate_engine.h, csrc/opponent_rows.hpp): tables, tapes, selection, goals.
-extern "C" int mate_engine_heuristic_camera_tables(mate_engine *e, const double *state_mesh, const double *coord_grid, const double *scores) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (!state_mesh || !coord_grid || !scores) return fail(MATE_EINVAL, "heuristic_camera_tables: null table");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the tables while they change)
-    CameraOpponent &o = e->camera_opponent;
-    if (!o.d_scores) {
-        int rc;
-        if ((rc = dev_alloc(e, &o.d_mesh, (size_t)kHcStates * 3, false))) return rc;
-        if ((rc = dev_alloc(e, &o.d_grid, (size_t)kHcPoints * 2, false))) return rc;
-        if ((rc = dev_alloc(e, &o.d_scores, (size_t)kHcPoints * kHcStates, false))) { return rc; }
-    }
-    HIP_TRY(hipMemcpy(o.d_mesh, state_mesh, sizeof(double) * kHcStates * 3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(o.d_grid, coord_grid, sizeof(double) * kHcPoints * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(o.d_scores, scores, sizeof(double) * (size_t)kHcPoints * kHcStates, hipMemcpyHostToDevice));
-    return MATE_OK;
-}
-extern "C" int mate_engine_heuristic_camera_tape(mate_engine *e, const int8_t *permutations_dev, int8_t *record_dev) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
-    e->camera_opponent.permutations = permutations_dev; e->camera_opponent.record = record_dev;
-    return MATE_OK;
-}
-extern "C" int mate_engine_heuristic_camera_goals(mate_engine *e, double *goals_dev, int32_t *indices_dev, void *stream) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    const CameraOpponent &o = e->camera_opponent;
-    if (!o.d_goals) return fail(MATE_ESTATE, "heuristic_camera_goals: the heuristic camera opponent has not been selected (mate_engine_set_camera_opponent)");
-    HIP_TRY(hipSetDevice(e->device));
-    note_stream(e, (hipStream_t)stream);
-    if (goals_dev) HIP_TRY(hipMemcpyAsync(goals_dev, o.d_goals, sizeof(double) * 2 * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (indices_dev) HIP_TRY(hipMemcpyAsync(indices_dev, o.d_index, sizeof(int32_t) * e->p.Nc * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return MATE_OK;
-}
-static int set_camera_opponent(mate_engine *e, int32_t opponent);
-extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (e->scripted.team[MATE_TEAM_CAMERA].installed)
-        return fail(MATE_ESTATE, "set_camera_opponent: an opponent mixture is installed for the camera team (mate_engine_set_opponent_mixture): clear it first (count = 0)");
-    if (opponent == MATE_OPPONENT_HEURISTIC && e->channel.team[MATE_TEAM_CAMERA].set)
-        return fail(MATE_ESTATE, "set_camera_opponent: a communication channel is set for the camera team (mate_engine_set_channel), and the heuristic camera agent's fallback for a lost response is not on the device: clear the channel first");
-    return set_camera_opponent(e, opponent);
-}
-static int set_camera_opponent(mate_engine *e, int32_t opponent) {
-    if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_camera_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
-    if (!e->policy_ready) return fail(MATE_ESTATE, "set_camera_opponent: call mate_engine_policy_enable() first (the Greedy agents of the other team, and the engine's own view masks)");
-    CameraOpponent &o = e->camera_opponent;
-    const int Nc = e->p.Nc;
-    if (opponent == MATE_OPPONENT_HEURISTIC && e->cam_mode != 0)
-        return fail(MATE_EINVAL, "set_camera_opponent: the heuristic camera opponent senses the targets of its plain rows, the camera team's observation mode is %d (mate_engine_set_obs_mode)", e->cam_mode);
-    if (opponent == MATE_OPPONENT_HEURISTIC && Nc > 0 && !o.d_scores)
-        return fail(MATE_ESTATE, "set_camera_opponent: install the heuristic camera tables first (mate_engine_heuristic_camera_tables)");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the buffers the getters switch between)
-    if (opponent == o.kind) return MATE_OK;
-    if (Nc == 0) { o.kind = opponent; return MATE_OK; }      // (nobody to play: a no-op, heuristic_cameras)
-    if (opponent == MATE_OPPONENT_HEURISTIC) {
-        if (!o.d_action) {
-            const size_t pairs = (size_t)e->N * Nc * 2;
-            int rc;
-            if ((rc = dev_alloc(e, &o.d_prev, pairs))) return rc;
-            if ((rc = dev_alloc(e, &o.d_goals, pairs))) return rc;
-            if ((rc = dev_alloc(e, &o.d_index, (size_t)e->N * Nc))) return rc;
-            if ((rc = dev_alloc(e, &o.d_episode, (size_t)e->N))) return rc;
-            const hipError_t err = set_dynamic_lds(heuristic_camera_function(), heuristic_camera_lds_bytes(Nc));
-            if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
-            if ((rc = dev_alloc(e, &o.d_action, pairs))) return rc;      // (last: its presence says all of the above is there)
-        }
-        // the agents start afresh: prev_action (0, 0), and their reset at the first acting call whatever the episode
-        HIP_TRY(hipMemset(o.d_prev, 0, sizeof(double) * 2 * Nc * (size_t)e->N));
-        HIP_TRY(hipMemset(o.d_episode, 0xff, sizeof(int32_t) * (size_t)e->N));
-        o.ran = false;
-    } else if (o.ran) {
-        // the Greedy camera agents sat out while the Heuristic ones played: their reset at their next acting call (PolCtx::cam_episode <- -1)
-        const size_t offset = sizeof(double) * ((size_t)e->q.TW + 2 * (size_t)Nc * e->p.Nt + 2 * (size_t)Nc) + sizeof(int32_t) * ((size_t)Nc * e->p.Nt + 2 * (size_t)Nc * Nc + Nc);
-        HIP_TRY(hipMemset2D(reinterpret_cast<unsigned char *>(e->q.pol) + offset, sizeof(double) * (size_t)e->q.PW, 0xff, sizeof(int32_t), (size_t)e->N));
-    }
-    o.kind = opponent; o.acted = false;
-    return MATE_OK;
-}
-
-// Which scripted agent plays the target team where the engine plays it (include/mate_engine.h).  No agent memory differs between the two, so the
-// switch is a flag and, once, the final-action buffer.
-static int set_target_opponent(mate_engine *e, int32_t opponent);
-extern "C" int mate_engine_set_target_opponent(mate_engine *e, int32_t opponent) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (e->scripted.team[MATE_TEAM_TARGET].installed)
-        return fail(MATE_ESTATE, "set_target_opponent: an opponent mixture is installed for the target team (mate_engine_set_opponent_mixture): clear it first (count = 0)");
-    return set_target_opponent(e, opponent);
-}
-static int set_target_opponent(mate_engine *e, int32_t opponent) {
-    if (opponent != MATE_OPPONENT_GREEDY && opponent != MATE_OPPONENT_HEURISTIC) return fail(MATE_EINVAL, "set_target_opponent: the opponent must be MATE_OPPONENT_GREEDY or MATE_OPPONENT_HEURISTIC");
-    if (!e->policy_ready) return fail(MATE_ESTATE, "set_target_opponent: call mate_engine_policy_enable() first (the Greedy agents the heuristic opponent builds on, and the engine's own view masks)");
-    if (opponent == MATE_OPPONENT_HEURISTIC && e->tgt_mode != 0)
-        return fail(MATE_EINVAL, "set_target_opponent: the heuristic target opponent senses the cameras of its plain rows, the target team's observation mode is %d (mate_engine_set_obs_mode)", e->tgt_mode);
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the buffer the getters switch between)
-    if (opponent == MATE_OPPONENT_HEURISTIC && !e->opponent.d_final) {
-        const int rc = dev_alloc(e, &e->opponent.d_final, (size_t)e->N * e->p.Nt * 2);
-        if (rc != MATE_OK) return rc;
-    }
-    e->opponent.kind = opponent;
-    return MATE_OK;
-}
-
-// The opponent mixtures (include/mate_engine.h, csrc/scripted_rows.hpp): install / clear, draws, memory, the external rows.
-// The Greedy agents of `team` run their agent.reset at their next acting call (PolCtx::cam_episode / tgt_episode <- -1): they may have sat out under a mixture.
-static int mark_greedy_reset(mate_engine *e, int team) {
-    const size_t Nc = (size_t)e->p.Nc, Nt = (size_t)e->p.Nt;
-    const size_t offset = team == MATE_TEAM_CAMERA ? sizeof(double) * ((size_t)e->q.TW + 2 * Nc * Nt + 2 * Nc) + sizeof(int32_t) * (Nc * Nt + 2 * Nc * Nc + Nc)
-                                                   : sizeof(double) * 4 * Nt + sizeof(int32_t) * 3 * Nt;
-    HIP_TRY(hipMemset2D(reinterpret_cast<unsigned char *>(e->q.pol) + offset, sizeof(double) * (size_t)e->q.PW, 0xff, sizeof(int32_t), (size_t)e->N));
-    return MATE_OK;
-}
-extern "C" int mate_engine_set_opponent_mixture(mate_engine *e, int32_t team, const int32_t *kinds, const double *weights, int32_t count, int32_t random_frame_skip) {
-    static const char *const names[2] = {"camera", "target"};
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "set_opponent_mixture: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    if (count < 0 || count > kScriptedKinds || (count > 0 && !kinds)) return fail(MATE_EINVAL, "set_opponent_mixture: the %s mixture takes 0 .. %d candidates (got %d) and their kinds", names[team], kScriptedKinds, count);
-    // every check ahead of every change: a refused call leaves the engine as it was
-    ScriptedMixture next;
-    double total = 0.0;
-    for (int i = 0; i < count; ++i) {
-        const int kind = kinds[i];
-        const double w = weights ? weights[i] : 1.0;
-        if (kind < 0 || kind >= kScriptedKinds) return fail(MATE_EINVAL, "set_opponent_mixture: candidate %d of the %s mixture has the unknown kind %d (MATE_SCRIPTED_*)", i, names[team], kind);
-        for (int k = 0; k < i; ++k) if (kinds[k] == kind) return fail(MATE_EINVAL, "set_opponent_mixture: kind %d appears twice in the %s mixture", kind, names[team]);
-        if (!std::isfinite(w) || w < 0.0) return fail(MATE_EINVAL, "set_opponent_mixture: weight %d of the %s mixture is negative or not finite", i, names[team]);
-        total += w;
-    }
-    if (count > 0 && !(total > 0.0)) return fail(MATE_EINVAL, "set_opponent_mixture: every weight of the %s mixture is zero", names[team]);
-    if (random_frame_skip < 1) return fail(MATE_EINVAL, "set_opponent_mixture: random_frame_skip of the %s mixture must be at least 1 (got %d)", names[team], random_frame_skip);
-    double running = 0.0;
-    for (int i = 0; i < count; ++i) {      // the candidates with positive weight in the order given (mixture.py:41-43): p = w / sum, cum = cumsum(p)
-        const double w = weights ? weights[i] : 1.0;
-        if (!(w > 0.0)) continue;
-        running += w / total;
-        next.kinds[next.count] = kinds[i]; next.cum[next.count] = running; next.has[kinds[i]] = true; ++next.count;
-    }
-    if (!e->policy_ready) return fail(MATE_ESTATE, "set_opponent_mixture (%s team): call mate_engine_policy_enable() first (the Greedy agents, and the engine's own view masks)", names[team]);
-    const int mode = team == MATE_TEAM_CAMERA ? e->cam_mode : e->tgt_mode;
-    if (next.has[MATE_SCRIPTED_HEURISTIC] && mode != 0)
-        return fail(MATE_EINVAL, "set_opponent_mixture: the Heuristic candidate of the %s mixture senses the opponents of its plain rows, the team's observation mode is %d (mate_engine_set_obs_mode)", names[team], mode);
-    if (next.has[MATE_SCRIPTED_HEURISTIC] && team == MATE_TEAM_CAMERA && e->p.Nc > 0 && !e->camera_opponent.d_scores)
-        return fail(MATE_ESTATE, "set_opponent_mixture: the camera mixture has a Heuristic candidate: install the heuristic camera tables first (mate_engine_heuristic_camera_tables)");
-    if (next.has[MATE_SCRIPTED_HEURISTIC] && team == MATE_TEAM_CAMERA && e->channel.team[MATE_TEAM_CAMERA].set)
-        return fail(MATE_ESTATE, "set_opponent_mixture: the camera mixture has a Heuristic candidate and a communication channel is set for the camera team (mate_engine_set_channel): clear the channel first");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads what changes below)
-    ScriptedMixture &m = e->scripted.team[team];
-    const int n = team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt;
-    const int plain_now = team == MATE_TEAM_CAMERA ? e->camera_opponent.kind : e->opponent.kind;
-    const int restore = m.installed ? m.restore : plain_now;
-    auto set_plain = [&](int kind) { return team == MATE_TEAM_CAMERA ? set_camera_opponent(e, kind) : set_target_opponent(e, kind); };
-    if (count == 0) {                      // clear: the plain selection the mixture replaced; Greedy agents that sat out start afresh
-        if (!m.installed) return MATE_OK;
-        const bool launched = m.launch;
-        { const int rc_ = set_plain(restore); if (rc_ != MATE_OK) return rc_; }
-        m.installed = m.launch = m.acted = false; m.count = 0;
-        for (bool &h : m.has) h = false;
-        return launched ? mark_greedy_reset(e, team) : MATE_OK;
-    }
-    next.launch = n > 0 && !(next.count == 1 && (next.kinds[0] == MATE_SCRIPTED_GREEDY || next.kinds[0] == MATE_SCRIPTED_HEURISTIC));
-    if (next.launch && !m.d_final) {       // the memory of scripted_opponent_kernel, once
-        const size_t pairs = (size_t)e->N * n * 2;
-        int rc;
-        if ((rc = dev_alloc(e, &m.d_external, pairs))) return rc;
-        if ((rc = dev_alloc(e, &m.d_prev_action, pairs))) return rc;
-        if ((rc = dev_alloc(e, &m.d_episode, (size_t)e->N))) return rc;
-        if ((rc = dev_alloc(e, &m.d_choice, (size_t)e->N))) return rc;
-        if ((rc = dev_alloc(e, &m.d_counter, (size_t)e->N))) return rc;
-        if (team == MATE_TEAM_TARGET) {
-            if ((rc = dev_alloc(e, &m.d_prev_location, pairs))) return rc;
-            if ((rc = dev_alloc(e, &m.d_prev_noise, pairs))) return rc;
-            if ((rc = dev_alloc(e, &m.d_goal, (size_t)e->N * n))) return rc;
-            if ((rc = dev_alloc(e, &m.d_inc, (size_t)e->N * n))) return rc;
-        }
-        if ((rc = dev_alloc(e, &m.d_final, pairs))) return rc;      // (last: its presence says all of the above is there)
-    }
-    // the Heuristic machinery of the team is on exactly where a candidate needs it (heuristic_targets / heuristic_cameras read the plain selection)
-    { const int rc_ = set_plain(next.has[MATE_SCRIPTED_HEURISTIC] ? MATE_OPPONENT_HEURISTIC : MATE_OPPONENT_GREEDY); if (rc_ != MATE_OK) return rc_; }
-    // Greedy agents that sat out under the old mixture and act under the new one (as a candidate, or as the plain selection) start afresh, as the
-    // reference's new mixture agent resets the candidate it draws
-    auto runs_greedy = [&](const ScriptedMixture &x) { return !x.launch || x.has[MATE_SCRIPTED_GREEDY] || (team == MATE_TEAM_TARGET && x.has[MATE_SCRIPTED_HEURISTIC]); };
-    if (m.launch && !runs_greedy(m) && runs_greedy(next)) { const int rc_ = mark_greedy_reset(e, team); if (rc_ != MATE_OK) return rc_; }
-    if (next.launch) {                     // the team's reset, the draw included, at its next acting call whatever the episode
-        HIP_TRY(hipMemset(m.d_episode, 0xff, sizeof(int32_t) * (size_t)e->N));
-        HIP_TRY(hipMemset(m.d_choice, 0xff, sizeof(int32_t) * (size_t)e->N));
-    }
-    m.installed = true; m.launch = next.launch; m.acted = false; m.restore = restore; m.frame_skip = random_frame_skip;
-    m.count = next.count;
-    for (int i = 0; i < kScriptedKinds; ++i) { m.kinds[i] = next.kinds[i]; m.cum[i] = next.cum[i]; m.has[i] = next.has[i]; }
-    return MATE_OK;
-}
-// The communication channels (include/mate_engine.h, csrc/channel_rows.hpp): settings, draws, edge matrices.
-static int channel_buffers(mate_engine *e) {      // the edge matrices of both teams and the kernel's LDS, once
-    Channels &c = e->channel;
-    if (c.lds_bytes) return MATE_OK;
-    const int lds = round_up(e->q.lds_bytes + channel_staging_bytes(e->p.Nc, e->p.Nt), 16);
-    if (4 * (size_t)lds > kLdsCeiling) return fail(MATE_EINVAL, "set_channel: %zu bytes of LDS per workgroup do not fit", 4 * (size_t)lds);
-    int rc;
-    for (int team = 0; team < 2; ++team) {
-        const size_t n = (size_t)(team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt);
-        if (!c.team[team].d_sent && (rc = dev_alloc(e, &c.team[team].d_sent, (size_t)e->N * n * n))) return rc;
-        if (!c.team[team].d_delivered && (rc = dev_alloc(e, &c.team[team].d_delivered, (size_t)e->N * n * n))) return rc;
-    }
-    for (int f64 = 0; f64 < 2; ++f64) {
-        const hipError_t err = set_dynamic_lds(greedy_channel_function(f64 != 0), 4 * (size_t)lds);
-        if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
-    }
-    c.lds_bytes = lds;
-    return MATE_OK;
-}
-extern "C" int mate_engine_set_channel(mate_engine *e, int32_t team, const mate_channel *cfg) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "set_channel: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    if (cfg && (!std::isfinite(cfg->dropout_rate) || cfg->dropout_rate < 0.0 || cfg->dropout_rate > 1.0))
-        return fail(MATE_EINVAL, "set_channel: the dropout rate must lie in [0, 1] (got %g)", cfg->dropout_rate);
-    if (cfg && std::isnan(cfg->range_limit)) return fail(MATE_EINVAL, "set_channel: the range limit is NaN (negative or +inf: no limit)");
-    if (!e->policy_ready) return fail(MATE_ESTATE, "set_channel: call mate_engine_policy_enable() first (the agents whose messages the channel carries)");
-    if (cfg && team == MATE_TEAM_CAMERA) {
-        const ScriptedMixture &m = e->scripted.team[MATE_TEAM_CAMERA];
-        if (e->camera_opponent.kind == MATE_OPPONENT_HEURISTIC || m.has[MATE_SCRIPTED_HEURISTIC] || (m.installed && m.restore == MATE_OPPONENT_HEURISTIC))
-            return fail(MATE_ESTATE, "set_channel: the heuristic camera agent plays (or is a candidate of) the camera team, and its fallback for a lost response is not on the device: select MATE_OPPONENT_GREEDY first");
-    }
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }      // (no launch in flight reads the settings)
-    { const int rc_ = channel_buffers(e); if (rc_ != MATE_OK) return rc_; }
-    Channels::Team &c = e->channel.team[team];
-    if (!cfg) { c.set = false; c.disabled = false; c.limit = -1.0; c.rate = 0.0; c.mask = nullptr; return MATE_OK; }
-    c.set = true; c.disabled = cfg->disabled != 0;
-    c.limit = (cfg->range_limit < 0.0 || std::isinf(cfg->range_limit)) ? -1.0 : cfg->range_limit;
-    c.rate = cfg->dropout_rate; c.mask = cfg->mask_dev;
-    return MATE_OK;
-}
-extern "C" int mate_engine_channel_tape(mate_engine *e, const double *camera_u_dev, const double *target_u_dev, double *record_camera_u_dev, double *record_target_u_dev) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if ((reinterpret_cast<uintptr_t>(camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(record_camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(record_target_u_dev) & 7u))
-        return fail(MATE_EINVAL, "channel_tape: a buffer is not aligned to its element size");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
-    e->channel.team[MATE_TEAM_CAMERA].tape_u = camera_u_dev; e->channel.team[MATE_TEAM_TARGET].tape_u = target_u_dev;
-    e->channel.team[MATE_TEAM_CAMERA].record_u = record_camera_u_dev; e->channel.team[MATE_TEAM_TARGET].record_u = record_target_u_dev;
-    return MATE_OK;
-}
-extern "C" int mate_engine_channel_edges(mate_engine *e, int32_t team, int8_t **sent_dev, int8_t **delivered_dev) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "channel_edges: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    if (!e->policy_ready) return fail(MATE_ESTATE, "channel_edges: call mate_engine_policy_enable() first");
-    if (!e->channel.lds_bytes) {
-        { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
-        { const int rc_ = channel_buffers(e); if (rc_ != MATE_OK) return rc_; }
-    }
-    if (sent_dev) *sent_dev = e->channel.team[team].d_sent;
-    if (delivered_dev) *delivered_dev = e->channel.team[team].d_delivered;
-    return MATE_OK;
-}
-extern "C" int mate_engine_scripted_tape(mate_engine *e, const double *camera_u_dev, const double *target_u_dev, const double *target_reset_dev, const int32_t *choice_dev,
-                                         double *record_camera_u_dev, double *record_target_u_dev, double *record_target_reset_dev, int32_t *record_choice_dev) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if ((reinterpret_cast<uintptr_t>(record_camera_u_dev) & 15u) || (reinterpret_cast<uintptr_t>(record_target_reset_dev) & 15u))
-        return fail(MATE_EINVAL, "scripted_tape: record_camera_u_dev and record_target_reset_dev must be aligned to 16 bytes (the launch stores pairs of doubles)");
-    if ((reinterpret_cast<uintptr_t>(camera_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(target_reset_dev) & 7u) ||
-        (reinterpret_cast<uintptr_t>(record_target_u_dev) & 7u) || (reinterpret_cast<uintptr_t>(choice_dev) & 3u) || (reinterpret_cast<uintptr_t>(record_choice_dev) & 3u))
-        return fail(MATE_EINVAL, "scripted_tape: a buffer is not aligned to its element size");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
-    // (ScriptedDraws is one type for both: the launch only ever reads through `tape`)
-    e->scripted.tape = ScriptedDraws{const_cast<double *>(camera_u_dev), const_cast<double *>(target_u_dev), const_cast<double *>(target_reset_dev), const_cast<int32_t *>(choice_dev)};
-    e->scripted.record = ScriptedDraws{record_camera_u_dev, record_target_u_dev, record_target_reset_dev, record_choice_dev};
-    return MATE_OK;
-}
-extern "C" int mate_engine_scripted_memory(mate_engine *e, int32_t team, int32_t *choice_dev, int32_t *goal_dev, int32_t *inc_dev, double *prev_noise_dev, double *prev_action_dev,
-                                           int32_t *counter_dev, void *stream_) {
-    if (!e) return fail(MATE_EINVAL, "null engine");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_memory: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    const ScriptedMixture &m = e->scripted.team[team];
-    if (!m.d_final) return fail(MATE_ESTATE, "scripted_memory: no opponent mixture with a launch of its own has been installed for the team (mate_engine_set_opponent_mixture)");
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(e->device));
-    note_stream(e, stream);
-    const size_t N = (size_t)e->N, n = (size_t)(team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt);
-    if (choice_dev) HIP_TRY(hipMemcpyAsync(choice_dev, m.d_choice, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, stream));
-    if (counter_dev) HIP_TRY(hipMemcpyAsync(counter_dev, m.d_counter, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, stream));
-    if (prev_action_dev) HIP_TRY(hipMemcpyAsync(prev_action_dev, m.d_prev_action, sizeof(double) * 2 * n * N, hipMemcpyDeviceToDevice, stream));
-    if (team == MATE_TEAM_TARGET) {
-        if (goal_dev) HIP_TRY(hipMemcpyAsync(goal_dev, m.d_goal, sizeof(int32_t) * n * N, hipMemcpyDeviceToDevice, stream));
-        if (inc_dev) HIP_TRY(hipMemcpyAsync(inc_dev, m.d_inc, sizeof(int32_t) * n * N, hipMemcpyDeviceToDevice, stream));
-        if (prev_noise_dev) HIP_TRY(hipMemcpyAsync(prev_noise_dev, m.d_prev_noise, sizeof(double) * 2 * n * N, hipMemcpyDeviceToDevice, stream));
-    }
-    return MATE_OK;
-}
-extern "C" int mate_engine_scripted_external(mate_engine *e, int32_t team, double **rows_dev) {
-    if (!e || !rows_dev) return fail(MATE_EINVAL, "null argument");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_external: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    if (!e->scripted.team[team].d_final) return fail(MATE_ESTATE, "scripted_external: no opponent mixture with a launch of its own has been installed for the team (mate_engine_set_opponent_mixture)");
-    *rows_dev = e->scripted.team[team].d_external;
-    return MATE_OK;
-}
-extern "C" int mate_engine_scripted_rows(mate_engine *e, int32_t team, int32_t kind, double *rows_dev, void *stream) {
-    if (!e || !rows_dev) return fail(MATE_EINVAL, "null argument");
-    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "scripted_rows: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    if (kind != MATE_SCRIPTED_GREEDY && kind != MATE_SCRIPTED_HEURISTIC && kind != MATE_SCRIPTED_EXTERNAL)
-        return fail(MATE_EINVAL, "scripted_rows: the sources are MATE_SCRIPTED_GREEDY, _HEURISTIC and _EXTERNAL (the Naive and Random rows exist as final rows only)");
-    if (!e->policy_ready) return fail(MATE_ESTATE, "scripted_rows: policies are not enabled");
-    const ScriptedTeam t = scripted_team_args(e, team, true);
-    const double *src = t.rows[kind];
-    if (!src || (kind == MATE_SCRIPTED_HEURISTIC && !e->scripted.team[team].has[MATE_SCRIPTED_HEURISTIC]))
-        return fail(MATE_ESTATE, "scripted_rows: the team's mixture (mate_engine_set_opponent_mixture) has no such source");
-    HIP_TRY(hipSetDevice(e->device));
-    note_stream(e, (hipStream_t)stream);
-    HIP_TRY(hipMemcpyAsync(rows_dev, src, sizeof(double) * 2 * (size_t)t.n * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return MATE_OK;
-}
-
 extern "C" int mate_engine_observe(mate_engine *e, const mate_step_io *io, void *stream) {
     return attached_last(e, launch_step(e, io, MODE_OBSERVE, 0, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *stream) {
     if (!e || !dst_dev) return fail(MATE_EINVAL, "null argument");
-    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream));
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(export_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, dst_dev);
     HIP_TRY(hipGetLastError());
@@ -2163,11 +1770,11 @@ extern "C" int mate_engine_export_state(mate_engine *e, double *dst_dev, void *s
 extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, void *stream) {
     if (!e || !src_dev) return fail(MATE_EINVAL, "null argument");
     if (e->dev_tick) return fail(MATE_ESTATE, "import_state while the step counter is device-resident (mate_engine_device_tick)");
-    { const int rc_ = enter(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream));
     note_stream(e, (hipStream_t)stream);
     hipLaunchKernelGGL(import_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, src_dev);
     HIP_TRY(hipGetLastError());
-    { const int rc_ = clear_episode_sums(e, (hipStream_t)stream); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(clear_episode_sums(e, (hipStream_t)stream));
     // all environments step together, so they share one tick: adopt the imported one
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     int32_t tick = 0;
@@ -2181,7 +1788,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
 static int lut_read_from(mate_engine *e, const double2 *knots_dev, const int32_t *counts_dev, int kmax, const char *who,
                          int64_t env, int32_t camera, double *phis, double *rhos, int32_t capacity, int32_t *count) {
     if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "%s: index out of range", who);
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     const int64_t lc = env * e->p.Nc + camera;
     int32_t n = 0;
     HIP_TRY(hipMemcpy(&n, counts_dev + lc, sizeof(n), hipMemcpyDeviceToHost));
@@ -2197,7 +1804,7 @@ static int lut_write_to(mate_engine *e, double2 *knots_dev, int32_t *counts_dev,
                         int64_t env, int32_t camera, const double *phis, const double *rhos, int32_t n) {
     if (env < 0 || env >= e->N || camera < 0 || camera >= e->p.Nc) return fail(MATE_EINVAL, "%s: index out of range", who);
     if (n < 2 || n > kmax) return fail(MATE_EINVAL, "%s: %d knots do not fit (capacity %d)", who, n, kmax);
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     std::vector<double2> knots((size_t)n);
     for (int i = 0; i < n; ++i) { knots[i].x = phis[i]; knots[i].y = rhos[i]; }
     const int64_t lc = env * e->p.Nc + camera;
@@ -2224,7 +1831,7 @@ extern "C" int mate_engine_enable_outer_boundary(mate_engine *e, int32_t *capaci
     const Params &p = e->p;
     if (p.Nc == 0) return fail(MATE_EINVAL, "no cameras in this scenario");
     if (e->g.lut_knots_outer) { if (capacity) *capacity = e->g.kmax_outer; return MATE_OK; }
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     // 360 + per obstacle (arc <= 181 rays + two 21-point flanks) rays are sorted in LDS
     const int rays = 360 + p.No * (181 + 42) + 1;
     ResetLds rl = e->rl;
@@ -2262,7 +1869,7 @@ extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_d
     if (e->p.Nc == 0) return fail(MATE_EINVAL, "no cameras in this scenario");
     if (e->p.Nt > kAuxMaxTargets) return fail(MATE_EINVAL, "soft_coverage: at most %d targets", kAuxMaxTargets);
     if (!e->g.lut_knots_outer) return fail(MATE_ESTATE, "outer boundary not enabled (mate_engine_enable_outer_boundary)");
-    { const int rc_ = enter(e, (hipStream_t)stream, "soft_coverage"); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter(e, (hipStream_t)stream, "soft_coverage"));
     note_stream(e, (hipStream_t)stream);
     launch_soft_coverage(e, plan_soft_coverage(e), masks_dev, matrix_dev, scores_dev, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -2271,7 +1878,7 @@ extern "C" int mate_engine_soft_coverage(mate_engine *e, const uint32_t *masks_d
 
 extern "C" int mate_engine_lut_write(mate_engine *e, int64_t env, int32_t camera, const double *phis, const double *rhos, int32_t n) {
     if (!e || !phis || !rhos) return fail(MATE_EINVAL, "null argument");
-    { const int rc_ = lut_write_to(e, e->g.lut_knots, e->g.lut_count, e->p.kmax, "lut_write", env, camera, phis, rhos, n); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(lut_write_to(e, e->g.lut_knots, e->g.lut_count, e->p.kmax, "lut_write", env, camera, phis, rhos, n));
     // the inner table's indices: built on the host, as the device builder in reset_kernels.hpp builds them
     std::vector<uint16_t> bucket((size_t)e->p.nbucket, 0);
     // per-degree index: bucket[d] = last knot with angle <= d - 180 (exact integer knots exist in real tables)
@@ -2343,7 +1950,7 @@ extern "C" int mate_engine_debug_skip(mate_engine *e, int32_t mask) {
 // Total number of (environment, step) slots spent idle waiting for a batched reset (auto_reset > 1) since creation.
 extern "C" int mate_engine_idle_steps(mate_engine *e, int64_t *total) {
     if (!e || !total) return fail(MATE_EINVAL, "null argument");
-    { const int rc_ = enter_host(e); if (rc_ != MATE_OK) return rc_; }
+    MATE_TRY(enter_host(e));
     std::vector<int32_t> host((size_t)e->N);
     HIP_TRY(hipMemcpy(host.data(), e->g.idle_steps, sizeof(int32_t) * host.size(), hipMemcpyDeviceToHost));
     int64_t sum = 0;

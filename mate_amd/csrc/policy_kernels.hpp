@@ -61,6 +61,12 @@ __host__ __device__ constexpr int pol_target_words(int Nt) { return 4 * Nt + (po
 __host__ __device__ constexpr int pol_camera_ints(int Nc, int Nt) { return Nc * Nt + 2 * Nc * Nc + Nc + 1; }
 __host__ __device__ constexpr int pol_camera_words(int Nc, int Nt) { return 2 * Nc * Nt + 2 * Nc + (pol_camera_ints(Nc, Nt) + 1) / 2; }
 __host__ __device__ constexpr int pol_record_words(int Nc, int Nt) { return pol_target_words(Nt) + pol_camera_words(Nc, Nt); }
+// Byte offset of a team's `episode` inside one environment's record, for the host (it marks agents that sat out for their reset: -1 there): the last
+// integer of the team's section, which PolCtx finds behind the section's doubles (ti: 4 * Nt of them; ci: pol_target_words, then 2 * Nc * Nt + 2 * Nc)
+__host__ __device__ constexpr size_t pol_episode_offset(bool camera, int Nc, int Nt) {
+    return camera ? sizeof(double) * (size_t)(pol_target_words(Nt) + 2 * Nc * Nt + 2 * Nc) + sizeof(int32_t) * (size_t)(pol_camera_ints(Nc, Nt) - 1)
+                  : sizeof(double) * (size_t)(4 * Nt) + sizeof(int32_t) * (size_t)(pol_target_ints(Nt) - 1);
+}
 
 template <typename ObsT>
 struct PolCtx {

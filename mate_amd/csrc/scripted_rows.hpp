@@ -1,5 +1,5 @@
 // scripted_rows.hpp -- the scripted agent families beyond the Greedy and Heuristic pairs, and the per-episode MIXTURE over all of them, as ONE launch
-// ("2c" of the written order, engine_host.h): scripted_opponent_kernel, behind the agents' launch, the Heuristic cameras' launch and the drift launch,
+// (OpponentPlan::team[].scripted, engine_host.h): scripted_opponent_kernel, behind the agents' launch, the Heuristic cameras' launch and the drift launch,
 // ahead of the stepping launch.  Per environment and per team the engine plays it (1) runs the team's reset, the mixture draw included, at the team's first
 // acting call of an episode, (2) computes the Naive or Random agents' action where the episode's choice asks for it, (3) writes the team's FINAL joint action --
 // one of five sources -- into an engine-owned [N][n][2] f64 buffer the stepping launch reads, (4) fills the record of the draws it used.

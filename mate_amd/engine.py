@@ -657,6 +657,21 @@ class Engine:
         if camera_agent != 'greedy' or self.camera_agent != 'greedy':
             self.set_camera_opponent(camera_agent)
 
+    def _install_camera_tables(self):
+        """The Heuristic camera agents' three tables (heuristic_tables.py), built and installed once per engine; a scenario without cameras needs none."""
+        if self.num_cameras == 0 or self._camera_tables_installed:
+            return
+        from mate_amd.heuristic_tables import heuristic_camera_tables
+        camera = scenario_tables(self.config)['camera']
+        tables = heuristic_camera_tables(camera['max_sight_range'], camera['min_viewing_angle'])
+        check(self.lib.mate_engine_heuristic_camera_tables(self._h, *(table.ctypes.data_as(ctypes.c_void_p) for table in tables)))
+        self._camera_tables_installed = True
+
+    def _check_tensor(self, what, value, dtype, shape, named=None):
+        """None, or a contiguous `dtype` tensor of `shape` on the engine's device (`named`: the type's word in the message; default: its short name)."""
+        if value is not None and (value.dtype != dtype or tuple(value.shape) != tuple(shape) or not value.is_contiguous() or value.device != self.device):
+            raise ValueError(f"{what} must be a contiguous {named or str(dtype).split('.')[-1]} tensor of shape {tuple(shape)} on {self.device}")
+
     def set_camera_opponent(self, camera_agent):
         """'greedy' (GreedyCameraAgent, the default) or 'heuristic' (HeuristicCameraAgent, mate/agents/heuristic.py:17-287: a central
         controller scores 756 poses per camera against the sensed targets in range, tries 32 orders of greedy assignment and hands
@@ -667,12 +682,8 @@ class Engine:
         without cameras is unaffected."""
         if camera_agent not in CAMERA_AGENTS:
             raise ValueError(f"camera_agent must be one of {CAMERA_AGENTS}, got {camera_agent!r}")
-        if camera_agent == 'heuristic' and self.num_cameras > 0 and not self._camera_tables_installed:
-            from mate_amd.heuristic_tables import heuristic_camera_tables
-            camera = scenario_tables(self.config)['camera']
-            mesh, grid, scores = heuristic_camera_tables(camera['max_sight_range'], camera['min_viewing_angle'])
-            check(self.lib.mate_engine_heuristic_camera_tables(self._h, *(table.ctypes.data_as(ctypes.c_void_p) for table in (mesh, grid, scores))))
-            self._camera_tables_installed = True
+        if camera_agent == 'heuristic':
+            self._install_camera_tables()
         check(self.lib.mate_engine_set_camera_opponent(self._h, CAMERA_AGENTS.index(camera_agent)))
         self.camera_agent = camera_agent
 
@@ -681,8 +692,7 @@ class Engine:
         tensor of that shape that receives the permutations every launch used (None: nothing is stored).  Both hold until replaced."""
         shape = (self.num_envs, 32, self.num_cameras)
         for name, value in (('permutations', permutations), ('record', record)):
-            if value is not None and (value.dtype != torch.int8 or tuple(value.shape) != shape or not value.is_contiguous() or value.device != self.device):
-                raise ValueError(f'{name} must be a contiguous int8 tensor of shape {shape} on {self.device}')
+            self._check_tensor(name, value, torch.int8, shape)
         check(self.lib.mate_engine_heuristic_camera_tape(self._h, None if permutations is None else ctypes.c_void_p(permutations.data_ptr()),
                                                          None if record is None else ctypes.c_void_p(record.data_ptr())))
         self._camera_tape = (permutations, record)
@@ -718,32 +728,22 @@ class Engine:
         team = _team_code(team)
         kinds, weights = mixture_table(candidates, weights, random_frame_skip)
         names = [SCRIPTED_AGENTS[k] for k, w in zip(kinds, weights) if w > 0.0]
-        if 'heuristic' in names and team == 0 and self.num_cameras > 0 and not self._camera_tables_installed:
-            from mate_amd.heuristic_tables import heuristic_camera_tables
-            camera = scenario_tables(self.config)['camera']
-            mesh, grid, scores = heuristic_camera_tables(camera['max_sight_range'], camera['min_viewing_angle'])
-            check(self.lib.mate_engine_heuristic_camera_tables(self._h, *(table.ctypes.data_as(ctypes.c_void_p) for table in (mesh, grid, scores))))
-            self._camera_tables_installed = True
+        if 'heuristic' in names and team == 0:
+            self._install_camera_tables()
         check(self.lib.mate_engine_set_opponent_mixture(self._h, team, (ctypes.c_int32 * len(kinds))(*kinds), (ctypes.c_double * len(kinds))(*weights),
                                                         len(kinds), int(random_frame_skip)))
         if self.mixtures[team] is None:
             self._plain_agents[team] = self.camera_agent if team == 0 else self.target_agent
         self.mixtures[team] = {SCRIPTED_AGENTS[k]: w for k, w in zip(kinds, weights) if w > 0.0}
         plain = 'heuristic' if 'heuristic' in names else 'greedy'      # (the Heuristic machinery of the team is on where a candidate needs it)
-        if team == 0:
-            self.camera_agent = plain
-        else:
-            self.target_agent = plain
+        setattr(self, ('camera_agent', 'target_agent')[team], plain)
 
     def clear_opponent_mixture(self, team):
         """Remove the team's mixture: the plain selection it replaced plays again (its Greedy agents reset at their next acting call)."""
         team = _team_code(team)
         check(self.lib.mate_engine_set_opponent_mixture(self._h, team, None, None, 0, 20))
         if self.mixtures[team] is not None:
-            if team == 0:
-                self.camera_agent = self._plain_agents[team]
-            else:
-                self.target_agent = self._plain_agents[team]
+            setattr(self, ('camera_agent', 'target_agent')[team], self._plain_agents[team])
         self.mixtures[team] = None
 
     def _scripted_shapes(self):
@@ -763,8 +763,7 @@ class Engine:
         for which, given in (('tape', tape), ('record', record)):
             for name, shape, dtype in self._scripted_shapes():
                 value = None if given is None else given.get(name)
-                if value is not None and (value.dtype != dtype or tuple(value.shape) != shape or not value.is_contiguous() or value.device != self.device):
-                    raise ValueError(f'{which}[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
+                self._check_tensor(f'{which}[{name!r}]', value, dtype, shape, named=str(dtype))
                 pointers.append(None if value is None else ctypes.c_void_p(value.data_ptr()))
         check(self.lib.mate_engine_scripted_tape(self._h, *pointers))
         self._scripted_tape = (tape, record)
@@ -816,8 +815,7 @@ class Engine:
         team = _team_code(team)
         limit, rate = channel_settings(range_limit, dropout_rate)
         n = (self.num_cameras, self.num_targets)[team]
-        if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (self.num_envs, n, n) or not mask.is_contiguous() or mask.device != self.device):
-            raise ValueError(f'mask must be a contiguous uint8 tensor of shape {(self.num_envs, n, n)} on {self.device}')
+        self._check_tensor('mask', mask, torch.uint8, (self.num_envs, n, n))
         cfg = MateChannel(int(bool(disabled)), limit, rate, None if mask is None else mask.data_ptr())
         check(self.lib.mate_engine_set_channel(self._h, team, ctypes.byref(cfg)))
         self.channels[team] = {'disabled': bool(disabled), 'range_limit': None if limit < 0 else limit, 'dropout_rate': rate, 'mask': mask}
@@ -834,8 +832,7 @@ class Engine:
         until replaced.  Returns (record_camera_u, record_target_u), or None."""
         N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
         for name, value, n in (('camera_u', camera_u, Nc), ('target_u', target_u, Nt)):
-            if value is not None and (value.dtype != torch.float64 or tuple(value.shape) != (N, n, n) or not value.is_contiguous() or value.device != self.device):
-                raise ValueError(f'{name} must be a contiguous float64 tensor of shape {(N, n, n)} on {self.device}')
+            self._check_tensor(name, value, torch.float64, (N, n, n))
         records = None
         if record:
             records = tuple(torch.full((N, n, n), float('nan'), dtype=torch.float64, device=self.device) for n in (Nc, Nt))
@@ -896,7 +893,8 @@ class Engine:
 
     def policy_actions(self, greedy_targets=False):
         """(camera_actions [N,Nc,2], target_actions [N,Nt,2]) f64: the joint actions of the last step_greedy, as the step consumed
-        them -- with the heuristic target opponent the final target actions.  greedy_targets=True: a third tensor, the Greedy
+        them -- with the heuristic target opponent the final target actions -- and until the next stepping call: a setter in between
+        (set_*_opponent, set_opponent_mixture, set_channel) does not change what is reported.  greedy_targets=True: a third tensor, the Greedy
         target agents' joint action of the same step ahead of the drift (equal to the second while the opponent is 'greedy')."""
         N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
         cam = torch.zeros((N, Nc, 2), dtype=torch.float64, device=self.device)

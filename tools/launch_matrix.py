@@ -10,6 +10,11 @@ python tools/launch_matrix.py attached [<shape>]      the ATTACHED column set: e
 attached launches (state rows, reward rows, target selection), and the calls the engine refuses, each on an engine of its own;
 `attached --record PATH` writes the record (status, error text, SHA-256 of every attached output and of export_state() per call) as JSON:
 the record of two builds of the library (MATE_ENGINE_LIB) must be the same bytes.
+python tools/launch_matrix.py opponents               the OPPONENTS column set: every per-step and fused call with the on-device agents under the opponent
+selections, mixtures and channels the setters can reach (one engine per shape, reconfigured between states), and the setters' refusals; per call the
+status, the error text, the flow, which buffer policy_actions() equals and whether the channel edges changed (tests/golden/opponent_flows.json);
+`opponents --golden PATH --commit ID` writes that file; `opponents --record PATH` adds the SHA-256 of every output, of policy_actions, scripted_memory, the channel edges and export_state(): the same bytes
+from two builds of the library.
 python tools/launch_matrix.py host-cost [<batch>]     microseconds of host time and per graph-replayed step of step_versus_greedy and
 step_selected with all three attached (default: 4096 environments of MATE-4v8-9)."""
 import hashlib
@@ -286,6 +291,249 @@ def attached_main(argv):
     print('done', sum(len(ATTACHED) * len(ATTACHED_CALLS) + len(REFUSED) for _ in shapes), 'calls')
 
 
+# ---- the opponents column set
+# Who plays each team of a call, which launches that takes and whose rows the step consumes (csrc/engine_host.h: plan_opponents), over the states the
+# setters can reach: ONE engine per shape, reconfigured between states, direct calls only.
+OPPONENT_SHAPES = ('MATE-4v8-9', '0v5-3', 'MATE-2v4-0 sub_wave')      # (no cameras: every camera selection is a no-op; set_sub_wave(True): the sub-wave one-launch step)
+OPPONENT_BATCH = 8
+TEAMS = ('camera', 'target')
+# a team's plain selection, or the candidates of its mixture
+TEAM_STATES = ('greedy', 'heuristic', ('greedy',), ('naive',), ('random', 'greedy'), ('heuristic', 'external'), ('greedy', 'heuristic', 'naive', 'random', 'external'))
+CHANNEL_STATES = ((), ('camera',), ('target',), ('camera', 'target'))
+CHANNEL = {'dropout_rate': 0.5, 'range_limit': 500.0}
+OPPONENT_AUTO_RESETS = (1, 3)
+OPPONENT_CALLS = [(name, k) for k in OPPONENT_AUTO_RESETS for name in ('step_greedy', 'step_versus_greedy_camera', 'step_versus_greedy_target', 'step_selected',
+                                                                       'rollout_greedy', 'rollout_versus_greedy_camera', 'rollout_versus_greedy_target')]
+# the setter refusals, each pair of calls in both orders: (id, the calls in order); a scenario starts from the plain Greedy state and a step_greedy follows it
+_PAIRS = ([('channel / heuristic cameras', ('set_channel', 'camera'), ('set_opponent', 'camera', 'heuristic')),
+           ('channel / heuristic camera candidate', ('set_channel', 'camera'), ('set_mixture', 'camera', ('heuristic', 'external')))] +
+          [pair for team in TEAMS for pair in (('%s mixture / setter' % team, ('set_mixture', team, ('naive',)), ('set_opponent', team, 'heuristic')),
+                                               ('%s observation mode / heuristic' % team, ('set_obs_mode', team, 'enhanced'), ('set_opponent', team, 'heuristic')),
+                                               ('%s observation mode / heuristic candidate' % team, ('set_obs_mode', team, 'shared'), ('set_mixture', team, ('heuristic', 'external'))))])
+REFUSALS = ([(what + ', in this order', (a, b)) for what, a, b in _PAIRS] + [(what + ', in the other order', (b, a)) for what, a, b in _PAIRS] +
+            [('channel under a mixture that replaced the heuristic cameras', (('set_opponent', 'camera', 'heuristic'), ('set_mixture', 'camera', ('naive',)), ('set_channel', 'camera')))])
+
+
+def opponent_states(shape):
+    """(camera state, target state, channels) indices: the whole product (196 states of 14 calls: about a second on an MI355X)"""
+    if shape.endswith('sub_wave'):      # the plain Greedy states only
+        return [(0, 0, ch) for ch in range(len(CHANNEL_STATES))]
+    return [(c, t, ch) for c in range(len(TEAM_STATES)) for t in range(len(TEAM_STATES)) for ch in range(len(CHANNEL_STATES))]
+
+
+def opponent_engine(shape):
+    name, _, sub = shape.partition(' ')
+    eng = Engine(config_of(name), OPPONENT_BATCH, seed=11, first_env_index=2)
+    if sub:
+        eng.set_sub_wave(True)
+    eng.enable_policies()
+    eng.reset()
+    eng.reserve_rollout(ROLLOUT_STEPS, want_masks=True, search='none')
+    try:      # (refused without cameras: step_selected then reports it call by call)
+        selection = torch.randint(0, 1 << eng.num_targets, (eng.num_envs, eng.num_cameras), generator=torch.Generator().manual_seed(5))
+        eng.enable_selection(multi_selection=True, selection=selection.to(dtype=torch.int32, device=eng.device))
+    except EngineError:
+        pass
+    return eng
+
+
+def attempt(fn, *args, **kwargs):
+    """[error code, error text] of one call"""
+    try:
+        fn(*args, **kwargs)
+    except EngineError as err:
+        return [err.code, str(err)]
+    return [0, '']
+
+
+def setter(eng, what, team, value=None):
+    if what == 'set_channel':
+        return attempt(eng.set_channel, team, **CHANNEL)
+    if what == 'set_mixture':
+        status = attempt(eng.set_opponent_mixture, team, value)
+        if status[0] == 0 and 'external' in value and (eng.num_cameras, eng.num_targets)[TEAMS.index(team)] > 0:
+            rows = eng.external_actions(team)      # the caller's rows: the same at every call
+            rows.copy_(torch.linspace(-1.0, 1.0, rows.numel(), dtype=torch.float64).reshape(rows.shape) * (2.0 if team == 'camera' else 15.0))
+        return status
+    if what == 'set_obs_mode':
+        return attempt(eng.set_obs_mode, **{team: value})
+    assert what == 'set_opponent', what
+    return attempt(eng.set_camera_opponent if team == 'camera' else eng.set_target_opponent, value)
+
+
+def plain_greedy(eng):
+    """Back to the state behind enable_policies(): no mixture, no channel, Greedy agents, plain rows."""
+    for team in TEAMS:
+        eng.clear_opponent_mixture(team)
+        eng.clear_channel(team)
+    eng.set_camera_opponent('greedy')
+    eng.set_target_opponent('greedy')
+    eng.set_obs_mode()
+
+
+def configure(eng, state):
+    """The state from the plain Greedy one: the opponents, then the channels.  Returns [error code, text] of every setter (a channel of the camera team
+    is refused where the heuristic camera agent plays or could play it: the state then goes without)."""
+    plain_greedy(eng)
+    statuses = []
+    for team, index in zip(TEAMS, state[:2]):
+        what = TEAM_STATES[index]
+        if what != 'greedy':
+            statuses.append(setter(eng, 'set_mixture' if isinstance(what, tuple) else 'set_opponent', team, what))
+    return statuses + [setter(eng, 'set_channel', team) for team in CHANNEL_STATES[state[2]]]
+
+
+def same_bytes(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+def consumed(eng, name, acts):
+    """Per team, which buffers policy_actions() equals bit for bit behind the call: the scripted_rows kinds, policy_actions(greedy_targets=True)
+    ('greedy_targets'), the caller's joint action ('caller'), or ['none'] (['empty']: the team has nobody)."""
+    got = eng.policy_actions(greedy_targets=True)
+    out = []
+    for team, name_of in enumerate(TEAMS):
+        if got[team].numel() == 0:
+            out.append(['empty'])
+            continue
+        sources = {}
+        for kind in ('greedy', 'heuristic', 'external'):
+            try:
+                sources[kind] = eng.scripted_rows(name_of, kind)
+            except EngineError:
+                pass
+        if team == 1:
+            sources['greedy_targets'] = got[2]
+        if name.endswith('_' + name_of):
+            sources['caller'] = acts[team].to(torch.float64)
+        elif name == 'step_selected' and team == 0 and getattr(eng, 'selection_actions', None) is not None:
+            sources['caller'] = eng.selection_actions.to(torch.float64)
+        out.append(sorted(kind for kind, rows in sources.items() if same_bytes(rows, got[team])) or ['none'])
+    return out
+
+
+def opponent_row(eng, name, k, acts, full=False):
+    """[error code, error text, last_flow, consumed(), whether each team's channel_edges changed]; `full`: + the SHA-256 of every output, of
+    policy_actions, of scripted_memory, of the channel edges and of export_state()"""
+    edges = [matrix for team in TEAMS for matrix in eng.channel_edges(team)]
+    before = [matrix.clone() for matrix in edges]
+    code, text, out = 0, '', None
+    try:
+        out = issue_attached(eng, name, k, acts)
+    except EngineError as err:
+        code, text = err.code, str(err)
+    changed = [not same_bytes(x, y) for x, y in zip(before, edges)]
+    row = [code, text, eng.last_flow, consumed(eng, name, acts), [changed[0] or changed[1], changed[2] or changed[3]]]
+    if full:
+        memory = {}
+        for team in TEAMS:
+            try:
+                memory[team] = {key: digest(value) for key, value in eng.scripted_memory(team).items()}
+            except EngineError as err:
+                memory[team] = err.code
+        row.append({'outputs': [digest(t) for t in out or ()], 'policy_actions': [digest(t) for t in eng.policy_actions(greedy_targets=True)],
+                    'scripted_memory': memory, 'channel_edges': [digest(matrix) for matrix in edges], 'state': digest(eng.export_state())})
+    return row
+
+
+def opponents_record(shape, full=False):
+    """{'states': {state id: {'setters': configure(), 'calls': [opponent_row of every call of OPPONENT_CALLS]}},
+        'refusals': {id: {'setters': [[error code, text] of each call of the scenario], 'step_greedy': opponent_row behind it}}}"""
+    eng = opponent_engine(shape)
+    acts = actions_of(eng)
+    record = {'states': {}, 'refusals': {}}
+    for state in opponent_states(shape):
+        label = 'camera %s | target %s | channels %s' % ('+'.join(TEAM_STATES[state[0]]) if isinstance(TEAM_STATES[state[0]], tuple) else 'plain ' + TEAM_STATES[state[0]],
+                                                         '+'.join(TEAM_STATES[state[1]]) if isinstance(TEAM_STATES[state[1]], tuple) else 'plain ' + TEAM_STATES[state[1]],
+                                                         '+'.join(CHANNEL_STATES[state[2]]) or 'none')
+        setters = configure(eng, state)
+        record['states'][label] = {'setters': setters, 'calls': [opponent_row(eng, name, k, acts, full) for name, k in OPPONENT_CALLS]}
+    if not shape.endswith('sub_wave'):
+        for what, calls in REFUSALS:
+            plain_greedy(eng)
+            setters = [setter(eng, *call) for call in calls]
+            record['refusals'][what] = {'setters': setters, 'step_greedy': opponent_row(eng, 'step_greedy', 1, acts, full)}
+    plain_greedy(eng)
+    torch.cuda.synchronize()
+    eng.close()
+    return record
+
+
+def interned(obj, texts, grow=False):
+    """`obj` with every error text replaced by '#<its index in texts>': the golden file holds each text once"""
+    if isinstance(obj, str) and obj.startswith('mate_engine error'):
+        if obj not in texts and grow:
+            texts.append(obj)
+        return '#%d' % texts.index(obj) if obj in texts else obj
+    if isinstance(obj, (list, tuple)):
+        return [interned(x, texts, grow) for x in obj]
+    if isinstance(obj, dict):
+        return {key: interned(value, texts, grow) for key, value in obj.items()}
+    return obj
+
+
+def one_entry_per_line(obj, depth):
+    """JSON with the dictionaries of the first `depth` levels, and the lists right under the top, one entry per line"""
+    compact = lambda value: json.dumps(value, separators=(',', ':'))
+    if isinstance(obj, dict) and depth > 0:
+        return '{\n' + ',\n'.join('%s:%s' % (compact(key), one_entry_per_line(value, depth - 1)) for key, value in obj.items()) + '\n}'
+    if isinstance(obj, list) and depth == 3:
+        return '[\n' + ',\n'.join(compact(value) for value in obj) + '\n]'
+    return compact(obj)
+
+
+def golden_of(record, commit):
+    """tests/golden/opponent_flows.json from the record of every shape: the rows without the digests of a full record; each error text ('#<index>'),
+    each distinct row (its index in 'rows') and each distinct list of a state's rows (its index in 'columns') once"""
+    texts, rows, columns = [], [], []
+
+    def row_index(row):
+        row = interned(row[:5], texts, grow=True)
+        if row not in rows:
+            rows.append(row)
+        return rows.index(row)
+    def column_index(calls):
+        column = [row_index(row) for row in calls]
+        if column not in columns:
+            columns.append(column)
+        return columns.index(column)
+    shapes = {shape: {'states': {label: {'setters': interned(state['setters'], texts, grow=True), 'calls': column_index(state['calls'])}
+                                 for label, state in part['states'].items()},
+                      'refusals': {what: {'setters': interned(scenario['setters'], texts, grow=True), 'step_greedy': row_index(scenario['step_greedy'])}
+                                   for what, scenario in part['refusals'].items()}}
+              for shape, part in record.items()}
+    return {'recorded_with': 'python tools/launch_matrix.py opponents --golden PATH --commit %s: the build of that commit' % commit,
+            'texts': texts, 'rows': rows, 'columns': columns, 'shapes': shapes}
+
+
+def opponents_main(argv):
+    """Every dispatch of the column set in order; --record PATH: the full record of every shape as JSON (two builds of the library: the same bytes);
+    --golden PATH --commit ID: tests/golden/opponent_flows.json of this build, which is the build of commit ID."""
+    record_to = argv[argv.index('--record') + 1] if '--record' in argv else None
+    golden_to = argv[argv.index('--golden') + 1] if '--golden' in argv else None
+    commit = argv[argv.index('--commit') + 1] if '--commit' in argv else 'unnamed'
+    calls = 0
+    record = {}
+    for shape in OPPONENT_SHAPES:
+        t0 = time.perf_counter()
+        record[shape] = opponents_record(shape, full=record_to is not None)
+        for label, state in record[shape]['states'].items():
+            print(shape, '|', label, '| setters', [status[0] for status in state['setters']])
+            for (name, k), row in zip(OPPONENT_CALLS, state['calls']):
+                print('  %-34s status %d flow %d consumed %s edges %s %s' % ('%s/%d' % (name, k), row[0], row[2], row[3], row[4], row[1]))
+                calls += 1
+        for what, row in record[shape]['refusals'].items():
+            print(shape, '| refusal:', what, '|', row['setters'], '| step_greedy:', row['step_greedy'][:5])
+        print(shape, 'took %.1f s' % (time.perf_counter() - t0), flush=True)
+    if record_to:
+        with open(record_to, 'w') as fh:
+            json.dump(record, fh, indent=0, sort_keys=True)
+    if golden_to:
+        with open(golden_to, 'w') as fh:
+            fh.write(one_entry_per_line(golden_of(record, commit), 4) + '\n')
+    print('done', calls, 'calls')
+
+
 # ---- host cost per step with everything attached
 def host_cost_main(argv):
     """One row per (call, form): step_versus_greedy (camera learner) and step_selected on MATE-4v8-9 with all three attached, direct (host
@@ -338,6 +586,8 @@ def host_cost_main(argv):
 def main(argv):
     if argv[1:2] == ['attached']:
         return attached_main(argv[2:])
+    if argv[1:2] == ['opponents']:
+        return opponents_main(argv[2:])
     if argv[1:2] == ['host-cost']:
         return host_cost_main(argv[2:])
     shapes = argv[1:2] or SHAPES
