@@ -868,6 +868,41 @@ int mate_engine_channel_tape(mate_engine *engine, const double *camera_u_dev, co
                              double *record_camera_u_dev, double *record_target_u_dev); /* [N][n][n]; NULL: Philox / not stored */
 int mate_engine_channel_edges(mate_engine *engine, int32_t team, int8_t **sent_dev, int8_t **delivered_dev);
 
+/* A learner seat among on-device teammates: the reference's SingleCamera / SingleTarget wrappers (mate/wrappers/single_team.py, SingleTeamSingleAgent) on the
+ * device.  The learner plays ONE slot of `team`, the seat; the team's other n - 1 slots are its Greedy agents with their true indices, the opposing team is
+ * whatever mate_engine_set_*_opponent / _set_opponent_mixture make of it.  Around the seat the teammates behave as the reference's: a Greedy camera teammate
+ * sends its one 'state' message to the seat (and draws that pair's delay) and never again, since the seat never answers and never becomes a neighbour; Greedy target
+ * teammates broadcast to every slot; the seat itself sends nothing, draws nothing and keeps no memory.  The learner's own messages are not provided.
+ *
+ * The seat of an episode is a pure function: MATE_SEAT_FIXED a constant (`fixed_seat`, < 0: n - 1, the wrapper's index with shuffle_entities off);
+ * MATE_SEAT_DRAW (uint64(philox(seed, global environment index, episode, stream 27, team).x) * n) >> 32, drawn anew for every episode (shuffle_entities on);
+ * MATE_SEAT_TAPE the caller-owned `seat_tape_dev` ([N] int32, read at every launch; a value outside [0, n) falls back to MATE_SEAT_DRAW).
+ *
+ * mate_engine_enable_seat: the caller's buffers `obs_out_dev` ([N][D_team] obs_dtype, 16-byte aligned: the seat's row of the call's output observations),
+ * `seat_index_dev` ([N] int32: the seat of the episode that row belongs to -- after an immediate restart the NEW episode's) and `seat_acted_dev` ([N] int32: the
+ * seat whose action the last mate_engine_step_seated consumed).  All three NULL: disable.  One seat team per engine.  Enabling, changing or disabling the seat marks
+ * that team's Greedy agents for their reset at their next acting call.  It needs mate_engine_policy_enable (MATE_ESTATE otherwise) and waits for the handle's launches.
+ * MATE_EINVAL: a team that is neither, a team without agents, a fixed seat outside [0, n), MATE_SEAT_TAPE without a tape, a missing or misaligned buffer.
+ * MATE_ESTATE: a seat on a team with a Heuristic selection, a mixture other than {Greedy} or a channel set -- and installing any of these on the seat team while
+ * the seat is enabled; a seat while the opposing team's channel is live (that flow's agents' launch is greedy_channel_kernel).  A refused call changes nothing.
+ *
+ * mate_engine_step_seated: `io`'s action pointer of the seat team holds the seat's action, [N][2] f32 / f64 pairs or [N] int32 grid indices with that team's
+ * *_DISCRETE bit; the other team's action pointer is ignored.  `tape` keeps its full shapes; the seat's entries are ignored.  Launches: greedy_seat_kernel (both
+ * teams' agents, the seat's lane writing the learner's action into the team's joint row), whatever the opposing team's plan adds (Heuristic cameras, drift, scripted
+ * launch), the stepping launch on both teams' engine-owned rows (mate_engine_policy_actions returns them), the attached launches and the restart as for
+ * mate_engine_step_greedy, seat_rows_kernel last.  Identical arguments at every call, no allocation, no synchronisation: capturable under
+ * mate_engine_device_tick.  An environment idling under a batched restart keeps its row, its seat_index and its seat_acted.  Reward and done are team-level:
+ * the scalar rows.  mate_engine_rollout_greedy / _rollout_versus_greedy and the fragment rows are untouched: there is no fused K-frame seat flow (FrameSkip is K
+ * calls with the action held).  With a seat enabled and mate_engine_step_seated never called, every other entry point gives the bytes it gives without.
+ * mate_engine_seat_rows: the gather on demand (behind a reset): every environment's row and seat from `io`'s observation rows of the seat team. */
+#define MATE_SEAT_FIXED 0
+#define MATE_SEAT_DRAW 1
+#define MATE_SEAT_TAPE 2
+int mate_engine_enable_seat(mate_engine *engine, int32_t team, int32_t mode, int32_t fixed_seat, const int32_t *seat_tape_dev,
+                            void *obs_out_dev, int32_t *seat_index_dev, int32_t *seat_acted_dev);      /* the three outputs NULL: disable */
+int mate_engine_step_seated(mate_engine *engine, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream);
+int mate_engine_seat_rows(mate_engine *engine, const mate_step_io *io, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,9 @@ PROTOTYPES = {
     'mate_engine_set_channel': (INT, [P, I32, ctypes.POINTER(MateChannel)]),
     'mate_engine_channel_tape': (INT, [P, P, P, P, P]),
     'mate_engine_channel_edges': (INT, [P, I32, ctypes.POINTER(P), ctypes.POINTER(P)]),
+    'mate_engine_enable_seat': (INT, [P, I32, I32, I32, P, P, P, P]),
+    'mate_engine_step_seated': (INT, [P, IO, TAPE, I32, P]),
+    'mate_engine_seat_rows': (INT, [P, IO, P]),
     'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
     'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
     'mate_engine_observe': (INT, [P, IO, P]),

@@ -23,6 +23,7 @@
 #include "info_rows.hpp"
 #include "scripted_rows.hpp"
 #include "channel_rows.hpp"
+#include "seat_rows.hpp"
 
 using namespace mate;
 
@@ -102,6 +103,13 @@ struct Channels {        // mate_engine_set_channel, one per team: the settings,
     } team[2];
     int lds_bytes = 0;                               // per wave of greedy_channel_kernel (ChannelArgs::lds_bytes), its dynamic LDS opted in: set with the edge matrices
 };
+struct Seat {            // mate_engine_enable_seat: the learner's seat among the on-device teammates of ONE team (seat_rows.hpp); `spec`, the caller's three buffers, the engine-owned flags
+    bool on = false;
+    SeatSpec spec{};                             // team, mode, the constant, the team's agents, the caller's tape
+    void *obs = nullptr;                         // [N][D_team] obs_dtype: seat_rows_kernel's rows
+    int32_t *index = nullptr, *acted = nullptr;  // [N] each: the seat of the row's episode; the seat whose action the last agents' launch consumed
+    int32_t *d_live = nullptr;                   // [N], allocated at the first enable: the environments greedy_seat_kernel ran in the call (an idle one keeps its row)
+};
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
     FragmentArgs args{};
@@ -172,6 +180,7 @@ struct mate_engine {
     CameraOpponent camera_opponent;      // the Heuristic camera agents' tables and memory
     Scripted scripted;                   // the opponent mixtures
     Channels channel;                    // the communication channels
+    Seat seat;                           // the learner's seat among on-device teammates
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -297,6 +306,7 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   6c             with reward rows the snapshot-only launch; with info rows theirs                        attached_behind_restart
 //   7 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
 //   8 state        state_rows_kernel, last                                                                  attached_last
+//   9 seat         seat_rows_kernel behind everything of a mate_engine_step_seated call: the seat's row, the seat      seat_rows_behind
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
     bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, info = false, action_mask = false, state = false;
@@ -343,7 +353,10 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
 // Who plays each team of ONE call with the on-device agents (`team_caller`: -1 both teams are the engine's, else the caller's team), which launches that takes
 // and whose rows the stepping launch consumes.  Everything else reads this: one_launch_step and step_with_policies (the launches, in the order of the fields),
 // rollout_with_policies (the refusal), scripted_team_args, channel_args.
+// `seat_team`: the call is mate_engine_step_seated (or the question whether it could be: mate_engine_enable_seat and the setters ask HERE) with the learner's
+// seat on that team -- both teams are the engine's, the seat team's Greedy agents act around the seat in greedy_seat_kernel, its rows stay the Greedy buffer.
 enum FusedRefusal { FUSED_OK, FUSED_MIXTURE, FUSED_CHANNEL, FUSED_HEURISTIC };
+enum SeatRefusal { SEAT_OK, SEAT_HEURISTIC, SEAT_MIXTURE, SEAT_CHANNEL, SEAT_OPPOSING_CHANNEL };      // what of the engine's state a seat on `seat_team` cannot live with
 struct OpponentPlan {
     struct Team {
         bool engine = false;       // the engine plays the team in this call: not the caller's, and it has agents (a scenario without cameras: every camera selection is a no-op)
@@ -357,7 +370,9 @@ struct OpponentPlan {
     int caller_team = -1;          // ... with this q.caller_team (the team whose Greedy agents sit out; -1: neither) ...
     bool channel_kernel = false;   // ... and it is greedy_channel_kernel (channel_rows.hpp)
     Tiles drift_rows;              // the drift launch's geometry (blocks 0: none)
-    bool one_launch = true;        // the opponents allow the one-launch step: plain Greedy agents, no live channel
+    bool one_launch = true;        // the opponents allow the one-launch step: plain Greedy agents, no live channel, no seat
+    bool seat = false;             // the agents' launch is greedy_seat_kernel (seat_rows.hpp)
+    int seat_refusal = SEAT_OK;    // why a seat on `seat_team` is refused: its teammates must be plain Greedy agents without a channel, and the opposing team's channel not live
     int refusal = FUSED_OK, refusal_team = -1;      // why a fused K-frame launch is refused (their kernels hold the Greedy agents and deliver every message), and for which team
 };
 static int agents_of(const mate_engine *e, int team) { return team == MATE_TEAM_CAMERA ? e->p.Nc : e->p.Nt; }
@@ -370,8 +385,9 @@ static const double *rows_of(const mate_engine *e, int team, int source) {
     default: return nullptr;
     }
 }
-static OpponentPlan plan_opponents(const mate_engine *e, int team_caller) {
+static OpponentPlan plan_opponents(const mate_engine *e, int team_caller, int seat_team = -1) {
     OpponentPlan pl;
+    pl.seat = seat_team >= 0;
     for (int team = 0; team < 2; ++team) {
         OpponentPlan::Team &t = pl.team[team];
         const ScriptedMixture &m = e->scripted.team[team];
@@ -392,6 +408,11 @@ static OpponentPlan plan_opponents(const mate_engine *e, int team_caller) {
     pl.caller_team = c.greedy && t.greedy ? -1 : c.greedy ? MATE_TEAM_TARGET : MATE_TEAM_CAMERA;
     pl.channel_kernel = c.channel || t.channel;
     if (t.heuristic) pl.drift_rows = plan_attached_tile(e);
-    pl.one_launch = !c.heuristic && !t.heuristic && !c.scripted && !t.scripted && !pl.channel_kernel;
+    pl.one_launch = !c.heuristic && !t.heuristic && !c.scripted && !t.scripted && !pl.channel_kernel && !pl.seat;
+    if (pl.seat) {
+        const OpponentPlan::Team &other = pl.team[1 - seat_team];
+        pl.seat_refusal = e->opponents.kind[seat_team] == MATE_OPPONENT_HEURISTIC ? SEAT_HEURISTIC : !e->scripted.team[seat_team].only_greedy() ? SEAT_MIXTURE
+                        : e->channel.team[seat_team].set ? SEAT_CHANNEL : other.channel ? SEAT_OPPOSING_CHANNEL : SEAT_OK;
+    }
     return pl;
 }

@@ -1574,6 +1574,68 @@ extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, cons
     return attached_last(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
 
+// The learner's seat among on-device teammates (include/mate_engine.h, csrc/seat_rows.hpp): step_with_policies' two-launch form with both teams the engine's,
+// greedy_seat_kernel as the agents' launch and the seat's action from the seat team's pointer of `io`; what the OTHER team's plan adds, in plan_opponents' order;
+// the stepping launch on both teams' engine-owned rows; the attached observers and the restart as for step_greedy.  Identical arguments at every call but for
+// the tapes, no allocation, no synchronisation.
+static int step_seated(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, hipStream_t stream) {
+    MATE_TRY(leave_pipelined(e, stream));
+    if (!e->policy_ready) return fail(MATE_ESTATE, "step_seated: call mate_engine_policy_enable() before the reset whose observations the policies act on");
+    const Seat &s = e->seat;
+    if (!s.on) return fail(MATE_ESTATE, "step_seated: call mate_engine_enable_seat() first");
+    const int team = s.spec.team;
+    const OpponentPlan op = plan_opponents(e, -1, team);
+    if (op.seat_refusal != SEAT_OK) return fail(MATE_ESTATE, "step_seated (%s team): %s", kTeamNames[team], seat_refusal_text(op.seat_refusal));
+    MATE_TRY(check_attached_call(e, io, false, false));      // (ahead of the agents' launch: a rejected call leaves their memory alone)
+    if (!e->was_reset) return fail(MATE_ESTATE, "step_seated called before reset() (or import_state)");
+    if (!io || !(team == MATE_TEAM_CAMERA ? io->camera_actions_dev : io->target_actions_dev)) return fail(MATE_EINVAL, "step_seated needs the seat's action in the %s team's action pointer", kTeamNames[team]);
+    if (!(team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev)) return fail(MATE_EINVAL, "step_seated needs the %s team's observation output (the seat's row is gathered from it)", kTeamNames[team]);
+    if ((io->act_dtype & (team == MATE_TEAM_CAMERA ? MATE_ACT_CAMERA_DISCRETE : MATE_ACT_TARGET_DISCRETE)) && !(team == MATE_TEAM_CAMERA ? e->g.cam_grid : e->g.tgt_grid))
+        return fail(MATE_ESTATE, "discrete actions passed before mate_engine_set_action_grids");
+    MATE_TRY(check_device_tick(e, auto_reset, 1, true));
+    HIP_TRY(hipSetDevice(e->device));
+    note_stream(e, stream);
+    PolicyPtrs q = e->q;
+    std::memset(&q.tape, 0, sizeof(q.tape));
+    q.caller_team = op.caller_team;      // (an opposing team other launches play sits out)
+    if (tape) {
+        q.tape.cam_binom_u = tape->camera_resample_u_dev; q.tape.cam_sample_u = tape->camera_sample_u_dev;
+        q.tape.cam_delay = tape->camera_delay_dev; q.tape.tgt_choice_u = tape->target_choice_u_dev;
+        q.tape.tgt_binom_u = tape->target_resample_u_dev; q.tape.tgt_sample_u = tape->target_sample_u_dev;
+        q.tape.tgt_reset_sample_u = tape->target_reset_sample_u_dev;
+    }
+    Ptrs gp = e->g;
+    apply_io(gp, io);                    // (the seat's action: pointer, type, grid)
+    gp.freeze_done = auto_reset > 1;
+    HIP_TRY(launch_greedy_seat(e->p.obs_f64 != 0, blocks_of(e, 4), 4 * (size_t)q.lds_bytes, stream, e->d_params, gp, q, SeatArgs{s.spec, s.acted, s.d_live}));
+    if (op.team[MATE_TEAM_CAMERA].heuristic) MATE_TRY(launch_heuristic_cameras(e, tape, gp.freeze_done, stream));
+    if (op.team[MATE_TEAM_TARGET].heuristic) MATE_TRY(launch_drift(e, op, gp.freeze_done, stream));
+    if (op.team[MATE_TEAM_CAMERA].scripted || op.team[MATE_TEAM_TARGET].scripted) MATE_TRY(launch_scripted(e, op, gp.freeze_done, stream));
+    mate_step_io io2 = *io;
+    io2.camera_actions_dev = rows_of(e, MATE_TEAM_CAMERA, op.team[MATE_TEAM_CAMERA].source);
+    io2.target_actions_dev = rows_of(e, MATE_TEAM_TARGET, op.team[MATE_TEAM_TARGET].source);
+    io2.act_dtype &= ~(MATE_ACT_CAMERA_DISCRETE | MATE_ACT_TARGET_DISCRETE);
+    for (int t = 0; t < 2; ++t) e->opponents.consumed[t] = op.team[t].source;
+    e->greedy_team_bits = 3;
+    const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, false);
+    e->greedy_team_bits = 0;
+    return rc;
+}
+extern "C" int mate_engine_step_seated(mate_engine *e, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    const int rc = attached_last(e, step_seated(e, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
+    return rc == MATE_OK ? seat_rows_behind(e, io, true, (hipStream_t)stream) : rc;
+}
+extern "C" int mate_engine_seat_rows(mate_engine *e, const mate_step_io *io, void *stream) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    if (!e->seat.on) return fail(MATE_ESTATE, "seat_rows: call mate_engine_enable_seat() first");
+    if (!e->was_reset) return fail(MATE_ESTATE, "seat_rows called before reset() (or import_state)");
+    if (!io || !(e->seat.spec.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev)) return fail(MATE_EINVAL, "seat_rows needs the %s team's observation rows", kTeamNames[e->seat.spec.team]);
+    MATE_TRY(enter(e, (hipStream_t)stream));
+    note_stream(e, (hipStream_t)stream);
+    return seat_rows_behind(e, io, false, (hipStream_t)stream);
+}
+
 // Target-selection camera actions (include/mate_engine.h).  The buffers are the caller's, but for the joint action the executor hands to
 // the stepping launch: engine-owned, f64 unless MATE_SELECTION_ACT_F32.
 extern "C" int mate_engine_enable_selection(mate_engine *e, int32_t mode, const void *selection_dev, double *metrics_dev, int32_t *frames_dev,

@@ -151,6 +151,11 @@ static int set_plain_opponent(mate_engine *e, int team, int32_t opponent) {
     kind = opponent;
     return MATE_OK;
 }
+// While a learner's seat is enabled on `team` (mate_engine_enable_seat) its teammates stay plain Greedy agents without a channel: the setters ask here.
+static int refuse_under_seat(const mate_engine *e, int team, const char *who, bool installs) {
+    if (!installs || !e->seat.on || e->seat.spec.team != team) return MATE_OK;
+    return fail(MATE_ESTATE, "%s: a learner's seat is enabled on the %s team (mate_engine_enable_seat), whose teammates are plain Greedy agents without a channel: disable the seat first", who, kTeamNames[team]);
+}
 static int refuse_under_mixture(const mate_engine *e, int team) {
     if (!e->scripted.team[team].installed) return MATE_OK;
     return fail(MATE_ESTATE, "set_%s_opponent: an opponent mixture is installed for the %s team (mate_engine_set_opponent_mixture): clear it first (count = 0)", kTeamNames[team], kTeamNames[team]);
@@ -158,6 +163,7 @@ static int refuse_under_mixture(const mate_engine *e, int team) {
 extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     MATE_TRY(refuse_under_mixture(e, MATE_TEAM_CAMERA));
+    MATE_TRY(refuse_under_seat(e, MATE_TEAM_CAMERA, "set_camera_opponent", opponent == MATE_OPPONENT_HEURISTIC));
     if (e->channel.team[MATE_TEAM_CAMERA].set && heuristic_camera_reachable(opponent, e->scripted.team[MATE_TEAM_CAMERA]))
         return fail(MATE_ESTATE, "set_camera_opponent: a communication channel is set for the camera team (mate_engine_set_channel), and the heuristic camera agent's fallback for a lost response is not on the device: clear the channel first");
     return set_plain_opponent(e, MATE_TEAM_CAMERA, opponent);
@@ -165,6 +171,7 @@ extern "C" int mate_engine_set_camera_opponent(mate_engine *e, int32_t opponent)
 extern "C" int mate_engine_set_target_opponent(mate_engine *e, int32_t opponent) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     MATE_TRY(refuse_under_mixture(e, MATE_TEAM_TARGET));
+    MATE_TRY(refuse_under_seat(e, MATE_TEAM_TARGET, "set_target_opponent", opponent == MATE_OPPONENT_HEURISTIC));
     return set_plain_opponent(e, MATE_TEAM_TARGET, opponent);
 }
 
@@ -195,6 +202,7 @@ extern "C" int mate_engine_set_opponent_mixture(mate_engine *e, int32_t team, co
         next.kinds[next.count] = kinds[i]; next.cum[next.count] = running; next.has[kinds[i]] = true; ++next.count;
     }
     if (!e->policy_ready) return fail(MATE_ESTATE, "set_opponent_mixture (%s team): call mate_engine_policy_enable() first (the Greedy agents, and the engine's own view masks)", names[team]);
+    MATE_TRY(refuse_under_seat(e, team, "set_opponent_mixture", next.count > 0 && !(next.count == 1 && next.kinds[0] == MATE_SCRIPTED_GREEDY)));
     const int mode = e->team_mode[team];
     if (next.has[MATE_SCRIPTED_HEURISTIC] && mode != 0)
         return fail(MATE_EINVAL, "set_opponent_mixture: the Heuristic candidate of the %s mixture senses the opponents of its plain rows, the team's observation mode is %d (mate_engine_set_obs_mode)", names[team], mode);
@@ -270,6 +278,7 @@ extern "C" int mate_engine_set_channel(mate_engine *e, int32_t team, const mate_
         return fail(MATE_EINVAL, "set_channel: the dropout rate must lie in [0, 1] (got %g)", cfg->dropout_rate);
     if (cfg && std::isnan(cfg->range_limit)) return fail(MATE_EINVAL, "set_channel: the range limit is NaN (negative or +inf: no limit)");
     if (!e->policy_ready) return fail(MATE_ESTATE, "set_channel: call mate_engine_policy_enable() first (the agents whose messages the channel carries)");
+    MATE_TRY(refuse_under_seat(e, team, "set_channel", cfg != nullptr));
     if (cfg && team == MATE_TEAM_CAMERA && heuristic_camera_reachable(e->opponents.kind[MATE_TEAM_CAMERA], e->scripted.team[MATE_TEAM_CAMERA]))
             return fail(MATE_ESTATE, "set_channel: the heuristic camera agent plays (or is a candidate of) the camera team, and its fallback for a lost response is not on the device: select MATE_OPPONENT_GREEDY first");
     MATE_TRY(enter_host(e));      // (no launch in flight reads the settings)
@@ -355,5 +364,60 @@ extern "C" int mate_engine_scripted_rows(mate_engine *e, int32_t team, int32_t k
     HIP_TRY(hipSetDevice(e->device));
     note_stream(e, (hipStream_t)stream);
     HIP_TRY(hipMemcpyAsync(rows_dev, src, sizeof(double) * 2 * (size_t)agents_of(e, team) * (size_t)e->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MATE_OK;
+}
+
+// The learner's seat among on-device teammates (include/mate_engine.h, csrc/seat_rows.hpp): enable / change / disable, the launches' arguments.
+static const char *seat_refusal_text(int refusal) {
+    switch (refusal) {
+    case SEAT_HEURISTIC: return "the team's plain selection is the Heuristic agent (mate_engine_set_camera_opponent / _set_target_opponent): select MATE_OPPONENT_GREEDY first";
+    case SEAT_MIXTURE: return "the team plays an opponent mixture other than {Greedy} (mate_engine_set_opponent_mixture): clear it first";
+    case SEAT_CHANNEL: return "a communication channel is set for the team (mate_engine_set_channel): clear it first";
+    case SEAT_OPPOSING_CHANNEL: return "the opposing team's communication channel is live (mate_engine_set_channel), and its agents' launch is greedy_channel_kernel: clear it first";
+    default: return "";
+    }
+}
+extern "C" int mate_engine_enable_seat(mate_engine *e, int32_t team, int32_t mode, int32_t fixed_seat, const int32_t *seat_tape_dev, void *obs_out_dev, int32_t *seat_index_dev, int32_t *seat_acted_dev) {
+    if (!e) return fail(MATE_EINVAL, "null engine");
+    Seat &s = e->seat;
+    if (!obs_out_dev && !seat_index_dev && !seat_acted_dev) {      // the disable form: the team's Greedy agents start afresh at their next acting call
+        if (!s.on) return MATE_OK;
+        MATE_TRY(enter_host(e));
+        MATE_TRY(mark_greedy_reset(e, s.spec.team));
+        s.on = false;
+        return MATE_OK;
+    }
+    if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "enable_seat: team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
+    const int n = agents_of(e, team);
+    if (n == 0) return fail(MATE_EINVAL, "enable_seat: the scenario has no %ss to sit among", kTeamNames[team]);
+    if (mode != MATE_SEAT_FIXED && mode != MATE_SEAT_DRAW && mode != MATE_SEAT_TAPE) return fail(MATE_EINVAL, "enable_seat: mode must be MATE_SEAT_FIXED, MATE_SEAT_DRAW or MATE_SEAT_TAPE");
+    if (mode == MATE_SEAT_FIXED && fixed_seat < 0) fixed_seat = n - 1;      // (the wrapper's index with shuffle_entities off)
+    if (mode == MATE_SEAT_FIXED && fixed_seat >= n) return fail(MATE_EINVAL, "enable_seat: the fixed seat %d is outside [0, %d)", fixed_seat, n);
+    if (mode == MATE_SEAT_TAPE && !seat_tape_dev) return fail(MATE_EINVAL, "enable_seat: MATE_SEAT_TAPE needs seat_tape_dev");
+    if (!obs_out_dev || !seat_index_dev || !seat_acted_dev) return fail(MATE_EINVAL, "enable_seat: obs_out_dev, seat_index_dev and seat_acted_dev must all be there (all three NULL: disable)");
+    if ((reinterpret_cast<uintptr_t>(obs_out_dev) & 15u) || ((reinterpret_cast<uintptr_t>(seat_index_dev) | reinterpret_cast<uintptr_t>(seat_acted_dev) | reinterpret_cast<uintptr_t>(seat_tape_dev)) & 3u))
+        return fail(MATE_EINVAL, "enable_seat: obs_out_dev must be 16-byte aligned, the int32 buffers aligned to their element size");
+    if (!e->policy_ready) return fail(MATE_ESTATE, "enable_seat: call mate_engine_policy_enable() first (the teammates, and the engine's own view masks)");
+    if (s.on && s.spec.team != team) return fail(MATE_ESTATE, "enable_seat: a seat is enabled on the %s team, and an engine has one seat team: disable it first", kTeamNames[s.spec.team]);
+    const OpponentPlan op = plan_opponents(e, -1, team);
+    if (op.seat_refusal != SEAT_OK) return fail(MATE_ESTATE, "enable_seat (%s team): %s", kTeamNames[team], seat_refusal_text(op.seat_refusal));
+    MATE_TRY(enter_host(e));      // (no launch in flight reads what changes below)
+    if (!s.d_live) MATE_TRY(dev_alloc(e, &s.d_live, (size_t)e->N));
+    for (int f64 = 0; f64 < 2; ++f64) {
+        const hipError_t err = set_dynamic_lds(greedy_seat_function(f64 != 0), 4 * (size_t)e->q.lds_bytes);
+        if (err != hipSuccess) return fail(MATE_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
+    }
+    MATE_TRY(mark_greedy_reset(e, team));      // enabling or changing the seat: the team's agents run their reset at their next acting call (the mixtures' rule)
+    s.spec = SeatSpec{team, mode, mode == MATE_SEAT_FIXED ? fixed_seat : 0, n, mode == MATE_SEAT_TAPE ? seat_tape_dev : nullptr};
+    s.obs = obs_out_dev; s.index = seat_index_dev; s.acted = seat_acted_dev;
+    s.on = true;
+    return MATE_OK;
+}
+// Behind everything else of a seat call (`live`: the call's agents' launch ran; else on demand: every environment is written)
+static int seat_rows_behind(mate_engine *e, const mate_step_io *io, bool live, hipStream_t stream) {
+    const Seat &s = e->seat;
+    const bool camera = s.spec.team == MATE_TEAM_CAMERA;
+    const SeatRowsArgs a{s.spec, camera ? io->camera_obs_dev : io->target_obs_dev, s.obs, s.index, live ? s.d_live : nullptr, camera ? e->p.Dc : e->p.Dt};
+    HIP_TRY(launch_seat_rows(e->p.obs_f64 != 0, blocks_of(e, kSeatRowsEnvs), stream, e->d_params, e->g, a));
     return MATE_OK;
 }

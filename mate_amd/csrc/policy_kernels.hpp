@@ -178,11 +178,24 @@ struct NoChannel {
     __device__ __forceinline__ constexpr void targets_done(uint32_t /*needers*/, int /*t*/) const {}
 };
 
-template <typename ObsT, int L = 64, typename Channel = NoChannel>
+// `Seat`: a slot of a team that no agent plays -- the learner's seat among on-device teammates (seat_rows.hpp: greedy_seat_kernel).  The default says
+// "nobody is absent": its hooks are constexpr, and every kernel of this header compiles to what it was without them.
+struct NoSeat {
+    static constexpr bool kLive = false;                    // (every use of a hook is `Seat::kLive && ...`: folded where the expression is written)
+    // camera slot c / target slot t is the absent one: it sends nothing, draws nothing, runs no agent
+    __device__ __forceinline__ constexpr bool camera(int /*c*/) const { return false; }
+    __device__ __forceinline__ constexpr bool target(int /*t*/) const { return false; }
+    // the absent slot's lane in the act phase: the learner's action into the team's joint-action row
+    __device__ __forceinline__ constexpr void act_camera(int /*c*/) const {}
+    __device__ __forceinline__ constexpr void act_target(int /*t*/, uint64_t /*capword*/) const {}
+};
+
+template <typename ObsT, int L = 64, typename Channel = NoChannel, typename Seat = NoSeat>
 __device__ __forceinline__ void greedy_policy_body(const Params &p, const PolicyPtrs &q, PolCtx<ObsT> &a, const double *st, const double *dy,
                                                    const int32_t *di, const uint32_t *mk,
                                                    int wave, int lane, int64_t env, bool active, double *lds_cam_act, double *lds_tgt_act,
-                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true, const Channel ch = Channel()) {
+                                                   long long *acc = nullptr, long long *t_prev = nullptr, bool publish = true, const Channel ch = Channel(),
+                                                   const Seat seat = Seat()) {
     constexpr int TB = L / 2;                       // the target agents' first lane
     const int shift = (int)(threadIdx.x & 63) & ~(L - 1);      // the group's first hardware lane (0 when L == 64)
     auto group_ballot = [&](bool x) -> unsigned long long {
@@ -229,7 +242,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     const double threshold = 1.1 * p.rmax;                  // filterout_beyond_range / the tracking reach: 110 % of the range
     if (cams && lane < Nc) a.near_bits(lane) = 0;
     if (fresh_c) {                                          // GreedyCameraAgent.reset (greedy.py:43-61)
-        if (lane < Nc) { a.prev_action(lane, 0) = 0.0; a.prev_action(lane, 1) = 0.0; a.has_state(lane) = 1; }
+        if (lane < Nc) { a.prev_action(lane, 0) = 0.0; a.prev_action(lane, 1) = 0.0; a.has_state(lane) = (Seat::kLive && seat.camera(lane)) ? 0 : 1; }
         for (int k = lane; k < Nc * Nc; k += L) { a.ci[Nc * Nt + k] = 0; a.ci[Nc * Nt + Nc * Nc + k] = 0; }   // delay, neighbor
     }
     wave_sync();
@@ -246,7 +259,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
         if (norm2(x - cam_x(c), y - cam_y(c)) < threshold) atomicOr(&a.near_bits(c), 1 << t);
     }
     const int tl = lane - TB;
-    if (tgts && tl >= 0 && tl < Nt) {                       // GreedyTargetAgent.reset / process_messages (greedy.py:262-283,326-332)
+    if (tgts && tl >= 0 && tl < Nt && !(Seat::kLive && seat.target(tl))) {   // GreedyTargetAgent.reset / process_messages (greedy.py:262-283,326-332)
         const int t = tl;
         const int gw = di[t * TI_STRIDE + TI_GW];
         const int state_goal = (gw & 0xff) - 1;
@@ -290,7 +303,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
         // message2send is non-empty iff it still holds 'state' or a target was seen this step
         const uint32_t seen_now = seen_mask(s);
         const bool has_state = a.has_state(s) != 0;
-        if ((has_state || seen_now) && s != c && d == 0) {
+        if ((has_state || seen_now) && s != c && d == 0 && !(Seat::kLive && seat.camera(s))) {
             // filterout_beyond_range: of the targets seen this step, those within 110 % of the teammate's range
             const uint32_t list = a.neighbor(s, c) ? (seen_now & (uint32_t)a.near_bits(c)) : 0u;
             bits = (int)list | (has_state ? (int)0x80000000u : 0);
@@ -356,7 +369,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     }
     // targets: broadcast non-empty warehouse sets (greedy.py:334-358).  Every lane's reads precede every lane's writes: one wave,
     // one instruction stream, LDS operations in order.
-    const bool broadcasts = tgts && tl >= 0 && tl < Nt && a.tgt_need(tl) != 0;
+    const bool broadcasts = tgts && tl >= 0 && tl < Nt && !(Seat::kLive && seat.target(tl)) && a.tgt_need(tl) != 0;
     const uint32_t needers = (uint32_t)(group_ballot(broadcasts) >> TB);      // (target t on lane L / 2 + t; nobody: the sets stay as they are)
     if (needers != 0u && tgts && tl >= 0 && tl < Nt) {
         int set = a.tgt_nonempty(tl);
@@ -373,7 +386,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     int best = -1;
     double theta = 0.0, orientation = 0.0, min_va = 0.0, best_orientation = 0.0, best_va = 0.0, K = 0.0;
     bool solve = false;
-    if (cams && lane < Nc) {
+    if (cams && lane < Nc && !(Seat::kLive && seat.camera(lane))) {
         const int c = lane;
         const double phi = dy[c];
         theta = dy[Nc + c];
@@ -411,7 +424,7 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
     POL_STAMP(12);
     if (cams && lane < Nc && solve) best_va = clipd(zoom_lookup(q, K), min_va, 180.0);      // greedy.py:139-146, tabulated (zoom_lookup)
     POL_STAMP(9);
-    if (cams && lane < Nc) {                                // part 2: the action
+    if (cams && lane < Nc && !(Seat::kLive && seat.camera(lane))) {      // part 2: the action
         const int c = lane;
         double a0, a1;
         if (best >= 0) {
@@ -432,7 +445,11 @@ __device__ __forceinline__ void greedy_policy_body(const Params &p, const Policy
         if (lds_cam_act) { lds_cam_act[2 * c] = a0; lds_cam_act[2 * c + 1] = a1; }
         if (active && publish) { q.cam_act[(env * Nc + c) * 2] = a0; q.cam_act[(env * Nc + c) * 2 + 1] = a1; }
     }
-    if (tgts && tl >= 0 && tl < Nt) {                       // GreedyTargetAgent.act (greedy.py:285-324)
+    if constexpr (Seat::kLive) {                            // the learner's seat: its action into the joint row, no agent
+        if (cams && lane < Nc && seat.camera(lane)) seat.act_camera(lane);
+        if (tgts && tl >= 0 && tl < Nt && seat.target(tl)) seat.act_target(tl, capword);
+    }
+    if (tgts && tl >= 0 && tl < Nt && !(Seat::kLive && seat.target(tl))) {   // GreedyTargetAgent.act (greedy.py:285-324)
         const int t = tl;
         const int gw = di[t * TI_STRIDE + TI_GW];
         const int state_goal = (gw & 0xff) - 1;

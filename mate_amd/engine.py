@@ -113,6 +113,20 @@ def channel_table(no_communication='none', message_dropout=0.0, communication_ra
     return table
 
 
+def seat_mode_of(seat, shuffle_entities):
+    """(mode, fixed seat, tape tensor) of Engine.enable_seat's `seat`: 'auto' is the reference's rule (single_team.py: index = num_teammates - 1,
+    or np_random.randint(num_teammates) at every reset() under shuffle_entities); -1 as the fixed seat means n - 1."""
+    if isinstance(seat, str):
+        if seat not in ('auto', 'draw'):
+            raise ValueError(f"seat = {seat!r}: 'auto', 'draw', an agent index or an [N] int32 tensor")
+        return ('draw', 0, None) if seat == 'draw' or shuffle_entities else ('fixed', -1, None)
+    if isinstance(seat, torch.Tensor):
+        return 'tape', 0, seat
+    if isinstance(seat, bool) or not isinstance(seat, (int, np.integer)) or seat < 0:
+        raise ValueError(f"seat = {seat!r}: 'auto', 'draw', an agent index or an [N] int32 tensor")
+    return 'fixed', int(seat), None
+
+
 def encode_selection(selection, multi, num_envs, num_cameras, num_targets, device=None):
     """The reference's HierarchicalCamera action (examples/hrl/wrappers.py) -> the int32 words [N, Nc] mate_engine_enable_selection reads:
     multi-selection [N, Nc, Nt] of 0 / 1 -> bit t of the word (already packed [N, Nc] words pass through); single selection [N, Nc]
@@ -231,6 +245,7 @@ class Engine:
         self._scripted_tape = (None, None)    # the tensors mate_engine_scripted_tape points at
         self.channels = [None, None]          # per team: None or the settings of its communication channel (set_channel)
         self._channel_tape = (None, None, None)      # the tensors mate_engine_channel_tape points at
+        self._clear_seat()
         self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
         self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
         # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
@@ -278,6 +293,11 @@ class Engine:
         # [1] int64, the team's code, and how many of them episode_records() has handed out
         self.episode_ring = self.episode_count = self.episode_team = None
         self._episode_read = 0
+
+    def _clear_seat(self):
+        # while a learner's seat is enabled (enable_seat): the team's code, the mode, the seat's rows [N, D_team] (obs dtype), the seat of the
+        # episode each row belongs to [N] int32, the seat whose action the last step_seated consumed [N] int32, the caller's tape (SEAT_TAPE)
+        self.seat_team = self.seat_mode = self.seat_obs = self.seat_index = self.seat_acted = self._seat_tape = None
 
     def _clear_info_rows(self):
         # while the training-information rows are attached (enable_info_rows): [N, Nc, 2] / [N, Nt, 9] / [N, 24] f64, None for an output that is off
@@ -858,6 +878,73 @@ class Engine:
         """Whether a channel is set for a team the engine plays in a call where `team_caller` (None: neither) is the caller's."""
         caller = None if team_caller is None else _team_code(team_caller)
         return any(self.channels[t] is not None and t != caller for t in (0, 1))
+
+    # ------------------------------------------------------------------ a learner seat among on-device teammates (mate/wrappers/single_team.py: SingleCamera / SingleTarget)
+    SEAT_MODES = ('fixed', 'draw', 'tape')
+
+    def enable_seat(self, team, seat='auto'):
+        """The learner plays ONE agent of `team` ('camera' / 'target'), the seat; its n - 1 teammates are the team's on-device Greedy agents with
+        their true indices, the opposing team is what set_*_opponent / set_opponent_mixture make of it.  `seat`: 'auto' -- the reference's rule:
+        the constant n - 1 when the config's shuffle_entities is off, drawn anew per episode when it is on; 'draw'; an int; or an [N] int32
+        device tensor read at every launch (a value outside [0, n) falls back to the draw).  enable_policies first.  Enabling, changing or
+        disabling the seat resets that team's Greedy agents at their next acting call.  Returns (seat_obs [N, D_team], seat_index [N], seat_acted [N])."""
+        team = _team_code(team)
+        n, D = ((self.num_cameras, self.camera_obs_dim), (self.num_targets, self.target_obs_dim))[team]
+        mode, fixed, tape = seat_mode_of(seat, bool(self.config['shuffle_entities']))
+        if tape is not None:
+            self._check_tensor('seat', tape, torch.int32, (self.num_envs,))
+        if self.seat_obs is None or self.seat_team != team:
+            with torch.cuda.device(self.device):
+                outputs = (torch.zeros((self.num_envs, D), dtype=self.obs_dtype, device=self.device),
+                           torch.zeros(self.num_envs, dtype=torch.int32, device=self.device), torch.zeros(self.num_envs, dtype=torch.int32, device=self.device))
+        else:
+            outputs = (self.seat_obs, self.seat_index, self.seat_acted)
+        check(self.lib.mate_engine_enable_seat(self._h, team, self.SEAT_MODES.index(mode), fixed, None if tape is None else ctypes.c_void_p(tape.data_ptr()),
+                                               *(ctypes.c_void_p(t.data_ptr()) for t in outputs)))
+        self.seat_team, self.seat_mode, self._seat_tape = team, mode, tape
+        self.seat_obs, self.seat_index, self.seat_acted = outputs
+        return outputs
+
+    def disable_seat(self):
+        """Remove the seat: the team's Greedy agents (all n of them again) start afresh at their next acting call."""
+        check(self.lib.mate_engine_enable_seat(self._h, 0, 0, 0, None, None, None, None))
+        self._clear_seat()
+
+    def _seat_io(self, action, tape_ct=None, tape_goal=None):
+        """The argument block of a seat call: the seat's action ([N, 2] reals or [N] grid indices) in the seat team's action pointer."""
+        assert self.seat_obs is not None, 'Engine.enable_seat() first'
+        io, keep = self._io(tape_ct=tape_ct, tape_goal=tape_goal)
+        if action is not None:
+            name, grid = (('camera', self.camera_action_grid), ('target', self.target_action_grid))[self.seat_team]
+            if action.dtype in (torch.int32, torch.int64, torch.int16, torch.uint8):
+                assert grid is not None, f'call set_action_grids({name}_levels=...) first'
+                action = action.to(torch.int32).contiguous()
+                assert action.numel() == self.num_envs and action.device == self.device
+                io.act_dtype = 0x100 if name == 'camera' else 0x200
+            else:
+                assert action.dtype in (torch.float32, torch.float64), 'the seat\'s action is f32 / f64 pairs or integer grid indices'
+                action = action.contiguous()
+                assert action.numel() == self.num_envs * 2 and action.device == self.device
+                io.act_dtype = 1 if action.dtype == torch.float64 else 0
+            setattr(io, name + '_actions_dev', action.data_ptr())
+            keep.append(action)
+        return io, keep
+
+    def step_seated(self, action, policy_tape=None, tape_ct=None, tape_goal=None, auto_reset=True):
+        """One step of SingleCamera / SingleTarget: `action` is the seat's ([N, 2] reals or [N] grid indices), the teammates and the opponents
+        act on the device.  `policy_tape` keeps its full shapes (the seat's entries are ignored).  Returns (seat_obs, scalars): the seat's row
+        of the new observations -- after an immediate restart the new episode's seat's -- and the team-level scalar rows; seat_index /
+        seat_acted say whose row that is and whose action the step consumed; camera_obs / target_obs hold the full rows as ever."""
+        io, keep = self._seat_io(action, tape_ct, tape_goal)
+        check(self.lib.mate_engine_step_seated(self._h, ctypes.byref(io), self._policy_tape(policy_tape, keep), int(auto_reset), self._stream()))
+        return self.seat_obs, self.scalars
+
+    def seat_rows(self):
+        """The gather on demand (behind reset()): every environment's seat row of the engine's observation tensors into seat_obs, its seat
+        into seat_index.  Returns (seat_obs, seat_index)."""
+        io, keep = self._seat_io(None)
+        check(self.lib.mate_engine_seat_rows(self._h, ctypes.byref(io), self._stream()))
+        return self.seat_obs, self.seat_index
 
     def _policy_tape(self, policy_tape, keep):
         if policy_tape is None:
@@ -1551,6 +1638,15 @@ class Stepper:
         # whole (_one), (b) the constructor closes whatever interval was open (device_tick on / off: what had finished restarts, the
         # count starts at 0) and (c) `auto_reset` must be 1 fragment.  Metrics, frames and accumulating reward rows are zeroed at the
         # head of every fragment, inside the graph too.
+        # versus = 'seat': the learner's seat among on-device teammates (Engine.enable_seat first); the seat team's tensor argument is the seat's
+        # action ([N, 2] or [N] grid indices), the other is ignored.  frame_skip = K: K per-step calls with the action held (there is no fused K-frame
+        # seat flow), under the engine's batched restart with the interval K -- auto_reset must be K: a finished environment idles to its fragment's end
+        self.seat = versus == 'seat'
+        if self.seat:
+            assert eng.seat_obs is not None, 'Engine.enable_seat() first'
+            assert self.frame_skip == 1 or self.auto_reset == self.frame_skip, "versus='seat', frame_skip = K: auto_reset = K (finished environments restart behind their fragment)"
+            seat_action = tgt_act if eng.seat_team == 1 else cam_act
+            versus, cam_act, tgt_act = None, None, None
         self.selection = versus == 'selection'
         if self.selection:
             assert eng.selection is not None, 'Engine.enable_selection() first'
@@ -1562,13 +1658,14 @@ class Stepper:
             tgt_act = None
         elif self.versus == 1:
             cam_act = None
-        self.io, self.keep = eng._io(cam_act, tgt_act)
+        self.io, self.keep = eng._seat_io(seat_action) if self.seat else eng._io(cam_act, tgt_act)
+        assert not self.seat or getattr(self.io, ('camera', 'target')[eng.seat_team] + '_actions_dev') == seat_action.data_ptr(), 'the seat\'s action tensor must be contiguous on the engine device'
         # _io may have made contiguous copies: the stepper must read the caller's own storage
         assert (tgt_act is None or self.io.target_actions_dev == tgt_act.data_ptr()) and \
             (cam_act is None or eng.num_cameras == 0 or self.io.camera_actions_dev == cam_act.data_ptr()), \
             'action tensors must be contiguous f32/f64 (or int32 grid indices) on the engine device'
         self.outputs = None
-        if self.frame_skip > 1 and not self.selection:
+        if self.frame_skip > 1 and not self.selection and not self.seat:
             # (the reward launch reads the last frame's masks; the fragment launch every frame's, for a mask term)
             shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus) or eng._info_attached()
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
@@ -1577,16 +1674,17 @@ class Stepper:
             self.keep = (self.keep, buf)
         self.ref = ctypes.byref(self.io)
         self._phase = 0                                   # steps into the current reset interval (graphs hold whole intervals)
-        self.warmup_steps = self.auto_reset if self.graph_steps > 0 else 0      # real steps the constructor runs (see the class note)
+        self._interval = 1 if self.seat and self.frame_skip > 1 else self.auto_reset      # _one() calls per reset interval (a seat fragment is a whole one)
+        self.warmup_steps = self._interval if self.graph_steps > 0 else 0      # real steps the constructor runs (see the class note)
         if self.selection and self.frame_skip > 1:
             eng.device_tick(self.frame_skip)              # (closes an open reset interval: fragments start on an interval boundary)
             if self.graph_steps == 0:
                 eng.device_tick(False)
         if self.graph_steps > 0:
-            assert self.auto_reset >= 1 and self.graph_steps % self.auto_reset == 0, \
+            assert self.auto_reset >= 1 and self.graph_steps % self._interval == 0, \
                 'graph replay needs auto_reset >= 1 (the auto-reset launch advances the device step counter) and whole reset intervals per graph'
             eng.device_tick(self.frame_skip if self.selection else self.auto_reset)
-            for _ in range(self.auto_reset):
+            for _ in range(self._interval):
                 self._one()                               # code objects loaded before the capture (one whole reset interval)
             torch.cuda.synchronize(eng.device)
             self.graph = torch.cuda.CUDAGraph()
@@ -1609,6 +1707,10 @@ class Stepper:
             status = 0
             for _ in range(self.frame_skip):
                 status = status or eng.lib.mate_engine_step_selected(eng._h, self.ref, None, self.frame_skip if self.frame_skip > 1 else self.auto_reset, eng._stream())
+        elif self.seat:
+            status = 0
+            for _ in range(self.frame_skip):
+                status = status or eng.lib.mate_engine_step_seated(eng._h, self.ref, None, self.auto_reset, eng._stream())
         elif self.versus is None:
             status = eng.lib.mate_engine_step(eng._h, self.ref, self.auto_reset, eng._stream())
         elif self.frame_skip > 1:
@@ -1623,12 +1725,12 @@ class Stepper:
         if self.graph is not None:
             while steps > 0 and self._phase != 0:         # finish a reset interval a previous call stopped in, launch by launch
                 self._one()
-                self._phase = (self._phase + 1) % self.auto_reset
+                self._phase = (self._phase + 1) % self._interval
                 steps -= 1
             while steps >= self.graph_steps:              # whole graphs (whole reset intervals)
                 self.graph.replay()
                 steps -= self.graph_steps
-            self._phase = steps % self.auto_reset
+            self._phase = steps % self._interval
         for _ in range(steps):
             self._one()
         if self.outputs is not None:

@@ -13,7 +13,7 @@ from mate_amd import constants as consts
 from mate_amd import spaces
 from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
-from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, channel_table, fragment_coefficient_table, mixture_table
+from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, channel_table, fragment_coefficient_table, mixture_table, seat_mode_of
 from mate_amd.utils import Message, Team, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
@@ -720,14 +720,19 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
 
     `training_information` = True: what the reference's mate.MoreTrainingInformation wrapper adds to the agents' infos, kept on the device
     behind every stepping call (Engine.enable_info_rows; attached behind the first reset()): `infos()` names the
-    columns, `target_dones()` is the per-target done of RepeatedRewardIndividualDone(target_done_at_destination=True)."""
+    columns, `target_dones()` is the per-target done of RepeatedRewardIndividualDone(target_done_at_destination=True).
+
+    `single_agent` = 'camera' | 'target': the reference's SingleCamera / SingleTarget -- the learner plays ONE agent of that team, the seat (`seat`:
+    'auto' = slot n - 1, or drawn per episode under shuffle_entities; 'draw'; an index; an [num_envs] int32 tensor), its teammates are the on-device
+    Greedy agents, `target_agent` / `camera_agent` / the mixtures name the OPPOSING team (Engine.enable_seat).  reset()
+    returns the seat's rows [num_envs, D]; step_single(action) returns (seat_obs, reward, done, info) with info['seat']."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
                  learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
-                 target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, **kwargs):
+                 target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, single_agent=None, seat='auto', **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -764,6 +769,21 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             episode_records = self._fragment['learner'] if self._fragment else 'target'
         self._episode_team = episode_records              # (attached behind the first reset(): Engine.enable_episode_records)
         self._training_information = bool(training_information)      # (attached behind the first reset(): Engine.enable_info_rows)
+        # single_agent = 'camera' | 'target': the reference's SingleCamera / SingleTarget (mate/wrappers/single_team.py) -- the learner plays ONE agent of that team,
+        # the seat; its teammates are the on-device Greedy agents, target_agent / camera_agent / the mixtures keep their meaning for the OPPOSING team
+        # (Engine.enable_seat).  Checked now, enabled with the policies.
+        assert single_agent in (None, 'camera', 'target'), f"single_agent = {single_agent!r}: None, 'camera' or 'target'"
+        if single_agent is None:
+            assert isinstance(seat, str) and seat == 'auto', "seat = ... belongs to single_agent = 'camera' | 'target'"
+        else:
+            seat_mode_of(seat, bool(self.config['shuffle_entities']))
+            assert not self._fragment, 'single_agent steps one frame per call: there is no fused K-frame seat flow (hold the action over K step_single calls)'
+            assert not camera_selection, 'single_agent: camera_selection plays the camera team itself'
+            assert (camera_agent if single_agent == 'camera' else target_agent) == 'greedy', \
+                f"single_agent = {single_agent!r}: the seat's teammates are the Greedy agents ({single_agent}_agent names an opposing team's agent only)"
+            assert set(_names_of(self._mixtures.get(single_agent))) <= {'greedy'}, f"single_agent = {single_agent!r}: the seat's teammates are the Greedy agents, not a mixture"
+            assert not any(self._channels), "single_agent: the seat flow carries no communication channel (its agents' launch is not the channel launch)"
+        self.single_agent, self._seat = single_agent, seat
         self._info_frames = 0                             # frames of the last stepping call (target_dones: individual_done is NaN behind a multi-frame one)
         assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
@@ -812,7 +832,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
-        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or ((self._mixtures or any(self._channels)) and not self._policies_on):
+        if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or ((self._mixtures or any(self._channels) or single_agent) and not self._policies_on):
             self.enable_greedy_policies()
 
     def seed(self, seed):
@@ -847,6 +867,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             shaper.observe_reset()
         if self._fragment:
             out = self._fragment_reset(env_mask)
+        if self.single_agent:
+            out = self.engine.seat_rows()[0]
         if self._episode_team and self.engine.episode_team is None:      # (behind the reward rows, which its launch reads)
             self.engine.enable_episode_records(self._episode_team)
         return out
@@ -989,6 +1011,9 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         for team, spec in enumerate(self._channels):
             if spec is not None and self.engine.channels[team] is None:
                 self.engine.set_channel(team, **spec)
+        if self.single_agent and self.engine.seat_obs is None:
+            assert (self.num_cameras if self.single_agent == 'camera' else self.num_targets) > 0, f'single_agent = {self.single_agent!r}: the scenario has no such agents'
+            self.engine.enable_seat(self.single_agent, self._seat)
         self._policies_on = True
 
     def communication_edges(self):
@@ -997,6 +1022,18 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         camera_communication_edges / target_communication_edges, per environment).  Views of engine-owned memory: copy what must outlive the next step."""
         self._need_policies()
         return tuple(self.engine.channel_edges(team) for team in (0, 1))
+
+    def step_single(self, action, **replay):
+        """One step of SingleCamera / SingleTarget (`single_agent`): `action` is the seat's, [num_envs, 2] reals or [num_envs] grid indices; the teammates
+        and the opponents act on the device.  Returns (seat_obs [num_envs, D], reward [num_envs], done [num_envs], info): the seat's row of the new
+        observations -- of the NEW episode's seat where the call restarted the environment --, the team's reward and done, and step()'s info plus
+        'seat' [num_envs] int32, the seat that row belongs to, and 'seat_acted', the seat whose action the step consumed.  The tensors are the engine's
+        own, rewritten by the next call.  `replay`: recorded draws, as Engine.step_seated takes them."""
+        assert self.single_agent, "built without single_agent = 'camera' | 'target'"
+        self.engine.step_seated(action, auto_reset=self.auto_reset, **replay)
+        _, rewards, done, info = self._result()
+        info.update(seat=self.engine.seat_index, seat_acted=self.engine.seat_acted)
+        return self.engine.seat_obs, rewards[0 if self.single_agent == 'camera' else 1], done, info
 
     def step_versus_greedy(self, team, joint_action):
         """MultiCamera(env, target_agent=GreedyTargetAgent()) for team = 'camera', MultiTarget(env,

@@ -101,18 +101,27 @@ def evaluate(env, joint_policy=None, verbose=False, history=None):
     return status
 
 
-def evaluate_batched(env, episodes, policy='greedy', chunk=16):
+def evaluate_batched(env, episodes, policy='greedy', chunk=16, seed=0):
     """Runs `env` (a BatchedMultiAgentTracking built with episode_records) under the on-device agents -- 'greedy': both teams' scripted
     agents, fused `chunk` frames per launch where both are the Greedy ones; 'random': the uniform policy -- until `episodes` episode
-    records have arrived.  Returns them, oldest first, [episodes, 16] f64 on the host."""
+    records have arrived.  An environment built with single_agent = ... runs a uniformly random learner in the seat (a generator seeded with
+    `seed`) among the on-device teammates, whatever `policy`.  Returns them, oldest first, [episodes, 16] f64 on the host."""
     import torch
     env.reset()
     # (an active communication channel is like a non-Greedy opponent: the fused launch delivers every message, so per-step calls)
     fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy' and not any(env.engine.mixtures) and not env.engine.channel_active())
     rows, have = [], 0
+    single = getattr(env, 'single_agent', None)
+    if single:
+        generator = torch.Generator(device=env.device).manual_seed(int(seed))
+        high = torch.tensor([env.engine._cfg.camera_rotation_step, env.engine._cfg.camera_zooming_step] if single == 'camera' else [env.engine._cfg.target_step_size] * 2,
+                            dtype=torch.float64, device=env.device)
     limit = (env.max_episode_steps + chunk) * (2 + episodes // env.num_envs)      # (every environment ends an episode within max_episode_steps frames)
     for _ in range(0, limit, chunk):
-        if policy == 'random':
+        if single:
+            for _ in range(chunk):
+                env.step_single((torch.rand((env.num_envs, 2), generator=generator, dtype=torch.float64, device=env.device) * 2.0 - 1.0) * high)
+        elif policy == 'random':
             env.rollout_random(chunk)
         elif fused:
             env.rollout_greedy(chunk)
@@ -181,6 +190,9 @@ def build_parser():
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--num-envs', type=int, default=None,
                     help='run the batched environment, this many episodes at a time, and report episode records (without: the N = 1 loop)')
+    ap.add_argument('--single-agent', choices=['camera', 'target'], default=None,
+                    help='with --num-envs: a uniformly random learner in ONE seat of that team among on-device Greedy teammates (mate.SingleCamera / mate.SingleTarget); '
+                         'the agent and mixture flags keep their meaning for the opposing team')
     ap.add_argument('--team', choices=['camera', 'target'], default='target',
                     help='with --num-envs: the team whose rewards the records hold (num_tracked is kept for the camera team)')
     return ap
@@ -196,10 +208,10 @@ def main(argv=None):
                                                  target_agent=args.target_agent, camera_agent=args.camera_agent,
                                                  target_mixture=args.target_mixture, camera_mixture=args.camera_mixture,
                                                  no_communication=args.no_communication, message_dropout=args.message_dropout,
-                                                 communication_range=args.communication_range, **overrides)
+                                                 communication_range=args.communication_range, single_agent=args.single_agent, **overrides)
         if args.policy == 'greedy':
             env.enable_greedy_policies()
-        records = evaluate_batched(env, args.episodes, args.policy)
+        records = evaluate_batched(env, args.episodes, args.policy, seed=args.seed)
         names = Engine.EPISODE_COLUMNS[EPISODE_REPORT]
         print(f'{len(records)} episodes of {args.config}, {args.num_envs} at a time, team {args.team}:')
         for name, column in zip(names, records[:, EPISODE_REPORT].T):
