@@ -903,6 +903,42 @@ int mate_engine_enable_seat(mate_engine *engine, int32_t team, int32_t mode, int
 int mate_engine_step_seated(mate_engine *engine, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream);
 int mate_engine_seat_rows(mate_engine *engine, const mate_step_io *io, void *stream);
 
+/* The learner's own messages through the team's channel: the environment's send_messages / receive_messages and the communication-edge counts of `info`
+ * (mate/environment.py) under the channel wrappers, as one launch on demand (csrc/message_rows.hpp: message_rows_kernel).  A message is `width` numbers of
+ * obs_dtype from sender s to recipient r of one team; one routing call handles at most one message per ordered pair and team.  `payload_dev` is [N][n][width]
+ * (one content per sender, to everyone it addresses) or, `pairwise`, [N][n][n][width] ([sender][recipient]).  `address_dev`: [N][n][n] uint8, [sender][recipient],
+ * non-zero = addressed, read at every launch; NULL: broadcast, to every slot of the team, the sender's own included (an edge like any other, distance 0).  A sent
+ * message arrives iff the team's channel (mate_engine_set_channel: disabled, range_limit over the positions of the current records, dropout_rate, mask) lets it;
+ * with no channel set everything arrives.  `inbox_dev`: [N][n recipient][n sender][width], the delivered content, zeros where nothing was sent or nothing arrived;
+ * the launch writes the whole block.  payload_dev and inbox_dev must be 16-byte aligned.
+ *
+ * mate_engine_enable_messages: per team; a NULL cfg disables.  It waits for the handle's launches and needs no mate_engine_policy_enable: the router reads the
+ * environments' records and the channel's settings, nothing of the on-device agents (mate_engine_set_channel itself needs it).  MATE_EINVAL: a team that is
+ * neither, a team without agents, a width outside [1, 65536], a missing or misaligned buffer.  A refused call changes nothing.  Enabling starts the counts afresh.
+ * mate_engine_route_messages: `team_mask` is 1 << MATE_TEAM_CAMERA, 1 << MATE_TEAM_TARGET or both, `round` lies in 0..15 and enters the draws' key (the
+ * reference's agents talk twice per step; a learner may route several times between two steps).  One launch for both teams; identical arguments at every call, no
+ * allocation, no synchronisation: capturable under mate_engine_device_tick.  MATE_EINVAL: a mask outside 1..3, a round outside 0..15.  MATE_ESTATE: a team of
+ * the mask that is not enabled, or no reset so far.  An environment whose episode is over (finished, waiting for a batched restart or for the caller's reset) is
+ * skipped and keeps every row.  Routing a team whose Greedy agents also act is allowed and does not reach them: their exchange is reference-format and stays
+ * where it is; no stepping flow changes a byte with messages enabled.
+ * Draws: one uniform per (team, round, sender, recipient), only where the team's dropout rate is > 0 and the message was sent: mate_engine_message_tape's
+ * [N][n][n] f64 tapes (NULL: Philox, stream 28, keyed by seed, global environment index, tick and round << 12 | team << 8 | sender << 4 | recipient, word .x as
+ * a 32-bit uniform -- independent of first_env_index and of sharding); its record buffers receive the uniform each verdict used, NaN where none was drawn.  All
+ * four hold until replaced.
+ * mate_engine_message_edges: the team's engine-owned matrices -- `sent`, `delivered` (int8 [N][n][n], [sender][recipient], of the last routing call), `step_edges`
+ * (int32 [N][n][n]: the deliveries since the last stepping launch, the reference's camera_ / target_communication_edges, which step reports and clears; two
+ * rounds of a pair within one step count 2), `total_edges` (int32 [N][n][n]: the reference's *_total_communication_edges of the episode as its last step left
+ * them, i.e. without the current step's), `agent_edges` (int32 [N][n][2]: out_ and in_communication_edges of `info`, the row and column sums of step_edges).  A
+ * (tick, episode) tag per team and environment in engine memory makes the counts a function of what a routing launch sees: a tick other than the tag's folds
+ * step_edges into total_edges and zeroes it, an episode other than the tag's zeroes both; mate_engine_seed, a reset of the whole batch and
+ * mate_engine_import_state clear the tags.  MATE_ESTATE before the team's first mate_engine_enable_messages. */
+typedef struct { int32_t width, pairwise; const void *payload_dev; const uint8_t *address_dev; void *inbox_dev; } mate_message_rows;
+int mate_engine_enable_messages(mate_engine *engine, int32_t team, const mate_message_rows *cfg);      /* NULL disables */
+int mate_engine_route_messages(mate_engine *engine, int32_t team_mask, int32_t round, void *stream);
+int mate_engine_message_edges(mate_engine *engine, int32_t team, int8_t **sent_dev, int8_t **delivered_dev, int32_t **step_edges_dev, int32_t **total_edges_dev,
+                              int32_t **agent_edges_dev);
+int mate_engine_message_tape(mate_engine *engine, const double *camera_u_dev, const double *target_u_dev, double *record_camera_u_dev, double *record_target_u_dev);
+
 #ifdef __cplusplus
 }
 #endif

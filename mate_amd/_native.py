@@ -91,6 +91,11 @@ class MateChannel(ctypes.Structure):
     _fields_ = [('disabled', ctypes.c_int32), ('range_limit', ctypes.c_double), ('dropout_rate', ctypes.c_double), ('mask_dev', ctypes.c_void_p)]
 
 
+class MateMessageRows(ctypes.Structure):
+    """mate_message_rows: one team's message buffers (mate_engine_enable_messages)."""
+    _fields_ = [('width', ctypes.c_int32), ('pairwise', ctypes.c_int32), ('payload_dev', ctypes.c_void_p), ('address_dev', ctypes.c_void_p), ('inbox_dev', ctypes.c_void_p)]
+
+
 P, I32, I64, U64, INT = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
 F64P, IO, TAPE = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(MateStepIO), ctypes.POINTER(MatePolicyTape)
 
@@ -135,6 +140,10 @@ PROTOTYPES = {
     'mate_engine_enable_seat': (INT, [P, I32, I32, I32, P, P, P, P]),
     'mate_engine_step_seated': (INT, [P, IO, TAPE, I32, P]),
     'mate_engine_seat_rows': (INT, [P, IO, P]),
+    'mate_engine_enable_messages': (INT, [P, I32, ctypes.POINTER(MateMessageRows)]),
+    'mate_engine_route_messages': (INT, [P, I32, I32, P]),
+    'mate_engine_message_edges': (INT, [P, I32, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)]),
+    'mate_engine_message_tape': (INT, [P, P, P, P, P]),
     'mate_engine_rollout_greedy': (INT, [P, IO, I32, I32, P]),
     'mate_engine_rollout_versus_greedy': (INT, [P, I32, IO, I32, I32, P]),
     'mate_engine_observe': (INT, [P, IO, P]),

@@ -19,7 +19,8 @@ DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('engine_kernels.hpp', 'r
                                                           'info_rows.hpp', 'info_kernels.hip',
                                                           'scripted_rows.hpp', 'scripted_kernels.hip',
                                                           'channel_rows.hpp', 'channel_kernels.hip',
-                                                          'seat_rows.hpp', 'seat_kernels.hip')] + [
+                                                          'seat_rows.hpp', 'seat_kernels.hip',
+                                                          'message_rows.hpp', 'message_kernels.hip', 'message_host.inc')] + [
     os.path.join(os.path.dirname(HERE), 'include', 'mate_engine.h')]
 OUT = os.path.join(HERE, 'lib', 'libmate_engine.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
@@ -77,6 +78,9 @@ CHANNEL_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_channel.json')
 # ... and the learner seat's (csrc/seat_kernels.hip: greedy_seat_kernel, seat_rows_kernel, tests/test_seat_host.py)
 SEAT_SRC = os.path.join(HERE, 'csrc', 'seat_kernels.hip')
 SEAT_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_seat.json')
+# ... and the learner's messages' (csrc/message_kernels.hip: message_rows_kernel, tests/test_message_host.py)
+MESSAGE_SRC = os.path.join(HERE, 'csrc', 'message_kernels.hip')
+MESSAGE_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_message.json')
 _REMARK = re.compile(r'remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Dynamic Stack|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\S+)')
 
 
@@ -95,11 +99,12 @@ N_SHAPE_GROUPS = 6      # csrc/shape_groups.hpp: the compiled scenario shapes in
 
 
 def _compile_and_link(out, extra=(), verbose=False, remarks=False):
-    """The engine as fourteen translation units compiled in parallel -- mate_engine.hip (host side, generic kernels, reset), one
+    """The engine as fifteen translation units compiled in parallel -- mate_engine.hip (host side, generic kernels, reset), one
     shape_group.hip per group of compiled scenario shapes, opponent_kernels.hip, headline_kernels.hip, episode_kernels.hip,
-    info_kernels.hip, scripted_kernels.hip, channel_kernels.hip and seat_kernels.hip -- and linked into `out`.  Returns the compilers' stderr (remarks) as
-    an octuple: of the engine's units, of the opponents' unit, of the headline's unit, of the episode records' unit, of the
-    training-information rows' unit, of the scripted opponents' unit, of the communication channels' unit, of the learner seat's unit."""
+    info_kernels.hip, scripted_kernels.hip, channel_kernels.hip, seat_kernels.hip and message_kernels.hip -- and linked into `out`.  Returns the compilers'
+    stderr (remarks) as a nonuple: of the engine's units, of the opponents' unit, of the headline's unit, of the episode records' unit, of the
+    training-information rows' unit, of the scripted opponents' unit, of the communication channels' unit, of the learner seat's unit, of the
+    learner's messages' unit."""
     import concurrent.futures
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objdir = os.path.join(os.path.dirname(OUT), 'obj', os.path.splitext(os.path.basename(out))[0])
@@ -114,6 +119,7 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     units += [(SCRIPTED_SRC, [], os.path.join(objdir, 'scripted_kernels.o'))]
     units += [(CHANNEL_SRC, [], os.path.join(objdir, 'channel_kernels.o'))]
     units += [(SEAT_SRC, [], os.path.join(objdir, 'seat_kernels.o'))]
+    units += [(MESSAGE_SRC, [], os.path.join(objdir, 'message_kernels.o'))]
 
     def compile_unit(unit):
         src, defs, obj = unit
@@ -126,7 +132,7 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     workers = max(1, min(len(units), int(os.environ.get('MATE_BUILD_JOBS', '0')) or (os.cpu_count() or 2)))
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
         results = list(pool.map(compile_unit, units))
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text = '', '', '', '', '', '', '', ''
+    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text = '', '', '', '', '', '', '', '', ''
     for (src, _, _), (cmd, done) in zip(units, results):
         if done.returncode != 0:
             sys.stderr.write(done.stderr)
@@ -145,6 +151,8 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
             channel_text += done.stderr
         elif src == SEAT_SRC:
             seat_text += done.stderr
+        elif src == MESSAGE_SRC:
+            message_text += done.stderr
         else:
             text += done.stderr
     link = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + [u[2] for u in units]
@@ -154,22 +162,23 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     if done.returncode != 0:
         sys.stderr.write(done.stderr)
         raise subprocess.CalledProcessError(done.returncode, link)
-    return text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text
+    return text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text
 
 
 def build_engine(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text = _compile_and_link(OUT, verbose=verbose, remarks=True)
+    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text = _compile_and_link(OUT, verbose=verbose, remarks=True)
     kernels, opponents, headline, episodes = parse_resources(text), parse_resources(opponent_text), parse_resources(headline_text), parse_resources(episode_text)
     info, scripted, channel, seat = parse_resources(info_text), parse_resources(scripted_text), parse_resources(channel_text), parse_resources(seat_text)
-    for path, table in ((RESOURCES, kernels), (OPPONENT_RESOURCES, opponents), (HEADLINE_RESOURCES, headline), (EPISODE_RESOURCES, episodes), (INFO_RESOURCES, info), (SCRIPTED_RESOURCES, scripted), (CHANNEL_RESOURCES, channel), (SEAT_RESOURCES, seat)):
+    message = parse_resources(message_text)
+    for path, table in ((RESOURCES, kernels), (OPPONENT_RESOURCES, opponents), (HEADLINE_RESOURCES, headline), (EPISODE_RESOURCES, episodes), (INFO_RESOURCES, info), (SCRIPTED_RESOURCES, scripted), (CHANNEL_RESOURCES, channel), (SEAT_RESOURCES, seat), (MESSAGE_RESOURCES, message)):
         with open(path, 'w') as f:
             json.dump(table, f, indent=1, sort_keys=True)
     # A kernel that needs private scratch memory (a spilled register, an outlined helper that takes the environment
     # context by reference) costs ~5 us more per LAUNCH than one that does not -- a third of the headline step.
-    bad = [k for k, r in list(kernels.items()) + list(opponents.items()) + list(headline.items()) + list(episodes.items()) + list(info.items()) + list(scripted.items()) + list(channel.items()) + list(seat.items()) if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
+    bad = [k for k, r in list(kernels.items()) + list(opponents.items()) + list(headline.items()) + list(episodes.items()) + list(info.items()) + list(scripted.items()) + list(channel.items()) + list(seat.items()) + list(message.items()) if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
     if bad:
         os.remove(OUT)
         raise RuntimeError('kernels with private scratch memory: ' + ', '.join(bad))

@@ -24,6 +24,7 @@
 #include "scripted_rows.hpp"
 #include "channel_rows.hpp"
 #include "seat_rows.hpp"
+#include "message_rows.hpp"
 
 using namespace mate;
 
@@ -110,6 +111,16 @@ struct Seat {            // mate_engine_enable_seat: the learner's seat among th
     int32_t *index = nullptr, *acted = nullptr;  // [N] each: the seat of the row's episode; the seat whose action the last agents' launch consumed
     int32_t *d_live = nullptr;                   // [N], allocated at the first enable: the environments greedy_seat_kernel ran in the call (an idle one keeps its row)
 };
+struct Messages {        // mate_engine_enable_messages, one per team: the learner's own messages through the team's channel (message_rows.hpp); the caller's three buffers, the draws (mate_engine_message_tape: hold until replaced), the engine-owned edge matrices, counts and tags
+    struct Team {
+        bool on = false, pairwise = false;
+        int width = 0;
+        const void *payload = nullptr; const uint8_t *address = nullptr; void *inbox = nullptr;
+        const double *tape_u = nullptr; double *record_u = nullptr;
+        int8_t *d_sent = nullptr, *d_delivered = nullptr;                          // [N][n][n] each, allocated at the first enable
+        int32_t *d_step = nullptr, *d_total = nullptr, *d_agent = nullptr, *d_tags = nullptr;      // [N][n][n], [N][n][n], [N][n][2], [N][2]
+    } team[2];
+};
 struct FragmentRows {    // mate_engine_enable_fragment_rows: scalars, masks, rows and K of `args` are the launch's own; the tables are engine-owned, one set per form
     bool on = false, f64 = false, need_masks = false;     // attached; the shaped rows' type; a mask term had a non-zero coefficient at enable
     FragmentArgs args{};
@@ -181,6 +192,7 @@ struct mate_engine {
     Scripted scripted;                   // the opponent mixtures
     Channels channel;                    // the communication channels
     Seat seat;                           // the learner's seat among on-device teammates
+    Messages messages;                   // the learner's own messages through the team's channel
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch

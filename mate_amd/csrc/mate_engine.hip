@@ -594,6 +594,13 @@ static int clear_episode_sums(mate_engine *e, hipStream_t stream) {
     HIP_TRY(hipMemsetAsync(e->episodes.d_sums, 0xff, (size_t)e->N * kEpisodeWords * sizeof(double), stream));
     return MATE_OK;
 }
+// The message counts' (tick, episode) tags (csrc/message_rows.hpp) likewise, behind seed(), a reset of the whole batch and import_state: every tag reads
+// (-1, -1), the next routing launch zeroes step_edges and total_edges of every environment it runs
+static int clear_message_tags(mate_engine *e, hipStream_t stream) {
+    for (const Messages::Team &m : e->messages.team)
+        if (m.d_tags) HIP_TRY(hipMemsetAsync(m.d_tags, 0xff, sizeof(int32_t) * 2 * (size_t)e->N, stream));
+    return MATE_OK;
+}
 
 extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     if (!e) return fail(MATE_EINVAL, "null engine");
@@ -606,6 +613,7 @@ extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     hipLaunchKernelGGL(rewind_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, e->last_stream, (const Params *)e->d_params, (const Ptrs)e->g);
     HIP_TRY(hipGetLastError());
     MATE_TRY(clear_episode_sums(e, e->last_stream));
+    MATE_TRY(clear_message_tags(e, e->last_stream));
     HIP_TRY(wait_for_launches(e));
     e->tick = 0;
     return MATE_OK;
@@ -1149,6 +1157,7 @@ extern "C" int mate_engine_reset(mate_engine *e, const uint8_t *env_mask_dev, co
             HIP_TRY(hipMemsetAsync(e->g.done_count, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
             e->steps_since_reset = 0; e->pending_interval = 0;
         }
+        MATE_TRY(clear_message_tags(e, (hipStream_t)stream));
     }
     return attached_behind_new_records(e, (hipStream_t)stream);
 }
@@ -1165,7 +1174,7 @@ extern "C" int mate_engine_reset_tape(mate_engine *e, const uint8_t *env_mask_de
     g.reset_mask = env_mask_dev;
     g.reset_tape = tape_dev; g.reset_tape_len = tape_len; g.reset_draws = draws_used_dev;
     MATE_TRY(launch_reset(e, g, env_mask_dev ? RESET_MASK : RESET_ALL, PH_PLACE | PH_LUT | PH_VIEW, (hipStream_t)stream));
-    if (!env_mask_dev) { e->was_reset = true; e->selection.masks_stale = false; }
+    if (!env_mask_dev) { e->was_reset = true; e->selection.masks_stale = false; MATE_TRY(clear_message_tags(e, (hipStream_t)stream)); }
     return attached_behind_new_records(e, (hipStream_t)stream);
 }
 
@@ -1506,6 +1515,7 @@ static bool one_launch_step(const mate_engine *e, const FusedCall &c, const Oppo
     return c.complete() && !e->sw.policy_split && !tape && !io->tape_camera_target_dev && !io->tape_goal_dev && !e->p.obs_f64 && op.one_launch;
 }
 #include "opponent_host.inc"      // the opponents' launches, setters and accessors
+#include "message_host.inc"       // the learner's own messages: enable, the routing launch, draws, accessors
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 
@@ -1837,6 +1847,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     hipLaunchKernelGGL(import_kernel, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, e->d_params, e->g, src_dev);
     HIP_TRY(hipGetLastError());
     MATE_TRY(clear_episode_sums(e, (hipStream_t)stream));
+    MATE_TRY(clear_message_tags(e, (hipStream_t)stream));
     // all environments step together, so they share one tick: adopt the imported one
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     int32_t tick = 0;

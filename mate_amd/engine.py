@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from mate_amd import _native, constants as consts, spaces
-from mate_amd._native import MateChannel, MateConfig, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
+from mate_amd._native import MateChannel, MateConfig, MateMessageRows, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_table, reward_term_keys      # noqa: F401 (this module's names too)
 from mate_amd.config import scenario_tables
 
@@ -246,6 +246,8 @@ class Engine:
         self.channels = [None, None]          # per team: None or the settings of its communication channel (set_channel)
         self._channel_tape = (None, None, None)      # the tensors mate_engine_channel_tape points at
         self._clear_seat()
+        self._clear_messages()
+        self._message_tape = (None, None, None)      # the tensors mate_engine_message_tape points at
         self.camera_action_grid = self.target_action_grid = None      # (set_action_grids)
         self.outer_capacity = 0           # knots of Camera.boundary_outer once it is built (enable_outer_boundary)
         # (reserve_rollout) the buffers: None or {'steps', 'search', 'camera_obs', 'target_obs', 'scalars', 'masks', '_calls': _run_rollout's cache}
@@ -298,6 +300,16 @@ class Engine:
         # while a learner's seat is enabled (enable_seat): the team's code, the mode, the seat's rows [N, D_team] (obs dtype), the seat of the
         # episode each row belongs to [N] int32, the seat whose action the last step_seated consumed [N] int32, the caller's tape (SEAT_TAPE)
         self.seat_team = self.seat_mode = self.seat_obs = self.seat_index = self.seat_acted = self._seat_tape = None
+
+    def _clear_messages(self, team=None):
+        # per team, while the learner's messages are enabled (enable_messages): the payload [N, n, M] / [N, n, n, M] and the inbox [N, n, n, M] (obs dtype),
+        # the address matrix [N, n, n] uint8 or None (broadcast), the width M and whether the payload is per [sender][recipient]
+        if team is None:
+            self.message_payload, self.message_address, self.message_inbox = [None, None], [None, None], [None, None]
+            self.message_width, self.message_pairwise = [0, 0], [False, False]
+        else:
+            self.message_payload[team] = self.message_address[team] = self.message_inbox[team] = None
+            self.message_width[team], self.message_pairwise[team] = 0, False
 
     def _clear_info_rows(self):
         # while the training-information rows are attached (enable_info_rows): [N, Nc, 2] / [N, Nt, 9] / [N, 24] f64, None for an output that is off
@@ -945,6 +957,85 @@ class Engine:
         io, keep = self._seat_io(None)
         check(self.lib.mate_engine_seat_rows(self._h, ctypes.byref(io), self._stream()))
         return self.seat_obs, self.seat_index
+
+    # ------------------------------------------------------------------ the learner's own messages through the team's channel (mate/environment.py: send_messages / receive_messages, the communication edges of `info`)
+    def enable_messages(self, team, width, pairwise=False, addressed=False):
+        """Fixed-width messages of `team`'s learner agents on the device: `width` numbers of the observation dtype per message, routed sender ->
+        recipient by route_messages() under the team's channel (set_channel; none: everything arrives).  Returns (payload, address, inbox): the
+        payload tensor the learner writes, [N, n, width] (one content per sender) or, `pairwise`, [N, n, n, width] ([sender][recipient]); with
+        `addressed` the [N, n, n] uint8 address matrix ([sender][recipient], non-zero = send; starts all ones), else None: every sender broadcasts
+        to every slot of its team, its own included; the inbox [N, n, n, width], [recipient][sender], zeros where nothing was sent or arrived.
+        Needs no enable_policies.  Enabling again with the same shapes keeps the tensors and starts the counts afresh."""
+        team = _team_code(team)
+        n, N, width = (self.num_cameras, self.num_targets)[team], self.num_envs, int(width)
+        if n == 0 or width < 1:
+            raise ValueError(f'enable_messages: a team with agents and width >= 1 (got {n} agents, width = {width})')
+        shape = (N, n, n, width) if pairwise else (N, n, width)
+        payload, address, inbox = self.message_payload[team], self.message_address[team], self.message_inbox[team]
+        with torch.cuda.device(self.device):
+            if payload is None or tuple(payload.shape) != shape:
+                payload = torch.zeros(shape, dtype=self.obs_dtype, device=self.device)
+            if inbox is None or tuple(inbox.shape) != (N, n, n, width):
+                inbox = torch.zeros((N, n, n, width), dtype=self.obs_dtype, device=self.device)
+            if not addressed:
+                address = None
+            elif address is None:
+                address = torch.ones((N, n, n), dtype=torch.uint8, device=self.device)
+        cfg = MateMessageRows(width, int(bool(pairwise)), payload.data_ptr(), None if address is None else address.data_ptr(), inbox.data_ptr())
+        check(self.lib.mate_engine_enable_messages(self._h, team, ctypes.byref(cfg)))
+        self.message_payload[team], self.message_address[team], self.message_inbox[team] = payload, address, inbox
+        self.message_width[team], self.message_pairwise[team] = width, bool(pairwise)
+        return payload, address, inbox
+
+    def disable_messages(self, team=None):
+        """Detach the messages of `team` (None: of both teams)."""
+        for t in ((0, 1) if team is None else (_team_code(team),)):
+            check(self.lib.mate_engine_enable_messages(self._h, t, None))
+            self._clear_messages(t)
+
+    def route_messages(self, teams=None, round=0):
+        """One launch: the payloads of `teams` ('camera' / 'target', a pair of them, None: every enabled team) go through their channels into the
+        inboxes, the edge counts follow (message_edges).  `round` (0..15) keys the dropout draws: route twice between two steps with two rounds.
+        Identical arguments at every call: replayable inside a Stepper graph (make_stepper(..., between=...))."""
+        if teams is None:
+            codes = [t for t in (0, 1) if self.message_inbox[t] is not None]
+        else:
+            codes = [_team_code(t) for t in (teams if isinstance(teams, (list, tuple)) else (teams,))]
+        status = self.lib.mate_engine_route_messages(self._h, sum(1 << t for t in set(codes)), int(round), self._stream())
+        if status != 0:
+            check(status)
+        return tuple(self.message_inbox[t] for t in codes)
+
+    MESSAGE_EDGES = ('sent', 'delivered', 'step_edges', 'total_edges', 'agent_edges')
+
+    def message_edges(self, team):
+        """{'sent', 'delivered': int8 [N, n, n] of the last routing call; 'step_edges': int32 [N, n, n], the deliveries since the last step (the
+        reference's *_communication_edges); 'total_edges': int32 [N, n, n], the episode's earlier steps (the reference's
+        *_total_communication_edges as its last step left them); 'agent_edges': int32 [N, n, 2], out_ / in_communication_edges of `info`}:
+        zero-copy views of the team's engine-owned matrices, [sender][recipient]."""
+        team = _team_code(team)
+        n, N = (self.num_cameras, self.num_targets)[team], self.num_envs
+        pointers = [ctypes.c_void_p() for _ in self.MESSAGE_EDGES]
+        check(self.lib.mate_engine_message_edges(self._h, team, *(ctypes.byref(p) for p in pointers)))
+        shapes = [(N, n, n)] * 4 + [(N, n, 2)]
+        typestrs = ['|i1', '|i1', '<i4', '<i4', '<i4']
+        return {name: torch.as_tensor(_EngineOwned(self, p.value, int(np.prod(shape)), typestr), device=self.device).view(shape)
+                for name, p, shape, typestr in zip(self.MESSAGE_EDGES, pointers, shapes, typestrs)}
+
+    def message_tape(self, camera_u=None, target_u=None, record=False):
+        """Recorded dropout uniforms for the routed messages ([N, n, n] f64 device tensors, [sender][recipient]; None: Philox) and -- `record` --
+        two tensors of those shapes that receive the uniform every verdict used, NaN where none was drawn (mate_engine_message_tape).  All hold
+        until replaced.  Returns (record_camera_u, record_target_u), or None."""
+        N, Nc, Nt = self.num_envs, self.num_cameras, self.num_targets
+        for name, value, n in (('camera_u', camera_u, Nc), ('target_u', target_u, Nt)):
+            self._check_tensor(name, value, torch.float64, (N, n, n))
+        records = None
+        if record:
+            records = tuple(torch.full((N, n, n), float('nan'), dtype=torch.float64, device=self.device) for n in (Nc, Nt))
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        check(self.lib.mate_engine_message_tape(self._h, ptr(camera_u), ptr(target_u), *(ptr(r) for r in (records or (None, None)))))
+        self._message_tape = (camera_u, target_u, records)
+        return records
 
     def _policy_tape(self, policy_tape, keep):
         if policy_tape is None:
@@ -1818,6 +1909,22 @@ class EngineGroups:
     def enable_info_rows(self, camera=True, target=True, cargo=True):
         """Engine.enable_info_rows on every group, each on its own stream; returns the groups' (camera, target, cargo) row tensors."""
         return self.each(lambda g, eng: eng.enable_info_rows(camera=camera, target=target, cargo=cargo))
+
+    def enable_messages(self, team, width, pairwise=False, addressed=False):
+        """Engine.enable_messages on every group; returns the groups' (payload, address, inbox) tensors."""
+        return self.each(lambda g, eng: eng.enable_messages(team, width, pairwise=pairwise, addressed=addressed))
+
+    def route_messages(self, teams=None, round=0):
+        """Engine.route_messages on every group, each on its own stream; returns the groups' inboxes."""
+        return self.each(lambda g, eng: eng.route_messages(teams, round))
+
+    def message_edges(self, team):
+        return self.each(lambda g, eng: eng.message_edges(team))
+
+    def message_tape(self, camera_u=None, target_u=None, record=False):
+        """Engine.message_tape on every group (`camera_u` / `target_u`: None, or one tensor per group); returns the groups' records."""
+        pick = lambda value, g: None if value is None else value[g]      # noqa: E731
+        return self.each(lambda g, eng: eng.message_tape(pick(camera_u, g), pick(target_u, g), record=record))
 
     def synchronize(self):
         for s in self.streams:

@@ -725,14 +725,20 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
     `single_agent` = 'camera' | 'target': the reference's SingleCamera / SingleTarget -- the learner plays ONE agent of that team, the seat (`seat`:
     'auto' = slot n - 1, or drawn per episode under shuffle_entities; 'draw'; an index; an [num_envs] int32 tensor), its teammates are the on-device
     Greedy agents, `target_agent` / `camera_agent` / the mixtures name the OPPOSING team (Engine.enable_seat).  reset()
-    returns the seat's rows [num_envs, D]; step_single(action) returns (seat_obs, reward, done, info) with info['seat']."""
+    returns the seat's rows [num_envs, D]; step_single(action) returns (seat_obs, reward, done, info) with info['seat'].
+
+    `camera_messages` / `target_messages` = M: the environment's own send_messages / receive_messages for that team's LEARNER agents, as tensors -- M
+    numbers of the observation dtype per message, routed on the device under the team's channel (no_communication / message_dropout /
+    communication_range apply to them as to the scripted agents' exchange), with the reference's communication-edge counts alongside
+    (send_messages, receive_messages, message_edges)."""
 
     def __init__(self, config=None, num_envs=1, device=0, seed=0, first_env_index=0, obs_dtype=torch.float32, auto_reset=True,
                  relative_coordinates=False, rescaled_observation=False, enhanced_observation=None, shared_field_of_view=None,
                  discrete_camera_levels=None, discrete_target_levels=None, state_rows=False,
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
                  learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
-                 target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, single_agent=None, seat='auto', **kwargs):
+                 target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, single_agent=None, seat='auto',
+                 camera_messages=None, target_messages=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -784,6 +790,13 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             assert set(_names_of(self._mixtures.get(single_agent))) <= {'greedy'}, f"single_agent = {single_agent!r}: the seat's teammates are the Greedy agents, not a mixture"
             assert not any(self._channels), "single_agent: the seat flow carries no communication channel (its agents' launch is not the channel launch)"
         self.single_agent, self._seat = single_agent, seat
+        # camera_messages / target_messages = M: the environment's own send_messages / receive_messages for that team's learner agents, M numbers of the
+        # observation dtype per message, routed on the device under the team's channel (Engine.enable_messages).  Checked now,
+        # enabled behind the engine's construction.
+        for name, width in (('camera_messages', camera_messages), ('target_messages', target_messages)):
+            if width is not None and (isinstance(width, bool) or not isinstance(width, (int, np.integer)) or width < 1):
+                raise ValueError(f'{name} = {width!r}: None or the message width, an integer >= 1')
+        self._message_widths = (camera_messages, target_messages)
         self._info_frames = 0                             # frames of the last stepping call (target_dones: individual_done is NaN behind a multi-frame one)
         assert not first_rows or self._fragment, 'first_rows belongs to frame_skip = K, learner = ... (the per-step flows hand the first rows over already)'
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
@@ -812,6 +825,10 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         # DiscreteCamera(levels) / DiscreteTarget(levels): integer action tensors are grid indices
         if discrete_camera_levels or discrete_target_levels:
             self.engine.set_action_grids(discrete_camera_levels, discrete_target_levels)
+        for team, width in enumerate(self._message_widths):
+            if width is not None:
+                assert (self.num_cameras, self.num_targets)[team] > 0, f"{('camera', 'target')[team]}_messages: the scenario has no such agents"
+                self.engine.enable_messages(team, int(width), pairwise=True, addressed=True)
 
         # the global state for centralised critics (RLlibMultiAgentCentralizedTraining, examples/utils/wrappers.py:114-121, 170-225):
         # True = raw rows, 'normalized' = mate.normalize_observation(state, state_space) fused into the row writer
@@ -1022,6 +1039,41 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         camera_communication_edges / target_communication_edges, per environment).  Views of engine-owned memory: copy what must outlive the next step."""
         self._need_policies()
         return tuple(self.engine.channel_edges(team) for team in (0, 1))
+
+    def send_messages(self, team, payload, address=None, round=0):
+        """The environment's send_messages for the learner agents of `team` ('camera' / 'target'; built with camera_messages / target_messages = M), one
+        call for the whole team and batch: `payload` is [num_envs, n, M] (one content per sender, to everyone it addresses) or [num_envs, n, n, M]
+        ([sender][recipient]); `address` [num_envs, n, n], non-zero = send, None: every sender broadcasts to every slot of its team, its own included
+        (route_messages).  At most one message per ordered pair and call; `round` (0..15) tells the calls between two steps apart.  The messages pass the
+        team's channel (no_communication / message_dropout / communication_range) at once; receive_messages(team) reads what arrived."""
+        code = 0 if team in ('camera', 0) else 1
+        assert team in ('camera', 'target', 0, 1) and self._message_widths[code] is not None, f'built without {team}_messages = M'
+        eng = self.engine
+        n, M = (self.num_cameras, self.num_targets)[code], int(self._message_widths[code])
+        payload = torch.as_tensor(payload, device=self.device).to(eng.obs_dtype)
+        assert tuple(payload.shape) in ((self.num_envs, n, M), (self.num_envs, n, n, M)), f'payload: [num_envs, n, M] or [num_envs, n, n, M], got {tuple(payload.shape)}'
+        eng.message_payload[code].copy_(payload if payload.dim() == 4 else payload[:, :, None, :].expand(-1, -1, n, -1))
+        if address is None:
+            eng.message_address[code].fill_(1)
+        else:
+            address = torch.as_tensor(address, device=self.device)
+            assert tuple(address.shape) == (self.num_envs, n, n), f'address: [num_envs, n, n], got {tuple(address.shape)}'
+            eng.message_address[code].copy_(address != 0)
+        eng.route_messages(code, round)
+
+    def receive_messages(self, team):
+        """(inbox, delivered) of the last send_messages(team): inbox [num_envs, n recipient, n sender, M], the delivered contents, zeros where nothing was
+        sent or arrived -- agent r's messages are inbox[:, r], in sender order; delivered [num_envs, n, n] int8, [sender][recipient].  The engine's own
+        tensors, rewritten by the next send_messages(team)."""
+        code = 0 if team in ('camera', 0) else 1
+        assert team in ('camera', 'target', 0, 1) and self._message_widths[code] is not None, f'built without {team}_messages = M'
+        return self.engine.message_inbox[code], self.engine.message_edges(code)['delivered']
+
+    def message_edges(self, team):
+        """{'sent', 'delivered', 'step_edges', 'total_edges', 'agent_edges'} of the team's learner messages (Engine.message_edges): 'step_edges' is the
+        reference's *_communication_edges (the deliveries since the last step), 'total_edges' its *_total_communication_edges as the last step left them,
+        'agent_edges'[:, a] = (out_communication_edges, in_communication_edges) of agent a's `info`."""
+        return self.engine.message_edges(team)
 
     def step_single(self, action, **replay):
         """One step of SingleCamera / SingleTarget (`single_agent`): `action` is the seat's, [num_envs, 2] reals or [num_envs] grid indices; the teammates
