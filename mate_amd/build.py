@@ -10,17 +10,25 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, 'csrc', 'mate_engine.hip')
-DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('engine_kernels.hpp', 'reset_kernels.hpp', 'policy_kernels.hpp', 'aux_kernels.hpp', 'attached_tile.hpp', 'state_rows.hpp', 'reward_rows.hpp', 'fragment_rows.hpp', 'selection_rows.hpp', 'device_math.hpp', 'instrument.hpp',
-                                                          'shape_groups.hpp', 'shape_group.inc', 'shape_group.hip', 'engine_host.h', 'opponent_host.inc',
-                                                          'opponent_rows.hpp', 'opponent_kernels.inc', 'opponent_kernels.hip',
-                                                          'headline_kernels.hpp', 'headline_kernels.hip',
-                                                          'episode_rows.hpp', 'episode_kernels.hip',
-                                                          'info_rows.hpp', 'info_kernels.hip',
-                                                          'scripted_rows.hpp', 'scripted_kernels.hip',
-                                                          'channel_rows.hpp', 'channel_kernels.hip',
-                                                          'seat_rows.hpp', 'seat_kernels.hip',
-                                                          'message_rows.hpp', 'message_kernels.hip', 'message_host.inc')] + [
+CSRC = os.path.join(HERE, 'csrc')
+SRC = os.path.join(CSRC, 'mate_engine.hip')
+# The translation units in link order: (object, source under csrc/, extra defines, resource record under lib/).  mate_engine.hip (host
+# side, generic kernels, reset) and one shape_group.hip per group of compiled scenario shapes (csrc/shape_groups.hpp) report into
+# kernel_resources.json, which tests/test_kernel_resources.py pins name by name and figure by figure.  A kernel that arrives later leaves
+# that record as it is: it comes in a unit of its own with a record of its own -- one row here, one entry in tests/test_unit_resources.py.
+UNITS = [('mate_engine', 'mate_engine.hip', (), 'kernel_resources.json')]
+UNITS += [(f'shape_group_{k}', 'shape_group.hip', (f'-DMATE_SHAPE_GROUP={k}',), 'kernel_resources.json') for k in range(6)]
+UNITS += [('opponent_kernels', 'opponent_kernels.hip', (), 'kernel_resources_opponents.json'),      # heuristic_drift_kernel, heuristic_camera_kernel
+          ('headline_kernels', 'headline_kernels.hip', (), 'kernel_resources_headline.json'),       # headline_rollout_kernel
+          ('episode_kernels', 'episode_kernels.hip', (), 'kernel_resources_episodes.json'),         # episode_rows_kernel
+          ('info_kernels', 'info_kernels.hip', (), 'kernel_resources_info.json'),                   # info_rows_kernel
+          ('scripted_kernels', 'scripted_kernels.hip', (), 'kernel_resources_scripted.json'),       # scripted_opponent_kernel
+          ('channel_kernels', 'channel_kernels.hip', (), 'kernel_resources_channel.json'),          # greedy_channel_kernel
+          ('seat_kernels', 'seat_kernels.hip', (), 'kernel_resources_seat.json'),                   # greedy_seat_kernel, seat_rows_kernel
+          ('message_kernels', 'message_kernels.hip', (), 'kernel_resources_message.json')]          # message_rows_kernel
+# Everything the library is built from: the sources in csrc/ by suffix (no editor backup, no stray object) in sorted order -- the same
+# digest on every machine -- and the public header.
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.splitext(f)[1] in ('.hip', '.hpp', '.h', '.inc')) + [
     os.path.join(os.path.dirname(HERE), 'include', 'mate_engine.h')]
 OUT = os.path.join(HERE, 'lib', 'libmate_engine.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
@@ -55,32 +63,7 @@ def needs_build():
         return True
 
 
-RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources.json')
-# The opponents' unit (csrc/opponent_kernels.hip) reports apart: kernel_resources.json is pinned, name by name and figure by figure, by
-# tests/test_kernel_resources.py; kernels that arrive in a unit of their own leave that record as it is and are checked by their own test.
-OPPONENT_SRC = os.path.join(HERE, 'csrc', 'opponent_kernels.hip')
-OPPONENT_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_opponents.json')
-# ... and so does the headline's unit (csrc/headline_kernels.hip: headline_rollout_kernel, tests/test_headline_resources.py)
-HEADLINE_SRC = os.path.join(HERE, 'csrc', 'headline_kernels.hip')
-HEADLINE_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_headline.json')
-# ... and the episode records' (csrc/episode_kernels.hip: episode_rows_kernel, tests/test_episode_host.py)
-EPISODE_SRC = os.path.join(HERE, 'csrc', 'episode_kernels.hip')
-EPISODE_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_episodes.json')
-# ... and the training-information rows' (csrc/info_kernels.hip: info_rows_kernel, tests/test_info_rows_host.py)
-INFO_SRC = os.path.join(HERE, 'csrc', 'info_kernels.hip')
-INFO_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_info.json')
-# ... and the scripted opponents' and mixtures' (csrc/scripted_kernels.hip: scripted_opponent_kernel, tests/test_scripted_host.py)
-SCRIPTED_SRC = os.path.join(HERE, 'csrc', 'scripted_kernels.hip')
-SCRIPTED_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_scripted.json')
-# ... and the communication channels' (csrc/channel_kernels.hip: greedy_channel_kernel, tests/test_channel_host.py)
-CHANNEL_SRC = os.path.join(HERE, 'csrc', 'channel_kernels.hip')
-CHANNEL_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_channel.json')
-# ... and the learner seat's (csrc/seat_kernels.hip: greedy_seat_kernel, seat_rows_kernel, tests/test_seat_host.py)
-SEAT_SRC = os.path.join(HERE, 'csrc', 'seat_kernels.hip')
-SEAT_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_seat.json')
-# ... and the learner's messages' (csrc/message_kernels.hip: message_rows_kernel, tests/test_message_host.py)
-MESSAGE_SRC = os.path.join(HERE, 'csrc', 'message_kernels.hip')
-MESSAGE_RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources_message.json')
+RESOURCES = os.path.join(HERE, 'lib', 'kernel_resources.json')      # (the engine's own record: UNITS)
 _REMARK = re.compile(r'remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Dynamic Stack|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\S+)')
 
 
@@ -95,90 +78,55 @@ def parse_resources(text):
     return kernels
 
 
-N_SHAPE_GROUPS = 6      # csrc/shape_groups.hpp: the compiled scenario shapes in six groups, one translation unit each
-
-
 def _compile_and_link(out, extra=(), verbose=False, remarks=False):
-    """The engine as fifteen translation units compiled in parallel -- mate_engine.hip (host side, generic kernels, reset), one
-    shape_group.hip per group of compiled scenario shapes, opponent_kernels.hip, headline_kernels.hip, episode_kernels.hip,
-    info_kernels.hip, scripted_kernels.hip, channel_kernels.hip, seat_kernels.hip and message_kernels.hip -- and linked into `out`.  Returns the compilers'
-    stderr (remarks) as a nonuple: of the engine's units, of the opponents' unit, of the headline's unit, of the episode records' unit, of the
-    training-information rows' unit, of the scripted opponents' unit, of the communication channels' unit, of the learner seat's unit, of the
-    learner's messages' unit."""
+    """The engine's translation units (UNITS) compiled in parallel and linked into `out`.  Returns the compilers' stderr (remarks) per
+    resource record, {record: text}, the units of one record concatenated in their order."""
     import concurrent.futures
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objdir = os.path.join(os.path.dirname(OUT), 'obj', os.path.splitext(os.path.basename(out))[0])
     os.makedirs(objdir, exist_ok=True)
-    compile_flags = [f for f in FLAGS if f != '-shared'] + list(extra) + ['-DMATE_SPLIT_BUILD'] + (['-Rpass-analysis=kernel-resource-usage'] if remarks else [])
-    units = [(SRC, [], os.path.join(objdir, 'mate_engine.o'))]
-    units += [(os.path.join(HERE, 'csrc', 'shape_group.hip'), [f'-DMATE_SHAPE_GROUP={k}'], os.path.join(objdir, f'shape_group_{k}.o')) for k in range(N_SHAPE_GROUPS)]
-    units += [(OPPONENT_SRC, [], os.path.join(objdir, 'opponent_kernels.o'))]
-    units += [(HEADLINE_SRC, [], os.path.join(objdir, 'headline_kernels.o'))]
-    units += [(EPISODE_SRC, [], os.path.join(objdir, 'episode_kernels.o'))]
-    units += [(INFO_SRC, [], os.path.join(objdir, 'info_kernels.o'))]
-    units += [(SCRIPTED_SRC, [], os.path.join(objdir, 'scripted_kernels.o'))]
-    units += [(CHANNEL_SRC, [], os.path.join(objdir, 'channel_kernels.o'))]
-    units += [(SEAT_SRC, [], os.path.join(objdir, 'seat_kernels.o'))]
-    units += [(MESSAGE_SRC, [], os.path.join(objdir, 'message_kernels.o'))]
+    compile_flags = [f for f in FLAGS if f != '-shared'] + list(extra) + (['-Rpass-analysis=kernel-resource-usage'] if remarks else [])
+    objects = [os.path.join(objdir, name + '.o') for name, _, _, _ in UNITS]
 
-    def compile_unit(unit):
-        src, defs, obj = unit
-        cmd = [hipcc] + compile_flags + defs + ['-c', '-o', obj, src]
+    def compile_unit(unit, obj):
+        cmd = [hipcc] + compile_flags + list(unit[2]) + ['-c', '-o', obj, os.path.join(CSRC, unit[1])]
         if verbose:
             print(' '.join(cmd), flush=True)
         done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
         return cmd, done
 
-    workers = max(1, min(len(units), int(os.environ.get('MATE_BUILD_JOBS', '0')) or (os.cpu_count() or 2)))
+    # (a fixed cap, not os.cpu_count(): a job on a shared machine may use far fewer CPUs than the machine reports)
+    workers = max(1, int(os.environ.get('MATE_BUILD_JOBS', '0')) or min(len(UNITS), 16))
     with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-        results = list(pool.map(compile_unit, units))
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text = '', '', '', '', '', '', '', '', ''
-    for (src, _, _), (cmd, done) in zip(units, results):
+        results = list(pool.map(compile_unit, UNITS, objects))
+    texts = {}
+    for unit, (cmd, done) in zip(UNITS, results):
         if done.returncode != 0:
             sys.stderr.write(done.stderr)
             raise subprocess.CalledProcessError(done.returncode, cmd)
-        if src == OPPONENT_SRC:
-            opponent_text += done.stderr
-        elif src == HEADLINE_SRC:
-            headline_text += done.stderr
-        elif src == EPISODE_SRC:
-            episode_text += done.stderr
-        elif src == INFO_SRC:
-            info_text += done.stderr
-        elif src == SCRIPTED_SRC:
-            scripted_text += done.stderr
-        elif src == CHANNEL_SRC:
-            channel_text += done.stderr
-        elif src == SEAT_SRC:
-            seat_text += done.stderr
-        elif src == MESSAGE_SRC:
-            message_text += done.stderr
-        else:
-            text += done.stderr
-    link = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + [u[2] for u in units]
+        texts[unit[3]] = texts.get(unit[3], '') + done.stderr
+    link = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', out] + objects
     if verbose:
         print(' '.join(link), flush=True)
     done = subprocess.run(link, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     if done.returncode != 0:
         sys.stderr.write(done.stderr)
         raise subprocess.CalledProcessError(done.returncode, link)
-    return text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text
+    return texts
 
 
 def build_engine(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    text, opponent_text, headline_text, episode_text, info_text, scripted_text, channel_text, seat_text, message_text = _compile_and_link(OUT, verbose=verbose, remarks=True)
-    kernels, opponents, headline, episodes = parse_resources(text), parse_resources(opponent_text), parse_resources(headline_text), parse_resources(episode_text)
-    info, scripted, channel, seat = parse_resources(info_text), parse_resources(scripted_text), parse_resources(channel_text), parse_resources(seat_text)
-    message = parse_resources(message_text)
-    for path, table in ((RESOURCES, kernels), (OPPONENT_RESOURCES, opponents), (HEADLINE_RESOURCES, headline), (EPISODE_RESOURCES, episodes), (INFO_RESOURCES, info), (SCRIPTED_RESOURCES, scripted), (CHANNEL_RESOURCES, channel), (SEAT_RESOURCES, seat), (MESSAGE_RESOURCES, message)):
-        with open(path, 'w') as f:
-            json.dump(table, f, indent=1, sort_keys=True)
-    # A kernel that needs private scratch memory (a spilled register, an outlined helper that takes the environment
-    # context by reference) costs ~5 us more per LAUNCH than one that does not -- a third of the headline step.
-    bad = [k for k, r in list(kernels.items()) + list(opponents.items()) + list(headline.items()) + list(episodes.items()) + list(info.items()) + list(scripted.items()) + list(channel.items()) + list(seat.items()) + list(message.items()) if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
+    bad = []
+    for record, text in _compile_and_link(OUT, verbose=verbose, remarks=True).items():
+        kernels = parse_resources(text)
+        with open(os.path.join(HERE, 'lib', record), 'w') as f:
+            json.dump(kernels, f, indent=1, sort_keys=True)
+        # A kernel that needs private scratch memory (a spilled register, an outlined helper that takes the environment
+        # context by reference) costs ~5 us more per LAUNCH than one that does not -- a third of the headline step.
+        bad += [k for k, r in kernels.items() if r.get('ScratchSize', 0) != 0 or r.get('Dynamic Stack') != 'False']
     if bad:
         os.remove(OUT)
         raise RuntimeError('kernels with private scratch memory: ' + ', '.join(bad))

@@ -1,5 +1,5 @@
 // headline_kernels.hip -- headline_rollout_kernel (headline_kernels.hpp), both store forms, as a translation unit of its own: its kernel-resource remarks
-// are kept apart from the other units' (mate_amd/build.py: lib/kernel_resources_headline.json).  Included by mate_engine.hip in a single-unit build.
+// are kept apart from the other units' (mate_amd/build.py: lib/kernel_resources_headline.json).
 #include <hip/hip_runtime.h>
 #include "headline_kernels.hpp"
 

@@ -44,34 +44,6 @@ static int fail(int code, const char *fmt, ...) {
     } while (0)
 #define MATE_TRY(expr) do { const int rc_ = (expr); if (rc_ != MATE_OK) return rc_; } while (0)      // (an engine function's own status: the error text is set)
 
-// Without -DMATE_SPLIT_BUILD (a plain `hipcc mate_engine.hip`, as the experiment scripts under tools/ do) the shape groups are
-// compiled right here, one after the other; mate_amd/build.py compiles them as translation units of their own, in parallel.
-#ifndef MATE_SPLIT_BUILD
-#define MATE_SHAPE_GROUP 0
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#define MATE_SHAPE_GROUP 1
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#define MATE_SHAPE_GROUP 2
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#define MATE_SHAPE_GROUP 3
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#define MATE_SHAPE_GROUP 4
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#define MATE_SHAPE_GROUP 5
-#include "shape_group.inc"
-#undef MATE_SHAPE_GROUP
-#include "opponent_kernels.inc"
-#include "headline_kernels.hip"
-#include "episode_kernels.hip"
-#include "info_kernels.hip"
-#include "scripted_kernels.hip"
-#endif
-
 // Kernels per (scenario shape, observation type): a compiled specialisation where one exists -- every scenario the reference
 // ships, shape_groups.hpp -- else the generic kernels.  step[flow]: the launch-flag specialisations (enum Flow) exist for f32
 // observations, the product path; f64 observations (the parity mirror) run the generic flow everywhere.

@@ -26,9 +26,8 @@
 // dynamic records; each target lane reads the (at most two) mask words that hold its row's camera bits.  f64 throughout, product then add
 // (-ffp-contract=off); fused where the Greedy agents' code fuses (norm2).
 //
-// This header holds the arguments and the launch function's declaration only; the kernel and that function are opponent_kernels.inc: not a
-// template, so compiled exactly once -- in a translation unit of its own (opponent_kernels.hip) under mate_amd/build.py, inside mate_engine.hip
-// in the single-unit build, as shape_group.inc is.
+// This header holds the arguments and the launch function's declaration only; the kernel and that function are opponent_kernels.hip: not a
+// template, so compiled exactly once, in a translation unit of its own (mate_amd/build.py: UNITS).
 #pragma once
 #include "attached_tile.hpp"
 #include "policy_kernels.hpp"

@@ -1,7 +1,6 @@
 """Host-side tests of the communication channels (csrc/channel_rows.hpp), no GPU: the NumPy verdict of tests/channel_ref.py against the sent -> delivered
 matrices the reference's own wrappers recorded (tests/golden/channel_*.npz, tests/golden/make_channel_golden.py); the binomial rule; the Python-level
-validation and the evaluation script's flags; the resource record of the new translation unit; the build's sources; the C ABI's prototypes."""
-import json
+validation and the evaluation script's flags; the C ABI's prototypes (the unit's resource record and the source digest: tests/test_unit_resources.py)."""
 import os
 import re
 
@@ -12,7 +11,6 @@ import channel_ref as C
 import golden_util as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 FIXTURES = {      # name -> (no_communication, range_limit (-1: none), dropout_rate)
     'channel_4v8-9_none': ('both', -1.0, 0.0), 'channel_4v8-9_camera_only': ('target', -1.0, 0.0), 'channel_4v8-9_drop30': ('none', -1.0, 0.3),
     'channel_4v8-9_drop70': ('none', -1.0, 0.7), 'channel_4v8-9_range1400': ('none', 1400.0, 0.0), 'channel_8v8-9_range1000': ('none', 1000.0, 0.0),
@@ -111,27 +109,10 @@ def test_environment_arguments_are_checked_ahead_of_the_device():
             MultiAgentTracking('MATE-4v8-9.yaml', **kw)
 
 
-def test_resource_record_of_the_channel_unit():
-    """csrc/channel_kernels.hip reports apart (mate_amd/build.py): only greedy_channel_kernel instances, no scratch, no dynamic stack, no spills, no kernel
-    name of another record -- and kernel_resources.json is still the parent's, byte for byte: no existing kernel changed."""
-    with open(os.path.join(LIB, 'kernel_resources_channel.json')) as fh:
-        mine = json.load(fh)
-    assert len(mine) == 2 and all('greedy_channel_kernel' in name for name in mine)      # f32 and f64 observations, the generic shape
-    for name, r in mine.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0, (name, r)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json',
-                  'kernel_resources_info.json', 'kernel_resources_scripted.json'):
-        with open(os.path.join(LIB, other)) as fh:
-            assert not set(json.load(fh)) & set(mine), other
-    with open(os.path.join(LIB, 'kernel_resources.json'), 'rb') as a, open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json'), 'rb') as b:
-        assert a.read() == b.read()
-
-
 def test_sources_are_in_the_digest_and_the_header_declares_the_calls():
+    """(The digest: tests/test_unit_resources.py.)"""
     import ctypes
-    from mate_amd import _native, build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'channel_rows.hpp', 'channel_kernels.hip'} <= names
+    from mate_amd import _native
     with open(os.path.join(ROOT, 'include', 'mate_engine.h')) as fh:
         header = fh.read()
     assert re.search(r'#define\s+MATE_ABI_VERSION\s+1\b', header)

@@ -1,11 +1,10 @@
 """Host side of the episode records (csrc/episode_rows.hpp, mate_engine_enable_episode_records): the contract's restatement
 (tests/episode_ref.py: EpisodeSums) against the restated callback of the reference's trainers (MetricCollector / on_episode_end) over the
-fragment fixtures, in both forms; the header, the column tuple, the kernel's resource report, the build's source list and the evaluate
-command's arguments.  No GPU.
+fragment fixtures, in both forms; the header, the column tuple and the evaluate command's arguments (the kernel's resource record
+and the source digest: tests/test_unit_resources.py).  No GPU.
 
 Bound of the fixture comparisons: 1e-12 absolute.  The contract adds in step order, np.mean / np.sum pairwise; the sums have at most 24 f64
 terms below 8 each (tests/test_gpu_fragment.py uses the same bound with the same reasoning), so their roundings differ by a few 2^-50."""
-import json
 import os
 import re
 
@@ -17,7 +16,6 @@ import golden_util as G
 from test_fragment_host import FIXTURES, fragments_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 BOUND = 1e-12
 CHECKED = ('raw_reward', 'normalized_raw_reward', 'coverage_rate', 'real_coverage_rate', 'mean_transport_rate', 'num_delivered_cargoes',
            'episode_raw_reward', 'episode_normalized_raw_reward')
@@ -121,29 +119,6 @@ def test_sixteen_columns_by_name():
     from mate_amd.engine import Engine
     assert len(Engine.EPISODE_COLUMNS) == 16 == len(set(Engine.EPISODE_COLUMNS))
     assert Engine.EPISODE_COLUMNS == R.COLUMNS
-
-
-def _load(name):
-    path = os.path.join(LIB, name)
-    assert os.path.exists(path), 'run __graft_entry__.build() first'
-    with open(path) as fh:
-        return json.load(fh)
-
-
-def test_the_episode_kernel_reports_apart_and_without_scratch():
-    kernels = _load('kernel_resources_episodes.json')
-    assert len(kernels) == 1 and all('episode_rows_kernel' in name for name in kernels), sorted(kernels)
-    for name, r in kernels.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['VGPRs Spill'] == 0 and r['SGPRs Spill'] == 0, (name, r)
-    mine = set(kernels)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json'):
-        assert not mine & set(_load(other)), other
-
-
-def test_the_source_digest_covers_the_episode_sources():
-    from mate_amd import build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'episode_rows.hpp', 'episode_kernels.hip'} <= names
 
 
 def test_evaluate_parser_takes_num_envs_and_keeps_its_defaults():

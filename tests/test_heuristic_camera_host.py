@@ -1,11 +1,10 @@
 """The Heuristic camera opponent (mate_engine_set_camera_opponent), the parts that need no GPU: the NumPy restatement of the controller and
 of act() (tests/heuristic_camera_ref.py) against the recorded reference on every step of the three heuristic_camera_*.npz fixtures, the
-tables of mate_amd/heuristic_tables.py against the recorded mesh, grid and score rows, the argument rules of the Python surface, and the
-new kernel's resource record."""
+tables of mate_amd/heuristic_tables.py against the recorded mesh, grid and score rows, and the argument rules of the Python surface
+(the new kernel's resource record: tests/test_unit_resources.py)."""
 import ctypes
 import hashlib
 import inspect
-import json
 import os
 import re
 
@@ -137,20 +136,6 @@ def test_library_header_and_binding_agree():
         assert hasattr(lib, name) and name in _native.EXPORTED_SYMBOLS, name
         assert re.search(r'int\s+' + name + r'\s*\(', header), name
     assert '#define MATE_ABI_VERSION 1' in header                      # additive: the ABI number stays
-
-
-def test_heuristic_camera_kernel_resources():
-    """No scratch, no dynamic stack, no spills (tests/test_opponent_resources.py holds the same record to its register and occupancy
-    bounds)."""
-    path = os.path.join(ROOT, 'mate_amd', 'lib', 'kernel_resources_opponents.json')
-    assert os.path.exists(path), 'run __graft_entry__.build() first'
-    with open(path) as fh:
-        table = json.load(fh)
-    mine = {k: r for k, r in table.items() if 'heuristic_camera_kernel' in k}
-    assert len(mine) == 1, sorted(table)
-    (name, r), = mine.items()
-    print(name, r)
-    assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0
 
 
 @pytest.mark.parametrize('argv,expected', [(['--camera-agent', 'heuristic'], {'target_agent': 'greedy', 'camera_agent': 'heuristic'}),

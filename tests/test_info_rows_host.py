@@ -1,11 +1,10 @@
 """CPU: the NumPy restatement of MoreTrainingInformation (tests/info_ref.py) against every recorded reference trace, the census of the
 seven traces tests/test_gpu_info_rows.py replays, and the host side of the training-information rows (csrc/info_rows.hpp): prototypes,
-header, resource record, source digest, column names, the environment's argument.
+header, column names, the environment's argument (resource record and source digest: tests/test_unit_resources.py).
 
 The traces hold, for every step of the reference, its own target_dones, target_warehouse_distances (the norms, ahead of the wrapper's
 `- 75, max 0`), the colliding flags, the masks and the cargo arrays: from the fixture's positions, goals and masks the restatement must
 give exactly those -- np.linalg.norm of a 2-vector and `dx dx + dy dy, the root` are the same three operations."""
-import json
 import os
 import re
 
@@ -16,7 +15,6 @@ import golden_util as G
 import info_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 GPU_TRACES = ['trace_1v1-9_greedy_s7', 'trace_2v3-64_random_s8', 'trace_2v4-0_greedy_s5', 'trace_4v2-9_greedy_ep1_s22', 'trace_4v8-9_greedy_done',
               'trace_8v8-9_greedy_ep1_s21', 'trace_nav_greedy_s1']
 
@@ -105,29 +103,6 @@ def test_column_tuples():
         assert isinstance(names, tuple) and len(names) == width == len(set(names))
     assert (len(Engine.INFO_CAMERA_COLUMNS), len(Engine.INFO_TARGET_COLUMNS), len(Engine.INFO_CARGO_COLUMNS)) == (2, 9, 24)
     assert Engine.INFO_TARGET_COLUMNS[0] == 'goal' and Engine.INFO_TARGET_COLUMNS[6:] == ('individual_done', 'is_tracked', 'is_colliding')
-
-
-def _load(name):
-    path = os.path.join(LIB, name)
-    assert os.path.exists(path), 'run __graft_entry__.build() first'
-    with open(path) as fh:
-        return json.load(fh)
-
-
-def test_the_info_kernel_reports_apart_and_without_scratch():
-    kernels = _load('kernel_resources_info.json')
-    assert kernels and all('info_rows_kernel' in name for name in kernels), sorted(kernels)
-    for name, r in kernels.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['VGPRs Spill'] == 0 and r['SGPRs Spill'] == 0, (name, r)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json'):
-        assert not set(kernels) & set(_load(other)), other
-        assert not any('info_rows_kernel' in name for name in _load(other)), other
-
-
-def test_the_source_digest_covers_the_info_sources():
-    from mate_amd import build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'info_rows.hpp', 'info_kernels.hip', 'attached_tile.hpp'} <= names
 
 
 def test_training_information_argument_of_the_batched_environment():

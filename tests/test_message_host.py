@@ -1,9 +1,7 @@
 """Host-side tests of the learner's messages through the team's channel (csrc/message_rows.hpp), no GPU: the NumPy router of tests/message_ref.py against
 what the reference's own send_messages / receive_messages / step recorded under its channel wrappers (tests/golden/message_*.npz,
-tests/golden/make_message_golden.py); the tag rule of the counts; the C ABI's prototypes; the resource record of the new translation unit; the build's
-sources; the draws' stream; the refusals that need no device."""
+tests/golden/make_message_golden.py); the tag rule of the counts; the C ABI's prototypes; the draws' stream; the refusals that need no device."""
 import ctypes
-import json
 import os
 import re
 
@@ -14,7 +12,6 @@ import golden_util as G
 import message_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 FIXTURES = {      # name -> (no_communication, range_limit, dropout_rate, filtering)
     'message_4v8-9_nocomm_target': ('target', -1.0, 0.0, False), 'message_4v8-9_drop30': ('none', -1.0, 0.3, True), 'message_4v8-9_drop70': ('none', -1.0, 0.7, True),
     'message_4v8-9_range1400': ('none', 1400.0, 0.0, True), 'message_8v8-9_range1000': ('none', 1000.0, 0.0, True),
@@ -136,27 +133,8 @@ def test_header_prototypes_and_exports_agree():
         assert callable(getattr(Engine, method)) and callable(getattr(EngineGroups, method))
 
 
-def test_resource_record_of_the_message_unit():
-    """csrc/message_kernels.hip reports apart (mate_amd/build.py): message_rows_kernel for f32 and f64 payloads, no scratch, no dynamic stack, no spills, no
-    kernel name of another record -- and kernel_resources.json is still the parent's, byte for byte: no existing kernel changed."""
-    with open(os.path.join(LIB, 'kernel_resources_message.json')) as fh:
-        mine = json.load(fh)
-    assert len(mine) == 2 and all('message_rows_kernel' in name for name in mine) and {name[name.index('message_rows_kernel'):][19:21] for name in mine} == {'Id', 'If'}
-    for name, r in mine.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0, (name, r)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json',
-                  'kernel_resources_info.json', 'kernel_resources_scripted.json', 'kernel_resources_channel.json', 'kernel_resources_seat.json'):
-        with open(os.path.join(LIB, other)) as fh:
-            assert not set(json.load(fh)) & set(mine), other
-    with open(os.path.join(LIB, 'kernel_resources.json'), 'rb') as a, open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json'), 'rb') as b:
-        assert a.read() == b.read()
-
-
 def test_sources_are_in_the_digest_and_the_stream_is_new():
-    from mate_amd import build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'message_rows.hpp', 'message_kernels.hip', 'message_host.inc'} <= names
-    assert os.path.basename(build.MESSAGE_SRC) == 'message_kernels.hip' and os.path.basename(build.MESSAGE_RESOURCES) == 'kernel_resources_message.json'
+    """(The digest: tests/test_unit_resources.py.)"""
     csrc = os.path.join(ROOT, 'mate_amd', 'csrc')
     with open(os.path.join(csrc, 'message_rows.hpp')) as fh:
         text = fh.read()

@@ -1,7 +1,6 @@
 """CPU: the host side of the Naive / Random opponents and the opponent mixtures (csrc/scripted_rows.hpp) -- the restatement of tests/scripted_ref.py
-against NumPy's own RandomState.choice(p=) and against hand-worked cases of the reference's rules, the resource record of the new translation unit, the
-source digest, the header, and the Python-level validation that needs no device."""
-import json
+against NumPy's own RandomState.choice(p=) and against hand-worked cases of the reference's rules, the header, and the Python-level validation that needs no
+device (the unit's resource record and the source digest: tests/test_unit_resources.py)."""
 import os
 import re
 
@@ -13,7 +12,6 @@ import scripted_ref as R
 
 FIXTURES = ['naive_4v8-9', 'naive_2v4-0', 'naive_8v8-9', 'random_4v8-9', 'random_2v4-0']
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 
 
 def test_mixture_choice_is_random_state_choice():
@@ -77,25 +75,9 @@ def test_naive_and_random_rules_on_worked_cases():
     assert np.array_equal(out['final'][0, 0], R.box_sample(np.array([0.8, 0.8]), np.array([5.0, 2.5])))
 
 
-def test_resource_record_of_the_scripted_unit():
-    """csrc/scripted_kernels.hip reports apart (mate_amd/build.py): no scratch, no dynamic stack, no spills, and no kernel name of another record."""
-    with open(os.path.join(LIB, 'kernel_resources_scripted.json')) as fh:
-        mine = json.load(fh)
-    assert len(mine) == 1 and 'scripted_opponent_kernel' in next(iter(mine))
-    for name, r in mine.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0, (name, r)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json',
-                  'kernel_resources_info.json'):
-        with open(os.path.join(LIB, other)) as fh:
-            assert not set(json.load(fh)) & set(mine), other
-    with open(os.path.join(LIB, 'kernel_resources.json'), 'rb') as a, open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json'), 'rb') as b:
-        assert a.read() == b.read()      # no existing kernel changed
-
-
 def test_sources_are_in_the_digest_and_the_header_declares_the_calls():
-    from mate_amd import _native, build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'scripted_rows.hpp', 'scripted_kernels.hip'} <= names
+    """(The digest: tests/test_unit_resources.py.)"""
+    from mate_amd import _native
     with open(os.path.join(ROOT, 'include', 'mate_engine.h')) as fh:
         header = fh.read()
     assert re.search(r'#define\s+MATE_ABI_VERSION\s+1\b', header)

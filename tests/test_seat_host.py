@@ -1,8 +1,6 @@
 """Host-side tests of the learner's seat among on-device teammates (csrc/seat_rows.hpp), no GPU: the NumPy agents of tests/seat_ref.py against what the
 reference's own SingleCamera / SingleTarget recorded (tests/golden/seat_*.npz, tests/golden/make_seat_golden.py) and, with nobody absent, against the oracle's
-restatement of the agents, closed loop; the DRAW formula; the Python-level argument rules; the resource record of the new translation unit; the build's
-sources; the C ABI's prototypes and what of the refusal table needs no device."""
-import json
+restatement of the agents, closed loop; the DRAW formula; the Python-level argument rules; the C ABI's prototypes and what of the refusal table needs no device."""
 import os
 import re
 
@@ -13,7 +11,6 @@ import golden_util as G
 import seat_ref as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, 'mate_amd', 'lib')
 FIXTURES = {      # name -> (team, seat, shuffle_entities)
     'seat_camera_4v8-9': ('camera', 3, False), 'seat_camera_8v8-9_shuffle': ('camera', 4, True),
     'seat_target_4v8-9': ('target', 7, False), 'seat_target_4v8-9_fewcargo': ('target', 7, False),
@@ -136,26 +133,9 @@ def test_environment_arguments_are_checked_ahead_of_the_device():
             BatchedMultiAgentTracking('MATE-4v8-9.yaml', num_envs=2, **kw)
 
 
-def test_resource_record_of_the_seat_unit():
-    """csrc/seat_kernels.hip reports apart (mate_amd/build.py): greedy_seat_kernel and seat_rows_kernel for f32 and f64 observations, no scratch, no dynamic
-    stack, no spills, no kernel name of another record -- and kernel_resources.json is still the parent's, byte for byte: no existing kernel changed."""
-    with open(os.path.join(LIB, 'kernel_resources_seat.json')) as fh:
-        mine = json.load(fh)
-    assert len(mine) == 4 and sum('greedy_seat_kernel' in name for name in mine) == 2 and sum('seat_rows_kernel' in name for name in mine) == 2
-    for name, r in mine.items():
-        assert r['ScratchSize'] == 0 and r['Dynamic Stack'] == 'False' and r['SGPRs Spill'] == 0 and r['VGPRs Spill'] == 0, (name, r)
-    for other in ('kernel_resources.json', 'kernel_resources_opponents.json', 'kernel_resources_headline.json', 'kernel_resources_episodes.json',
-                  'kernel_resources_info.json', 'kernel_resources_scripted.json', 'kernel_resources_channel.json'):
-        with open(os.path.join(LIB, other)) as fh:
-            assert not set(json.load(fh)) & set(mine), other
-    with open(os.path.join(LIB, 'kernel_resources.json'), 'rb') as a, open(os.path.join(ROOT, 'tests', 'golden', 'kernel_resources_parent.json'), 'rb') as b:
-        assert a.read() == b.read()
-
-
 def test_sources_are_in_the_digest_and_the_header_declares_the_calls():
-    from mate_amd import _native, build
-    names = {os.path.basename(d) for d in build.DEPS}
-    assert {'seat_rows.hpp', 'seat_kernels.hip'} <= names
+    """(The digest: tests/test_unit_resources.py.)"""
+    from mate_amd import _native
     with open(os.path.join(ROOT, 'include', 'mate_engine.h')) as fh:
         header = fh.read()
     assert re.search(r'#define\s+MATE_ABI_VERSION\s+1\b', header)

@@ -2,8 +2,10 @@
 """Static instruction mix per phase of a fused rollout kernel.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -disable-machine-licm \
-          --cuda-device-only -DMATE_ISA_MARKS -S -o marked.s mate_amd/csrc/mate_engine.hip
+          --cuda-device-only -DMATE_ISA_MARKS -S -o marked.s mate_amd/csrc/shape_group.hip -DMATE_SHAPE_GROUP=0
     python tools/isa_phases.py marked.s [mangled-name-prefix]
+
+(shape group 0 holds MATE-4v8-9, the default prefix: csrc/shape_groups.hpp; another shape is another group's unit.)
 
 -DMATE_ISA_MARKS turns the ROLL_STAMP phase boundaries of rollout_kernel into assembler comments; this script
 cuts the kernel's text at them and counts VALU / SALU / LDS / VMEM instructions per segment (static counts: every
@@ -13,7 +15,7 @@ import re
 import sys
 
 path = sys.argv[1]
-prefix = sys.argv[2] if len(sys.argv) > 2 else '_ZN4mate14rollout_kernelIfNS_10FixedShapeILi4ELi8ELi9ELb0EEELi1EEE'
+prefix = sys.argv[2] if len(sys.argv) > 2 else '_ZN4mate14rollout_kernelIfNS_10FixedShapeILi4ELi8ELi9ELb0ELb0EEELi1ELi1EEE'
 names = {0: 'draws', 1: 'cameras', 2: 'targets', 3: 'visibility', 4: 'goals', 5: 'scratch', 6: 'pack', 7: 'loop head'}
 seg, inside = 'prologue', False
 counts = collections.OrderedDict()
