@@ -1,6 +1,7 @@
 // headline_kernels.hpp -- the fused random-policy rollout of ONE form, the headline's: MATE-4v8-9 (FixedShape 4 / 8 / 9), row image, held lane roles,
 // held step state, f32 rows, one environment per wave.  It is rollout_kernel<float, FixedShape<4, 8, 9, false, true>, FLOW_RANDOM, 1> (engine_kernels.hpp)
-// with the branches of the other forms folded away and its own versions of what moves the rows -- nothing that computes:
+// with the branches of the other forms folded away, its own versions of what moves the rows, and the cameras' kinematics -- the one phase that needs
+// nothing of the step it runs in -- computed sixteen steps per pass (headline_camera_pass, headline_camera_step) with the shared math, bit for bit:
 //   * headline_blocks   a pair's verdict selects the SOURCE of its block (the other's public state, or a block of zeros) instead of masking the
 //                       four to seven words that were read: same bytes (x & ~0 = x, x & 0 = the zero word), one select per pair;
 //   * headline_store    the row store: its form (Ptrs::store_shifted) is a template parameter of the kernel -- one form per instantiation, no branch per
@@ -8,7 +9,8 @@
 // The loop head is rollout_kernel's: with the launch arguments read once ahead of the loop (passed by value instead of through kernarg_ptrs) the compiler
 // spills 42 scalar registers instead of 13 and reloads them with 75 v_readlane per step instead of 21 -- on the unit that bounds the kernel -- so they are
 // still read where they are used.
-// Every phase that computes (draws, kinematics, views, scores) and the prologue / epilogue are the shared functions, called as rollout_kernel calls them.
+// Every other phase that computes (draws, the targets' kinematics, views, scores) and the prologue / epilogue are the shared functions, called as
+// rollout_kernel calls them.
 // The kernels live in a translation unit of their own (headline_kernels.hip) with a resource report of their own (mate_amd/build.py:
 // lib/kernel_resources_headline.json); the host picks them per launch (engine_host.h: plan_rollout_random).  No profiling stamps, no phase ablation,
 // no debug_skip: a launch that asks for any of them runs rollout_kernel.
@@ -92,6 +94,61 @@ __device__ __forceinline__ void headline_store(const Ctx<float> &c, uint64_t row
     }
 }
 
+// The cameras, sixteen steps per pass.  Under the random policy a camera's kinematics (simulate_cameras_held) are a function of its previous (ph, th) and
+// its own Philox words alone -- targets, views, goals and the episode's bookkeeping never feed back into them -- and run on 4 of 64 lanes at every step.
+// Here lane l stands for camera l >> 4 at step tick + (l & 15): one 64-lane Philox call, a scan of (ph, th) down each row of sixteen lanes, the pointwise
+// part (quotient, sine / cosine, root, products) once on every lane, and the lane keeps its step's values until headline_camera_step hands them over.
+// Same operations in the same order as step_draws and simulate_cameras_held: same bits.
+struct CameraAhead { double ph, th, sr2; float x, y; };
+
+// a row's lane takes `v` of the lane below it (DPP row_shr:1); the row's first lane keeps `keep`
+__device__ __forceinline__ double headline_row_pred(double keep, double v) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(v), 0x111, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(keep), __double2hiint(v), 0x111, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// `tick`: the tick of the step at hand (the row's first lane's).  The cameras' current pair is the record's in LDS, c.phi / c.theta: written at every step,
+// and what a launch, a restart or an imported state starts from.
+__device__ __forceinline__ void headline_camera_pass(Ctx<float> &c, uint32_t tick, CameraAhead &a) {
+    const Params &p = c.p;
+    const int cam = c.lane >> 4;
+    const uint32_t t = tick + (uint32_t)(c.lane & 15);
+    // the lane's own block; the two lanes that share one compute it twice (no carry, no parity case)
+    const U4 w = philox(p.seed_lo, p.seed_hi, c.env_global(), t >> 1, S_ACT_CAM, (uint32_t)cam);
+    const uint32_t w0 = (t & 1u) ? w.z : w.x, w1 = (t & 1u) ? w.w : w.y;
+    const double da = clip_uniform(action_component(w0, p.rot), -p.rot, p.rot);
+    const double dz = clip_uniform(action_component(w1, p.zoom), -p.zoom, p.zoom);
+    // the scan, systolic: in round j every lane steps from the pair of the lane below it, the row's first lane from the camera's current pair; behind
+    // round j the lanes 0..j of a row hold their step's pair (a lane above them holds a pair stepped from an unfinished one: an angle in range like any other)
+    double pph = c.phi(cam), pth = c.theta(cam);
+    double ph = normalize_angle(pph + da);
+    double th = clip_uniform(pth + dz, p.theta_min, kMaxViewingAngle);
+#pragma clang loop unroll(disable)
+    for (int j = 1; j < 16; ++j) {
+        pph = headline_row_pred(pph, ph); pth = headline_row_pred(pth, th);
+        ph = normalize_angle(pph + da);
+        th = clip_uniform(pth + dz, p.theta_min, kMaxViewingAngle);
+    }
+    const double sr2 = div_nz(p.area, th);
+    float sn, cs;
+    sincos_deg_f32(ph, sn, cs);
+    const float srf = sqrt_f32_1ulp((float)sr2);
+    a.ph = ph; a.th = th; a.sr2 = sr2; a.x = srf * cs; a.y = srf * sn;
+}
+
+// The step's hand-over, in place of simulate_cameras_held: the four lanes whose step this is write the words it writes.
+__device__ __forceinline__ void headline_camera_step(Ctx<float> &c, int r, const CameraAhead &a) {
+    if ((c.lane & 15) == (r & 15)) {
+        const int cam = c.lane >> 4;
+        c.phi(cam) = a.ph; c.theta(cam) = a.th;                // (the sector tests of the pair lanes read these)
+        c.sight2(cam) = a.sr2;
+        float *pc = c.pub_cam(cam), *row = c.img_cam_row(cam) + 13;
+        const float tf = (float)a.th;
+        pc[3] = a.x; pc[4] = a.y; pc[5] = tf; row[3] = a.x; row[4] = a.y; row[5] = tf;
+    }
+}
+
 // `SHIFTED`: the form of the row stores (image_store_form), what Ptrs::store_shifted says for this launch -- the host launches the instantiation that matches.
 template <bool SHIFTED>
 __global__ __launch_bounds__(256, 4) void headline_rollout_kernel(const Params *__restrict__ pp, const Ptrs g) {
@@ -145,6 +202,7 @@ __global__ __launch_bounds__(256, 4) void headline_rollout_kernel(const Params *
         draws_of_lane = draw_role(c);
     }
     HeldState h{};
+    CameraAhead ahead{};             // the lane's camera step of the pass at hand (headline_camera_pass)
     int finished = 0;                // the episode is over (wave-uniform)
     const uint32_t tick0 = g.tick;   // (launch arguments read once: inside the loop each read is a scalar load and a wait)
     const int n_steps = g.rollout_steps;
@@ -189,11 +247,13 @@ __global__ __launch_bounds__(256, 4) void headline_rollout_kernel(const Params *
             else { if (turn & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
         }
         HEADLINE_MARK(7);      // loop overhead: from the end of the previous step to here
+        if ((r & 15) == 0) headline_camera_pass(c, tick, ahead);      // (every launch starts one, whatever its first tick's parity)
+        HEADLINE_MARK(8);
         StepDraws draws{0.0, 0.0};
         pin_draw_role(draws_of_lane);
         draws = step_draws(c, tick, &carry, &draws_of_lane);
         HEADLINE_MARK(0);
-        simulate_cameras_held(c, draws, h);
+        headline_camera_step(c, r, ahead);
         HEADLINE_MARK(1);
         simulate_targets_held(c, draws, near, h);
         HEADLINE_MARK(2);

@@ -16,7 +16,8 @@ import sys
 
 path = sys.argv[1]
 prefix = sys.argv[2] if len(sys.argv) > 2 else '_ZN4mate14rollout_kernelIfNS_10FixedShapeILi4ELi8ELi9ELb0ELb0EEELi1ELi1EEE'
-names = {0: 'draws', 1: 'cameras', 2: 'targets', 3: 'visibility', 4: 'goals', 5: 'scratch', 6: 'pack', 7: 'loop head'}
+names = {0: 'draws', 1: 'cameras', 2: 'targets', 3: 'visibility', 4: 'goals', 5: 'scratch', 6: 'pack', 7: 'loop head',
+         8: 'camera pass'}      # (the headline unit's own: csrc/headline_kernels.hpp, prefix _ZN4mate23headline_rollout_kernelILb0EEE / ILb1EEE)
 seg, inside = 'prologue', False
 counts = collections.OrderedDict()
 ops = collections.defaultdict(collections.Counter)
