@@ -88,7 +88,7 @@
 extern "C" {
 #endif
 
-/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows, the target and camera opponents) is purely additive -- new symbols,
+/* Stays 1: everything added since (mate_engine_enable_state_rows / mate_engine_state_rows, mate_engine_enable_reward_rows, target selection, fragment rows, first rows, the target and camera opponents, the per-frame fragments) is purely additive -- new symbols,
  * no change to a struct or to an existing entry point's arguments -- so a binding built against the older header keeps working. */
 #define MATE_ABI_VERSION 1
 
@@ -682,6 +682,47 @@ typedef struct mate_first_rows {
     void  *final_obs_dev;  /* [N][A][D] obs_dtype or NULL: the row obs_dev held before the first row replaced it */
 } mate_first_rows;
 int mate_engine_enable_first_rows(mate_engine *engine, const mate_first_rows *config);   /* NULL detaches */
+
+/* FrameSkip fragments FRAME BY FRAME (csrc/frame_rows.hpp): the fragment above, built by one small launch behind each per-step call, so that a fragment of K
+ * frames is K calls of mate_engine_step_versus_greedy -- against any opponent the per-step flows have (Heuristic, mixtures, channels) and with every shaping
+ * term, since the per-step reward launch sees every frame's state.  The fused flow above stays exactly as it is; the two attach independently.
+ * While attached, mate_engine_step_versus_greedy for `team` (no other call) enqueues fragment_frame_kernel behind the stepping launch, the reward launch and
+ * the selection metrics and AHEAD of the restart (the fused fragment's position).  phase = the host's count of calls inside the open restart interval modulo
+ * `frames`; live = the call's scalar record does not say done = 2.  Per environment:
+ *   phase 0           frames_dev, done_dev, rewards_dev, info_dev, shaped_dev, restarted_dev are OVERWRITTEN with zeros first (no memset in front)
+ *   a live frame      frames_dev += 1; done_dev |= (done == 1); rewards_dev += (f64) columns 0, 1, 7 and the negated 7, in frame order; info_dev[0..1] += columns
+ *                     3, 4; info_dev[2..3] = columns 5, 6; shaped_dev[a] += the learner team's reward row of this call, in the row type
+ *   phase frames - 1  info_dev[0..1] /= frames_dev (0 where it is 0)
+ *   obs_dev           on the environment's last live frame of the fragment (done == 1, or live at the last phase) the learner team's rows of the call, a plain
+ *                     copy: the packer's fused transform (mate_engine_set_obs_transform) has been applied.  No live frame: the row is not written.
+ * With the Greedy opponents every tensor equals the fused fragment's bit for bit.  shaped_dev needs mate_engine_enable_reward_rows attached for `team` in
+ * overwrite mode with the same out_dtype: its launch stays in overwrite mode, so the per-frame rows stay defined, and all of its terms are available.
+ * first_rows != 0: on the call that closes a restart interval, behind the restart launch and ahead of the reward snapshot launch, the same kernel's second form
+ * runs -- for every environment whose record of the call says done != 0 (what the restart has restarted): final_obs_dev <- obs_dev (if set), obs_dev <- the
+ * call's rows (the restart has just packed the new episode's first rows there), restarted_dev = 1.
+ * Every stepping call for `team` needs auto_reset = a positive multiple of `frames`, io->scalars_dev 16-byte aligned and the team's observation rows.  No
+ * allocation, no synchronisation; under mate_engine_device_tick a captured interval has identical arguments at every replay.
+ * mate_engine_frame_fragment: the on-demand form over caller buffers (`rows`: scalars_dev and the team's rows) -- closes = 0: the frame form at `phase`;
+ * closes = 1: the second form (rows: the first rows), whatever first_rows says.  shaped_dev there reads the attached reward rows.
+ * MATE_EINVAL: an unknown team or out_dtype, a camera team without cameras, frames < 1, phase outside [0, frames), a stepping call whose auto_reset is not a
+ * positive multiple of frames or that lacks scalars_dev or the team's rows, info_dev without frames_dev, first_rows without obs_dev, buffers not aligned to their
+ * element, obs_dev = final_obs_dev, shaped_dev with an out_dtype other than the attached reward
+ * rows'.  MATE_ESTATE: shaped_dev while no overwrite-mode reward rows are attached for the team (at enable and at every call), attaching inside an open
+ * restart interval, before the first reset, pipelined restarts while attached.  A refused call changes nothing.  NULL `config` detaches. */
+typedef struct {
+    int32_t team;                      /* MATE_TEAM_CAMERA / MATE_TEAM_TARGET: the learner's */
+    int32_t frames;                    /* K >= 1 */
+    void *obs_dev, *final_obs_dev;     /* [N][A][D] obs_dtype each, or NULL */
+    uint8_t *restarted_dev;            /* [N] or NULL */
+    double *rewards_dev, *info_dev;    /* [N][4] each, or NULL */
+    uint8_t *done_dev;                 /* [N] or NULL */
+    int32_t *frames_dev;               /* [N] or NULL */
+    void *shaped_dev;                  /* [N][A] of out_dtype, or NULL */
+    int32_t out_dtype;                 /* of shaped_dev: MATE_OBS_F32 / MATE_OBS_F64 */
+    int32_t first_rows;                /* != 0: the second form behind the closing call's restart */
+} mate_frame_fragments;
+int mate_engine_enable_frame_fragments(mate_engine *engine, const mate_frame_fragments *config);
+int mate_engine_frame_fragment(mate_engine *engine, const mate_frame_fragments *config, const mate_step_io *rows, int32_t phase, int32_t closes, void *stream);
 
 /* Per-episode metric records (csrc/episode_rows.hpp): what the reference's example trainers report at every episode's end (examples/utils/callbacks.py:
  * MetricCollector's mean over the agents of each learner step's infos, CustomMetricCallback.on_episode_end's mean / last / episode_<key> sums over the

@@ -7,7 +7,7 @@ module raises, and every engine call that returns a non-zero status raises
 import ctypes
 import os
 
-__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'MateRewardRows', 'MateFragmentRows', 'MateFirstRows', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
+__all__ = ['lib', 'load', 'EngineError', 'MateConfig', 'MateLayout', 'MateStepIO', 'MatePolicyTape', 'MateRewardRows', 'MateFragmentRows', 'MateFirstRows', 'MateFrameFragments', 'LIB_PATH', 'check', 'EXPORTED_SYMBOLS']
 
 LIB_PATH = os.environ.get('MATE_ENGINE_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'libmate_engine.so')
 
@@ -86,6 +86,15 @@ class MateFirstRows(ctypes.Structure):
     _fields_ = [('rows_dev', ctypes.c_void_p), ('scalars_dev', ctypes.c_void_p), ('final_obs_dev', ctypes.c_void_p)]
 
 
+class MateFrameFragments(ctypes.Structure):
+    """mate_frame_fragments: the FrameSkip fragment built frame by frame behind the per-step calls (mate_engine_enable_frame_fragments / mate_engine_frame_fragment)."""
+    _fields_ = [
+        ('team', ctypes.c_int32), ('frames', ctypes.c_int32), ('obs_dev', ctypes.c_void_p), ('final_obs_dev', ctypes.c_void_p),
+        ('restarted_dev', ctypes.c_void_p), ('rewards_dev', ctypes.c_void_p), ('info_dev', ctypes.c_void_p), ('done_dev', ctypes.c_void_p),
+        ('frames_dev', ctypes.c_void_p), ('shaped_dev', ctypes.c_void_p), ('out_dtype', ctypes.c_int32), ('first_rows', ctypes.c_int32),
+    ]
+
+
 class MateChannel(ctypes.Structure):
     """mate_channel: one team's communication channel (mate_engine_set_channel)."""
     _fields_ = [('disabled', ctypes.c_int32), ('range_limit', ctypes.c_double), ('dropout_rate', ctypes.c_double), ('mask_dev', ctypes.c_void_p)]
@@ -160,6 +169,8 @@ PROTOTYPES = {
     'mate_engine_fragment_coefficients': (INT, [P, ctypes.POINTER(P), ctypes.POINTER(I32)]),
     'mate_engine_fragment_rows': (INT, [P, ctypes.POINTER(MateFragmentRows), IO, I32, P]),
     'mate_engine_enable_first_rows': (INT, [P, ctypes.POINTER(MateFirstRows)]),
+    'mate_engine_enable_frame_fragments': (INT, [P, ctypes.POINTER(MateFrameFragments)]),
+    'mate_engine_frame_fragment': (INT, [P, ctypes.POINTER(MateFrameFragments), IO, I32, I32, P]),
     'mate_engine_enable_episode_records': (INT, [P, I32, P, I64, P]),
     'mate_engine_clear_episode_records': (INT, [P, P]),
     'mate_engine_enable_info_rows': (INT, [P, P, P, P]),

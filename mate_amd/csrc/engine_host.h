@@ -14,6 +14,7 @@
 #include "reset_kernels.hpp"
 #include "reward_rows.hpp"
 #include "fragment_rows.hpp"
+#include "frame_rows.hpp"
 #include "selection_rows.hpp"
 #include "opponent_rows.hpp"
 #include "state_rows.hpp"
@@ -133,6 +134,15 @@ struct FirstRows {       // mate_engine_enable_first_rows: the caller's buffers;
     float *scalars = nullptr;                    // [N][8]: 2.0f everywhere behind the fragment launch, then the restart's own record (column 2 = 0) where it restarted
     void *final_obs = nullptr;                   // [N][A][D] obs_dtype or null: what the fragment's obs held before the first row replaced it
 };
+struct FrameFragments {  // mate_engine_enable_frame_fragments: the per-frame fragment (frame_rows.hpp); scalars, rows, reward_rows, phase and closes of `args` are the launch's own
+    bool on = false, first_rows = false;
+    int team = 0;
+    FrameArgs args{};                            // the caller's buffers, K, A, D, the shaped rows' type
+    // of the call in progress: set by mate_engine_step_versus_greedy for `team`, cleared when it returns (plan_attached reads them)
+    bool in_call = false;                        // the call enqueues the frame launch
+    bool closing = false;                        // ... and has enqueued it as the interval's last: its restart carries the second form
+    const float *call_scalars = nullptr; const void *call_rows = nullptr;      // ... over these buffers of the call
+};
 struct EpisodeRecords {  // mate_engine_enable_episode_records: scalars, masks, rows and K of `args` are the launch's own
     bool on = false;
     EpisodeArgs args{};                          // team, A, the caller's ring and counter, the engine-owned sums
@@ -193,7 +203,7 @@ struct mate_engine {
     Channels channel;                    // the communication channels
     Seat seat;                           // the learner's seat among on-device teammates
     Messages messages;                   // the learner's own messages through the team's channel
-    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
+    StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; FrameFragments frames; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
     int64_t timing_tick = 0;
@@ -308,6 +318,8 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   3b info        info_rows_kernel: MoreTrainingInformation's per-agent rows of the launch's last frame       attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step
 //   5 fragment     fragment_rows_kernel over the K frames of a fused learner-versus-greedy launch           attached_behind_step
+//   5' frame       fragment_frame_kernel behind a mate_engine_step_versus_greedy call of the attached team: that frame into the     attached_behind_step
+//                  per-frame fragment (frame_rows.hpp) -- the fused fragment's position
 //   5b first_rows  a memset node: every record of the first-row scalars reads 2.0f, "not restarted"          attached_behind_step
 //   5c episodes    episode_rows_kernel over the call's frames: the learner steps into the episodes' running    attached_behind_step
 //                  sums, one record per episode that ends (it reads 3's rows)
@@ -315,14 +327,16 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //                  stores the learner team's plain first rows and its record into the first-row buffers)
 //   6b first_rows  behind THAT restart only: fragment_rows_kernel, K = 1, twice over the restart's records   attached_behind_restart
 //                  -- obs -> final_obs (plain copy; where asked for), then first rows -> obs (column table)
+//   6b' frame      behind the restart of the call that closes an interval, where first rows were asked for: fragment_frame_kernel's     attached_behind_restart
+//                  second form -- obs -> final_obs, the call's rows (now the first rows) -> obs, restarted = 1
 //   6c             with reward rows the snapshot-only launch; with info rows theirs                        attached_behind_restart
 //   7 action_mask  selection_kernel, SELECTION_ACTION_MASK: of the rows the learner sees next               attached_last
 //   8 state        state_rows_kernel, last                                                                  attached_last
 //   9 seat         seat_rows_kernel behind everything of a mate_engine_step_seated call: the seat's row, the seat      seat_rows_behind
 struct Tiles { unsigned blocks = 0, threads = 256; size_t lds = 0; int E = 0; };      // grid, workgroup, dynamic LDS, environments per workgroup (blocks 0: no launch)
 struct AttachedPlan {
-    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, episodes = false, info = false, action_mask = false, state = false;
-    Tiles soft_coverage, reward_rows, selection, fragment_rows, episode_rows, info_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
+    bool execute = false, reward = false, observe = false, fragment = false, first_rows = false, frame = false, frame_first = false, episodes = false, info = false, action_mask = false, state = false;
+    Tiles soft_coverage, reward_rows, selection, fragment_rows, frame_rows, episode_rows, info_rows, state_rows;      // (selection: the three phases are one kernel on one grid)
 };
 static Tiles plan_attached_tile(const mate_engine *e) { return {blocks_of(e, kAttachedEnvsPerBlock), 256, (size_t)attached_tile_lds_bytes(e->p.DW), kAttachedEnvsPerBlock}; }      // the shared tile of attached_tile.hpp
 static Tiles plan_soft_coverage(const mate_engine *e) { return {(unsigned)((e->N * e->p.Nc + 3) / 4), 256, 0, 0}; }      // a wave per (environment, camera)
@@ -349,6 +363,9 @@ static AttachedPlan plan_attached(const mate_engine *e, bool selected, int fused
     pl.reward = e->reward.on;
     pl.fragment = e->fragment.on && fused_team == e->fragment.args.team;
     pl.first_rows = pl.fragment && e->first.on;
+    pl.frame = e->frames.on && e->frames.in_call;
+    pl.frame_first = pl.frame && e->frames.closing && e->frames.first_rows;
+    if (pl.frame) pl.frame_rows = plan_fragment_rows(e);
     pl.episodes = e->episodes.on;
     pl.info = e->info.on;
     pl.state = e->state.on();

@@ -724,6 +724,7 @@ static int launch_info(mate_engine *e, const AttachedPlan &pl, int mode, const f
     HIP_TRY(launch_info_rows(pl.info_rows.blocks, pl.info_rows.lds, stream, e->d_params, a));
     return MATE_OK;
 }
+static int launch_frame_of_call(mate_engine *e, const AttachedPlan &pl, const mate_step_io *io, hipStream_t stream);      // (5', below)
 // What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
 // `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own);
 // `fused_team`: it is mate_engine_rollout_versus_greedy for that team (-1: any other call).
@@ -747,6 +748,7 @@ static int check_attached_call(const mate_engine *e, const mate_step_io *io, boo
         if (e->fragment.need_masks && !io->masks_dev)
             return fail(MATE_EINVAL, "fragment rows are attached with a mask term (num_tracked / is_tracked): the call needs io->masks_dev");
     }
+    if (pipelined && e->frames.on) return fail(MATE_ESTATE, no_pipeline, "per-frame fragments are", "frame_fragments", "them");
     if (pipelined && e->episodes.on) return fail(MATE_ESTATE, no_pipeline, "episode records are", "episode_records", "them");
     if (e->episodes.on) {      // (the episode launch walks the call's scalar records, 16 bytes at a time; the masks are optional: without them num_tracked reads NaN)
         if (!io || !io->scalars_dev || (reinterpret_cast<uintptr_t>(io->scalars_dev) & 15u))
@@ -779,8 +781,29 @@ static int attached_behind_step(mate_engine *e, bool selected, const mate_step_i
         a.rows = a.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev;
         MATE_TRY(launch_fragment_rows(e, pl.fragment_rows, a, e->fragment.f64, stream));
     }
+    if (pl.frame) MATE_TRY(launch_frame_of_call(e, pl, io, stream));
     if (pl.first_rows) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->first.scalars), 0x40000000 /* 2.0f */, 8 * (size_t)e->N, stream));
     if (pl.episodes) MATE_TRY(launch_episode_records(e, pl, io, frames, stream));
+    return MATE_OK;
+}
+// 5': the call's frame into the per-frame fragment.  phase: the calls already made inside the open restart interval, modulo K; the call closes the interval
+// where its restart follows (restart_finished: auto_reset = 1, or the interval's last call) -- its second form then goes behind that restart (6b')
+static int launch_frame_of_call(mate_engine *e, const AttachedPlan &pl, const mate_step_io *io, hipStream_t stream) {
+    FrameFragments &f = e->frames;
+    FrameArgs a = f.args;
+    a.scalars = io->scalars_dev;
+    a.rows = f.team == MATE_TEAM_CAMERA ? io->camera_obs_dev : io->target_obs_dev;
+    a.reward_rows = a.shaped ? (f.team == MATE_TEAM_CAMERA ? e->reward.args.cam_rows : e->reward.args.tgt_rows) : nullptr;
+    a.phase = (int32_t)(e->steps_since_reset % a.K); a.closes = 0;
+    f.call_scalars = a.scalars; f.call_rows = a.rows;
+    HIP_TRY(launch_fragment_frame(e->p.obs_f64 != 0, pl.frame_rows.blocks, stream, a));
+    return MATE_OK;
+}
+static int launch_frame_first_rows(mate_engine *e, const AttachedPlan &pl, hipStream_t stream) {
+    FrameArgs a = e->frames.args;
+    a.scalars = e->frames.call_scalars; a.rows = e->frames.call_rows; a.reward_rows = nullptr;
+    a.phase = a.K - 1; a.closes = 1;
+    HIP_TRY(launch_fragment_frame(e->p.obs_f64 != 0, pl.frame_rows.blocks, stream, a));
     return MATE_OK;
 }
 // One K = 1 launch of the fragment kernel over the first-row records: the rows of `src` through `columns` into `dst`, for exactly the environments whose record the restart
@@ -801,6 +824,7 @@ static int attached_behind_restart(mate_engine *e, hipStream_t stream, int fused
         if (e->first.final_obs) MATE_TRY(launch_first_rows(e, pl.fragment_rows, obs, e->first.final_obs, nullptr, stream));
         MATE_TRY(launch_first_rows(e, pl.fragment_rows, e->first.rows, obs, e->fragment.args.columns, stream));
     }
+    if (pl.frame_first) MATE_TRY(launch_frame_first_rows(e, pl, stream));
     if (pl.reward) MATE_TRY(launch_reward_rows(e, pl, REWARD_SNAPSHOT, nullptr, nullptr, stream));
     return pl.info ? launch_info(e, pl, INFO_SNAPSHOT, nullptr, nullptr, 1, stream) : MATE_OK;
 }
@@ -1320,6 +1344,7 @@ static int restart_finished(mate_engine *e, int auto_reset, const Restart &how, 
         if (++e->steps_since_reset < auto_reset) return MATE_OK;
     }
     e->steps_since_reset = 0; e->pending_interval = 0;
+    e->frames.closing = e->frames.in_call;      // (the restart of the call that has just enqueued its frame: the interval closes)
     Ptrs r = restart_ptrs(e, how.io);
     if (!how.keep_actions) { r.cam_act = r.tgt_act = nullptr; r.act_f64 = 0; r.act_discrete = 0; }
     if (plan_attached(e, false, how.fused_team).first_rows) {      // (the view launch computes the first view and packs it anyway: now it also stores -- the learner team's rows, its own record)
@@ -1488,6 +1513,7 @@ static bool one_launch_step(const mate_engine *e, const FusedCall &c, const Oppo
 }
 #include "opponent_host.inc"      // the opponents' launches, setters and accessors
 #include "message_host.inc"       // the learner's own messages: enable, the routing launch, draws, accessors
+#include "frame_host.inc"         // the per-frame FrameSkip fragments: enable, the call's check, the on-demand launch
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 
@@ -1553,7 +1579,13 @@ extern "C" int mate_engine_step_greedy(mate_engine *e, const mate_step_io *io, c
 
 extern "C" int mate_engine_step_versus_greedy(mate_engine *e, int32_t team, const mate_step_io *io, const mate_policy_tape *tape, int32_t auto_reset, void *stream) {
     if (team != MATE_TEAM_CAMERA && team != MATE_TEAM_TARGET) return fail(MATE_EINVAL, "team must be MATE_TEAM_CAMERA or MATE_TEAM_TARGET");
-    return attached_last(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
+    if (e && e->frames.on && e->frames.team == team) {      // (the call enqueues the frame launch: plan_attached reads in_call / closing while it runs)
+        MATE_TRY(check_frame_call(e, io, auto_reset));
+        e->frames.in_call = true; e->frames.closing = false;
+    }
+    const int rc = attached_last(e, step_with_policies(e, team, io, tape, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
+    if (e) e->frames.in_call = e->frames.closing = false;
+    return rc;
 }
 
 // The learner's seat among on-device teammates (include/mate_engine.h, csrc/seat_rows.hpp): step_with_policies' two-launch form with both teams the engine's,

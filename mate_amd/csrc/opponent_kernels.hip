@@ -1,8 +1,10 @@
 // opponent_kernels.hip -- heuristic_drift_kernel, heuristic_camera_kernel and their launch functions (opponent_rows.hpp describes them): the opponents' kernels
-// beyond the Greedy pair, both teams', as a translation unit of its own.  Their kernel-resource remarks are kept apart from the other units'
+// beyond the Greedy pair, both teams', as a translation unit of its own; and fragment_frame_kernel (frame_rows.hpp), the per-frame FrameSkip fragment that
+// makes those opponents usable under frame_skip > 1.  Their kernel-resource remarks are kept apart from the other units'
 // (mate_amd/build.py: lib/kernel_resources_opponents.json).
 #include <hip/hip_runtime.h>
 #include "opponent_rows.hpp"
+#include "frame_rows.hpp"
 
 namespace mate {
 
@@ -315,5 +317,11 @@ hipError_t launch_heuristic_camera(unsigned blocks, size_t lds, hipStream_t stre
     return hipGetLastError();
 }
 const void *heuristic_camera_function() { return reinterpret_cast<const void *>(heuristic_camera_kernel); }
+
+hipError_t launch_fragment_frame(bool obs_f64, unsigned blocks, hipStream_t stream, const FrameArgs &a) {
+    if (obs_f64) hipLaunchKernelGGL(fragment_frame_kernel<double>, dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(fragment_frame_kernel<float>, dim3(blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
 
 }  // namespace mate

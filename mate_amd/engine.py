@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from mate_amd import _native, constants as consts, spaces
-from mate_amd._native import MateChannel, MateConfig, MateMessageRows, MateFirstRows, MateFragmentRows, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
+from mate_amd._native import MateChannel, MateConfig, MateMessageRows, MateFirstRows, MateFragmentRows, MateFrameFragments, MateLayout, MatePolicyTape, MateRewardRows, MateStepIO, check
 from mate_amd.auxiliary_rewards import REWARD_REDUCTIONS, reward_coefficient_table, reward_term_keys      # noqa: F401 (this module's names too)
 from mate_amd.config import scenario_tables
 
@@ -285,6 +285,7 @@ class Engine:
         self.fragment_shaped = self.fragment_team = None
         self._fragment_coefficients_view = None      # (fragment_coefficients: built at every read, never kept)
         self.fragment_frame_skip, self._fragment_masks = 0, False
+        self.fragment_per_frame, self._frame_restarted = False, None      # (enable_fragment_rows(per_frame=True): built frame by frame behind step_versus_greedy)
         self._clear_first_rows()
 
     def _clear_first_rows(self):
@@ -1235,7 +1236,7 @@ class Engine:
             }
 
     def enable_fragment_rows(self, team, frame_skip, shaping=None, relative_coordinates=False, rescaled_observation=False, dtype=torch.float64,
-                             first_rows=False, final_obs=False):
+                             first_rows=False, final_obs=False, per_frame=False):
         """Attach the tail of the example trainers' wrapper chain -- RelativeCoordinates -> RescaledObservation ->
         RepeatedRewardIndividualDone -> [AuxiliaryCameraRewards | AuxiliaryTargetRewards] -> FrameSkip(frame_skip) -- to the fused
         K-frame launch: from now on rollout_versus_greedy(team, ...) (and a Stepper(versus=team, frame_skip=K) built afterwards)
@@ -1262,10 +1263,21 @@ class Engine:
         buffer of the plain first rows, fragment_first_scalars [N, 8] f32 the restart's own records (2.0 where nothing restarted).
         Costs one memset node and one or two K = 1 launches of the fragment kernel per call; no stepping kernel changes.  A restart that
         closes an interval because auto_reset or the flow changed (at the head of a later call) delivers no first rows.
+        `per_frame` = True builds the SAME tensors frame by frame instead (mate_engine_enable_frame_fragments): one small launch behind each
+        step_versus_greedy(team, ...) call folds that frame in, a fragment is `frame_skip` such calls (step_fragment_frames, or a
+        Stepper(versus=team, frame_skip=K) built afterwards) under auto_reset = a multiple of K -- against ANY opponent the per-step flows
+        have (Heuristic, mixtures, channels).  `shaping` then attaches the team's reward rows in overwrite mode (enable_reward_rows) and
+        allows all of its terms (soft_coverage_score still needs the outer boundary); fragment_coefficients is that launch's table.
+        relative_coordinates / rescaled_observation set the packer's transform (set_obs_transform): the rows arrive transformed, there is
+        no column table.  With `first_rows` the dict gains 'restarted' [N] u8 and (`final_obs`) 'final_obs'; there are no first-row working
+        buffers, since the per-step restart packs the first rows into the call's own.  Against the Greedy opponents every tensor equals
+        the fused fragment's bit for bit.
         Call after the first reset().  Returns fragment_obs."""
         frame_skip = int(frame_skip)
         assert frame_skip >= 1
         assert first_rows or not final_obs, 'final_obs belongs to first_rows = True'
+        if per_frame:
+            return self._enable_frame_fragments(team, frame_skip, shaping, relative_coordinates, rescaled_observation, dtype, first_rows, final_obs)
         out = self._fragment_outputs(team, shaping is not None, dtype)
         cfg, keep, masks = self._fragment_config(team, shaping, relative_coordinates, rescaled_observation, dtype, out)
         torch.cuda.current_stream(self.device).synchronize()
@@ -1289,9 +1301,71 @@ class Engine:
         self.reserve_rollout(frame_skip, want_masks=masks)
         return self.fragment_obs
 
+    def _enable_frame_fragments(self, team, frame_skip, shaping, relative_coordinates, rescaled_observation, dtype, first_rows, final_obs):
+        code = _team_code(team)
+        name = ('camera', 'target')[code]
+        assert dtype in (torch.float32, torch.float64)
+        if self.fragment_team is not None:
+            self.disable_fragment_rows()
+        self.set_obs_transform(relative_coordinates=relative_coordinates, rescaled_observation=rescaled_observation)
+        if shaping is not None:
+            self.enable_reward_rows(**{name: shaping}, dtype=dtype, accumulate=False)
+        out = self._fragment_outputs(code, shaping is not None, dtype)
+        with torch.cuda.device(self.device):
+            restarted = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device) if first_rows else None
+            final = torch.zeros_like(out['obs']) if final_obs else None
+        cfg = MateFrameFragments()
+        cfg.team, cfg.frames, cfg.out_dtype, cfg.first_rows = code, frame_skip, int(dtype == torch.float64), int(bool(first_rows))
+        for key, tensor in dict(out, final_obs=final, restarted=restarted).items():
+            if tensor is not None:
+                setattr(cfg, key + '_dev', tensor.data_ptr())
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.mate_engine_enable_frame_fragments(self._h, ctypes.byref(cfg)))
+        self.fragment_obs, self.fragment_rewards, self.fragment_done = out['obs'], out['rewards'], out['done']
+        self.fragment_frames, self.fragment_info, self.fragment_shaped = out['frames'], out['info'], out['shaped']
+        self.fragment_team, self.fragment_frame_skip, self._fragment_masks = code, frame_skip, False
+        self.fragment_per_frame, self._frame_restarted, self.fragment_final_obs = True, restarted, final
+        self._forget_calls()
+        return self.fragment_obs
+
+    def frame_fragment(self, team, rows, scalars, phase, frame_skip, closes=False, out=None, dtype=torch.float64):
+        """The frame launch on demand over caller buffers (mate_engine_frame_fragment): `rows` [N, A, D] (obs_dtype) the team's rows of ONE frame,
+        `scalars` [N, 8] f32 its records, folded as frame `phase` of `frame_skip` into `out` -- a dict of tensors by the fragment's names (any subset
+        of obs, rewards, info, done, frames, shaped, final_obs, restarted; None: new ones, without shaped) that the NEXT phases keep adding to.
+        `closes`: the second form instead -- `rows` are the first rows of what the record says finished.  'shaped' sums the attached reward rows.
+        Returns `out`."""
+        code = _team_code(team)
+        if out is None:
+            out = {k: v for k, v in self._fragment_outputs(code, False, dtype).items() if v is not None}
+        cfg = MateFrameFragments()
+        cfg.team, cfg.frames, cfg.out_dtype = code, int(frame_skip), int(dtype == torch.float64)
+        for key, tensor in out.items():
+            assert tensor.is_contiguous() and tensor.device == self.device
+            setattr(cfg, key + '_dev', tensor.data_ptr())
+        assert rows.is_contiguous() and rows.dtype == self.obs_dtype and scalars.is_contiguous() and scalars.dtype == torch.float32
+        io = MateStepIO()
+        io.scalars_dev = scalars.data_ptr()
+        setattr(io, ('camera', 'target')[code] + '_obs_dev', rows.data_ptr())
+        check(self.lib.mate_engine_frame_fragment(self._h, ctypes.byref(cfg), ctypes.byref(io), int(phase), int(bool(closes)), self._stream()))
+        return out
+
+    def step_fragment_frames(self, team, joint_action, auto_reset=None, policy_tape=None):
+        """One learner step of FrameSkip(K) over the per-frame fragments (enable_fragment_rows(per_frame=True)): K calls of
+        step_versus_greedy(team, joint_action) with the action held, under `auto_reset` (a multiple of K; default K: finished environments
+        idle to their fragment's end and restart behind it).  Returns the fragment dict."""
+        code = _team_code(team)
+        assert self.fragment_per_frame and self.fragment_team == code, 'enable_fragment_rows(team, K, per_frame=True) first'
+        K = self.fragment_frame_skip
+        auto_reset = K if auto_reset is None else int(auto_reset)
+        for _ in range(K):
+            self.step_versus_greedy(code, joint_action, policy_tape=policy_tape, auto_reset=auto_reset)
+        return self.fragment
+
     def disable_fragment_rows(self):
-        """Detach the fragment launch (and the first rows with it): rollout_versus_greedy goes back to its launch sequence without it; the tensors become None."""
+        """Detach the fragment launch (and the first rows with it): rollout_versus_greedy goes back to its launch sequence without it; the tensors become None.
+        The per-frame form: step_versus_greedy goes back to its own (reward rows it attached for `shaping` stay: disable_reward_rows)."""
         check(self.lib.mate_engine_enable_fragment_rows(self._h, None))
+        check(self.lib.mate_engine_enable_frame_fragments(self._h, None))
         self._clear_fragment_rows()
 
     # ------------------------------------------------------------------ per-episode metric records
@@ -1419,6 +1493,8 @@ class Engine:
     def fragment_restarted(self):
         """[N] bool: the environments the last rollout_versus_greedy of the attached team restarted -- whose fragment_obs row is the new
         episode's first row (enable_fragment_rows(first_rows=True)); None while first rows are off.  A new tensor at every read."""
+        if self.fragment_per_frame:
+            return None if self._frame_restarted is None else self._frame_restarted != 0
         if self.fragment_first_scalars is None:
             return None
         return self.fragment_first_scalars[:, 2] != 2
@@ -1430,6 +1506,11 @@ class Engine:
             return None
         out = {'obs': self.fragment_obs, 'rewards': self.fragment_rewards, 'done': self.fragment_done, 'frames': self.fragment_frames,
                'info': self.fragment_info, 'shaped': self.fragment_shaped, 'coefficients': self.fragment_coefficients}
+        if self.fragment_per_frame:
+            if self.fragment_shaped is not None:
+                out['coefficients'] = self.reward_coefficients[('camera', 'target')[self.fragment_team]]
+            if self._frame_restarted is not None:
+                out.update(restarted=self._frame_restarted, final_obs=self.fragment_final_obs)
         if self.fragment_first_scalars is not None:      # (first rows on: the keys exist only then)
             out.update(first_rows=self.fragment_first_rows, first_scalars=self.fragment_first_scalars, final_obs=self.fragment_final_obs)
         return out
@@ -1704,18 +1785,27 @@ class Stepper:
         # ([K, N, ...]: the caller sums the reward rows, reads the last frame's observation) instead of the engine's per-step ones
         self.frame_skip = int(frame_skip)
         assert self.frame_skip >= 1 and (self.frame_skip == 1 or versus is not None), 'frame_skip belongs to the learner-versus-greedy flow'
-        if self.frame_skip > 1 and versus in ('camera', 0) and eng.target_agent != 'greedy':
+        # per-frame fragments attached for `versus` (Engine.enable_fragment_rows(per_frame=True)): every "step" of this stepper is K per-step calls with the
+        # action held, each followed by the frame launch -- any opponent; auto_reset counts ENGINE calls and is a multiple of K, graphs hold whole intervals
+        self.per_frame = eng.fragment_per_frame and versus in (('camera', 'target')[eng.fragment_team], eng.fragment_team)
+        if self.per_frame:
+            assert self.frame_skip == eng.fragment_frame_skip, f'per-frame fragments of {eng.fragment_frame_skip} frames are attached: frame_skip must be that'
+            if auto_reset is True:
+                auto_reset = self.frame_skip
+            assert int(auto_reset) >= 1 and int(auto_reset) % self.frame_skip == 0, 'per-frame fragments: auto_reset (engine calls) is a positive multiple of frame_skip'
+        fused = self.frame_skip > 1 and not self.per_frame
+        if fused and versus in ('camera', 0) and eng.target_agent != 'greedy':
             raise ValueError(f"make_stepper(versus='camera', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the target opponent is "
                              f"{eng.target_agent!r} (Engine.set_target_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
-        if self.frame_skip > 1 and versus in ('target', 1) and eng.camera_agent != 'greedy' and eng.num_cameras > 0:
+        if fused and versus in ('target', 1) and eng.camera_agent != 'greedy' and eng.num_cameras > 0:
             raise ValueError(f"make_stepper(versus='target', frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the camera opponent is "
                              f"{eng.camera_agent!r} (Engine.set_camera_opponent) -- step per frame (frame_skip=1) or select 'greedy'")
         for team, name in ((1, 'camera'), (0, 'target')):      # (the team the ENGINE plays against the learner `name`)
-            if self.frame_skip > 1 and versus in (name, 1 - team) and eng.mixtures[team] is not None and set(eng.mixtures[team]) != {'greedy'} and (team == 1 or eng.num_cameras > 0):
+            if fused and versus in (name, 1 - team) and eng.mixtures[team] is not None and set(eng.mixtures[team]) != {'greedy'} and (team == 1 or eng.num_cameras > 0):
                 raise ValueError(f"make_stepper(versus={name!r}, frame_skip={self.frame_skip}) is one fused K-frame launch, which holds the Greedy agents: the opponents play the mixture "
                                  f"{eng.mixtures[team]} (Engine.set_opponent_mixture) -- step per frame (frame_skip=1) or clear the mixture")
         for team, name in ((1, 'camera'), (0, 'target')):
-            if self.frame_skip > 1 and versus in (name, 1 - team) and eng.channels[team] is not None and (team == 1 or eng.num_cameras > 0):
+            if fused and versus in (name, 1 - team) and eng.channels[team] is not None and (team == 1 or eng.num_cameras > 0):
                 raise ValueError(f"make_stepper(versus={name!r}, frame_skip={self.frame_skip}) is one fused K-frame launch, which delivers every message: the opponents' team has the "
                                  f"communication channel {eng.channels[team]} (Engine.set_channel) -- step per frame (frame_skip=1) or clear the channel")
         self.auto_reset = int(auto_reset)        # True / 1: immediate; k > 1: batched (finished environments idle up to k - 1 steps)
@@ -1756,7 +1846,7 @@ class Stepper:
             (cam_act is None or eng.num_cameras == 0 or self.io.camera_actions_dev == cam_act.data_ptr()), \
             'action tensors must be contiguous f32/f64 (or int32 grid indices) on the engine device'
         self.outputs = None
-        if self.frame_skip > 1 and not self.selection and not self.seat:
+        if self.frame_skip > 1 and not self.selection and not self.seat and not self.per_frame:
             # (the reward launch reads the last frame's masks; the fragment launch every frame's, for a mask term)
             shaped = eng.reward_coefficients is not None or (eng._fragment_masks and eng.fragment_team == self.versus) or eng._info_attached()
             buf = eng.reserve_rollout(self.frame_skip, want_masks=shaped)
@@ -1765,7 +1855,7 @@ class Stepper:
             self.keep = (self.keep, buf)
         self.ref = ctypes.byref(self.io)
         self._phase = 0                                   # steps into the current reset interval (graphs hold whole intervals)
-        self._interval = 1 if self.seat and self.frame_skip > 1 else self.auto_reset      # _one() calls per reset interval (a seat fragment is a whole one)
+        self._interval = 1 if self.seat and self.frame_skip > 1 else self.auto_reset // self.frame_skip if self.per_frame else self.auto_reset      # _one() calls per reset interval (a seat fragment is a whole one)
         self.warmup_steps = self._interval if self.graph_steps > 0 else 0      # real steps the constructor runs (see the class note)
         if self.selection and self.frame_skip > 1:
             eng.device_tick(self.frame_skip)              # (closes an open reset interval: fragments start on an interval boundary)
@@ -1802,6 +1892,10 @@ class Stepper:
             status = 0
             for _ in range(self.frame_skip):
                 status = status or eng.lib.mate_engine_step_seated(eng._h, self.ref, None, self.auto_reset, eng._stream())
+        elif self.per_frame:
+            status = 0
+            for _ in range(self.frame_skip):
+                status = status or eng.lib.mate_engine_step_versus_greedy(eng._h, self.versus, self.ref, None, self.auto_reset, eng._stream())
         elif self.versus is None:
             status = eng.lib.mate_engine_step(eng._h, self.ref, self.auto_reset, eng._stream())
         elif self.frame_skip > 1:
@@ -1909,6 +2003,17 @@ class EngineGroups:
     def enable_info_rows(self, camera=True, target=True, cargo=True):
         """Engine.enable_info_rows on every group, each on its own stream; returns the groups' (camera, target, cargo) row tensors."""
         return self.each(lambda g, eng: eng.enable_info_rows(camera=camera, target=target, cargo=cargo))
+
+    def enable_fragment_rows(self, team, frame_skip, **kwargs):
+        """Engine.enable_fragment_rows (per_frame=True included) on every group; returns the groups' fragment_obs tensors."""
+        return self.each(lambda g, eng: eng.enable_fragment_rows(team, frame_skip, **kwargs))
+
+    def step_fragment_frames(self, team, joint_actions, auto_reset=None):
+        """Engine.step_fragment_frames on every group, each on its own stream (`joint_actions`: one tensor per group); returns the groups' fragment dicts."""
+        return self.each(lambda g, eng: eng.step_fragment_frames(team, joint_actions[g], auto_reset=auto_reset))
+
+    def disable_fragment_rows(self):
+        return self.each(lambda g, eng: eng.disable_fragment_rows())
 
     def enable_messages(self, team, width, pairwise=False, addressed=False):
         """Engine.enable_messages on every group; returns the groups' (payload, address, inbox) tensors."""

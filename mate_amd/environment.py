@@ -654,13 +654,16 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
 
 
 def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, target_reward_shaping=None, enhanced_observation=None,
-                       shared_field_of_view=None, camera_selection=None, target_agent='greedy', camera_agent='greedy'):
+                       shared_field_of_view=None, camera_selection=None, target_agent='greedy', camera_agent='greedy', per_frame=False):
     """The argument rules of BatchedMultiAgentTracking(frame_skip=K, learner=...), checked ahead of everything that needs a GPU.
-    Returns None without `frame_skip`, else {'frame_skip', 'learner', 'shaping'}: the learner's (coefficients, reduction) or None."""
+    Returns None without `frame_skip`, else {'frame_skip', 'learner', 'shaping'}: the learner's (coefficients, reduction) or None.
+    `per_frame`: the fragments are built frame by frame behind K per-step calls -- any `target_agent` / `camera_agent`
+    and every shaping term of the learner's team; the result then also says 'per_frame': True."""
     assert target_agent in TARGET_AGENTS, f'target_agent = {target_agent!r}: one of {TARGET_AGENTS}'
     assert camera_agent in CAMERA_AGENTS, f'camera_agent = {camera_agent!r}: one of {CAMERA_AGENTS}'
     if frame_skip is None:
         assert learner is None, "learner = ... belongs to frame_skip = K (the fused learner-versus-greedy fragments)"
+        assert not per_frame, 'per_frame belongs to frame_skip = K, learner = ...'
         return None
     assert isinstance(frame_skip, (int, np.integer)) and not isinstance(frame_skip, bool) and frame_skip >= 1, \
         f'frame_skip = {frame_skip!r}: a positive number of frames (examples/utils/wrappers.py FrameSkip)'
@@ -671,17 +674,20 @@ def fragment_arguments(config, frame_skip, learner, camera_reward_shaping=None, 
     for name, value in (('enhanced_observation', enhanced_observation), ('shared_field_of_view', shared_field_of_view)):
         assert value in (None, False, 'none'), f'{name} is not available with frame_skip: the fused launch packs plain rows'
     assert not camera_selection, 'camera_selection steps one frame per call: it does not combine with frame_skip'
-    assert learner != 'camera' or target_agent == 'greedy', \
+    assert per_frame or learner != 'camera' or target_agent == 'greedy', \
         f"target_agent = {target_agent!r} is not available with frame_skip, learner = 'camera': the fused K-frame launch holds the Greedy agents (step per frame instead)"
-    assert learner != 'target' or camera_agent == 'greedy', \
+    assert per_frame or learner != 'target' or camera_agent == 'greedy', \
         f"camera_agent = {camera_agent!r} is not available with frame_skip, learner = 'target': the fused K-frame launch holds the Greedy agents (step per frame instead)"
     other = target_reward_shaping if learner == 'camera' else camera_reward_shaping
     assert other is None, f"frame_skip with learner = {learner!r} shapes the learner's rewards only (the other team is the greedy agents)"
     shaping = camera_reward_shaping if learner == 'camera' else target_reward_shaping
     if shaping is not None:
         shaping = (dict(shaping[0]), shaping[1])
-        fragment_coefficient_table(learner, *shaping)
-    return {'frame_skip': int(frame_skip), 'learner': learner, 'shaping': shaping}
+        (reward_coefficient_table if per_frame else fragment_coefficient_table)(learner, *shaping)
+    spec = {'frame_skip': int(frame_skip), 'learner': learner, 'shaping': shaping}
+    if per_frame:
+        spec['per_frame'] = True
+    return spec
 
 
 class BatchedMultiAgentTracking(_ScenarioMixin):
@@ -738,14 +744,16 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
                  learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
                  target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, single_agent=None, seat='auto',
-                 camera_messages=None, target_messages=None, **kwargs):
+                 camera_messages=None, target_messages=None, per_frame=False, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
         self._target_shapers = {}                         # (auxiliary_target_rewards: one shaper per (coefficients, reduction))
         self._fragment_live = None                        # (_fragment_reset: the scalar record that says which environments were reset)
         self._fragment = fragment_arguments(self.config, frame_skip, learner, camera_reward_shaping, target_reward_shaping, enhanced_observation,
-                                            shared_field_of_view, camera_selection, target_agent, camera_agent)
+                                            shared_field_of_view, camera_selection, target_agent, camera_agent, per_frame=bool(per_frame))
+        per_frame = bool(self._fragment and self._fragment.get('per_frame'))
+        assert not per_frame or int(auto_reset) >= 1, 'per_frame: finished environments restart behind their fragment (auto_reset >= 1, counted in fragments)'
         assert target_agent == 'greedy' or not any(team in ('both', 'target') for team in (enhanced_observation, shared_field_of_view)), \
             f"target_agent = {target_agent!r} senses the cameras of its plain rows: no enhanced_observation / shared_field_of_view for the target team"
         assert camera_agent == 'greedy' or not any(team in ('both', 'camera') for team in (enhanced_observation, shared_field_of_view)), \
@@ -758,7 +766,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         for team, spec in self._mixtures.items():
             kinds, weights = mixture_table(spec)
             only_greedy = [SCRIPTED_AGENTS[k] for k, w in zip(kinds, weights) if w > 0.0] == ['greedy']
-            assert not self._fragment or self._fragment['learner'] == team or only_greedy, \
+            assert not self._fragment or per_frame or self._fragment['learner'] == team or only_greedy, \
                 f"{team}_mixture = {spec!r} is not available with frame_skip against that team: the fused K-frame launch holds the Greedy agents (step per frame instead)"
             assert team != 'camera' or not camera_selection, 'camera_mixture: camera_selection plays the camera team itself'
             assert (target_agent if team == 'target' else camera_agent) == 'greedy', f'{team}_mixture replaces {team}_agent: name the agent as a candidate'
@@ -766,7 +774,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         # wrappers as the channel of the teams the engine plays (Engine.set_channel), checked now, set by enable_greedy_policies
         self._channels = channel_table(no_communication, message_dropout, communication_range)
         for team, spec in zip(('camera', 'target'), self._channels):
-            assert spec is None or not self._fragment or self._fragment['learner'] == team, \
+            assert spec is None or not self._fragment or per_frame or self._fragment['learner'] == team, \
                 f"a communication channel of the {team} team is not available with frame_skip against that team: the fused K-frame launch delivers every message (step per frame instead)"
             assert spec is None or team != 'camera' or (camera_agent == 'greedy' and 'heuristic' not in _names_of(camera_mixture)), \
                 "a communication channel of the camera team needs Greedy cameras: HeuristicCameraAgent's fallback for a lost response is not on the device"
@@ -802,7 +810,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if self._fragment:      # the transforms and the shaping belong to the fragment launch (attached behind the first reset())
             self._fragment.update(relative_coordinates=bool(relative_coordinates), rescaled_observation=bool(rescaled_observation), dtype=reward_dtype,
                                   first_rows=bool(first_rows))
-            relative_coordinates = rescaled_observation = False
+            if not per_frame:      # (per_frame: the packer transforms the rows, of reset() too)
+                relative_coordinates = rescaled_observation = False
             camera_reward_shaping = target_reward_shaping = None
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
         self.engine = Engine(self.config, self.num_envs, device=device, seed=seed, first_env_index=first_env_index, obs_dtype=obs_dtype)
@@ -942,7 +951,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         transform = {'relative_coordinates': spec['relative_coordinates'], 'rescaled_observation': spec['rescaled_observation']}
         if eng.fragment_team is None:
             eng.enable_fragment_rows(spec['learner'], spec['frame_skip'], shaping=spec['shaping'], dtype=spec['dtype'], first_rows=spec['first_rows'],
-                                     final_obs=spec['first_rows'], **transform)
+                                     final_obs=spec['first_rows'], per_frame=bool(spec.get('per_frame')), **transform)
         rows = eng.camera_obs if spec['learner'] == 'camera' else eng.target_obs
         if self._fragment_live is None:      # (a scalar record that says "this frame ran": the step's own may be older than the reset)
             self._fragment_live = torch.zeros((self.num_envs, 8), dtype=torch.float32, device=self.device)
@@ -950,7 +959,10 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             self._fragment_live[:, 2] = 0.0
         else:
             self._fragment_live[:, 2] = torch.where(env_mask.to(device=self.device).bool().reshape(-1), 0.0, 2.0)
-        eng.fragment_rows(spec['learner'], rows, self._fragment_live, out={'obs': eng.fragment_obs}, **transform)
+        if spec.get('per_frame'):      # (the packer has transformed the rows: the frame launch's last phase copies the live ones)
+            eng.frame_fragment(spec['learner'], rows, self._fragment_live, spec['frame_skip'] - 1, spec['frame_skip'], out={'obs': eng.fragment_obs})
+        else:
+            eng.fragment_rows(spec['learner'], rows, self._fragment_live, out={'obs': eng.fragment_obs}, **transform)
         return eng.fragment_obs
 
     def step_fragment(self, joint_action):
@@ -964,8 +976,12 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         assert self._fragment, 'built without frame_skip = K, learner = ...'
         spec, eng = self._fragment, self.engine
         assert eng.fragment_team is not None, 'reset() first'
-        self._info_frames = spec['frame_skip']
-        eng.rollout_versus_greedy(spec['learner'], joint_action, spec['frame_skip'], auto_reset=int(self.auto_reset), want_masks=self._training_information)
+        if spec.get('per_frame'):      # K per-step calls, each folded in by the frame launch; the restart interval counts engine calls
+            self._info_frames = 1
+            eng.step_fragment_frames(spec['learner'], joint_action, auto_reset=int(self.auto_reset) * spec['frame_skip'])
+        else:
+            self._info_frames = spec['frame_skip']
+            eng.rollout_versus_greedy(spec['learner'], joint_action, spec['frame_skip'], auto_reset=int(self.auto_reset), want_masks=self._training_information)
         camera = spec['learner'] == 'camera'
         sums, means = eng.fragment_rewards, eng.fragment_info
         if eng.fragment_shaped is not None:
