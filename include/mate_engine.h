@@ -724,6 +724,23 @@ typedef struct {
 int mate_engine_enable_frame_fragments(mate_engine *engine, const mate_frame_fragments *config);
 int mate_engine_frame_fragment(mate_engine *engine, const mate_frame_fragments *config, const mate_step_io *rows, int32_t phase, int32_t closes, void *stream);
 
+/* Off-screen render: MultiAgentTracking.render(mode='rgb_array') (environment.py:986-1180) rasterised on the device (csrc/render_rows.hpp; the rules: DESIGN.md
+ * section 3.20).  ONE launch on `stream` writes out_dev[count][size][size][3] uint8, frame k the picture of environment env_indices_dev[k] (any order, repeats
+ * allowed; null: the environments 0 .. count - 1): the reference's display list point-sampled at the pixel centres of the view [-1050, 1050]^2, row 0 at the top,
+ * white background, every primitive blended once per pixel in f32, one quantisation at the end.  The warehouse icons and the render callbacks are not drawn.
+ * It reads the records and the engine's own mask words as the last call left them, and writes nothing but the frames.  The engine keeps that copy of the mask
+ * words once mate_engine_keep_masks (that buffer alone) or mate_engine_policy_enable has allocated it: call either ahead of the reset; every launch that
+ * writes a view fills it from then on, whether the call brings masks_dev or not.  headings_dev: [count][num_targets] f64, the reference's render-only target_orientations in degrees (the engine
+ * keeps none); null: zeros.  No allocation, no synchronisation, identical arguments at every call: capturable.
+ * MATE_EINVAL: count < 1, an index outside [0, N) (without indices: count > N; indices on the device are not read by the host -- the kernel leaves the frame
+ * of an index outside [0, N) untouched), size outside [16, 4096], out_dev null or not 16-byte aligned, misaligned indices or headings, more tiles than one
+ * launch takes.  MATE_ESTATE: before the first reset / import_state, or without the engine's own mask words; an argument error is reported
+ * ahead of a state error.  A refused call changes nothing and launches nothing. */
+#define MATE_RENDER_MIN_SIZE 16
+#define MATE_RENDER_MAX_SIZE 4096
+int mate_engine_keep_masks(mate_engine *engine);
+int mate_engine_render(mate_engine *engine, const int32_t *env_indices_dev, int64_t count, int32_t size, const double *headings_dev, uint8_t *out_dev, void *stream);
+
 /* Per-episode metric records (csrc/episode_rows.hpp): what the reference's example trainers report at every episode's end (examples/utils/callbacks.py:
  * MetricCollector's mean over the agents of each learner step's infos, CustomMetricCallback.on_episode_end's mean / last / episode_<key> sums over the
  * episode's steps), kept on the device for ONE team's perspective.  While attached every stepping call -- step, step_random, step_greedy,

@@ -26,6 +26,7 @@
 #include "channel_rows.hpp"
 #include "seat_rows.hpp"
 #include "message_rows.hpp"
+#include "render_rows.hpp"
 
 using namespace mate;
 

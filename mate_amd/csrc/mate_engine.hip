@@ -1514,6 +1514,7 @@ static bool one_launch_step(const mate_engine *e, const FusedCall &c, const Oppo
 #include "opponent_host.inc"      // the opponents' launches, setters and accessors
 #include "message_host.inc"       // the learner's own messages: enable, the routing launch, draws, accessors
 #include "frame_host.inc"         // the per-frame FrameSkip fragments: enable, the call's check, the on-demand launch
+#include "render_host.inc"        // the off-screen render: the argument check, the launch
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 

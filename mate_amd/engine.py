@@ -254,6 +254,7 @@ class Engine:
         self._rollout, self._block_search, self._reserve_t0 = None, None, None
         self.block_rates, self.store_form, self.reserve_seconds = [], 0, 0.0
         self._random_io = {}              # the cached argument blocks of step_random (_forget_calls)
+        self._own_masks = False           # (keep_masks, enable_policies)
         self._staged = self._softcov = self._export_slices = None      # (stage_outputs, soft_coverage, state_dict_from)
         self._clear_state_rows()
         self._clear_reward_rows()
@@ -685,6 +686,7 @@ class Engine:
             if value not in known:
                 raise ValueError(f"{name} must be one of {known}, got {value!r}")
         check(self.lib.mate_engine_policy_enable(self._h))
+        self._own_masks = True            # (the engine's own copy of the mask words exists from here on: render)
         if target_agent != 'greedy' or self.target_agent != 'greedy':
             self.set_target_opponent(target_agent)
         if camera_agent != 'greedy' or self.camera_agent != 'greedy':
@@ -1469,6 +1471,46 @@ class Engine:
         check(self.lib.mate_engine_info_rows(self._h, ctypes.c_void_p(masks.data_ptr()) if masks is not None else None, *self._row_pointers(rows), self._stream()))
         return rows
 
+    # ------------------------------------------------------------------ off-screen render (MultiAgentTracking.render(mode='rgb_array'))
+    RENDER_SIZES = (16, 4096)      # MATE_RENDER_MIN_SIZE, MATE_RENDER_MAX_SIZE
+
+    def keep_masks(self):
+        """Have the engine keep its own copy of the packed mask words (mate_engine_keep_masks): every later launch that writes a view fills it, whether the
+        call brings its masks output or not.  What render() reads; call it ahead of the reset.  enable_policies() allocates the same copy."""
+        check(self.lib.mate_engine_keep_masks(self._h))
+        self._own_masks = True
+
+    def render(self, envs=None, size=800, headings=None, out=None):
+        """uint8 [k, size, size, 3] on the device: the reference's render(mode='rgb_array') pictures of the environments `envs` (indices into this
+        engine's batch, any order, repeats allowed; None: all of them) by ONE launch on the current stream, from the CURRENT records and the engine's
+        own mask words (what is drawn, what is not).  `headings`: [k, Nt] degrees, the reference's render-only
+        target_orientations of each requested frame (None: zeros).  `out`: a contiguous uint8 [k, size, size, 3] tensor to write instead of a new one.
+        It reads, and writes nothing but the frames.  The engine keeps its own mask words from keep_masks() (or enable_policies()) on: call it ahead of
+        the reset, as both environment classes do; without it the call is refused (EngineError, MATE_ESTATE).  With `envs` given the indices are uploaded at
+        every call, so only `envs=None` into a preallocated `out` is capturable."""
+        lo, hi = self.RENDER_SIZES
+        size = int(size)
+        if not lo <= size <= hi:
+            raise ValueError(f'render: size must lie in [{lo}, {hi}], got {size}')
+        if envs is None:
+            index, k = None, self.num_envs
+        else:
+            host = np.asarray(envs.cpu() if torch.is_tensor(envs) else envs, dtype=np.int64).reshape(-1)
+            if host.size < 1 or host.min() < 0 or host.max() >= self.num_envs:
+                raise ValueError(f'render: the environments must be indices in [0, {self.num_envs}) and at least one, got {host.tolist()}')
+            index, k = torch.from_numpy(host.astype(np.int32)).to(self.device), int(host.size)
+        if headings is not None:
+            headings = torch.as_tensor(headings, dtype=torch.float64).to(self.device).contiguous()
+            if headings.shape != (k, self.num_targets):
+                raise ValueError(f'render: headings must be [{k}, {self.num_targets}], got {tuple(headings.shape)}')
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty((k, size, size, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.shape == (k, size, size, 3)
+        check(self.lib.mate_engine_render(self._h, ctypes.c_void_p(index.data_ptr()) if index is not None else None, k, size,
+                                          ctypes.c_void_p(headings.data_ptr()) if headings is not None else None, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
     @staticmethod
     def info_views(camera_rows, target_rows, cargo_rows):
         """{name: view} over the three row tensors (None: that output's names are absent): [N, Nc] / [N, Nt] columns,
@@ -2014,6 +2056,29 @@ class EngineGroups:
 
     def disable_fragment_rows(self):
         return self.each(lambda g, eng: eng.disable_fragment_rows())
+
+    def keep_masks(self):
+        return self.each(lambda g, eng: eng.keep_masks())
+
+    def render(self, envs=None, size=800, headings=None):
+        """Engine.render of the batch's environments `envs` (indices into the WHOLE batch; None: all of them), each drawn by its group's engine on its
+        group's stream into a tensor of that stream; the groups' streams are waited for, then ONE uint8 [k, size, size, 3] tensor in the order of `envs` is
+        put together on the current stream.  The groups' engines need their own mask words (keep_masks(), or policies=True)."""
+        index = np.arange(self.groups * self.per_group) if envs is None else np.asarray(envs, dtype=np.int64).reshape(-1)
+        if index.size < 1 or index.min() < 0 or index.max() >= self.groups * self.per_group:
+            raise ValueError(f'render: the environments must be indices in [0, {self.groups * self.per_group}) and at least one')
+        headings = None if headings is None else np.asarray(torch.as_tensor(headings).cpu(), dtype=np.float64).reshape(index.size, -1)
+
+        def draw(g, eng):      # (everything a group touches -- indices, headings, frames -- is allocated and uploaded on the group's own stream)
+            mine = np.flatnonzero(index // self.per_group == g)
+            return mine, (eng.render(index[mine] - g * self.per_group, size=size, headings=None if headings is None else headings[mine]) if mine.size else None)
+        parts = self.each(draw)
+        self.synchronize()
+        out = torch.empty((index.size, int(size), int(size), 3), dtype=torch.uint8, device=self.device)
+        for mine, frames in parts:
+            if frames is not None:
+                out[torch.from_numpy(mine).to(self.device)] = frames
+        return out
 
     def enable_messages(self, team, width, pairwise=False, addressed=False):
         """Engine.enable_messages on every group; returns the groups' (payload, address, inbox) tensors."""

@@ -14,7 +14,7 @@ from mate_amd import spaces
 from mate_amd.auxiliary_rewards import CAMERA_REWARD_KEYS, AuxiliaryTargetRewards, reward_coefficient_table
 from mate_amd.config import DEFAULT_CONFIG_FILE, read_config
 from mate_amd.engine import CAMERA_AGENTS, SCALAR_NAMES, SCRIPTED_AGENTS, TARGET_AGENTS, Engine, channel_table, fragment_coefficient_table, mixture_table, seat_mode_of
-from mate_amd.utils import Message, Team, polar2cartesian
+from mate_amd.utils import Message, Team, arctan2_deg, normalize_angle, polar2cartesian
 
 __all__ = ['MultiAgentTracking', 'BatchedMultiAgentTracking', 'EnvMeta']
 
@@ -304,6 +304,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self._device_index, self._obs_dtype = device, obs_dtype
         self._seed_value = 0
         self.engine = Engine(self.config, 1, device=device, seed=0, obs_dtype=obs_dtype)
+        self.engine.keep_masks()             # (render() reads the engine's own mask words: kept from the first reset on)
         self.engine.stage_outputs()          # one device-to-host copy per step (Engine.fetch_host)
         Na = self.engine.num_cameras * consts.CAMERA_ACTION_DIM + self.engine.num_targets * consts.TARGET_ACTION_DIM
         self._act_dev = torch.zeros(Na, dtype=torch.float64, device=self.engine.device)      # ... and one host-to-device copy of the joint action,
@@ -334,6 +335,8 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self._cache = self._masks = self._np_random = None
         self._policies_on = False                         # (enable_greedy_policies)
         self.target_dones, self._last_goals = np.zeros(Nt, dtype=bool), None                  # (reset, _finish_step)
+        # render-only state the engine does not keep (environment.py:1347-1352 of the reference): kept here from consecutive locations
+        self.target_orientations, self._last_locations = np.zeros(Nt, dtype=np.float64), None
         self._last_episode_rewards = self._last_step_rewards = (0.0, 0.0)
         self.seed(0)
 
@@ -403,6 +406,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
             raise ValueError(f'Seed must be a non-negative integer or omitted, not {seed}')
         self._seed_value = int(seed)
         self._np_random = np.random.RandomState(self._seed_value % (2 ** 32))
+        self._heading_random = np.random.RandomState(self._seed_value % (2 ** 32))      # (the headings of targets without a goal at reset: a stream of its own, np_random stays where the reference leaves it)
         self.engine.seed(self._seed_value)
         int_max = np.iinfo(int).max
         entities = self.num_cameras + self.num_targets + self.num_obstacles
@@ -439,7 +443,15 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self._last_goals = self.target_goals.copy()
         self._last_episode_rewards = (self.target_team_episode_reward, self.delayed_target_team_episode_reward)
         self.episode_step = 0
+        self._last_locations = self._target_locations()
+        for t, goal in enumerate(self._last_goals):      # environment.py:814-821: towards the goal, a random heading without one
+            away = consts.WAREHOUSES[goal] - self._last_locations[t] if goal >= 0 else None
+            self.target_orientations[t] = arctan2_deg(away[1], away[0]) if goal >= 0 else normalize_angle(360.0 * self._heading_random.random_sample())
         return cam, tgt
+
+    def _target_locations(self):
+        f = self._fields()
+        return np.stack([f['tgt_x'], f['tgt_y']], axis=-1).reshape(self.num_targets, 2).astype(np.float64)
 
     #: parity hook: {'camera_target': [Nc, Nt] uniforms, 'goal': [Nt] uniforms} consumed by the NEXT step() instead of the
     #: engine's Philox draws (how the golden traces recorded from the reference are replayed through this API)
@@ -523,6 +535,11 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self.target_dones = (goals != self._last_goals) & (self._last_goals >= 0)
         self._last_goals = goals.copy()
         self.episode_step += 1
+        locations = self._target_locations()
+        moved = locations - self._last_locations
+        for t in np.flatnonzero((moved != 0.0).any(axis=-1)):      # environment.py:1347-1352
+            self.target_orientations[t] = arctan2_deg(moved[t, 1], moved[t, 0])
+        self._last_locations = locations
         # the step's team reward in f64: the increment of the episode sums (integers: exact), environment.py:618-624
         sums = (self.target_team_episode_reward, self.delayed_target_team_episode_reward)
         r_tgt = float(sums[1] - self._last_episode_rewards[1]) if self._sparse_reward else float(sums[0] - self._last_episode_rewards[0])
@@ -588,8 +605,14 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         self.__init__(config=config, device=self._device_index, obs_dtype=self._obs_dtype)
         self.seed(seed)
 
-    def render(self, mode='human', **kwargs):
-        raise NotImplementedError('rendering is out of scope of the MI355X step engine (no display on the GPU box)')
+    def render(self, mode='human', window_size=800, **kwargs):
+        """mode='rgb_array': the picture of the current state, uint8 [window_size, window_size, 3] (row 0 at the top), rasterised on the device by
+        Engine.render under the rules of DESIGN.md section 3.20 -- the reference's display list without the warehouse icons and without the render
+        callbacks.  mode='human' needs a window: there is no display on the GPU box."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("only mode='rgb_array' is rendered (off-screen, on the device): there is no display on the GPU box")
+        frames = self.engine.render([0], size=window_size, headings=self.target_orientations[None])
+        return frames[0].cpu().numpy()
 
     def add_render_callback(self, name, callback):
         self.render_callbacks[name] = callback
@@ -815,6 +838,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             camera_reward_shaping = target_reward_shaping = None
         self.num_envs, self.auto_reset = int(num_envs), int(auto_reset)   # 0 / False: never; 1 / True: immediately; k > 1: batched, every k-th call
         self.engine = Engine(self.config, self.num_envs, device=device, seed=seed, first_env_index=first_env_index, obs_dtype=obs_dtype)
+        self.engine.keep_masks()      # (render() reads the engine's own mask words, which the stepping calls fill whether they bring their masks output or not)
         self.num_cameras, self.num_targets, self.num_obstacles = self.engine.num_cameras, self.engine.num_targets, self.engine.num_obstacles
         assert self._episode_team != 'camera' or self.num_cameras > 0, "episode_records = 'camera' needs cameras"
         self._setup_spaces()
@@ -898,6 +922,11 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         if self._episode_team and self.engine.episode_team is None:      # (behind the reward rows, which its launch reads)
             self.engine.enable_episode_records(self._episode_team)
         return out
+
+    def render(self, envs=(0,), size=800, headings=None):
+        """uint8 [k, size, size, 3] on the device: the reference's render(mode='rgb_array') pictures of the environments `envs` (Engine.render; DESIGN.md
+        section 3.20).  `headings`: [k, num_targets] degrees, the render-only target_orientations the engine does not keep (None: zeros)."""
+        return self.engine.render(list(envs), size=size, headings=headings)
 
     def _want_masks(self):
         """The calls that may go without the view masks bring them for the reward launch, for the camera team's num_tracked record and for the

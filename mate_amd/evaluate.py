@@ -74,14 +74,50 @@ class _EpisodeLog:
             env.episode_step / (time.perf_counter() - self.started))))
 
 
-def evaluate(env, joint_policy=None, verbose=False, history=None):
+def write_png(path, image):
+    """An RGB uint8 [H, W, 3] array as a PNG file, with the standard library only: 8-bit truecolour, filter 0 on every row, one IDAT chunk."""
+    import struct
+    import zlib
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    assert image.ndim == 3 and image.shape[2] == 3, image.shape
+    height, width = image.shape[:2]
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+    rows = np.concatenate([np.zeros((height, 1), dtype=np.uint8), image.reshape(height, width * 3)], axis=1)
+    with open(path, 'wb') as fh:
+        fh.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', width, height, 8, 2, 0, 0, 0))
+                 + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+class FrameSaver:
+    """--save-frames: every `every`-th call writes `directory`/frame_<call>.png from the picture `draw(size)` returns (uint8 [size, size, 3])."""
+
+    def __init__(self, directory, size=800, every=1):
+        import os
+        assert every >= 1
+        os.makedirs(directory, exist_ok=True)
+        self.directory, self.size, self.every, self.calls, self.written = directory, int(size), int(every), 0, []
+
+    def __call__(self, draw):
+        import os
+        if self.calls % self.every == 0:
+            self.written.append(os.path.join(self.directory, 'frame_%06d.png' % self.calls))
+            write_png(self.written[-1], draw(self.size))
+        self.calls += 1
+
+
+def evaluate(env, joint_policy=None, verbose=False, history=None, frames=None):
     """One episode (mate/evaluate.py:85-167).  `joint_policy(env, (camera_obs, target_obs), (camera_infos, target_infos))`
     returns the joint action of both teams; None = the on-device Greedy agents of both teams
     (`env.enable_greedy_policies()` must then precede this call).  Returns the reference's status dict -- the row of
     the last step once a cargo has been delivered or the episode is done, else empty; `history` (a list) receives
     every step's row.  The loop ends at `max_episode_steps` like the reference's, one call before the environment's own
-    time-limit `done`."""
+    time-limit `done`.  `frames` (a FrameSaver): the picture behind the reset and behind every step (mate/evaluate.py's env.render())."""
     observations, infos, status = env.reset(), None, {}
+    draw = lambda size: env.render(mode='rgb_array', window_size=size)      # noqa: E731
+    if frames is not None:
+        frames(draw)
     log = _EpisodeLog(env)
     if verbose:
         print('|'.join([''] + [f' {name} ' for name in COLUMNS] + ['']))
@@ -98,16 +134,22 @@ def evaluate(env, joint_policy=None, verbose=False, history=None):
             history.append(dict(row))
         if verbose:
             print(format_row(list(row.values())))
+        if frames is not None:
+            frames(draw)
     return status
 
 
-def evaluate_batched(env, episodes, policy='greedy', chunk=16, seed=0):
+def evaluate_batched(env, episodes, policy='greedy', chunk=16, seed=0, frames=None):
     """Runs `env` (a BatchedMultiAgentTracking built with episode_records) under the on-device agents -- 'greedy': both teams' scripted
     agents, fused `chunk` frames per launch where both are the Greedy ones; 'random': the uniform policy -- until `episodes` episode
     records have arrived.  An environment built with single_agent = ... runs a uniformly random learner in the seat (a generator seeded with
-    `seed`) among the on-device teammates, whatever `policy`.  Returns them, oldest first, [episodes, 16] f64 on the host."""
+    `seed`) among the on-device teammates, whatever `policy`.  Returns them, oldest first, [episodes, 16] f64 on the host.  `frames` (a
+    FrameSaver): the picture of environment 0 behind the reset and behind every `chunk` frames (no headings: the engine keeps none)."""
     import torch
     env.reset()
+    draw = lambda size: env.render((0,), size=size)[0].cpu().numpy()      # noqa: E731
+    if frames is not None:
+        frames(draw)
     # (an active communication channel is like a non-Greedy opponent: the fused launch delivers every message, so per-step calls)
     fused = policy == 'random' or (env.target_agent == 'greedy' and env.camera_agent == 'greedy' and not any(env.engine.mixtures) and not env.engine.channel_active())
     rows, have = [], 0
@@ -128,6 +170,8 @@ def evaluate_batched(env, episodes, policy='greedy', chunk=16, seed=0):
         else:
             for _ in range(chunk):
                 env.engine.step_greedy(auto_reset=env.auto_reset)
+        if frames is not None:
+            frames(draw)
         records = env.episodes()
         rows.append(torch.stack([records[name] for name in env.engine.EPISODE_COLUMNS], dim=1).cpu())
         have += rows[-1].shape[0]
@@ -195,12 +239,19 @@ def build_parser():
                          'the agent and mixture flags keep their meaning for the opposing team')
     ap.add_argument('--team', choices=['camera', 'target'], default='target',
                     help='with --num-envs: the team whose rewards the records hold (num_tracked is kept for the camera team)')
+    ap.add_argument('--save-frames', default=None, metavar='DIR',
+                    help="write the episode's pictures as DIR/frame_<n>.png (mate.evaluate's --save-video: rgb_array frames rasterised on the device; "
+                         'with --num-envs: environment 0)')
+    ap.add_argument('--frame-size', type=int, default=800, metavar='S', help='with --save-frames: S x S pixels')
+    ap.add_argument('--frame-every', type=int, default=1, metavar='K',
+                    help='with --save-frames: every K-th picture (a picture per step; with --num-envs: per launch of 16 frames)')
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     import mate_amd
+    frames = FrameSaver(args.save_frames, args.frame_size, args.frame_every) if args.save_frames else None
     overrides = {} if args.max_episode_steps is None else {'max_episode_steps': args.max_episode_steps}
     if args.num_envs is not None:
         from .engine import Engine
@@ -211,7 +262,7 @@ def main(argv=None):
                                                  communication_range=args.communication_range, single_agent=args.single_agent, **overrides)
         if args.policy == 'greedy':
             env.enable_greedy_policies()
-        records = evaluate_batched(env, args.episodes, args.policy, seed=args.seed)
+        records = evaluate_batched(env, args.episodes, args.policy, seed=args.seed, frames=frames)
         names = Engine.EPISODE_COLUMNS[EPISODE_REPORT]
         print(f'{len(records)} episodes of {args.config}, {args.num_envs} at a time, team {args.team}:')
         for name, column in zip(names, records[:, EPISODE_REPORT].T):
@@ -232,7 +283,7 @@ def main(argv=None):
     env.seed(args.seed)
     rows = []
     for episode in range(args.episodes):
-        status = evaluate(env, None if args.policy == 'greedy' else random_policy(args.seed + episode), verbose=args.verbose)
+        status = evaluate(env, None if args.policy == 'greedy' else random_policy(args.seed + episode), verbose=args.verbose, frames=frames)
         rows.append(status)
         print(f'episode {episode}: ' + ', '.join(f'{k}: {fmt(status[k])}' for k, fmt in COLUMNS.items() if k in status))
     return rows
