@@ -741,6 +741,29 @@ int mate_engine_frame_fragment(mate_engine *engine, const mate_frame_fragments *
 int mate_engine_keep_masks(mate_engine *engine);
 int mate_engine_render(mate_engine *engine, const int32_t *env_indices_dev, int64_t count, int32_t size, const double *headings_dev, uint8_t *out_dev, void *stream);
 
+/* Communication trace: the state of mate.RenderCommunication (mate/wrappers/render_communication.py) on the device (csrc/trace_rows.hpp; the rules: DESIGN.md
+ * section 3.21).  Per enabled team an engine-owned uint8 matrix remaining[N][n sender][n recipient] and an int32 episode tag per environment.  While enabled,
+ * every per-step call -- step, step_random, step_greedy, step_versus_greedy, step_selected, step_seated -- enqueues ONE more launch, comm_trace_kernel, behind
+ * the agents' launches and ahead of the stepping launch (the wrapper updates before env.step).  For every environment that takes a live step in the call:
+ * remaining = max(remaining - 1, 0), then remaining[s][r] = duration wherever a message s -> r was DELIVERED since the previous step -- the team's `delivered`
+ * matrix of this call's agents' launch where it ran under a channel (mate_engine_set_channel: a team the engine plays WITHOUT a channel never materialises its
+ * edges and marks nothing; a channel with default settings is transparent), the team's step_edges > 0 of mate_engine_route_messages since the last stepping
+ * launch, both where both exist.  An environment idling under a batched restart keeps its bytes.  A launch that finds an episode number other than the tag starts
+ * that environment from zeros and retags it (the wrapper's reset()): resets and restarts need no launch; enable, mate_engine_seed and mate_engine_import_state
+ * clear the tags.  mate_engine_render draws the arrows of every enabled team's matrix whose tag is the environment's episode number, at the wrapper's list
+ * position: behind the obstacles, ahead of the first camera's sector.
+ * mate_engine_enable_comm_trace: teams_mask = 1 << MATE_TEAM_CAMERA, 1 << MATE_TEAM_TARGET or both (0 detaches; the buffers stay the engine's), duration in
+ * [1, 255] (the wrapper's default: 20); the enabled matrices start from zeros.  MATE_EINVAL: a mask outside [0, 3], a duration outside [1, 255], a team
+ * without agents.  Under a mixture the `delivered` rows of the environments whose episode drew a candidate that does not talk read zero, and a team of Naive / Random
+ * agents alone is not in the agents' launch: nothing is marked.  While enabled, mate_engine_rollout_random, _rollout_greedy and _rollout_versus_greedy (their frames'
+ * edges are never materialised: step per frame) and every call with auto_reset = MATE_RESET_PIPELINED return MATE_ESTATE.  A refused call changes nothing.
+ * mate_engine_comm_trace: the engine-owned matrix and tags of an enabled team (either pointer may be null).
+ * mate_engine_set_comm_trace: copies the caller's [N][n][n] matrix on the device into the engine's and tags every environment with its current episode number;
+ * complete when the call returns.  MATE_ESTATE: the team is not enabled, or before the first reset / import_state. */
+int mate_engine_enable_comm_trace(mate_engine *engine, int32_t teams_mask, int32_t duration);
+int mate_engine_comm_trace(mate_engine *engine, int32_t team, uint8_t **remaining_dev, int32_t **tag_dev);
+int mate_engine_set_comm_trace(mate_engine *engine, int32_t team, const uint8_t *remaining_dev);
+
 /* Per-episode metric records (csrc/episode_rows.hpp): what the reference's example trainers report at every episode's end (examples/utils/callbacks.py:
  * MetricCollector's mean over the agents of each learner step's infos, CustomMetricCallback.on_episode_end's mean / last / episode_<key> sums over the
  * episode's steps), kept on the device for ONE team's perspective.  While attached every stepping call -- step, step_random, step_greedy,

@@ -177,6 +177,9 @@ PROTOTYPES = {
     'mate_engine_info_rows': (INT, [P, P, P, P, P, P]),
     'mate_engine_keep_masks': (INT, [P]),
     'mate_engine_render': (INT, [P, P, I64, I32, P, P, P]),
+    'mate_engine_enable_comm_trace': (INT, [P, I32, I32]),
+    'mate_engine_comm_trace': (INT, [P, I32, ctypes.POINTER(P), ctypes.POINTER(P)]),
+    'mate_engine_set_comm_trace': (INT, [P, I32, P]),
     'mate_engine_lut_read': (INT, [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]),
     'mate_engine_lut_read_outer': (INT, [P, I64, I32, P, P, I32, ctypes.POINTER(I32)]),
     'mate_engine_enable_outer_boundary': (INT, [P, ctypes.POINTER(I32)]),

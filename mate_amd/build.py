@@ -29,6 +29,8 @@ UNITS += [('opponent_kernels', 'opponent_kernels.hip', (), 'kernel_resources_opp
 # The units outside that table: compiled and linked with it, each with a record of its own that no test of the table's reads.  render_kernel came after
 # tests/test_gpu_frame_fragments.py had pinned the set of kernels the opponents' record may gain, so it could join neither that unit nor the table.
 LATER_UNITS = [('render_kernels', 'render_kernels.hip', (), 'render_resources.json')]                  # render_kernel
+# ... and the units that came behind tests/test_render_host.py, which pins LATER_UNITS to its one row: a third list, compiled and linked with the others.
+TRACE_UNITS = [('trace_kernels', 'trace_kernels.hip', (), 'trace_resources.json')]                    # comm_trace_kernel, trace_plant_kernel
 # Everything the library is built from: the sources in csrc/ by suffix (no editor backup, no stray object) in sorted order -- the same
 # digest on every machine -- and the public header.
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.splitext(f)[1] in ('.hip', '.hpp', '.h', '.inc')) + [
@@ -89,7 +91,7 @@ def _compile_and_link(out, extra=(), verbose=False, remarks=False):
     objdir = os.path.join(os.path.dirname(OUT), 'obj', os.path.splitext(os.path.basename(out))[0])
     os.makedirs(objdir, exist_ok=True)
     compile_flags = [f for f in FLAGS if f != '-shared'] + list(extra) + (['-Rpass-analysis=kernel-resource-usage'] if remarks else [])
-    units = UNITS + LATER_UNITS
+    units = UNITS + LATER_UNITS + TRACE_UNITS
     objects = [os.path.join(objdir, name + '.o') for name, _, _, _ in units]
 
     def compile_unit(unit, obj):

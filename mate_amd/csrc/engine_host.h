@@ -27,6 +27,7 @@
 #include "seat_rows.hpp"
 #include "message_rows.hpp"
 #include "render_rows.hpp"
+#include "trace_rows.hpp"
 
 using namespace mate;
 
@@ -154,6 +155,16 @@ struct InfoRows {        // mate_engine_enable_info_rows: scalars, masks, mode a
     InfoArgs args{};                             // the caller's three row buffers (any may be null), the engine-owned snapshot
     int32_t *d_snapshot = nullptr;               // [N][Nt + 1], allocated at the first enable: the goals and the episode the next step's individual_done compares with
 };
+struct CommTrace {      // mate_engine_enable_comm_trace: RenderCommunication's state (trace_rows.hpp), one matrix per team; the buffers are engine-owned and kept across re-attachments
+    int duration = 0;                            // 0: detached
+    struct Team {
+        bool on = false;
+        uint8_t *d_remaining = nullptr;          // [N][n][n], allocated at the first enable
+        int32_t *d_tags = nullptr;               // [N]: the episode number the matrix belongs to (-1: none)
+        bool call_delivered = false;             // of the call in progress: its agents' launch ran under a channel and wrote the team's `delivered` matrix (step_with_policies sets it, step_launches clears it)
+    } team[2];
+    bool on() const { return duration > 0; }
+};
 struct mate_engine {
     Switches sw{};
     hipStream_t last_stream = nullptr;   // stream of the most recent launch: what the host-side accessors wait for ...
@@ -204,6 +215,7 @@ struct mate_engine {
     Channels channel;                    // the communication channels
     Seat seat;                           // the learner's seat among on-device teammates
     Messages messages;                   // the learner's own messages through the team's channel
+    CommTrace trace;                     // RenderCommunication's per-pair countdowns
     StateRows state; RewardRows reward; Selection selection; FragmentRows fragment; FirstRows first; FrameFragments frames; EpisodeRecords episodes; InfoRows info;      // what is attached around the stepping launches (plan_attached)
     // kernel timing (HIP events on the launch stream)
     int timing = 0;            // 0 = off, k = time every k-th step launch
@@ -315,6 +327,8 @@ static LaunchPlan plan_with_policies(const mate_engine *e, bool per_step, int te
 //   2a..2c         the two-launch form's launches between the two, in this order: the agents' launch (policy_kernel or greedy_channel_kernel),     step_with_policies
 //                  heuristic_camera_kernel, heuristic_drift_kernel, scripted_opponent_kernel -- WHICH of them a call runs, for which teams, and whose
 //                  rows the stepping launch then consumes is the call's OpponentPlan (plan_opponents, below)
+//   2d trace       comm_trace_kernel, behind the agents' launches (their `delivered` edges, the learner's routed step_edges) and ahead of the stepping     step_launches, rollout_with_policies
+//                  launch, as the wrapper updates before env.step: the per-pair countdowns of RenderCommunication (trace_rows.hpp)
 //   3 reward       soft_coverage_kernel where the term exists, reward_rows_kernel: the step's rows          attached_behind_step
 //   3b info        info_rows_kernel: MoreTrainingInformation's per-agent rows of the launch's last frame       attached_behind_step
 //   4 observe      selection_kernel, SELECTION_OBSERVE: the selection metrics against that step's masks     attached_behind_step

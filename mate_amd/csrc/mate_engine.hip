@@ -574,6 +574,14 @@ static int clear_message_tags(mate_engine *e, hipStream_t stream) {
     return MATE_OK;
 }
 
+// The communication trace's episode tags (csrc/trace_rows.hpp) likewise, behind seed() and import_state.  Every tag reads -1: no episode number equals it, the next launch starts every environment's matrix from zeros and no arrow is drawn until then.  Behind
+// enable, seed() and import_state (whose episode numbers may repeat the tags'); every reset and restart advances the number and needs nothing.
+static int clear_trace_tags(mate_engine *e, hipStream_t stream) {
+    for (const CommTrace::Team &t : e->trace.team)
+        if (t.d_tags) HIP_TRY(hipMemsetAsync(t.d_tags, 0xff, sizeof(int32_t) * (size_t)e->N, stream));
+    return MATE_OK;
+}
+
 extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     if (e->dev_tick) return fail(MATE_ESTATE, "seed() while the step counter is device-resident (mate_engine_device_tick)");
@@ -586,6 +594,7 @@ extern "C" int mate_engine_seed(mate_engine *e, uint64_t seed) {
     HIP_TRY(hipGetLastError());
     MATE_TRY(clear_episode_sums(e, e->last_stream));
     MATE_TRY(clear_message_tags(e, e->last_stream));
+    MATE_TRY(clear_trace_tags(e, e->last_stream));
     HIP_TRY(wait_for_launches(e));
     e->tick = 0;
     return MATE_OK;
@@ -725,6 +734,7 @@ static int launch_info(mate_engine *e, const AttachedPlan &pl, int mode, const f
     return MATE_OK;
 }
 static int launch_frame_of_call(mate_engine *e, const AttachedPlan &pl, const mate_step_io *io, hipStream_t stream);      // (5', below)
+static int launch_trace(mate_engine *e, int freeze_done, hipStream_t stream);      // (2d, trace_host.inc)
 // What the attachments ask of a stepping call and what they refuse: made ONCE per call, by the flow the call enters, ahead of everything it enqueues.
 // `pipelined`: the call asks for pipelined restarts in a flow that has them; `selected`: it is mate_engine_step_selected (`auto_reset`: its own);
 // `fused_team`: it is mate_engine_rollout_versus_greedy for that team (-1: any other call).
@@ -755,6 +765,7 @@ static int check_attached_call(const mate_engine *e, const mate_step_io *io, boo
             return fail(MATE_EINVAL, "episode records are attached (mate_engine_enable_episode_records): the call needs io->scalars_dev, 16-byte aligned");
     }
     if (pipelined && e->info.on) return fail(MATE_ESTATE, no_pipeline, "training-information rows are", "info_rows", "them");
+    if (pipelined && e->trace.on()) return fail(MATE_ESTATE, no_pipeline, "the communication trace is", "comm_trace", "it");
     if (e->info.on && (!io || !io->scalars_dev || !io->masks_dev))      // (the info launch reads the step's scalar record and masks)
         return fail(MATE_EINVAL, "training-information rows are attached (mate_engine_enable_info_rows): the call needs io->scalars_dev and io->masks_dev");
     return MATE_OK;
@@ -1378,6 +1389,7 @@ static int step_launches(mate_engine *e, const mate_step_io *io, int mode, int a
     const LaunchPlan pl = plan_step(e, mode, g);
     e->last_flow = pl.last_flow;
     if (pl.E > 1) { g.per_step = 1; g.rollout_steps = 1; g.rotate_prio = 0; }      // (the sub-wave rollout kernel with ONE step)
+    if (mode != MODE_OBSERVE) MATE_TRY(launch_trace(e, g.freeze_done, stream));      // (2d: behind the agents' launches, ahead of the step)
     launch(pl.step, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
@@ -1403,9 +1415,14 @@ extern "C" int mate_engine_step(mate_engine *e, const mate_step_io *io, int32_t 
 extern "C" int mate_engine_step_random(mate_engine *e, const mate_step_io *io, int32_t auto_reset, void *stream) {
     return attached_last(e, launch_step(e, io, MODE_STEP_RANDOM, auto_reset, (hipStream_t)stream), (hipStream_t)stream);
 }
+// The fused K-frame launches never materialise their frames' edges: refused while a communication trace is enabled, as under a channel
+static int refuse_traced_rollout(const mate_engine *e, const char *who) {
+    return e->trace.on() ? fail(MATE_ESTATE, "%s: a communication trace is enabled (mate_engine_enable_comm_trace) and the fused launches keep no per-frame edges: step per frame, or detach the trace", who) : MATE_OK;
+}
 static int rollout_random_impl(mate_engine *e, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_) {
     if (!e) return fail(MATE_EINVAL, "null engine");
     hipStream_t stream = (hipStream_t)stream_;
+    MATE_TRY(refuse_traced_rollout(e, "rollout_random"));
     MATE_TRY(enter(e, stream, "rollout"));
     if (e->dev_tick) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     if (steps < 1) return fail(MATE_EINVAL, "rollout needs at least one step");
@@ -1515,6 +1532,7 @@ static bool one_launch_step(const mate_engine *e, const FusedCall &c, const Oppo
 #include "message_host.inc"       // the learner's own messages: enable, the routing launch, draws, accessors
 #include "frame_host.inc"         // the per-frame FrameSkip fragments: enable, the call's check, the on-demand launch
 #include "render_host.inc"        // the off-screen render: the argument check, the launch
+#include "trace_host.inc"         // the communication trace: enable, the one launch of a stepping call, the accessor
 
 static int rollout_with_policies(mate_engine *e, int team_caller, const mate_step_io *io, int32_t steps, int32_t auto_reset, void *stream_, bool per_step = false, bool selected = false);
 
@@ -1569,7 +1587,11 @@ static int step_with_policies(mate_engine *e, int team_caller, const mate_step_i
     if (team_caller != MATE_TEAM_TARGET) { io2.target_actions_dev = rows_of(e, MATE_TEAM_TARGET, op.team[MATE_TEAM_TARGET].source); io2.act_dtype &= ~MATE_ACT_TARGET_DISCRETE; }
     for (int team = 0; team < 2; ++team) e->opponents.consumed[team] = op.team[team].source;
     e->greedy_team_bits = team_caller < 0 ? 3 : (team_caller == 0 ? 2 : 1);
+    // (greedy_channel_kernel writes the edges of every team that acts in it -- OpponentPlan::Team::greedy: the team's Greedy agents run in the agents' launch, as the
+    // team's players or for a mixture that has a Greedy candidate, or Heuristic targets built on them; a team of Naive / Random agents alone is not in that launch and sends nothing)
+    for (int team = 0; team < 2; ++team) e->trace.team[team].call_delivered = op.channel_kernel && op.team[team].greedy;
     const int rc = step_launches(e, &io2, MODE_STEP, auto_reset, stream, selected);
+    for (int team = 0; team < 2; ++team) e->trace.team[team].call_delivered = false;
     e->greedy_team_bits = 0;
     return rc;
 }
@@ -1750,6 +1772,7 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     const PolicyFlow flow = per_step ? PolicyFlow{Restart{io, false, RESET_DONE, full, false, true, 1u, kStepFlow}, auto_reset != 0, false, true}
                                      : PolicyFlow{Restart{nullptr, false, RESET_FLAGGED, full, true, false, (uint32_t)steps, kRolloutFlow, team_caller}, auto_reset == 1 || pipelined, true, team_caller >= 0};
     if (!c.reset) return fail(MATE_ESTATE, "rollout_greedy called before reset() (or import_state)");
+    if (!per_step) MATE_TRY(refuse_traced_rollout(e, team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy"));
     MATE_TRY(refuse_fused(plan_opponents(e, team_caller), team_caller < 0 ? "rollout_greedy" : "rollout_versus_greedy"));      // (a per-step call never arrives here with one: one_launch_step)
     if (e->dev_tick && !flow.may_count_on_device) return fail(MATE_ESTATE, "not available while the step counter is device-resident (mate_engine_device_tick)");
     MATE_TRY(check_device_tick(e, auto_reset, steps, false));
@@ -1792,6 +1815,9 @@ static int rollout_with_policies(mate_engine *e, int team_caller, const mate_ste
     MATE_TRY(take_timing_events(e, !e->dev_tick, &t));
     e->last_flow = pl.last_flow;
     e->opponents.consumed[MATE_TEAM_CAMERA] = e->opponents.consumed[MATE_TEAM_TARGET] = ROWS_GREEDY;      // (the joint actions of this launch are in q.cam_act / q.tgt_act: the Greedy agents', or the caller's)
+    // (2d: the one-launch step holds its agents, so only the learner's routed messages mark; an engine-played team's trace needs its channel, which takes the two-launch
+    // form.  This launch idles EVERY finished environment, whatever auto_reset is -- its record then says done = 2 --, so the trace's liveness rule is the record's done word alone)
+    if (per_step) MATE_TRY(launch_trace(e, 1, stream));
     launch(pl.policy, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, t, e->d_params, g, q);
     HIP_TRY(hipGetLastError());
     e->selection.masks_stale = false;
@@ -1853,6 +1879,7 @@ extern "C" int mate_engine_import_state(mate_engine *e, const double *src_dev, v
     HIP_TRY(hipGetLastError());
     MATE_TRY(clear_episode_sums(e, (hipStream_t)stream));
     MATE_TRY(clear_message_tags(e, (hipStream_t)stream));
+    MATE_TRY(clear_trace_tags(e, (hipStream_t)stream));
     // all environments step together, so they share one tick: adopt the imported one
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     int32_t tick = 0;

@@ -25,7 +25,9 @@ extern "C" int mate_engine_render(mate_engine *e, const int32_t *env_indices_dev
     const int64_t tiles = (int64_t)((size + kRenderTile - 1) / kRenderTile) * ((size + kRenderTile - 1) / kRenderTile);
     if (count > (int64_t)0x7fffffff / tiles) return fail(MATE_EINVAL, "render: %lld frames of %d x %d pixels are more tiles than one launch takes", (long long)count, size, size);
     if (render_slots(p.Nc, p.Nt, p.No) > kRenderMaxSlots) return fail(MATE_EINVAL, "render: the display list of this scenario is longer than %d primitives", kRenderMaxSlots);
-    const size_t lds = (size_t)render_lds_bytes(p.Nc, p.Nt, p.No);
+    const bool arrows = e->trace.on();         // (the arrows of whichever teams have a communication trace: their part of the LDS only then)
+    if (arrows && (p.Nc > 16 || p.Nt > 16)) return fail(MATE_EINVAL, "render: the arrows of a communication trace take teams of at most 16 agents");
+    const size_t lds = (size_t)render_lds_bytes(p.Nc, p.Nt, p.No) + (arrows ? (size_t)kRenderArrowBytes : 0);
     if (lds > 64 * 1024) return fail(MATE_EINVAL, "render: the display list does not fit the dynamic LDS a launch has without opting in");
     MATE_TRY(enter(e, (hipStream_t)stream, "render"));
     mate_layout layout;
@@ -34,6 +36,9 @@ extern "C" int mate_engine_render(mate_engine *e, const int32_t *env_indices_dev
     a.stat = e->g.stat; a.dyn = e->g.dyn; a.knots = e->g.lut_knots; a.bucket = e->g.lut_bucket; a.knot_count = e->g.lut_count;
     a.masks = e->g.own_masks; a.envs = env_indices_dev; a.headings = headings_dev; a.out = out_dev;
     a.N = e->N; a.count = (int32_t)count; a.size = size; a.bit_ct = layout.bit_camera_target; a.bit_tr = layout.bit_target_row;
+    for (int team = 0; arrows && team < 2; ++team)
+        if (e->trace.team[team].on) { a.trace[team] = e->trace.team[team].d_remaining; a.trace_tags[team] = e->trace.team[team].d_tags; }
+    a.duration = e->trace.duration;
     note_stream(e, (hipStream_t)stream);
     HIP_TRY(launch_render(size % kRenderTile == 0, (unsigned)(count * tiles), lds, (hipStream_t)stream, e->d_params, a));
     return MATE_OK;

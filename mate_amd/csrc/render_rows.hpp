@@ -12,6 +12,12 @@
 //   per target   the tracked marker (a 15-gon), where tracked
 //   per target   the arrow (capacity 1: six vertices, else five; fans from vertex 0) in its goal's colour, turned by its heading; then, loaded without a bounty,
 //                the same at scale 0.4 in white, alpha .66
+// With a communication trace (trace_rows.hpp) RenderCommunication's arrows go where its callback prepends them to the one-time list: behind the
+// obstacles, ahead of the first camera's sector.  Cameras' pairs then targets', sender-major, every pair with remaining > 0 and distinct positions: draw_arrow's two
+// or three lines (render_communication.py:66-92), each a dashed segment of width 2.5 pixels -- a centre is covered within 1.25 pitches of the segment and where
+// floor(u) mod 8 < 4, u the distance of its clamped projection from the line's FIRST vertex along the segment's major axis in pitches (stipple 0x0F0F, factor 1).
+// The workgroup keeps the pairs whose endpoints' box, padded by 60 + 1.25 pitches, meets the tile (the same ordered compaction), builds their lines in LDS
+// kRenderArrowChunk pairs at a time at that list position, and every pixel walks them.
 // A primitive blends ONCE per pixel, dst = src a + dst (1 - a) in f32 without contraction, and the pixel is quantised once, floor(255 c + 0.5).
 //
 // Mapping: one 256-thread workgroup per 16 x 16 pixel tile of one requested environment, thread = pixel.  The workgroup first writes the environment's
@@ -48,6 +54,9 @@ struct RenderArgs {
     uint8_t *out;                                     // [count][size][size][3]
     int64_t N;
     int32_t count, size, bit_ct, bit_tr;
+    const uint8_t *trace[2];                          // the teams' remaining[N][n][n] of the communication trace (trace_rows.hpp), or null
+    const int32_t *trace_tags[2];                     // [N] the episode number each matrix belongs to
+    int32_t duration;                                 // of the trace; 0: no arrows, and nothing below is read
 };
 
 __host__ __device__ constexpr int render_slots(int Nc, int Nt, int No) { return 5 + No + 4 * Nc + 3 * Nt; }
@@ -56,6 +65,11 @@ constexpr int kRenderImageBytes = kRenderTile * kRenderTile * 3, kRenderFlagWord
 __host__ __device__ constexpr int render_lds_bytes(int Nc, int Nt, int No) {
     return (render_slots(Nc, Nt, No) * kRenderPrimWords + (Nc > 0 ? Nc : 1) * kRenderCamWords + 2 * (72 + 15)) * 8 + kRenderMaxSlots * 2 + kRenderImageBytes + kRenderFlagWords * 4;
 }
+
+// the arrows' part, behind everything above and only in a launch with a trace: the lines of a chunk of pairs, the listed pairs, 4 wave counts
+constexpr int kRenderArrowChunk = 128, kRenderArrowWords = 9, kRenderMaxPairs = 512;      // doubles per pair: start | end | end - vec1 | end - vec2 | alpha (f32), lines (i32)
+constexpr int kRenderArrowBytes = kRenderArrowChunk * kRenderArrowWords * 8 + kRenderMaxPairs * 2 + 16;
+constexpr double kArrowHead = 0.05 * kTerrain, kArrowOffset = 0.01 * kTerrain, kArrowHalfWidth = 1.25;      // render_communication.py:71-80; half of stroke 2.5, in pitches
 
 __device__ __forceinline__ double render_cross(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
 
@@ -88,6 +102,17 @@ __device__ __forceinline__ float render_blend(float dst, float src, float a) { r
 __device__ __forceinline__ uint32_t render_quantise(float c) {
     const float q = __builtin_floorf(__fadd_rn(__fmul_rn(255.0f, c), 0.5f));
     return (uint32_t)(q < 0.0f ? 0.0f : (q > 255.0f ? 255.0f : q));
+}
+
+// One dashed line a -> b at the pixel centre (px, py): within `half` of the segment, and in an on-phase of the stipple counted from a
+__device__ __forceinline__ bool render_dash(double px, double py, double ax, double ay, double bx, double by, double half, double pitch) {
+    const double ex = bx - ax, ey = by - ay;
+    const double t = clipd(((px - ax) * ex + (py - ay) * ey) / (ex * ex + ey * ey), 0.0, 1.0);
+    const double qx = t * ex, qy = t * ey;
+    const double ox = px - (ax + qx), oy = py - (ay + qy);
+    if (!(ox * ox + oy * oy <= half * half)) return false;
+    const double along = __builtin_fabs(ex) >= __builtin_fabs(ey) ? __builtin_fabs(qx) : __builtin_fabs(qy);
+    return ((int)floor(along / pitch) & 7) < 4;
 }
 
 // `kWide`: the size is a multiple of 16 -- the tile's rows leave as 16-byte pieces
@@ -297,11 +322,95 @@ __global__ __launch_bounds__(256, 4) void render_kernel(const Params *__restrict
     }
     const int listed = (int)(wave_hits[0] + wave_hits[1] + wave_hits[2] + wave_hits[3]);
 
+    // ---------------------------------------------------------------------------------------------- 2b: the pairs of the trace whose arrow can touch the tile, in the wrapper's order
+    double *arrows = reinterpret_cast<double *>(render_lds + render_lds_bytes(Nc, Nt, No));
+    uint16_t *pairs = reinterpret_cast<uint16_t *>(arrows + kRenderArrowChunk * kRenderArrowWords);      // team << 8 | sender << 4 | recipient
+    uint32_t *pair_hits = reinterpret_cast<uint32_t *>(pairs + kRenderMaxPairs);
+    int kept = 0, split = -1;                                                // split: the list position the arrows go in front of (-1: there are none)
+    if (a.duration > 0) {
+        const int32_t episode = (di + Nt * TI_STRIDE)[EI_EPISODE];
+        const int nnc = a.trace[0] && a.trace_tags[0][env] == episode ? Nc * Nc : 0;
+        const int nnt = a.trace[1] && a.trace_tags[1][env] == episode ? Nt * Nt : 0;
+        const double pad = kArrowHead + kArrowOffset + kArrowHalfWidth * pitch;
+        const double tx0 = -kRenderBound + ((double)c0 + 0.5) * pitch - pad, tx1 = -kRenderBound + ((double)(c0 + kRenderTile - 1) + 0.5) * pitch + pad;
+        const double ty1 = kRenderBound - ((double)r0 + 0.5) * pitch + pad, ty0 = kRenderBound - ((double)(r0 + kRenderTile - 1) + 0.5) * pitch - pad;
+        for (int base = 0; base < nnc + nnt; base += 256) {                  // (the same trip count in every lane)
+            const int j = base + tid;
+            bool hit = false;
+            int code = 0;
+            if (j < nnc + nnt) {
+                const int team = j >= nnc, jj = team ? j - nnc : j, n = team ? Nt : Nc, s = jj / n, r = jj - s * n;
+                if (s != r && a.trace[team][env * (n * n) + jj] > 0) {
+                    const double *xs = team ? dy + 2 * Nc : st, *ys = xs + n;
+                    const double sx = xs[s], sy = ys[s], rx = xs[r], ry = ys[r];
+                    hit = !(sx == rx && sy == ry) && (sx < rx ? sx : rx) <= tx1 && (sx > rx ? sx : rx) >= tx0 && (sy < ry ? sy : ry) <= ty1 && (sy > ry ? sy : ry) >= ty0;
+                }
+                code = team << 8 | s << 4 | r;
+            }
+            const unsigned long long ballot = __ballot(hit);
+            if (lane == 0) pair_hits[wave] = (uint32_t)__popcll(ballot);
+            __syncthreads();
+            int before = kept;
+            for (int w = 0; w < 4; ++w) before += w < wave ? (int)pair_hits[w] : 0;
+            if (hit) pairs[before + __popcll(ballot & ((1ull << lane) - 1ull))] = (uint16_t)code;
+            kept += (int)(pair_hits[0] + pair_hits[1] + pair_hits[2] + pair_hits[3]);
+            __syncthreads();
+        }
+        if (kept > 0) for (split = 0; split < listed && (int)list[split] < 5 + No; ++split) {}
+    }
+
     // ---------------------------------------------------------------------------------------------- 3: the pixel walks the list
     const int pc = c0 + (tid & (kRenderTile - 1)), pr = r0 + (tid >> 4);
     const double px = -kRenderBound + ((double)pc + 0.5) * pitch, py = kRenderBound - ((double)pr + 0.5) * pitch;
     float fr = 1.0f, fg = 1.0f, fb = 1.0f;
-    for (int i = 0; i < listed; ++i) {
+    for (int i = 0; i <= listed; ++i) {
+        if (i == split) {                                                    // the arrows' list position: behind the static geoms (the same in every lane)
+            const double half = kArrowHalfWidth * pitch;
+            for (int first = 0; first < kept; first += kRenderArrowChunk) {
+                const int chunk = kept - first < kRenderArrowChunk ? kept - first : kRenderArrowChunk;
+                if (tid < chunk) {                                           // draw_arrow (render_communication.py:66-92) of one pair
+                    const int code = pairs[first + tid], team = code >> 8, s = (code >> 4) & 15, r = code & 15, n = team ? Nt : Nc;
+                    const double *xs = team ? dy + 2 * Nc : st, *ys = xs + n;
+                    const uint8_t *rem = a.trace[team] + env * (n * n);
+                    const int remaining = rem[s * n + r];
+                    const bool both = rem[r * n + s] > 0;
+                    const double sx = xs[s], sy = ys[s], ex = xs[r], ey = ys[r];
+                    double vx = ex - sx, vy = ey - sy;
+                    const double norm = sqrt(vx * vx + vy * vy);
+                    const double shrink = (norm - kArrowHead) / norm, scale = 0.9 > shrink ? 0.9 : shrink;
+                    vx = vx * scale; vy = vy * scale;
+                    double v1x = 0.04 * vx + 0.015 * vy, v1y = -0.015 * vx + 0.04 * vy, v2x = 0.04 * vx + -0.015 * vy, v2y = 0.015 * vx + 0.04 * vy;
+                    const double n1 = kArrowHead / sqrt(v1x * v1x + v1y * v1y), n2 = kArrowHead / sqrt(v2x * v2x + v2y * v2y);
+                    const double k1 = 1.0 < n1 ? 1.0 : n1, k2 = 1.0 < n2 ? 1.0 : n2;
+                    v1x = v1x * k1; v1y = v1y * k1; v2x = v2x * k2; v2y = v2y * k2;
+                    double ax = ex - vx, ay = ey - vy, bx = sx + vx, by = sy + vy;      // start, end = end - vec, start + vec
+                    if (both) {
+                        double ux = 0.0 * vx + -1.0 * vy, uy = 1.0 * vx + 0.0 * vy;
+                        const double ku = kArrowOffset / sqrt(ux * ux + uy * uy);
+                        ux = ux * ku; uy = uy * ku;
+                        ax = ax + ux; ay = ay + uy; bx = bx + ux; by = by + uy;
+                    }
+                    double *w = arrows + tid * kRenderArrowWords;
+                    w[0] = ax; w[1] = ay; w[2] = bx; w[3] = by; w[4] = bx - v1x; w[5] = by - v1y; w[6] = bx - v2x; w[7] = by - v2y;
+                    const double alpha = 1.2 * (double)remaining / (double)a.duration;
+                    reinterpret_cast<float *>(w + 8)[0] = (float)(1.0 < alpha ? 1.0 : alpha);
+                    reinterpret_cast<int32_t *>(w + 8)[1] = (both ? 2 : 3) | team << 2;
+                }
+                __syncthreads();
+                for (int j = 0; j < chunk; ++j) {
+                    const double *w = arrows + j * kRenderArrowWords;
+                    const float al = reinterpret_cast<const float *>(w + 8)[0];
+                    const int meta = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(w + 8)[1]), lines = meta & 3;
+                    const float red = (meta >> 2) ? 1.0f : 0.0f, blue = (meta >> 2) ? 0.0f : 1.0f;      // targets red, cameras blue
+                    for (int l = 0; l < lines; ++l) {
+                        const double *from = l == 0 ? w : w + 2 + 2 * l;
+                        if (render_dash(px, py, from[0], from[1], w[2], w[3], half, pitch)) { fr = render_blend(fr, red, al); fg = render_blend(fg, 0.0f, al); fb = render_blend(fb, blue, al); }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (i == listed) break;
         const double *q = prims + (int)list[i] * kRenderPrimWords;
         const float *rgba = reinterpret_cast<const float *>(q + 18);
         const int32_t *meta = reinterpret_cast<const int32_t *>(q + 20);

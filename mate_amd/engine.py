@@ -255,6 +255,8 @@ class Engine:
         self.block_rates, self.store_form, self.reserve_seconds = [], 0, 0.0
         self._random_io = {}              # the cached argument blocks of step_random (_forget_calls)
         self._own_masks = False           # (keep_masks, enable_policies)
+        self._policies = False            # (enable_policies)
+        self.trace_duration, self.trace_teams = 0, ()      # (enable_communication_trace)
         self._staged = self._softcov = self._export_slices = None      # (stage_outputs, soft_coverage, state_dict_from)
         self._clear_state_rows()
         self._clear_reward_rows()
@@ -686,6 +688,7 @@ class Engine:
             if value not in known:
                 raise ValueError(f"{name} must be one of {known}, got {value!r}")
         check(self.lib.mate_engine_policy_enable(self._h))
+        self._policies = True
         self._own_masks = True            # (the engine's own copy of the mask words exists from here on: render)
         if target_agent != 'greedy' or self.target_agent != 'greedy':
             self.set_target_opponent(target_agent)
@@ -1511,6 +1514,69 @@ class Engine:
                                           ctypes.c_void_p(headings.data_ptr()) if headings is not None else None, ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ communication arrows (mate/wrappers/render_communication.py: RenderCommunication)
+    def enable_communication_trace(self, teams=('camera', 'target'), duration=20, channels=True):
+        """Keep RenderCommunication's state on the device (mate_engine_enable_comm_trace): per team of `teams` a uint8 matrix
+        remaining[N, sender, recipient], counted down at every live per-step call and set to `duration` (1 .. 255) wherever a message was delivered since the
+        previous step; render() then draws the wrapper's dashed arrows, cameras blue and targets red, behind the obstacles and under the sectors.  The
+        learner's own messages (enable_messages / route_messages) are seen as they are.  A team the ENGINE plays materialises its agents' edges only where
+        its agents' launch runs under a channel, so with the on-device agents enabled this call installs a transparent channel -- set_channel(team), every
+        message arrives -- for every team of `teams` that has none (step_greedy / step_versus_greedy then take the two-launch form); where set_channel
+        refuses the team (a seat, the Heuristic camera agent) so does this call.  While enabled the fused rollouts (rollout_random, rollout_greedy,
+        rollout_versus_greedy, frame_skip > 1 steppers) and pipelined restarts are refused: step per frame.  The matrices start from zeros; every reset and
+        restart starts its environments from zeros again.  channels=False: install no channel (the caller plants the matrices itself).  teams=(): detach."""
+        codes = sorted({_team_code(t) for t in teams})
+        duration = int(duration)
+        if codes and not 1 <= duration <= 255:
+            raise ValueError(f'enable_communication_trace: duration must lie in [1, 255], got {duration}')
+        for team in codes:
+            if (self.num_cameras, self.num_targets)[team] == 0:
+                raise ValueError(f"enable_communication_trace: the scenario has no {('camera', 'target')[team]}s to talk")
+        installed = []
+        try:
+            if self._policies and channels:
+                for team in codes:
+                    if self.channels[team] is None:
+                        self.set_channel(team)
+                        installed.append(team)
+            check(self.lib.mate_engine_enable_comm_trace(self._h, sum(1 << t for t in codes), duration if codes else 0))
+        except Exception:      # (a refused call changes nothing: the channels it installed go again)
+            for team in installed:
+                self.clear_channel(team)
+            raise
+        self.trace_duration, self.trace_teams = (duration, tuple(codes)) if codes else (0, ())
+
+    def disable_communication_trace(self):
+        """Detach the trace (a channel enable_communication_trace installed stays: clear_channel removes it)."""
+        self.enable_communication_trace(teams=())
+
+    def communication_trace(self, team):
+        """The team's remaining[N, n, n] as a zero-copy uint8 view of the engine-owned matrix, [sender][recipient] (mate_engine_comm_trace).  An environment
+        whose episode has changed since its last live step still shows the old episode's bytes until its next step; communication_trace_tags() says which."""
+        return self._trace_views(team)[0]
+
+    def communication_trace_tags(self, team):
+        """int32 [N]: the episode number each environment's matrix belongs to (-1: none yet); render() draws a matrix only where it is the current one."""
+        return self._trace_views(team)[1]
+
+    def _trace_views(self, team):
+        team = _team_code(team)
+        n, N = (self.num_cameras, self.num_targets)[team], self.num_envs
+        remaining, tags = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self.lib.mate_engine_comm_trace(self._h, team, ctypes.byref(remaining), ctypes.byref(tags)))
+        return (torch.as_tensor(_EngineOwned(self, remaining.value, N * n * n, '|u1'), device=self.device).view(N, n, n),
+                torch.as_tensor(_EngineOwned(self, tags.value, N, '<i4'), device=self.device))
+
+    def set_communication_trace(self, team, remaining):
+        """Plant `remaining` ([N, n, n] uint8, [sender][recipient]; host or device) as the team's matrix, tagged with the environments' current episodes
+        (mate_engine_set_comm_trace): what the next render() draws.  The N = 1 class's host mailbox and the tests come here."""
+        team = _team_code(team)
+        n = (self.num_cameras, self.num_targets)[team]
+        value = torch.from_numpy(np.array(remaining.cpu().numpy() if torch.is_tensor(remaining) else remaining, dtype=np.uint8, order='C')).to(self.device)
+        self._check_tensor('remaining', value, torch.uint8, (self.num_envs, n, n))
+        torch.cuda.current_stream(self.device).synchronize()      # (the upload is complete before the engine's own stream copies it)
+        check(self.lib.mate_engine_set_comm_trace(self._h, team, ctypes.c_void_p(value.data_ptr())))
+
     @staticmethod
     def info_views(camera_rows, target_rows, cargo_rows):
         """{name: view} over the three row tensors (None: that output's names are absent): [N, Nc] / [N, Nt] columns,
@@ -2079,6 +2145,14 @@ class EngineGroups:
             if frames is not None:
                 out[torch.from_numpy(mine).to(self.device)] = frames
         return out
+
+    def enable_communication_trace(self, teams=('camera', 'target'), duration=20):
+        """Engine.enable_communication_trace on every group."""
+        return self.each(lambda g, eng: eng.enable_communication_trace(teams=teams, duration=duration))
+
+    def communication_trace(self, team):
+        """Engine.communication_trace of every group: the groups' [N / G, n, n] views."""
+        return self.each(lambda g, eng: eng.communication_trace(team))
 
     def enable_messages(self, team, width, pairwise=False, addressed=False):
         """Engine.enable_messages on every group; returns the groups' (payload, address, inbox) tensors."""

@@ -338,6 +338,8 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         # render-only state the engine does not keep (environment.py:1347-1352 of the reference): kept here from consecutive locations
         self.target_orientations, self._last_locations = np.zeros(Nt, dtype=np.float64), None
         self._last_episode_rewards = self._last_step_rewards = (0.0, 0.0)
+        self.render_communication_duration = 0            # (enable_render_communication)
+        self.camera_comm_matrix, self.target_comm_matrix = np.zeros((Nc, Nc), dtype=np.int64), np.zeros((Nt, Nt), dtype=np.int64)
         self.seed(0)
 
     # ------------------------------------------------------------------ state access
@@ -433,7 +435,35 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
                                     if self.num_delivered_cargoes > 0 else 0.0)
         return cam, tgt, scalars
 
+    def enable_render_communication(self, duration=20):
+        """mate.RenderCommunication(env, duration) for this class: the wrapper's two matrices, camera_comm_matrix / target_comm_matrix [n, n] int64
+        ([sender][recipient]), kept on the host from message_buffers -- counted down and marked at every step(), ahead of the step, and cleared at reset(),
+        as the wrapper does -- and uploaded for the launch by render(), which then draws the dashed arrows.  The messages are the
+        host mailbox's (send_messages).  The on-device agents of step_greedy() / step_versus_greedy() send none through it: with enable_greedy_policies()
+        ahead of this call the engine traces theirs itself (Engine.enable_communication_trace, which installs a transparent channel for a team without
+        one), and render() draws the union -- the element-wise maximum, both count down alike.  duration: 1 .. 255; 0 disables."""
+        duration = int(duration)
+        if not 0 <= duration <= 255:
+            raise ValueError(f'enable_render_communication: duration must lie in [1, 255] (0 disables), got {duration}')
+        self.render_communication_duration = duration
+        self.camera_comm_matrix.fill(0)
+        self.target_comm_matrix.fill(0)
+        teams = [t for t, n in (('camera', self.num_cameras), ('target', self.num_targets)) if n > 0] if duration else []
+        self.engine.enable_communication_trace(teams=teams, duration=duration or 20, channels=self._policies_on)
+
+    def _trace_messages(self):
+        """RenderCommunication.step ahead of env.step (render_communication.py:47-54)."""
+        if not self.render_communication_duration:
+            return
+        for matrix, buffer in zip((self.camera_comm_matrix, self.target_comm_matrix), self.message_buffers):
+            np.maximum(matrix - 1, 0, out=matrix)
+            for packs in buffer.values():
+                for message in packs:
+                    matrix[message.sender, message.recipient] = self.render_communication_duration
+
     def reset(self, *, seed=None):
+        self.camera_comm_matrix.fill(0)
+        self.target_comm_matrix.fill(0)
         self._clear_messages(totals=True)
         if seed is not None:
             self.seed(seed)
@@ -482,6 +512,8 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
             if spec is not None:
                 self.engine.set_channel(team, **spec)
         self._policies_on = True
+        if self.render_communication_duration:      # (enabled ahead of the agents: the engine-played teams' transparent channels now)
+            self.enable_render_communication(self.render_communication_duration)
 
     def communication_edges(self):
         """((camera sent, camera delivered), (target sent, target delivered)) of the last step_greedy() / step_versus_greedy(): [n, n] int8 arrays,
@@ -493,6 +525,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         """`env.step(mate.group_step(...))` of both teams with the reference's Greedy agents computed on the device
         (mate/agents/greedy.py through Engine.step_greedy); same return value as step()."""
         self._need_policies()
+        self._trace_messages()
         tape_ct, tape_goal = self._tapes()
         self.engine.step_greedy(tape_ct=tape_ct, tape_goal=tape_goal, auto_reset=False)
         return self._finish_step()
@@ -508,6 +541,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         agents, dim = (self.num_cameras, consts.CAMERA_ACTION_DIM) if team == 'camera' else (self.num_targets, consts.TARGET_ACTION_DIM)
         act = np.asarray(joint_action, dtype=np.float64).reshape(agents, dim)
         assert np.isfinite(act).all(), f'Got unexpected joint action {act}.'
+        self._trace_messages()
         tape_ct, tape_goal = self._tapes()
         self.engine.step_versus_greedy(team, torch.from_numpy(act[None]).to(self.engine.device), tape_ct=tape_ct, tape_goal=tape_goal,
                                        auto_reset=False)
@@ -519,6 +553,7 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
         tgt_act = np.asarray(target_joint_action, dtype=np.float64).reshape(self.num_targets, consts.TARGET_ACTION_DIM)
         assert np.isfinite(cam_act).all(), f'Got unexpected joint action {cam_act}.'
         assert np.isfinite(tgt_act).all(), f'Got unexpected joint action {tgt_act}.'
+        self._trace_messages()
         tape_ct, tape_goal = self._tapes()
         nc = cam_act.size
         act_np = self._act_host.numpy()
@@ -607,10 +642,19 @@ class MultiAgentTracking(_ScenarioMixin, _EnvBase, metaclass=EnvMeta):
 
     def render(self, mode='human', window_size=800, **kwargs):
         """mode='rgb_array': the picture of the current state, uint8 [window_size, window_size, 3] (row 0 at the top), rasterised on the device by
-        Engine.render under the rules of DESIGN.md section 3.20 -- the reference's display list without the warehouse icons and without the render
-        callbacks.  mode='human' needs a window: there is no display on the GPU box."""
+        Engine.render under the rules of DESIGN.md sections 3.20 and 3.21 -- the reference's display list without the warehouse icons and without the
+        render callbacks, but for RenderCommunication's arrows after enable_render_communication().  mode='human' needs a window: there is no display on
+        the GPU box."""
         if mode != 'rgb_array':
             raise NotImplementedError("only mode='rgb_array' is rendered (off-screen, on the device): there is no display on the GPU box")
+        if self.render_communication_duration:
+            episode = int(self._fields()['episode'])
+            for team, matrix in enumerate((self.camera_comm_matrix, self.target_comm_matrix)):
+                if matrix.size:
+                    merged = matrix      # (the wrapper's matrices stay as step() left them: the union goes to the device only)
+                    if int(self.engine.communication_trace_tags(team)[0]) == episode:      # (the engine's own trace of the on-device agents, where it is this episode's)
+                        merged = np.maximum(matrix, self.engine.communication_trace(team)[0].cpu().numpy().astype(np.int64))
+                    self.engine.set_communication_trace(team, merged.astype(np.uint8)[None])
         frames = self.engine.render([0], size=window_size, headings=self.target_orientations[None])
         return frames[0].cpu().numpy()
 
@@ -767,7 +811,7 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
                  camera_reward_shaping=None, target_reward_shaping=None, reward_dtype=torch.float64, camera_selection=None, frame_skip=None,
                  learner=None, first_rows=False, target_agent='greedy', camera_agent='greedy', episode_records=None, training_information=False,
                  target_mixture=None, camera_mixture=None, no_communication='none', message_dropout=0.0, communication_range=None, single_agent=None, seat='auto',
-                 camera_messages=None, target_messages=None, per_frame=False, **kwargs):
+                 camera_messages=None, target_messages=None, per_frame=False, render_communication=None, **kwargs):
         assert state_rows in (False, True, 'normalized'), f"state_rows = {state_rows!r}: False, True or 'normalized'"
         self._setup_scenario(config, kwargs)
         self._policies_on = False                         # (enable_greedy_policies)
@@ -879,11 +923,30 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
         # (examples/hrl/wrappers.py), one frame per call: 'multi' / 'single'; attached behind the first reset() (Engine.enable_selection)
         assert camera_selection in (None, 'multi', 'single'), f"camera_selection = {camera_selection!r}: None, 'multi' or 'single'"
         self.camera_selection = camera_selection
+        # render_communication = duration: mate.RenderCommunication(env, duration) -- the per-pair countdowns on the device behind every per-step call, the
+        # dashed arrows in render() (Engine.enable_communication_trace)
+        if render_communication is not None and (isinstance(render_communication, bool) or not 1 <= int(render_communication) <= 255):
+            raise ValueError(f'render_communication = {render_communication!r}: None or the duration, an integer in [1, 255]')
+        assert render_communication is None or not single_agent, 'render_communication: the seat flow carries no communication channel, so its teammates draw no arrows'
+        assert render_communication is None or not self._fragment or per_frame, 'render_communication steps one frame per call: the fused K-frame launch keeps no per-frame edges (per_frame=True instead)'
+        self._render_communication = None if render_communication is None else int(render_communication)
         if camera_selection:
             assert self.num_cameras > 0, 'camera_selection needs cameras'
             self.enable_greedy_policies()
         if self._fragment or ((target_agent != 'greedy' or camera_agent != 'greedy') and not camera_selection) or ((self._mixtures or any(self._channels) or single_agent) and not self._policies_on):
             self.enable_greedy_policies()
+        self._enable_render_communication()
+
+    def _enable_render_communication(self):
+        if self._render_communication:
+            teams = [team for team, n in (('camera', self.num_cameras), ('target', self.num_targets)) if n > 0]
+            self.engine.enable_communication_trace(teams=teams, duration=self._render_communication)
+
+    def communication_trace(self):
+        """(camera remaining, target remaining): uint8 [num_envs, n, n] views of the engine's matrices, [sender][recipient] -- RenderCommunication's
+        camera_comm_matrix / target_comm_matrix per environment (None for a team without agents).  Built with render_communication = duration."""
+        assert self._render_communication, 'built without render_communication = duration'
+        return tuple(self.engine.communication_trace(team) if n > 0 else None for team, n in enumerate((self.num_cameras, self.num_targets)))
 
     def seed(self, seed):
         self.engine.seed(int(seed))
@@ -1077,6 +1140,8 @@ class BatchedMultiAgentTracking(_ScenarioMixin):
             assert (self.num_cameras if self.single_agent == 'camera' else self.num_targets) > 0, f'single_agent = {self.single_agent!r}: the scenario has no such agents'
             self.engine.enable_seat(self.single_agent, self._seat)
         self._policies_on = True
+        if getattr(self, '_render_communication', None) and self.engine.trace_duration:      # (enabled behind the construction: the engine-played teams' transparent channels)
+            self._enable_render_communication()
 
     def communication_edges(self):
         """((camera sent, camera delivered), (target sent, target delivered)): [num_envs, n, n] int8 tensors on the GPU, [sender][recipient], as the

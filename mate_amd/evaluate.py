@@ -245,6 +245,9 @@ def build_parser():
     ap.add_argument('--frame-size', type=int, default=800, metavar='S', help='with --save-frames: S x S pixels')
     ap.add_argument('--frame-every', type=int, default=1, metavar='K',
                     help='with --save-frames: every K-th picture (a picture per step; with --num-envs: per launch of 16 frames)')
+    ap.add_argument('--render-communication', type=int, nargs='?', const=20, default=None, metavar='DURATION',
+                    help="with --save-frames and --policy greedy: draw intra-team messages as dashed arrows for DURATION steps each, default 20 (mate.evaluate's "
+                         '--render-communication: mate.RenderCommunication; the random policy sends no messages, so the flag has no effect there)')
     return ap
 
 
@@ -259,7 +262,8 @@ def main(argv=None):
                                                  target_agent=args.target_agent, camera_agent=args.camera_agent,
                                                  target_mixture=args.target_mixture, camera_mixture=args.camera_mixture,
                                                  no_communication=args.no_communication, message_dropout=args.message_dropout,
-                                                 communication_range=args.communication_range, single_agent=args.single_agent, **overrides)
+                                                 communication_range=args.communication_range, single_agent=args.single_agent,
+                                                 render_communication=args.render_communication if frames is not None and args.policy == 'greedy' else None, **overrides)
         if args.policy == 'greedy':
             env.enable_greedy_policies()
         records = evaluate_batched(env, args.episodes, args.policy, seed=args.seed, frames=frames)
@@ -280,6 +284,8 @@ def main(argv=None):
         if args.camera_mixture is not None:
             agents['camera_mixture'] = args.camera_mixture
         env.enable_greedy_policies(**agents)
+    if args.render_communication is not None and frames is not None and args.policy == 'greedy':
+        env.enable_render_communication(args.render_communication)
     env.seed(args.seed)
     rows = []
     for episode in range(args.episodes):
